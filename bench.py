@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- symmetric D1+D2 PSNR throughput of the CloudPair/MetricCalculator hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--engine auto|brute|grid] [--points 1000000]
+    python bench.py --gpus N --steps K --warmup W [--engine auto|brute|grid] [--points 1000000] [--dump-outputs DIR]
 
 One *step* = one pass of the hot path over one synthetic cloud pair already resident in HBM:
 the search-structure build (the reference's two KD-tree builds, cloud_pair.py:65), both directional exact
@@ -38,6 +38,8 @@ FP32_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: fp32 vector == f32-MFMA dens
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E spec peak
 FLOP_PER_PAIR = 8            # 3 sub + 1 mul + 2 fma
 PROFILE_ROUND = "r04"
+DUMP_BYTES = 64_000_000      # --dump-outputs: what the files may hold in all
+DUMP_SEED = 2024             # --dump-outputs: the rows sampled from columns too long to store whole
 
 
 def synth(n):
@@ -111,6 +113,28 @@ def cpu_reference_pattern(a, b, na, nb, sample=20000):
             "d2_mse_of_sample": float(mse2)}
 
 
+def last_step_outputs(pair, report):
+    """What the timed path computed in its last step, as float64 arrays: every row of the report its caller receives, and the
+    per-point columns the report was reduced from (squared nearest-neighbour distances and signed point-to-plane projections
+    of both directions), read from the pair before anything else runs on it.  A column too long for DUMP_BYTES is replaced by
+    the same seeded sample of its rows on every run; the sampled rows are stored as sample_rows_<direction>."""
+    out = {"report." + "_".join(str(p) for p in key): np.asarray(val, dtype=np.float64) for key, val in report.items()}
+    cap = (DUMP_BYTES - (1 << 20)) // (8 * 6)          # rows per array: four columns and two row lists, 1 MB for the report
+    for side, is_left in (("left", True), ("right", False)):
+        cols = {"neighbour_distances": pair.get_left_neighbour_distances if is_left else pair.get_right_neighbour_distances,
+                "point_to_plane": lambda: pair.point_to_plane_column(is_left)}
+        rows = None
+        for name, get in cols.items():
+            col = np.asarray(get(), dtype=np.float64)
+            if len(col) > cap:
+                if rows is None:
+                    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(col), cap, replace=False))
+                    out[f"sample_rows_{side}"] = rows.astype(np.float64)
+                col = col[rows]
+            out[f"{name}_{side}"] = col
+    return out
+
+
 def committed_traffic(kernel, n, world):
     """HBM bytes per launch of `kernel` from the PMC passes committed under profiles/ (FETCH_SIZE / WRITE_SIZE,
     separate rocprofv3 --pmc runs over this same command, corrected as MI355X_MICROARCH.md prescribes: a PMC pass
@@ -159,7 +183,13 @@ def main():
     ap.add_argument("--shard-mode", default="direction", choices=["direction", "rows"], help="how N > 1 ranks split the pair")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse several ranks on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.content_only or args.content_full_only or args.content_cli_only):
+        ap.error("--dump-outputs writes the headline workload's outputs: it does not go with the --content-*-only runs")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD process (never an exec), before
@@ -442,6 +472,8 @@ def main():
     eng.profile(args.no_graph)   # HIP events time eager launches; a hipGraph replay cannot carry them (ROCm 7.2)
     eng.profile_reset()
     elapsed, result = timed(step, args.steps)
+    # (every rank reads the columns: a sharded pair gathers them across ranks)
+    outputs = last_step_outputs(pair, result) if args.dump_outputs else None
     prof_leg = "HIP events over the timed region"
     if not args.no_graph:
         # kernel durations: the same steps issued eagerly right after the timed region, same process,
@@ -732,6 +764,10 @@ def main():
         line["parity_vs_oracle"] = "bit-exact" if not bad else f"MISMATCH in {bad}"
     elif rank == 0:
         line["cpu_baseline"] = None
+    if rank == 0 and outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -35,6 +35,7 @@ def _torchrun(script, nproc, env, timeout):
 WORKER = r'''
 import json, os, sys
 import numpy as np
+import torch
 import torch.distributed as dist
 sys.path.insert(0, os.environ["PCCM_ROOT"]); sys.path.insert(0, os.path.join(os.environ["PCCM_ROOT"], "tests"))
 from open_pcc_metric_amd.calculator import MetricCalculator
@@ -60,7 +61,11 @@ out = {"rank": dist.get_rank(), "shard": pair._engine.shard_range(0), "shards": 
        "calls": sorted(set(c[0] for c in pair._engine.calls if c[0].startswith("reduce")))}
 with open(os.path.join(os.environ["PCCM_OUT"], f"rank{dist.get_rank()}.json"), "w") as fh:
     json.dump(out, fh)
-dist.barrier()                      # (orderly teardown: a rank that leaves while a peer's gloo thread still talks to it aborts that peer)
+# (orderly teardown: a rank that leaves while a peer's gloo thread still talks to it aborts that peer)  The barrier dist.barrier()
+# runs for a gloo group, without its accelerator lookup: that lookup opens the GPU of a GPU host in every rank
+opts = dist.BarrierOptions()
+opts.device = torch.device("cpu")
+dist.group.WORLD.barrier(opts=opts).wait()
 dist.destroy_process_group()
 '''
 
@@ -118,6 +123,7 @@ def test_gloo_ranks_match_single_process(tmp_path, n, world, mode):
 Q1_WORKER = r'''
 import json, os, sys
 import numpy as np
+import torch
 import torch.distributed as dist
 sys.path.insert(0, os.environ["PCCM_ROOT"]); sys.path.insert(0, os.path.join(os.environ["PCCM_ROOT"], "tests"))
 from open_pcc_metric_amd.calculator import MetricCalculator
@@ -140,7 +146,11 @@ except IndexError as exc:
     outcome = "IndexError: " + str(exc)
 with open(os.path.join(os.environ["PCCM_OUT"], f"q1_rank{dist.get_rank()}.json"), "w") as fh:
     json.dump({"rank": dist.get_rank(), "outcome": outcome, "shard": pair._engine.shard_range(0)}, fh)
-dist.barrier()                      # (orderly teardown: a rank that leaves while a peer's gloo thread still talks to it aborts that peer)
+# (orderly teardown: a rank that leaves while a peer's gloo thread still talks to it aborts that peer)  The barrier dist.barrier()
+# runs for a gloo group, without its accelerator lookup: that lookup opens the GPU of a GPU host in every rank
+opts = dist.BarrierOptions()
+opts.device = torch.device("cpu")
+dist.group.WORLD.barrier(opts=opts).wait()
 dist.destroy_process_group()
 '''
 
