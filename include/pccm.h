@@ -232,6 +232,20 @@ int pccm_reduce_chunks_many(pccm_ctx *ctx, int n, const int *dirs, const int *me
                             double *minmax);
 int pccm_finish_chunks(const double *cvec, int64_t n_iter, double *sum);
 
+/* How the calls that hand reduced numbers to the caller (pccm_reduce, pccm_reduce_total[_many], pccm_reduce_chunks_many: the
+ * np.sum / np.max of metric.py:226-228, 366, where the reference has its numbers at once) wait for the GPU.
+ *   PCCM_WAIT_SPIN (default): one wave behind a batch's last reduction kernel bumps the context's completion counter, a word
+ *     in host memory, once the batch's numbers are there, and the calling thread spins on it.  The host sees the numbers
+ *     about 13 us sooner than through the runtime's event completion.  After 2 ms of spinning it waits on the batch's
+ *     event instead, so a fault or a hang still comes back as a HIP error.
+ *   PCCM_WAIT_EVENT: hipEventSynchronize on the batch's event (the thread sleeps: for oversubscribed hosts).
+ * Either way, the device error word is checked behind the wait.  Per context; pccm_ctx_reset keeps it. */
+#define PCCM_WAIT_SPIN 0
+#define PCCM_WAIT_EVENT 1
+int pccm_set_wait(pccm_ctx *ctx, int mode);
+/* The context's completion counter: the number of reduction batches whose numbers have reached the host so far. */
+int pccm_wait_counter(pccm_ctx *ctx, uint64_t *out);
+
 /* Colours of cloud `which` ([n][3] RGB in [0, 1] as Open3D holds them; n = the cloud's point count):
  * replaces np.asarray(cloud.colors) behind get_left/right_colors(), cloud_pair.py:114-118. */
 int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dtype, int on_device);

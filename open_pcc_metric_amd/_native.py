@@ -33,6 +33,7 @@ SYMBOLS = (
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
+    "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
     "pccm_color_transform", "pccm_lzf_decompress", "pccm_drop_caches", "pccm_graph_begin", "pccm_graph_end", "pccm_graph_launch", "pccm_graph_destroy",
     "pccm_sync",
@@ -90,6 +91,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_set_normals_deferred.argtypes = [vp, i32, vp, i64, i32]
     lib.pccm_flush_uploads.argtypes = [vp]
     lib.pccm_set_io_staged.argtypes = [vp, i32]
+    lib.pccm_set_wait.argtypes = [vp, i32]
+    lib.pccm_wait_counter.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.pccm_set_shard.argtypes = [vp, i32, i32]
     lib.pccm_set_shard_dir.argtypes = [vp, i32, i32, i32]
     lib.pccm_estimate_normals.argtypes = [vp, i32, i32]
@@ -353,6 +356,20 @@ class Engine:
         """Large transfers through the context's own pinned buffers (default) or straight from / to the caller's arrays
         (see pccm_set_io_staged in include/pccm.h)."""
         _check(self._lib.pccm_set_io_staged(self._ctx, 1 if on else 0))
+
+    def set_wait(self, mode: str) -> None:
+        """How reductions wait for the GPU: "spin" (default: on the context's completion counter) or "event" (the thread
+        sleeps in hipEventSynchronize; see pccm_set_wait in include/pccm.h)."""
+        modes = {"spin": 0, "event": 1}
+        if mode not in modes:
+            raise ValueError(f"wait mode {mode!r}: expected one of {sorted(modes)}")
+        _check(self._lib.pccm_set_wait(self._ctx, modes[mode]))
+
+    def wait_counter(self) -> int:
+        """Reduction batches whose numbers have reached the host so far (pccm_wait_counter)."""
+        out = ctypes.c_uint64(0)
+        _check(self._lib.pccm_wait_counter(self._ctx, ctypes.byref(out)))
+        return int(out.value)
 
     def flush_uploads(self) -> None:
         try:

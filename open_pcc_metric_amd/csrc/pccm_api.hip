@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <chrono>
 #include <new>
 #include <thread>
 
@@ -420,11 +421,17 @@ int pccm_ctx_create(int device, void *hip_stream, pccm_ctx **out)
         ctx->own_stream = true;
     }
     int rc = ensure(ctx, ctx->counters, 16 * sizeof(uint32_t));      // [0..5] per-direction counters, [8..11] rescan tickets, [12..15] tail-launch counts
-    if (!rc && hipHostMalloc((void **)&ctx->host_err, 64, hipHostMallocDefault) != hipSuccess) {
+    // host-coherent: the host may read it on the completion counter's word alone (wait_slot), with no end-of-stream flush
+    if (!rc && hipHostMalloc((void **)&ctx->host_err, 64, hipHostMallocCoherent) != hipSuccess) {
         ctx->host_err = nullptr;
         rc = fail(PCCM_E_OOM, "hipHostMalloc of the device error word failed");
     }
     if (!rc) *ctx->host_err = 0u;
+    if (!rc && hipHostMalloc((void **)&ctx->done, 128, hipHostMallocCoherent) != hipSuccess) {     // a cache line of its own
+        ctx->done = nullptr;
+        rc = fail(PCCM_E_OOM, "hipHostMalloc of the completion counter failed");
+    }
+    if (!rc) *ctx->done = 0;
     if (!rc && hipEventCreateWithFlags(&ctx->batch_ev, hipEventDisableTiming) != hipSuccess) rc = fail(PCCM_E_HIP, "hipEventCreate failed");
     if (!rc) rc = ensure(ctx, ctx->stats, 32 * sizeof(unsigned long long));      // [0..9] the main stream's scratch, [12..14] the copy stream's, [16..22] colour reduction of the other direction
     if (!rc && hipMemsetAsync(ctx->counters.p, 0, 16 * sizeof(uint32_t), ctx->stream) != hipSuccess)
@@ -452,6 +459,8 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     ctx->batch_ev = nullptr;
     if (ctx->host_err) (void)hipHostFree(ctx->host_err);
     ctx->host_err = nullptr;
+    if (ctx->done) (void)hipHostFree(ctx->done);
+    ctx->done = nullptr;
     for (int k = 0; k < 2; ++k) free_cloud(ctx->cloud[k]);
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
@@ -585,6 +594,25 @@ int pccm_set_io_staged(pccm_ctx *ctx, int on)
     NOT_CAPTURING(ctx);
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     ctx->io_staged = on != 0;
+    return PCCM_OK;
+}
+
+int pccm_set_wait(pccm_ctx *ctx, int mode)
+{
+    CHECK_CTX(ctx);
+#ifdef PCCM_DIAG
+    if (mode == 2) { ctx->wait_mode = mode; return PCCM_OK; }     // diagnostic build: a hipEventQuery spin, for A/B timing
+#endif
+    if (mode != PCCM_WAIT_SPIN && mode != PCCM_WAIT_EVENT) return fail(PCCM_E_ARG, "bad wait mode %d", mode);
+    ctx->wait_mode = mode;
+    return PCCM_OK;
+}
+
+int pccm_wait_counter(pccm_ctx *ctx, uint64_t *out)
+{
+    CHECK_CTX(ctx);
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    *out = __atomic_load_n(ctx->done, __ATOMIC_ACQUIRE);
     return PCCM_OK;
 }
 
@@ -1239,6 +1267,35 @@ int64_t pccm_xvec_len(int64_t n_iter)
 // the unit arrays and of the shard's raw tail values into pinned host memory -> event.  pccm_reduce()
 // consumes a slot (enqueuing it first when nobody prefetched it), so a caller that prefetches every
 // column it will need waits for the GPU once per step instead of once per column.
+
+// Until a slot's numbers are on the host.  PCCM_WAIT_SPIN: a wave behind the batch's last kernel bumps the context's completion
+// counter once they are (k_publish, pccm_point.hip), and the host watches that word -- the runtime's event completion path
+// wakes a waiting thread ~13 us after the kernel ends.  The spin is bounded: past kSpinBound, or for a
+// slot the counter does not cover (wait_seq 0), the batch event says it, and reports a fault or a hang as a HIP error.
+static int wait_slot(pccm_ctx *ctx, const ReduceSlot *s)
+{
+    constexpr auto kSpinBound = std::chrono::milliseconds(2);
+    const uint64_t want = s->wait_seq;
+    if (ctx->wait_mode == PCCM_WAIT_SPIN && want) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned k = 0;; ++k) {
+            if (__atomic_load_n(ctx->done, __ATOMIC_ACQUIRE) >= want) return PCCM_OK;
+            __builtin_ia32_pause();
+            if ((k & 255) == 255 && std::chrono::steady_clock::now() - t0 > kSpinBound) break;
+        }
+    }
+#ifdef PCCM_DIAG
+    if (ctx->wait_mode == 2 && s->wait_ev) {
+        hipError_t e;
+        while ((e = hipEventQuery(s->wait_ev)) == hipErrorNotReady) __builtin_ia32_pause();
+        PCCM_HIP(e);
+        return PCCM_OK;
+    }
+#endif
+    if (s->wait_ev) PCCM_HIP(hipEventSynchronize(s->wait_ev));
+    return PCCM_OK;
+}
+
 // bookkeeping + buffers of one slot; the kernels are launched for all new slots together (slots_launch)
 static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int normal_mode, bool want_units, PointJobs &pj,
                         UnitJobs &uj)
@@ -1305,7 +1362,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         ctx->epoch++;
         if (s.host) (void)hipHostFree(s.host);
         s.host = nullptr; s.host_cap = 0;
-        PCCM_HIP(hipHostMalloc((void **)&s.host, need, hipHostMallocDefault));
+        PCCM_HIP(hipHostMalloc((void **)&s.host, need, hipHostMallocCoherent));   // no XCD's L2 keeps any of it (wait_slot)
         s.host_cap = need;
     }
     if (!s.ev) PCCM_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
@@ -1419,7 +1476,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
         ReduceSlot *s = slot_free(ctx, fresh, nfresh);
         if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 8 live columns in one batch");
-        if (s->pending && !ctx->capturing && s->wait_ev) PCCM_HIP(hipEventSynchronize(s->wait_ev));
+        if (s->pending && !ctx->capturing && s->wait_ev) { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
         s->pending = false;
         int rc = slot_prepare(ctx, *s, dirs[k], metrics[k], normal_modes[k], want_units, pj, uj);
         if (rc) return rc;
@@ -1429,9 +1486,11 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     if (nfresh == 0) return PCCM_OK;
     int rc;
     if ((rc = launch_point_jobs(ctx, pj))) return rc;
-    if ((rc = launch_unit_jobs(ctx, uj))) return rc;
+    uint64_t seq = 0;
+    if ((rc = launch_unit_jobs(ctx, uj, &seq))) return rc;
     for (int k = 0; k < nfresh; ++k) {
         ReduceSlot &s = *fresh[k];
+        s.wait_seq = seq;                  // (while capturing: the batch's ordinal in the captured sequence)
         if (ctx->capturing) {
             GraphOp op;
             op.kind = 2;
@@ -1465,7 +1524,7 @@ int pccm_reduce(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *xve
         s = slot_find(ctx, dir, metric, normal_mode, true);
         if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
     }
-    if (s->wait_ev) PCCM_HIP(hipEventSynchronize(s->wait_ev));
+    { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
     { int rce = check_device_errors(ctx); if (rce) return rce; }
     s->pending = false;
     const int64_t n = s->n_iter;
@@ -1526,7 +1585,7 @@ static int total_from_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, 
         s = slot_find(ctx, dir, metric, normal_mode);
         if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
     }
-    if (s->wait_ev) PCCM_HIP(hipEventSynchronize(s->wait_ev));
+    { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
     { int rce = check_device_errors(ctx); if (rce) return rce; }
     s->pending = false;
     const int64_t n = s->n_iter, nunits = s->nunits, nblocks = s->nblocks;
@@ -1572,7 +1631,7 @@ static int chunks_from_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode,
         s = slot_find(ctx, dir, metric, normal_mode);
         if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
     }
-    if (s->wait_ev) PCCM_HIP(hipEventSynchronize(s->wait_ev));
+    { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
     { int rce = check_device_errors(ctx); if (rce) return rce; }
     s->pending = false;
     const int64_t n = s->n_iter, nunits = s->nunits, nblocks = s->nblocks;
@@ -1760,7 +1819,10 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
             ctx->nn[op.dir].plain_d2_valid = op.plain_valid;
         } else if (op.kind == 2) {
             ReduceSlot &s = ctx->slots[op.slot];
-            if (s.pending && s.gen == ctx->nn_gen[s.dir] && s.wait_ev) PCCM_HIP(hipEventSynchronize(s.wait_ev));   // still in use by someone else
+            if (s.pending && s.gen == ctx->nn_gen[s.dir] && s.wait_ev) {      // still in use by someone else
+                int rcw = wait_slot(ctx, &s);
+                if (rcw) return rcw;
+            }
             s.dir = op.snap.dir; s.metric = op.snap.metric; s.mode = op.snap.mode;
             s.n_iter = op.snap.n_iter; s.begin = op.snap.begin; s.end = op.snap.end;
             s.nunits = op.snap.nunits; s.nblocks = op.snap.nblocks; s.has_units = op.snap.has_units;
@@ -1768,8 +1830,10 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
             s.gen = ctx->nn_gen[s.dir];
             s.pending = true;
             s.wait_ev = ctx->batch_ev;
+            s.wait_seq = op.snap.wait_seq ? ctx->batches_issued + op.snap.wait_seq : 0;
         }
     }
+    ctx->batches_issued += g.batches;                            // before the launch: a failed one only delays a waiter
     PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));          // one record for every reduction of the graph
     return PCCM_OK;
@@ -1782,6 +1846,7 @@ int pccm_graph_begin(pccm_ctx *ctx)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     for (auto &s : ctx->slots) s.pending = false;      // nothing outside the graph may be half-consumed
     ctx->cap_ops.clear();
+    ctx->cap_batches = 0;
     ctx->capture_failed = false;
     PCCM_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     ctx->capturing = true;
@@ -1825,11 +1890,16 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
             op.no_rows = ctx->nn[op.dir].no_rows;
         }
     g.epoch = ctx->epoch;
+    g.batches = ctx->cap_batches;
     g.valid = true;
     // the captured calls changed the host bookkeeping but nothing ran yet: run the graph once now
-    PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     for (auto &op : g.ops)
-        if (op.kind == 2) ctx->slots[op.slot].wait_ev = ctx->batch_ev;
+        if (op.kind == 2) {
+            ctx->slots[op.slot].wait_ev = ctx->batch_ev;
+            ctx->slots[op.slot].wait_seq = op.snap.wait_seq ? ctx->batches_issued + op.snap.wait_seq : 0;
+        }
+    ctx->batches_issued += g.batches;
+    PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
     int id = -1;
     for (size_t k = 0; k < ctx->graphs.size(); ++k)

@@ -176,6 +176,8 @@ struct ReduceSlot {            // one enqueued reduction (pccm_reduce_prefetch /
     hipEvent_t ev = nullptr;
     hipEvent_t wait_ev = nullptr;   // what says "this slot's numbers are on the host": the context's batch event (one record serves
                                     // every slot of a call / of a graph replay; waiting on a later record of it only waits longer)
+    uint64_t wait_seq = 0;          // ... or, sooner, the context's completion counter reaching this value (0: the event only;
+                                    // in a GraphOp's snapshot: the batch's ordinal within the captured sequence)
 };
 
 struct ProfSpan {
@@ -197,6 +199,7 @@ struct GraphRec {
     hipGraphExec_t exec = nullptr;
     std::vector<GraphOp> ops;
     uint64_t epoch = 0;        // pccm_ctx::epoch it was captured under
+    uint64_t batches = 0;      // reduction batches in it that publish on the completion counter (each replay adds as many)
     bool valid = false;
 };
 
@@ -248,6 +251,14 @@ struct pccm_ctx {
     pccm::DevBuf g_cell_of, g_rank, g_hist, g_blocksum, g_qrecs;   // grid-engine scratch (g_qrecs: cell-sorted shard rows)
     pccm::DevBuf g_bins, g_tmp;            // grid build: per-tile bin histogram + scan state; bin-partitioned records
     hipEvent_t batch_ev = nullptr;   // recorded once behind every batch of reductions (ReduceSlot::wait_ev)
+    // completion counter: k_publish, behind the last kernel of a reduction batch, adds 1 to *done (host-coherent pinned memory, a
+    // cache line of its own) when the batch's results are on the host; batches_issued counts the publishing batches enqueued
+    // so far, so a slot waits for *done to reach the count its batch was given (ReduceSlot::wait_seq) -- a spin on host
+    // memory instead of the runtime's event completion path (pccm_set_wait)
+    uint64_t *done = nullptr;
+    uint64_t batches_issued = 0;
+    uint64_t cap_batches = 0;        // ... publishing batches recorded by the capture in progress
+    int wait_mode = PCCM_WAIT_SPIN;
     // device error word (pinned host memory the kernels can write): a kernel that meets a state it cannot be in -- a cell start
     // that contradicts the occupancy brick (pccm_vox.hip), a tail wait that ran out (k_grid_tail) -- sets a bit instead of
     // answering wrongly in silence; every call that hands results to the caller checks it behind its wait (check_device_errors)
@@ -392,7 +403,9 @@ constexpr unsigned kRescanCap = 512;   // most workgroups that ever share one jo
 int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs);
 // result records -> plain columns (q32 / row0: the iterating cloud's rows, for records of layout 1)
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2);
-int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs);
+// *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when
+// nothing was launched
+int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 
 int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,
                         int normal_mode, double *out_val /*[ns]*/, double *out_err /*[ns][3] or null*/);

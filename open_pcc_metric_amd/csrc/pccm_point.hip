@@ -613,6 +613,23 @@ __global__ __launch_bounds__(256) void k_unit_lean(UnitJobs jobs)
     for (int c = 0; c < NC; ++c) J.c[c].out_tail[e] = w[c];
 }
 
+// A batch's completion, published to the host: one wave launched behind the batch's last reduction kernel on the same stream
+// bumps the context's completion counter (pccm_ctx::done).  The stream starts it once that kernel has ended, i.e. once every store
+// of the batch has left its workgroup; the outputs live in host-coherent memory, so no XCD's L2 holds any of them, and the
+// system-scope release covers whatever else this wave's L2 holds.  The inline wait stays in asm: the compiler may drop the
+// s_waitcnt behind buffer_wbl2 when it thinks the counter empty (MI355X_MICROARCH.md).  This wave costs ~4 us of GPU time at
+// the end of the batch.  Publishing from k_unit_lean itself was measured too: every workgroup drained its stores, and the last
+// one to arrive bumped the counter.  That made the kernel 3.6 us longer at 1M + 1M points for the same step time (DESIGN.md
+// section 4).
+__global__ __launch_bounds__(64) void k_publish(unsigned long long *done)
+{
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                                    // system scope
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_fetch_add(done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // a job's shape, or -1: (stride, CFG, defer) as stride * 4 + cfg + 64 * defer
 static int job_shape(const UnitJob &J)
 {
@@ -663,8 +680,9 @@ static bool lean_has(int shape)
     }
 }
 
-int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs)
+int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
 {
+    *seq = 0;
     const int64_t total = jobs.uoff[jobs.njobs] + jobs.toff[jobs.njobs];
     if (total <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_REDUCE);
@@ -704,6 +722,10 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs)
             launch_unit_shape(ctx, sub, shape[first_of[g]]);
         }
     }
+    // the batch's completion, published behind its last launch.  The count the counter will reach is taken before the launch
+    // is issued, so that a launch that fails can only make a waiter fall back to the event, never wake it early.
+    *seq = ctx->capturing ? ++ctx->cap_batches : ++ctx->batches_issued;
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, ctx->stream, (unsigned long long *)ctx->done);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
