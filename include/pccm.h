@@ -189,6 +189,26 @@ int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out);
  * out[2] = out[3] = out[4].  normal_mode -1: counts only (no normals needed).  Sums are plain fp64 accumulations. */
 int pccm_tie_exposure(pccm_ctx *ctx, int dir, int normal_mode, double out[8]);
 
+/* Which of several EXACTLY equidistant nearest points stands for the matched point of directions 0 and 1 (the self search is
+ * not affected).  The reference keeps whichever one nanoflann's traversal meets (cloud_pair.py:22-23), so its point-to-plane
+ * and colour rows depend on the order of the points in the files.
+ *   PCCM_TIES_PICK (default; pccm_ctx_reset restores it): the point of the smallest row -- idx[] of pccm_nn_fetch.
+ *   PCCM_TIES_MEAN: a virtual neighbour built from the tie set T_i = { j : d2(a_i, b_j) == d2_i }, rows ascending j_1 < ... < j_k:
+ *     position c_i = (((b_j1 + b_j2) + b_j3) + ... ) / k per component in fp64 (sequential adds, one correctly rounded division
+ *     by (double)k; k = 1 gives b_j1 exactly); colour: the same mean of the searched cloud's rgb doubles (bytes: k / 255.0),
+ *     the scheme transform applies to the mean; normal under PCCM_NORMAL_NEIGHBOUR: the same mean of its normals, not
+ *     renormalised (PCCM_NORMAL_ROW: row i, as always).  Error vectors, projections, D2 and every colour call read it; the
+ *     squared distances, the D1 reductions and the matched rows of pccm_nn_fetch are those of PCCM_TIES_PICK (every tie
+ *     shares d2_i).  Not order dependent: a permutation of the searched cloud leaves it as it is (up to the rounding of the
+ *     sums).  Takes effect at the next pccm_nn / pccm_nn_pair.  Searches under MEAN cannot be captured (pccm_graph_begin:
+ *     PCCM_E_STATE); run them eagerly. */
+#define PCCM_TIES_PICK 0
+#define PCCM_TIES_MEAN 1
+int pccm_set_ties(pccm_ctx *ctx, int policy);
+/* The size k of every tie set of the shard's rows of direction `dir` (0 or 1), as pccm_nn_fetch lays out its rows; the search
+ * must have run under PCCM_TIES_MEAN (else PCCM_E_STATE). */
+int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
+
 /* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
@@ -329,8 +349,12 @@ int pccm_profile_get(pccm_ctx *ctx, int kernel_class, double *ms_total, int64_t 
 /* Bookkeeping of the last pccm_nn() in `dir`: out[0] = queries sent to the exact fallback
  * rescan, out[1] = ref-axis splits of the brute-force scan / number of cells of the grid the
  * grid engine searched, out[2] = (query, ref) pairs evaluated by the brute-force scan (grid: 0).
- * `dir | PCCM_STATS_TAIL`: out[0] = queries the grid engine's ring-1 kernel left to the tail launch, out[1] = out[2] = 0. */
+ * `dir | PCCM_STATS_TAIL`: out[0] = queries the grid engine's ring-1 kernel left to the tail launch, out[1] = out[2] = 0.
+ * `dir | PCCM_STATS_TIES`: see below. */
 #define PCCM_STATS_TAIL 0x10
+/* `dir | PCCM_STATS_TIES` (search under PCCM_TIES_MEAN): out[0] = queries whose tie set the cell walk could not settle (a ball over
+ * more than 4096 cells, more than 16 ties, no tie met) and the exact scan of the whole searched cloud enumerated; out[1] = out[2] = 0. */
+#define PCCM_STATS_TIES 0x20
 int pccm_nn_stats(pccm_ctx *ctx, int dir, int64_t out[3]);
 
 #ifdef __cplusplus

@@ -23,6 +23,7 @@ F32, F64 = 0, 1
 DIR_LEFT, DIR_RIGHT, DIR_SELF = 0, 1, 2
 ENGINES = {"auto": 0, "brute": 1, "grid": 2}
 NORMAL_MODES = {"row": 0, "neighbour": 1}
+TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
@@ -31,7 +32,7 @@ KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
-    "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
+    "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
@@ -106,6 +107,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_error_vectors.argtypes = [vp, i32, vp]
     lib.pccm_point_metric.argtypes = [vp, i32, i32, i32, vp]
     lib.pccm_tie_exposure.argtypes = [vp, i32, i32, dp]
+    lib.pccm_set_ties.argtypes = [vp, i32]
+    lib.pccm_tie_counts.argtypes = [vp, i32, vp]
     lib.pccm_xvec_len.argtypes = [i64]
     lib.pccm_xvec_len.restype = i64
     lib.pccm_reduce.argtypes = [vp, i32, i32, i32, vp, vp]
@@ -521,6 +524,17 @@ class Engine:
         return {"queries": int(out[0]), "tied": int(out[1]), "sum_min": float(out[2]), "sum_max": float(out[3]), "sum_pick": float(out[4]),
                 "not_enumerated": int(out[5]), "max_multiplicity": int(out[6])}
 
+    def set_ties(self, policy: str) -> None:
+        """Neighbour policy for exact ties of the next searches (pccm_set_ties): "pick" (smallest row) or "mean"."""
+        _check(self._lib.pccm_set_ties(self._ctx, TIES[policy]))
+
+    def tie_counts(self, direction: int) -> np.ndarray:
+        """Size of the tie set of every shard row of ``direction`` (pccm_tie_counts; the search ran under "mean")."""
+        b, e = self.shard_range(direction)
+        out = np.empty(e - b, dtype=np.int32)
+        _check(self._lib.pccm_tie_counts(self._ctx, int(direction), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def reduce_prefetch(self, direction: int, metric: int, normal_mode: str = "row") -> None:
         """Enqueue a reduction without waiting; a later reduce() with the same arguments consumes it."""
         _check(self._lib.pccm_reduce_prefetch(self._ctx, int(direction), int(metric), NORMAL_MODES[normal_mode]))
@@ -621,3 +635,9 @@ class Engine:
         _check(self._lib.pccm_nn_stats(self._ctx, int(direction) | 0x10, out))      # PCCM_STATS_TAIL
         stats["tail_queries"] = int(out[0])
         return stats
+
+    def tie_scan_queries(self, direction: int) -> int:
+        """Queries of the last "mean" search of ``direction`` whose tie set the exact scan enumerated (PCCM_STATS_TIES)."""
+        out = (ctypes.c_int64 * 3)()
+        _check(self._lib.pccm_nn_stats(self._ctx, int(direction) | 0x20, out))
+        return int(out[0])

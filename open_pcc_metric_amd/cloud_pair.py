@@ -18,7 +18,10 @@ Differences from the reference, all deliberate:
 * ``normal_index="row"`` (default) reproduces the reference's D2, including its ``IndexError``
   when the iterating cloud is larger than the other one (quirk Q1); ``"neighbour"`` uses the
   matched point's normal;
-* exact ties go to the smallest row index (Open3D's order is traversal dependent);
+* exact ties go to the smallest row index (Open3D's order is traversal dependent); ``ties="mean"`` replaces the matched
+  point of both directional sweeps by the mean of ALL equidistant nearest points (position, colour and -- with
+  ``normal_index="neighbour"`` -- normal; include/pccm.h, PCCM_TIES_MEAN), so that D2 and the colour rows no longer
+  depend on the order of the points; D1, Hausdorff D1 and the matched rows are the same under either policy;
 * ``extent=`` injects ``get_extent()`` (the minimal-OBB is CPU code and not parity-pinned);
 * ``group=`` shards the pair over the ranks of a ``torch.distributed`` group: by direction first (half of the ranks
   search cloud_pair.py:67-72, the other half :73-78, so every rank builds one cloud's search structure), then by
@@ -244,15 +247,18 @@ class CloudPair:
                  nn_engine: str = "auto", normal_index: str = "row", extent=None, group=None,
                  use_graph: bool = False, estimate_normals: bool = True, normals_knn: int = 30,
                  shard_mode: str = "direction", _engine=None, _uploads_first: bool = False,
-                 staged_io: typing.Optional[bool] = None):
+                 staged_io: typing.Optional[bool] = None, ties: str = "pick"):
         if normal_index not in nat.NORMAL_MODES:
             raise ValueError("normal_index must be 'row' or 'neighbour'")
+        if not isinstance(ties, str) or ties not in nat.TIES:
+            raise ValueError("ties must be 'pick' or 'mean'")
         if nn_engine not in nat.ENGINES:
             raise ValueError(f"nn_engine must be one of {sorted(nat.ENGINES)}")
         self.clouds = (origin_cloud, reconst_cloud)
         self.normal_index = normal_index
         self.nn_engine = nn_engine
-        self._use_graph = bool(use_graph)
+        self.ties = ties
+        self._use_graph = bool(use_graph) and ties == "pick"        # (searches under "mean" are not captured: pccm_set_ties)
         self._estimate_normals, self._normals_knn = bool(estimate_normals), int(normals_knn)
         self._estimated = [False, False]
         self._xchg, self._xchg_wanted = {}, []
@@ -270,6 +276,10 @@ class CloudPair:
             self._owns_engine = True
             self._coll.device = device            # the nccl exchange is staged on the same GPU
         self._engine = _engine
+        if hasattr(_engine, "set_ties"):
+            _engine.set_ties(ties)                # (every time: a pooled context comes back with the default, pccm_ctx_reset)
+        elif ties != "pick":
+            raise ValueError("this engine has no tie policy other than 'pick'")
         # ``staged_io``: the clouds' arrays will be FREED while this context is still in use (a sequence of pairs read from files):
         # their bytes then go through the context's own pinned buffers instead of being handed to the HIP runtime, which pins
         # the caller's pages and keeps the mapping -- and whose tear-down, when such an array is freed, stops every GPU queue of
@@ -301,6 +311,7 @@ class CloudPair:
         self._update_fusion()
         if deferred and _uploads_first:
             _engine.flush_uploads()                       # (A/B for bench.py: everything uploaded before the first search starts)
+        self._colours_for_ties()
         self.recompute()
         if deferred:
             _engine.flush_uploads()                       # (the searches are running: the normals' upload runs beside them)
@@ -319,7 +330,7 @@ class CloudPair:
         if self._coll.sharded or not hasattr(eng, "nn_pair"):
             # (a sharded pair keeps nothing that pays: every rank would have to agree on what is resident)
             kw = dict(nn_engine=self.nn_engine, normal_index=self.normal_index, extent=self._extent, use_graph=self._use_graph,
-                      estimate_normals=self._estimate_normals, normals_knn=self._normals_knn)
+                      estimate_normals=self._estimate_normals, normals_knn=self._normals_knn, ties=self.ties)
             group, owns = self._coll.group, self._owns_engine
             self.__dict__.pop("_engine")
             if owns:
@@ -345,6 +356,7 @@ class CloudPair:
         if _has_normals(reconst_cloud):
             (eng.set_normals_deferred if deferred else eng.set_normals)(1, reconst_cloud.normals)
         new._update_fusion()
+        new._colours_for_ties()
         new.recompute()
         if deferred:
             eng.flush_uploads()
@@ -378,12 +390,20 @@ class CloudPair:
         eng = self._engine
         if not hasattr(eng, "nn_fuse"):
             return
+        # (under "mean" the fused projection would be the pick's: the virtual neighbours are formed from the matched rows instead)
+        mean = getattr(self, "ties", "pick") == "mean"
         for direction, other in ((nat.DIR_LEFT, 1), (nat.DIR_RIGHT, 0)):
-            eng.nn_fuse(direction, self.normal_index if self._normals_ready(other) else None)
+            eng.nn_fuse(direction, self.normal_index if self._normals_ready(other) and not mean else None)
         # the matched rows (cloud_pair.py:34-42) are only read by the colour metrics and the error-vector / neighbour
         # getters: clouds without colours leave them out of the result records (a getter that asks later still gets them)
         if hasattr(eng, "nn_want_idx"):
-            eng.nn_want_idx(any(_has_colors(c) for c in self.clouds))
+            eng.nn_want_idx(mean or any(_has_colors(c) for c in self.clouds))
+
+    def _colours_for_ties(self) -> None:
+        """Under ``ties="mean"`` the colours go up before the searches, so that the one averaging pass per direction (pccm_set_ties)
+        averages them together with the positions and normals instead of walking the tie sets once more for the colour rows."""
+        if self.ties == "mean" and all(_has_colors(c) for c in self.clouds) and hasattr(self._engine, "set_colors"):
+            self._ensure_colours()
 
     def recompute(self) -> None:
         """Run both directional sweeps again on the clouds already resident in HBM
@@ -538,6 +558,13 @@ class CloudPair:
             out.update(d2_mse_min=float(vec[2] / n), d2_mse_max=float(vec[3] / n), d2_mse_pick=float(vec[4] / n),
                        normal_index=self.normal_index)
         return out
+
+    def tie_counts(self, is_left: bool = True) -> np.ndarray:
+        """Under ``ties="mean"``: how many equidistant nearest neighbours every point of the iterating cloud has (1: no tie)."""
+        if self.ties != "mean":
+            raise ValueError("tie counts exist for ties='mean'")
+        direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
+        return self._gather(direction, self._engine.tie_counts(direction)).astype(np.int64)
 
     def _neighbour_index(self, direction: int) -> np.ndarray:
         if direction not in self._idx_cache:

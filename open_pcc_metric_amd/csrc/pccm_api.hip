@@ -309,6 +309,7 @@ static int upload(pccm_ctx *ctx, const void *src, size_t bytes, int on_device, c
 // upload + widening copy + validation of one cloud's normals on stream `st` (staging buffer `stage` for host sources)
 static int ingest_normals(pccm_ctx *ctx, Cloud &c, int which, const void *nrm, int64_t n, int dtype, int on_device, hipStream_t st, DevBuf &stage)
 {
+    ctx->nrm_gen++;                                      // (averaged normals of PCCM_TIES_MEAN are stale)
     const size_t esz = dtype == PCCM_F32 ? 4 : 8;
     const void *dsrc = nrm;
     if (!on_device) {
@@ -368,6 +369,7 @@ using namespace pccm;
 
 static void graph_free(GraphRec &g);
 static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx = true);
+static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb);
 
 #define NOT_CAPTURING(ctx)                                                                          \
     do {                                                                                           \
@@ -692,10 +694,12 @@ int pccm_set_colors_u8(pccm_ctx *ctx, int which, const unsigned char *rgb, int64
 
 // common front end of the two colour calls: operands of direction `dir` and the neighbour rows to use
 // (*drecs: matched records that carry the rows -- the kernel reads the row out of the record, no unpacked copy is made for it)
+// (*dmean: PCCM_TIES_MEAN -- the averaged neighbour colour of every row, read instead of the gather)
 static int color_operands(pccm_ctx *ctx, int dir, int scheme, const int32_t *rows, int64_t nrows,
-                          const Cloud **own, const Cloud **other, const int32_t **drows, const float4 **drecs)
+                          const Cloud **own, const Cloud **other, const int32_t **drows, const float4 **drecs, const double **dmean)
 {
     *drecs = nullptr;
+    *dmean = nullptr;
     if (dir != PCCM_DIR_LEFT && dir != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "colour metrics exist for directions 0 and 1");
     if (scheme < 0 || scheme > 2) return fail(PCCM_E_ARG, "unknown colour scheme %d", scheme);
     const Cloud &it = ctx->cloud[dir == PCCM_DIR_LEFT ? 0 : 1], &se = ctx->cloud[dir == PCCM_DIR_LEFT ? 1 : 0];
@@ -706,6 +710,17 @@ static int color_operands(pccm_ctx *ctx, int dir, int scheme, const int32_t *row
         if (rc) return rc;
         { int rch = h2d(ctx, ctx->color_idx.p, rows, (size_t)nrows * sizeof(int32_t), ctx->stream); if (rch) return rch; }
         *drows = (const int32_t *)ctx->color_idx.p;
+        const NNResult &res = ctx->nn[dir];
+        if ((res.valid ? res.ties : ctx->ties) == PCCM_TIES_MEAN) {
+            // the gathered rows of a sharded search: the tie sets of the whole iterating cloud, distances formed from the rows
+            pccm_ctx::TieCols &t = ctx->tie_rows;
+            const size_t n3 = (size_t)nrows * 3 * sizeof(double);
+            if ((rc = ensure(ctx, t.pos, n3)) || (rc = ensure(ctx, t.rgb, n3)) || (rc = ensure(ctx, t.k, (size_t)nrows * sizeof(int32_t)))) return rc;
+            if ((rc = tie_mean(ctx, dir, *drows, nullptr, 0, nrows, nullptr, se.rgb64, (double *)t.pos.p, (int32_t *)t.k.p, nullptr,
+                               (double *)t.rgb.p)))
+                return rc;
+            *dmean = (const double *)t.rgb.p;
+        }
     } else {
         NNResult &res = ctx->nn[dir];
         if (!res.valid) return fail(PCCM_E_STATE, "run pccm_nn for direction %d first", dir);
@@ -718,6 +733,11 @@ static int color_operands(pccm_ctx *ctx, int dir, int scheme, const int32_t *row
             int rc = ensure_plain(ctx, res);
             if (rc) return rc;
             *drows = res.idx;
+        }
+        if (res.ties == PCCM_TIES_MEAN) {
+            int rc = ensure_ties(ctx, dir, false, true);
+            if (rc) return rc;
+            *dmean = (const double *)ctx->tie[dir].rgb.p;
         }
     }
     *own = &it;
@@ -734,7 +754,8 @@ int pccm_color_reduce(pccm_ctx *ctx, int dir, int scheme, double scale, const in
     const Cloud *own[2], *other[2];
     const int32_t *drows[2];
     const float4 *drecs[2];
-    int rc = color_operands(ctx, dir, scheme, rows, nrows, &own[0], &other[0], &drows[0], &drecs[0]);
+    const double *dmean[2] = {nullptr, nullptr};
+    int rc = color_operands(ctx, dir, scheme, rows, nrows, &own[0], &other[0], &drows[0], &drecs[0], &dmean[0]);
     if (rc) return rc;
     pccm_ctx::ColorMemo &memo = ctx->color_memo;
     if (!rows && memo.valid && memo.dir == dir && memo.scheme == scheme && memo.scale == scale && memo.gen == ctx->nn_gen[dir] &&
@@ -750,7 +771,7 @@ int pccm_color_reduce(pccm_ctx *ctx, int dir, int scheme, double scale, const in
     int njobs = 1;
     const int sib = dir == PCCM_DIR_LEFT ? PCCM_DIR_RIGHT : PCCM_DIR_LEFT;
     if (!rows && ctx->nn[sib].valid && ctx->nn[sib].begin == 0 && ctx->nn[sib].end == ctx->cloud[sib == PCCM_DIR_LEFT ? 0 : 1].n &&
-        color_operands(ctx, sib, scheme, nullptr, 0, &own[1], &other[1], &drows[1], &drecs[1]) == PCCM_OK)
+        color_operands(ctx, sib, scheme, nullptr, 0, &own[1], &other[1], &drows[1], &drecs[1], &dmean[1]) == PCCM_OK)
         njobs = 2;
     const int64_t n[2] = {own[0]->n, njobs == 2 ? own[1]->n : 0};
     rc = ensure(ctx, ctx->color_cols, (size_t)(n[0] + n[1]) * 3 * sizeof(double));
@@ -763,7 +784,8 @@ int pccm_color_reduce(pccm_ctx *ctx, int dir, int scheme, double scale, const in
     for (int k = 0; k < njobs; ++k) {
         const bool bytes = own[k]->rgb8_valid && other[k]->rgb8_valid;
         rc = launch_color_rows(ctx, own[k]->rgb64, other[k]->rgb64, drows[k], n[k], other[k]->n, scheme, scale, 4, (double *)cols[k], nullptr,
-                               (unsigned int *)(small[k] + 6), bytes ? own[k]->rgb8 : nullptr, bytes ? other[k]->rgb8 : nullptr, drecs[k]);
+                               (unsigned int *)(small[k] + 6), bytes ? own[k]->rgb8 : nullptr, bytes ? other[k]->rgb8 : nullptr, drecs[k],
+                               dmean[k]);
         if (rc) return rc;
     }
     rc = launch_color_colsums(ctx, njobs, cols, n, sums, small);      // (+ the columns' maxima as bit keys into small[k][0..2])
@@ -891,7 +913,8 @@ int pccm_color_rows(pccm_ctx *ctx, int dir, int scheme, double scale, int what, 
     const Cloud *own, *other;
     const int32_t *drows;
     const float4 *drecs;
-    int rc = color_operands(ctx, dir, scheme, rows, nrows, &own, &other, &drows, &drecs);
+    const double *dmean;
+    int rc = color_operands(ctx, dir, scheme, rows, nrows, &own, &other, &drows, &drecs, &dmean);
     if (rc) return rc;
     const int64_t n = own->n;
     rc = ensure(ctx, ctx->color_cols, (size_t)n * 3 * sizeof(double));
@@ -900,7 +923,7 @@ int pccm_color_rows(pccm_ctx *ctx, int dir, int scheme, double scale, int what, 
     PCCM_HIP(hipMemsetAsync(small + 6, 0, sizeof(unsigned long long), ctx->stream));
     const bool bytes = own->rgb8_valid && other->rgb8_valid;
     rc = launch_color_rows(ctx, own->rgb64, other->rgb64, drows, n, other->n, scheme, scale, what, (double *)ctx->color_cols.p,
-                           small, (unsigned int *)(small + 6), bytes ? own->rgb8 : nullptr, bytes ? other->rgb8 : nullptr, drecs);
+                           small, (unsigned int *)(small + 6), bytes ? own->rgb8 : nullptr, bytes ? other->rgb8 : nullptr, drecs, dmean);
     if (rc) return rc;
     unsigned long long flag = 0;
     if ((rc = d2h(ctx, out, ctx->color_cols.p, (size_t)n * 3 * sizeof(double)))) return rc;
@@ -915,6 +938,7 @@ int pccm_estimate_normals(pccm_ctx *ctx, int which, int knn)
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
     if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    ctx->nrm_gen++;
     return estimate_normals(ctx, which, knn);
 }
 
@@ -1012,6 +1036,7 @@ static int prepare_nn(pccm_ctx *ctx, int dir, int *trivial)
     res.no_rows = false;
     res.plain_valid = res.plain_d2_valid = ns <= 0;          // an empty shard has nothing to unpack
     res.fused_mode = -1;
+    res.ties = dir == PCCM_DIR_SELF ? PCCM_TIES_PICK : ctx->ties;
     res.stats[0] = res.stats[1] = res.stats[2] = 0;
     *trivial = 0;
     if (dir == PCCM_DIR_SELF && it->n < 2) {
@@ -1119,6 +1144,77 @@ static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx)
     return PCCM_OK;
 }
 
+// PCCM_TIES_MEAN: the virtual neighbours of the shard's rows of direction `dir` (0 or 1), made once per search and kept;
+// want_nrm / want_rgb: the averaged normals (the caller has checked them: check_normals) / colours too
+static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb)
+{
+    pccm_ctx::TieCols &t = ctx->tie[dir];
+    NNResult &res = ctx->nn[dir];
+    const Cloud &se = ctx->cloud[dir == PCCM_DIR_LEFT ? 1 : 0];
+    // the colours the searched cloud has on the device ride along (one walk per direction and search, not one per consumer);
+    // what is wanted but missing is not averaged (the consumers report the missing normals / colours themselves)
+    const bool nrm_on = se.n_nrm == se.n && !se.nrm_deferred, rgb_on = se.n_rgb == se.n;
+    want_nrm = want_nrm && nrm_on;
+    want_rgb = want_rgb && rgb_on;
+    const bool fresh = t.gen == ctx->nn_gen[dir];
+    const bool have_nrm = fresh && t.nrm_gen == ctx->nrm_gen, have_rgb = fresh && t.rgb_gen == ctx->rgb_gen;
+    if (fresh && (!want_nrm || have_nrm) && (!want_rgb || have_rgb)) return PCCM_OK;
+    if (ctx->capturing) {
+        ctx->capture_failed = true;
+        return fail(PCCM_E_STATE, "PCCM_TIES_MEAN cannot be captured in a graph");
+    }
+    want_nrm = (want_nrm || have_nrm) && nrm_on;            // (averaged normals only where a neighbour-indexed projection asks)
+    want_rgb = rgb_on;
+    int rc = ensure_plain(ctx, res, true);
+    if (rc) return rc;
+    const int64_t ns = res.end - res.begin;
+    const size_t n3 = (size_t)(ns > 0 ? ns : 1) * 3 * sizeof(double);
+    if ((rc = ensure(ctx, t.pos, n3)) || (rc = ensure(ctx, t.k, (size_t)(ns + 1) * sizeof(int32_t)))) return rc;   // (+ the scan count)
+    if (want_nrm && (rc = ensure(ctx, t.nrm, n3))) return rc;
+    if (want_rgb && (rc = ensure(ctx, t.rgb, n3))) return rc;
+    t.gen = 0;
+    rc = tie_mean(ctx, dir, res.idx, res.d2, res.begin, ns, want_nrm ? se.nrm64 : nullptr, want_rgb ? se.rgb64 : nullptr, (double *)t.pos.p,
+                  (int32_t *)t.k.p, (double *)t.nrm.p, (double *)t.rgb.p);
+    if (rc) return rc;
+    // behind the k column: how many of these queries the pass left to the exact scan (pccm_nn_stats, PCCM_STATS_TIES)
+    if (ns > 0) PCCM_HIP(hipMemcpyAsync((int32_t *)t.k.p + ns, ctx->tie_list.p, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    else PCCM_HIP(hipMemsetAsync(t.k.p, 0, sizeof(int32_t), ctx->stream));
+    t.gen = ctx->nn_gen[dir];
+    t.nrm_gen = want_nrm ? ctx->nrm_gen : 0;
+    t.rgb_gen = want_rgb ? ctx->rgb_gen : 0;
+    return PCCM_OK;
+}
+
+int pccm_set_ties(pccm_ctx *ctx, int policy)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (policy != PCCM_TIES_PICK && policy != PCCM_TIES_MEAN) return fail(PCCM_E_ARG, "unknown tie policy %d", policy);
+    if (ctx->ties != policy) {
+        ctx->ties = policy;
+        ctx->epoch++;                                        // captured searches carry the old policy
+    }
+    return PCCM_OK;
+}
+
+int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (!k) return fail(PCCM_E_ARG, "null pointer");
+    if (dir != PCCM_DIR_LEFT && dir != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "ties are resolved for directions 0 and 1");
+    const Cloud *it, *se;
+    NNResult *res;
+    int rc = need_nn(ctx, dir, &it, &se, &res);
+    if (rc) return rc;
+    if (res->ties != PCCM_TIES_MEAN) return fail(PCCM_E_STATE, "the search of direction %d did not run under PCCM_TIES_MEAN", dir);
+    if ((rc = ensure_ties(ctx, dir, false, false))) return rc;
+    const int64_t ns = res->end - res->begin;
+    if (ns > 0 && (rc = d2h(ctx, k, ctx->tie[dir].k.p, (size_t)ns * sizeof(int32_t)))) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return check_device_errors(ctx);
+}
+
 int pccm_nn_want_idx(pccm_ctx *ctx, int on)
 {
     CHECK_CTX(ctx);
@@ -1192,7 +1288,10 @@ int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
     if (ns <= 0) return PCCM_OK;
     if ((rc = ensure_plain(ctx, *res))) return rc;
     if ((rc = ensure(ctx, ctx->val, (size_t)ns * 3 * sizeof(double)))) return rc;
-    if ((rc = launch_point_metric(ctx, *it, *se, *res, PCCM_METRIC_D1, PCCM_NORMAL_ROW, nullptr, (double *)ctx->val.p))) return rc;
+    const bool mean = res->ties == PCCM_TIES_MEAN;
+    if (mean && (rc = ensure_ties(ctx, dir, false, false))) return rc;
+    if ((rc = launch_point_metric(ctx, *it, *se, *res, PCCM_METRIC_D1, PCCM_NORMAL_ROW, nullptr, (double *)ctx->val.p,
+                                  mean ? (const double *)ctx->tie[dir].pos.p : nullptr))) return rc;
     { int rcd = d2h(ctx, out, ctx->val.p, (size_t)ns * 3 * sizeof(double)); if (rcd) return rcd; }
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     return PCCM_OK;
@@ -1220,7 +1319,11 @@ static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode,
     if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
     if ((rc = check_normals(ctx, *it, *se, *res, normal_mode))) return rc;
     if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
-    if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, normal_mode, (double *)vb.p, nullptr))) return rc;
+    const bool mean = res->ties == PCCM_TIES_MEAN, nmean = mean && normal_mode == PCCM_NORMAL_NEIGHBOUR;
+    if (mean && (rc = ensure_ties(ctx, dir, nmean, false))) return rc;
+    if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, normal_mode, (double *)vb.p, nullptr,
+                                  mean ? (const double *)ctx->tie[dir].pos.p : nullptr,
+                                  nmean ? (const double *)ctx->tie[dir].nrm.p : nullptr))) return rc;
     *dev = (const double *)vb.p;
     return PCCM_OK;
 }
@@ -1322,7 +1425,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
         if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
         if ((rc = check_normals(ctx, *it, *se, *res, normal_mode))) return rc;
-        if (res->rec_valid && !res->no_rows &&
+        if (res->rec_valid && !res->no_rows && res->ties != PCCM_TIES_MEAN &&      // (the records hold the pick's projection)
             (res->fused_mode == normal_mode || (res->rec_layout == 1 && (normal_mode == PCCM_NORMAL_ROW || normal_mode == PCCM_NORMAL_NEIGHBOUR)))) {
             dev = (const double *)res->rec.p + 1;
             stride = res->rec_stride;
@@ -1338,6 +1441,13 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
                 if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane columns per call");
                 PointJob &P = pj.j[pj.njobs];
                 P.q64 = it->xyz64; P.r64 = se->xyz64; P.nrm = se->nrm64; P.idx = res->idx;
+                P.c64 = P.cn64 = nullptr;
+                if (res->ties == PCCM_TIES_MEAN) {
+                    const bool nmean = normal_mode == PCCM_NORMAL_NEIGHBOUR;
+                    if ((rc = ensure_ties(ctx, dir, nmean, false))) return rc;
+                    P.c64 = (const double *)ctx->tie[dir].pos.p;
+                    if (nmean) P.cn64 = (const double *)ctx->tie[dir].nrm.p;
+                }
                 P.q_begin = res->begin; P.metric = metric; P.normal_mode = normal_mode; P.val = (double *)s.val.p;
                 pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;
                 pj.njobs++;
@@ -1466,7 +1576,9 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (metrics[k] == PCCM_METRIC_D1 || dirs[k] == PCCM_DIR_SELF) continue;
         NNResult &res = ctx->nn[dirs[k]];
-        if (!res.valid || !res.rec_valid || ((res.fused_mode == normal_modes[k] || res.rec_stride == 4 || res.rec_layout == 1) && !res.no_rows)) continue;
+        const bool mean = res.valid && res.ties == PCCM_TIES_MEAN;      // (the virtual neighbours need the plain columns)
+        if (!res.valid || (!res.rec_valid && !mean) ||
+            (!mean && (res.fused_mode == normal_modes[k] || res.rec_stride == 4 || res.rec_layout == 1) && !res.no_rows)) continue;
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
         int rc = ensure_plain(ctx, res, true);
         if (rc) return rc;
@@ -1843,6 +1955,7 @@ int pccm_graph_begin(pccm_ctx *ctx)
 {
     CHECK_CTX(ctx);
     if (ctx->capturing) return fail(PCCM_E_STATE, "already capturing");
+    if (ctx->ties != PCCM_TIES_PICK) return fail(PCCM_E_STATE, "searches under PCCM_TIES_MEAN run eagerly: no graph capture");
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     for (auto &s : ctx->slots) s.pending = false;      // nothing outside the graph may be half-consumed
     ctx->cap_ops.clear();
@@ -1946,6 +2059,7 @@ int pccm_ctx_reset(pccm_ctx *ctx)
     }
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     ctx->io_staged = false;                            // (the next owner of the context says what it wants)
+    ctx->ties = PCCM_TIES_PICK;
     for (int k = 0; k < 2; ++k) {
         drop_cloud(ctx->cloud[k]);
         ctx->cloud[k].version++;
@@ -2011,10 +2125,21 @@ int pccm_nn_stats(pccm_ctx *ctx, int dir, int64_t out[3])
     if (!out) return fail(PCCM_E_ARG, "null pointer");
     const Cloud *it, *se;
     NNResult *res;
-    const bool tail = (dir & PCCM_STATS_TAIL) != 0;
-    dir &= ~PCCM_STATS_TAIL;
+    const bool tail = (dir & PCCM_STATS_TAIL) != 0, ties = (dir & PCCM_STATS_TIES) != 0;
+    dir &= ~(PCCM_STATS_TAIL | PCCM_STATS_TIES);
     int rc = need_nn(ctx, dir, &it, &se, &res);
     if (rc) return rc;
+    if (ties) {
+        if (res->ties != PCCM_TIES_MEAN) return fail(PCCM_E_STATE, "the search of direction %d did not run under PCCM_TIES_MEAN", dir);
+        if ((rc = ensure_ties(ctx, dir, false, false))) return rc;
+        const int64_t ns = res->end - res->begin;
+        int32_t nl = 0;
+        PCCM_HIP(hipMemcpyAsync(&nl, (const int32_t *)ctx->tie[dir].k.p + (ns > 0 ? ns : 0), sizeof(nl), hipMemcpyDeviceToHost, ctx->stream));
+        PCCM_HIP(hipStreamSynchronize(ctx->stream));
+        out[0] = nl;
+        out[1] = out[2] = 0;
+        return PCCM_OK;
+    }
     if (tail) {
         uint32_t nt = 0;
         PCCM_HIP(hipMemcpyAsync(&nt, res->nflag_dev + 1, sizeof(nt), hipMemcpyDeviceToHost, ctx->stream));

@@ -57,7 +57,8 @@ __global__ __launch_bounds__(256) void k_color_rows(const double *__restrict__ o
                                                     const uint32_t *__restrict__ own8, const uint32_t *__restrict__ other8,
                                                     const int32_t *__restrict__ rows, const float4 *__restrict__ recs, int64_t n, int64_t n_other,
                                                     int scheme, double scale, int what, double *__restrict__ out,
-                                                    unsigned long long *__restrict__ maxkeys, unsigned int *__restrict__ bad)
+                                                    unsigned long long *__restrict__ maxkeys, unsigned int *__restrict__ bad,
+                                                    const double *__restrict__ other_q)
 {
     __shared__ unsigned long long s_max[4][3];
     __shared__ double s_lut[U8 ? 256 : 1];
@@ -75,11 +76,17 @@ __global__ __launch_bounds__(256) void k_color_rows(const double *__restrict__ o
             r = 0;
         }
         if (U8) {
-            const uint32_t pa = own8[i], pb = other8[r];
+            const uint32_t pa = own8[i];
             a[0] = s_lut[pa & 255u]; a[1] = s_lut[(pa >> 8) & 255u]; a[2] = s_lut[(pa >> 16) & 255u];
-            b[0] = s_lut[pb & 255u]; b[1] = s_lut[(pb >> 8) & 255u]; b[2] = s_lut[(pb >> 16) & 255u];
         } else {
             a[0] = own[3 * i]; a[1] = own[3 * i + 1]; a[2] = own[3 * i + 2];
+        }
+        if (other_q) {                      // PCCM_TIES_MEAN: the averaged colour of row i's tie set
+            b[0] = other_q[3 * i]; b[1] = other_q[3 * i + 1]; b[2] = other_q[3 * i + 2];
+        } else if (U8) {
+            const uint32_t pb = other8[r];
+            b[0] = s_lut[pb & 255u]; b[1] = s_lut[(pb >> 8) & 255u]; b[2] = s_lut[(pb >> 16) & 255u];
+        } else {
             b[0] = other[3 * r]; b[1] = other[3 * r + 1]; b[2] = other[3 * r + 2];
         }
         to_scheme(scheme, a, ta);
@@ -651,16 +658,17 @@ int launch_colors_from_u8(pccm_ctx *ctx, const unsigned char *src, int64_t n3, d
 
 int launch_color_rows(pccm_ctx *ctx, const double *own, const double *other, const int32_t *rows, int64_t n,
                       int64_t n_other, int scheme, double scale, int what, double *out,
-                      unsigned long long *maxkeys, unsigned int *bad, const uint32_t *own8, const uint32_t *other8, const float4 *recs)
+                      unsigned long long *maxkeys, unsigned int *bad, const uint32_t *own8, const uint32_t *other8, const float4 *recs,
+                      const double *other_q)
 {
     ProfScope ps(ctx, PCCM_K_POINT);
     const dim3 grid((unsigned)((n + 255) / 256));
     if (own8 && other8)
         hipLaunchKernelGGL(k_color_rows<true>, grid, dim3(256), 0, ctx->stream, own, other, own8, other8, rows, recs, n, n_other, scheme, scale, what, out,
-                           maxkeys, bad);
+                           maxkeys, bad, other_q);
     else
         hipLaunchKernelGGL(k_color_rows<false>, grid, dim3(256), 0, ctx->stream, own, other, own8, other8, rows, recs, n, n_other, scheme, scale, what, out,
-                           maxkeys, bad);
+                           maxkeys, bad, other_q);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

@@ -1701,6 +1701,183 @@ int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const
     return PCCM_OK;
 }
 
+// ---- PCCM_TIES_MEAN: the mean of all equidistant nearest neighbours ----------------------------------------------
+// Per query the complete tie set T_i = { j : d2(a_i, b_j) == d2_i } of the searched cloud, in ascending row order, and its mean:
+// c = (((b_j1 + b_j2) + b_j3) + ...) / k per component (include/pccm.h, PCCM_TIES_MEAN).  k_tie_mean walks the grid cells of the
+// query's ball as k_tie_exposure does and keeps the tie rows in a small sorted list; a query whose ball spans more than
+// kTieCells cells (an outlier far from the searched cloud), whose tie set overflows the list, or whose ball met no tie at all
+// goes to a compacted list that k_tie_mean_scan settles exactly by a scan of the whole searched cloud in row order.
+constexpr int kTieList = 16;
+constexpr int64_t kTieCells = 4096;
+
+struct TieMeanJob {
+    const void *srecs;          // cell-sorted records of the searched cloud
+    const uint32_t *cs;         // ... its cell starts
+    const double *q64, *s64;    // iterating / searched cloud, fp64 rows
+    const double *snrm, *srgb;  // searched cloud's normals / colours to average, or null
+    const int32_t *idx;         // matched rows of the queries
+    const double *d2;           // ... their squared distances, or null (formed from idx)
+    int64_t q_begin, ns, n_se;
+    double *pos, *nrm, *rgb;    // [ns][3] outputs (nrm / rgb when snrm / srgb)
+    int32_t *k;                 // [ns]
+    uint32_t *list;             // [0] queries for the scan, [1 ..] their indices
+};
+
+struct TieAcc {                 // sequential sums in ascending row order
+    double p[3] = {0, 0, 0}, n[3] = {0, 0, 0}, c[3] = {0, 0, 0};
+    int k = 0;
+    __device__ void add(const TieMeanJob &J, int64_t r)
+    {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double v = J.s64[3 * r + a];
+            p[a] = k ? __dadd_rn(p[a], v) : v;
+            if (J.snrm) { const double w = J.snrm[3 * r + a]; n[a] = k ? __dadd_rn(n[a], w) : w; }
+            if (J.srgb) { const double w = J.srgb[3 * r + a]; c[a] = k ? __dadd_rn(c[a], w) : w; }
+        }
+        ++k;
+    }
+    __device__ void store(const TieMeanJob &J, int64_t i) const
+    {
+        const double dk = (double)k;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            J.pos[3 * i + a] = __ddiv_rn(p[a], dk);
+            if (J.snrm) J.nrm[3 * i + a] = __ddiv_rn(n[a], dk);
+            if (J.srgb) J.rgb[3 * i + a] = __ddiv_rn(c[a], dk);
+        }
+        J.k[i] = k;
+    }
+};
+
+__device__ __forceinline__ double tie_d2(const TieMeanJob &J, int64_t i, double qx, double qy, double qz)
+{
+    if (J.d2) return J.d2[i];
+    const int64_t j = J.idx[i];
+    if (j < 0 || j >= J.n_se) return INFINITY;            // caller-supplied row out of range: no tie (the colour call reports it)
+    const double *r = J.s64 + 3 * j;
+    return gdist64(qx, qy, qz, r[0], r[1], r[2]);
+}
+
+template <typename REC>
+__global__ __launch_bounds__(256) void k_tie_mean(TieMeanJob J, GridGeom g)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= J.ns) return;
+    const int64_t row = J.q_begin + i;
+    const double qx = J.q64[3 * row], qy = J.q64[3 * row + 1], qz = J.q64[3 * row + 2];
+    const double d = tie_d2(J, i, qx, qy, qz);
+    const double rad = sqrt(d) * (1.0 + 0x1.0p-40) + fmax(g.slack[0], fmax(g.slack[1], g.slack[2]));
+    const int xa = cell_coord(qx - rad, g.org[0], g.inv_h[0], g.dim[0]), xb = cell_coord(qx + rad, g.org[0], g.inv_h[0], g.dim[0]);
+    const int ya = cell_coord(qy - rad, g.org[1], g.inv_h[1], g.dim[1]), yb = cell_coord(qy + rad, g.org[1], g.inv_h[1], g.dim[1]);
+    const int za = cell_coord(qz - rad, g.org[2], g.inv_h[2], g.dim[2]), zb = cell_coord(qz + rad, g.org[2], g.inv_h[2], g.dim[2]);
+    int rows[kTieList];
+    int m = 0;
+    bool over = (int64_t)(xb - xa + 1) * (yb - ya + 1) * (zb - za + 1) > kTieCells;
+    const REC *__restrict__ srecs = (const REC *)J.srecs;
+    for (int z = za; z <= zb && !over; ++z)
+        for (int y = ya; y <= yb && !over; ++y) {
+            const uint32_t rowc = ((uint32_t)z * g.dim[1] + y) * g.dim[0];
+            for (uint32_t p = J.cs[rowc + xa], e = J.cs[rowc + xb + 1]; p < e; ++p) {
+                const P3 a = load_rec(srecs, p);
+                if (gdist64(qx, qy, qz, a.x, a.y, a.z) != d) continue;
+                if (m == kTieList) {
+                    over = true;
+                    break;
+                }
+                int t = m++;                                   // insertion into the ascending list
+                while (t > 0 && rows[t - 1] > a.row) {
+                    rows[t] = rows[t - 1];
+                    --t;
+                }
+                rows[t] = a.row;
+            }
+        }
+    if (over || m == 0) {
+        const uint32_t slot = atomicAdd(&J.list[0], 1u);
+        J.list[1 + slot] = (uint32_t)i;
+        return;
+    }
+    TieAcc acc;
+    for (int t = 0; t < m; ++t) acc.add(J, rows[t]);
+    acc.store(J, i);
+}
+
+// The listed queries, one workgroup each (grid-stride over the list, whose length only the device knows): every row of the
+// searched cloud is tested in row order, 256 at a time; lane 0 adds the tile's ties in ascending row order.
+__global__ __launch_bounds__(256) void k_tie_mean_scan(TieMeanJob J)
+{
+    __shared__ unsigned long long s_mask[4];
+    const uint32_t cnt = J.list[0];
+    for (uint32_t e = blockIdx.x; e < cnt; e += gridDim.x) {
+        const int64_t i = J.list[1 + e];
+        const int64_t row = J.q_begin + i;
+        const double qx = J.q64[3 * row], qy = J.q64[3 * row + 1], qz = J.q64[3 * row + 2];
+        const double d = tie_d2(J, i, qx, qy, qz);
+        TieAcc acc;
+        for (int64_t base = 0; base < J.n_se; base += 256) {
+            const int64_t r = base + threadIdx.x;
+            const bool hit = r < J.n_se && gdist64(qx, qy, qz, J.s64[3 * r], J.s64[3 * r + 1], J.s64[3 * r + 2]) == d;
+            const unsigned long long mk = __ballot(hit);
+            if ((threadIdx.x & 63) == 0) s_mask[threadIdx.x >> 6] = mk;
+            __syncthreads();
+            if (threadIdx.x == 0)
+                for (int w = 0; w < 4; ++w)
+                    for (unsigned long long mm = s_mask[w]; mm; mm &= mm - 1)
+                        acc.add(J, base + 64 * w + (__ffsll((long long)mm) - 1));
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) acc.store(J, i);
+    }
+}
+
+int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64_t q_begin, int64_t ns, const double *snrm,
+             const double *srgb, double *pos, int32_t *k, double *nrm, double *rgb)
+{
+    if (dir != PCCM_DIR_LEFT && dir != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "ties are resolved for directions 0 and 1");
+    if (ns <= 0) return PCCM_OK;
+    const int si = (dir == PCCM_DIR_LEFT) ? 1 : 0;
+    const Cloud &it = ctx->cloud[1 - si], &se = ctx->cloud[si];
+    // the grid the search left behind serves the walk (lattice, boxed: the same cell-sorted records and cell starts) -- except the
+    // voxel-brick grid, whose 8-voxel cells hold so many points that the walk took 4x as long as over a plain grid (measured on the
+    // 0.8M surrogate: ~625 vs ~150 us per pass) while the plain rebuild, and the bricks' rebuild at the next search, cost far less
+    const Grid &g0 = ctx->grid;
+    const uint64_t key = ctx->cloud[0].version * 1000003ull + ctx->cloud[1].version + 1;
+    const bool reuse = g0.key == key && g0.recs.p && !g0.vox && g0.n[0] == ctx->cloud[0].n && g0.n[1] == ctx->cloud[1].n &&
+                       (g0.built & (1 << si));
+    int rc = reuse ? PCCM_OK : ensure_grid(ctx, false, 1 << si);
+    if (rc) return rc;
+    if ((rc = ensure(ctx, ctx->tie_list, (size_t)(ns + 1) * sizeof(uint32_t)))) return rc;
+    const Grid &gr = ctx->grid;
+    const GridGeom g = geom_of(gr);
+    TieMeanJob J;
+    J.srecs = (const char *)gr.recs.p + (size_t)(si ? gr.n[0] : 0) * (gr.rec32 ? sizeof(Rec32) : sizeof(GridRec));
+    J.cs = (const uint32_t *)gr.cell_start.p + (si ? gr.ncells + 1 : 0);
+    J.q64 = it.xyz64;
+    J.s64 = se.xyz64;
+    J.snrm = snrm;
+    J.srgb = srgb;
+    J.idx = idx;
+    J.d2 = d2;
+    J.q_begin = q_begin;
+    J.ns = ns;
+    J.n_se = se.n;
+    J.pos = pos;
+    J.nrm = nrm;
+    J.rgb = rgb;
+    J.k = k;
+    J.list = (uint32_t *)ctx->tie_list.p;
+    PCCM_HIP(hipMemsetAsync(J.list, 0, sizeof(uint32_t), ctx->stream));
+    ProfScope ps(ctx, PCCM_K_POINT);
+    dim3 grid((unsigned)((ns + 255) / 256));
+    if (gr.rec32) hipLaunchKernelGGL((k_tie_mean<Rec32>), grid, dim3(256), 0, ctx->stream, J, g);
+    else hipLaunchKernelGGL((k_tie_mean<GridRec>), grid, dim3(256), 0, ctx->stream, J, g);
+    PCCM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_tie_mean_scan, dim3(256), dim3(256), 0, ctx->stream, J);      // (an empty list: every workgroup exits)
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
 // A grid over ONE cloud with cells sized for that cloud (GridRec records: pccm_normals.hip): the pair's geometry follows its
 // larger cloud, and a decoded cloud of a fifteenth of the reference's points -- a low rate of BASELINE configs[4] -- had its
 // k = 30 neighbourhoods spread over six rings of such cells (43 ms of normal estimation for 59 000 points, round 4).

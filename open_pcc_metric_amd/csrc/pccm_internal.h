@@ -98,6 +98,7 @@ struct NNResult {
     int rec_layout = 0;         // 0: {d2, projection[, row, -]}; 1 (stride 2): the matched record {rx, ry, rz, row}: distance and
                                 //    row-indexed projection are formed by the reduction that reads the records (NNOut::layout)
     bool no_rows = false;       // layout 1 records whose row word is void (voxel-brick search): good for distances only
+    int ties = PCCM_TIES_PICK;  // pccm_set_ties policy the search ran under (consumers read the virtual neighbours under MEAN)
     int64_t stats[3] = {0, 0, 0};
     uint32_t *nflag_dev = nullptr;  // device counters of the last run: [0] fallback queries, [1] grid tail length
     DevBuf flagged, flag_thr;       // queries handed to the exact rescan (k2b_fallback) and their thresholds
@@ -229,6 +230,16 @@ struct pccm_ctx {
     int shard_rank[3] = {0, 0, 0}, shard_world[3] = {1, 1, 1};
     bool sharded() const { return shard_world[0] != 1 || shard_world[1] != 1 || shard_world[2] != 1; }
     pccm::NNResult nn[3];
+    // pccm_set_ties: PCCM_TIES_MEAN replaces the matched point of directions 0 and 1 by the mean of all equidistant nearest
+    // points (tie_mean, pccm_grid.hip): per shard row the virtual neighbour's position, tie count and -- when asked for --
+    // averaged normal and colour; valid for the search generation / colour upload / normals they were made from
+    int ties = PCCM_TIES_PICK;
+    struct TieCols {
+        pccm::DevBuf pos, nrm, rgb, k;
+        uint64_t gen = 0, rgb_gen = 0, nrm_gen = 0;   // 0: not made
+    } tie[2], tie_rows;                   // tie_rows: the whole iterating cloud, from caller-supplied rows (sharded colours)
+    pccm::DevBuf tie_list;                // queries left to the exact scan (k_tie_mean_scan): [0] count, then shard rows
+    uint64_t nrm_gen = 1;                 // bumped whenever any normals change
     // scratch
     pccm::DevBuf part_b1, part_g, part_b2, val, stats, staging, counters;
     pccm::DevBuf rescan_part;             // k2b_fallback's split regime: partial minima per (query, workgroup)
@@ -324,6 +335,10 @@ int grid_decide(pccm_ctx *ctx, bool *hostile);   // geometry decision for the cu
 int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; isolation verdict (cached per pair)
 int estimate_normals(pccm_ctx *ctx, int which, int k);
 int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int normal_mode, double out[8]);
+// PCCM_TIES_MEAN producer: for the ns queries q_begin.. of direction dir (matched rows idx, squared distances d2 or null = formed
+// from idx) the ascending-row mean of all equidistant nearest points -> pos[ns][3], k[ns]; nrm / rgb likewise when snrm / srgb
+int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64_t q_begin, int64_t ns, const double *snrm,
+             const double *srgb, double *pos, int32_t *k, double *nrm, double *rgb);
 int check_device_errors(pccm_ctx *ctx);
 int normals_ready(pccm_ctx *ctx, Cloud &c);       // uploads normals announced by pccm_set_normals_deferred (no-op otherwise)           // PCCM_E_STATE when a kernel raised the context's device error word
 // exact rescan of the flagged queries of njobs <= 2 results (k2b_fallback)
@@ -355,6 +370,7 @@ struct RescanJobs {
 
 struct PointJob {               // one D2 / PROJ column (k_point_jobs)
     const double *q64, *r64, *nrm;
+    const double *c64, *cn64;   // PCCM_TIES_MEAN: per shard row the virtual neighbour / its averaged normal (null: gather via idx)
     const int32_t *idx;
     int64_t q_begin;
     int metric, normal_mode;
@@ -408,7 +424,8 @@ int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, cons
 int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 
 int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,
-                        int normal_mode, double *out_val /*[ns]*/, double *out_err /*[ns][3] or null*/);
+                        int normal_mode, double *out_val /*[ns]*/, double *out_err /*[ns][3] or null*/,
+                        const double *c64 = nullptr, const double *cn64 = nullptr);   // PCCM_TIES_MEAN columns (PointJob)
 
 double np_pairwise_sum(const double *a, int64_t n);
 
@@ -423,7 +440,8 @@ int launch_rgb8(pccm_ctx *ctx, Cloud &c, const unsigned char *bytes, unsigned in
 int launch_color_rows(pccm_ctx *ctx, const double *own, const double *other, const int32_t *rows, int64_t n,
                       int64_t n_other, int scheme, double scale, int what, double *out,
                       unsigned long long *maxkeys, unsigned int *bad, const uint32_t *own8 = nullptr, const uint32_t *other8 = nullptr,
-                      const float4 *recs = nullptr);   // recs: matched records {x, y, z, row} instead of `rows`
+                      const float4 *recs = nullptr,    // recs: matched records {x, y, z, row} instead of `rows`
+                      const double *other_q = nullptr); // PCCM_TIES_MEAN: per row the averaged neighbour colour (no gather)
 int launch_color_colsum(pccm_ctx *ctx, const double *cols, int64_t n, double *out3);
 int launch_color_colsums(pccm_ctx *ctx, int njobs, const double *const cols[2], const int64_t n[2], double *const out3[2],
                          unsigned long long *const outmax[2]);   // outmax: [3] bit keys of the columns' maxima per job, or null

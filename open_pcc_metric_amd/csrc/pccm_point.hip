@@ -159,38 +159,40 @@ __global__ __launch_bounds__(256) void k_point_metric(const double *__restrict__
                                                       const double *__restrict__ r64,
                                                       const int32_t *__restrict__ idx,
                                                       const double *__restrict__ nrm, int metric, int normal_mode,
-                                                      double *__restrict__ val, double *__restrict__ err)
+                                                      double *__restrict__ val, double *__restrict__ err,
+                                                      const double *__restrict__ c64, const double *__restrict__ cn64)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= ns) return;
     const int64_t gi = q_begin + i;
     const int64_t j = idx[i];
-    const double ex = __dsub_rn(q64[3 * gi], r64[3 * j]);
-    const double ey = __dsub_rn(q64[3 * gi + 1], r64[3 * j + 1]);
-    const double ez = __dsub_rn(q64[3 * gi + 2], r64[3 * j + 2]);
+    const double *r = c64 ? c64 + 3 * i : r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
+    const double ex = __dsub_rn(q64[3 * gi], r[0]);
+    const double ey = __dsub_rn(q64[3 * gi + 1], r[1]);
+    const double ez = __dsub_rn(q64[3 * gi + 2], r[2]);
     if (err) {
         err[3 * i] = ex;
         err[3 * i + 1] = ey;
         err[3 * i + 2] = ez;
     }
     if (val) {
-        const int64_t k = (normal_mode == PCCM_NORMAL_ROW) ? gi : j;
-        double p = __dmul_rn(ex, nrm[3 * k]);
-        p = __fma_rn(ey, nrm[3 * k + 1], p);
-        p = __fma_rn(ez, nrm[3 * k + 2], p);
+        const double *nv = (normal_mode == PCCM_NORMAL_ROW) ? nrm + 3 * gi : cn64 ? cn64 + 3 * i : nrm + 3 * j;
+        double p = __dmul_rn(ex, nv[0]);
+        p = __fma_rn(ey, nv[1], p);
+        p = __fma_rn(ez, nv[2], p);
         val[i] = (metric == PCCM_METRIC_PROJ) ? p : __dmul_rn(p, p);
     }
 }
 
 int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,
-                        int normal_mode, double *out_val, double *out_err)
+                        int normal_mode, double *out_val, double *out_err, const double *c64, const double *cn64)
 {
     const int64_t ns = res.end - res.begin;
     if (ns <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_POINT);
     dim3 grid((unsigned)((ns + 255) / 256));
     hipLaunchKernelGGL(k_point_metric, grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, ns, se.xyz64, res.idx,
-                       se.nrm64, metric, normal_mode, out_val, out_err);
+                       se.nrm64, metric, normal_mode, out_val, out_err, c64, cn64);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -217,13 +219,14 @@ __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
     const int64_t i = i0 - jobs.off[jb];
     const int64_t gi = J.q_begin + i;
     const int64_t j = J.idx[i];
-    const double ex = __dsub_rn(J.q64[3 * gi], J.r64[3 * j]);
-    const double ey = __dsub_rn(J.q64[3 * gi + 1], J.r64[3 * j + 1]);
-    const double ez = __dsub_rn(J.q64[3 * gi + 2], J.r64[3 * j + 2]);
-    const int64_t k = (J.normal_mode == PCCM_NORMAL_ROW) ? gi : j;
-    double p = __dmul_rn(ex, J.nrm[3 * k]);
-    p = __fma_rn(ey, J.nrm[3 * k + 1], p);
-    p = __fma_rn(ez, J.nrm[3 * k + 2], p);
+    const double *r = J.c64 ? J.c64 + 3 * i : J.r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
+    const double ex = __dsub_rn(J.q64[3 * gi], r[0]);
+    const double ey = __dsub_rn(J.q64[3 * gi + 1], r[1]);
+    const double ez = __dsub_rn(J.q64[3 * gi + 2], r[2]);
+    const double *nv = (J.normal_mode == PCCM_NORMAL_ROW) ? J.nrm + 3 * gi : J.cn64 ? J.cn64 + 3 * i : J.nrm + 3 * j;
+    double p = __dmul_rn(ex, nv[0]);
+    p = __fma_rn(ey, nv[1], p);
+    p = __fma_rn(ez, nv[2], p);
     J.val[i] = (J.metric == PCCM_METRIC_PROJ) ? p : __dmul_rn(p, p);
 }
 

@@ -7,7 +7,9 @@ Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engi
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
 differ in size), ``--extent X Y Z`` (inject the PSNR peak box instead of the
 Qhull minimal-OBB restatement), ``--tie-exposure`` (diagnostic on stderr: how much of the point-to-plane result hangs
-on the order of exact ties, which nanoflann decides by traversal -- cloud_pair.py:22-23).  Files without normals get them estimated on the GPU when
+on the order of exact ties, which nanoflann decides by traversal -- cloud_pair.py:22-23), ``--ties pick|mean``
+(pick = the smallest row of several equidistant nearest neighbours; mean = their mean, which makes the point-to-plane and
+colour rows independent of the order of the points; D1 rows are the same either way).  Files without normals get them estimated on the GPU when
 --point-to-plane asks for them (k = 30 covariance normals, as Open3D's estimate_normals does at
 cloud_pair.py:61-64).  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
@@ -35,7 +37,10 @@ import click
 @click.option("--tie-exposure", is_flag=True,
               help="After the report, print to stderr how many points have several equidistant nearest neighbours and the "
                    "interval of point-to-plane MSE values the order of those ties can produce (diagnostic).")
-def cli(ocloud, pcloud, color, hausdorff, point_to_plane, csv, device, engine, normal_index, extent, tie_exposure) -> None:
+@click.option("--ties", type=click.Choice(["pick", "mean"]), default="pick", show_default=True,
+              help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
+                   "(point-to-plane and colour rows then do not depend on the order of the points).")
+def cli(ocloud, pcloud, color, hausdorff, point_to_plane, csv, device, engine, normal_index, extent, tie_exposure, ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
@@ -50,7 +55,7 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, csv, device, engine, n
             # (clouds read from files are freed while the GPU context works on -- with several decoded clouds, when the next one
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)
             cloud_pair = CloudPair(ocloud_cloud, pcloud_cloud, device=device, nn_engine=engine, normal_index=normal_index,
-                                   extent=list(extent) if extent else None, staged_io=True)
+                                   extent=list(extent) if extent else None, staged_io=True, ties=ties)
         else:
             cloud_pair = cloud_pair.with_reconst(pcloud_cloud)     # the original cloud stays in HBM with all that belongs to it
         calculator = MetricCalculator(cloud_pair)
