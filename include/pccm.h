@@ -357,6 +357,25 @@ int pccm_profile_get(pccm_ctx *ctx, int kernel_class, double *ms_total, int64_t 
 #define PCCM_STATS_TIES 0x20
 int pccm_nn_stats(pccm_ctx *ctx, int dir, int64_t out[3]);
 
+/* Which kernel variants served a call: the library picks them from the data (density, size ratio, fp32-exactness, integer
+ * coordinates, the normals' precision, the shard) and from a few environment switches, never from the caller.  `which`:
+ *   PCCM_DIR_LEFT / _RIGHT / _SELF  the last search of that direction (pccm_nn, pccm_nn_pair, or the repeat of a search that
+ *                                   left its rows out), with the tie means and tie exposure made from it later;
+ *   PCCM_PATH_REDUCE                the last batch of reductions (pccm_reduce_prefetch[_many] or a call that enqueued one).
+ * buf receives the kernels that call enqueued, in launch order without repeats, separated by ';', each named as `nm -C` names
+ * its host stub after "__device_stub__" -- "k_brick_query<false, 4, 2, 2176, false, 0, true>", "k_grid_tail<pccm::Rec32, false>",
+ * "k_unit_lean<2, 1, 3>" -- NUL-terminated and cut to cap - 1 bytes; *len (may be NULL) = the full length.  Noted when the
+ * kernels are enqueued (host bookkeeping only: no GPU work, no wait), so a captured call is described by its capture; graph
+ * replays do not change it.  A launch the device decides to leave idle (a tail with no queries) is still listed.  A log holds
+ * 64 distinct kernels; a call that enqueued more ends its list with the entry "..." (the path is incomplete). */
+#define PCCM_PATH_REDUCE 3
+int pccm_nn_path(pccm_ctx *ctx, int which, char *buf, int64_t cap, int64_t *len);
+
+/* The uniform grid the last grid-engine search ran on: cell (i, j, k) spans org + (i, j, k) * h .. org + (i + 1, j + 1, k + 1) * h
+ * per axis, dim cells per axis (voxel-brick searches: cells of 8 voxels).  Lets a caller place points exactly on cell faces.
+ * PCCM_E_STATE before the first grid search. */
+int pccm_grid_geometry(pccm_ctx *ctx, double org[3], double h[3], int32_t dim[3]);
+
 #ifdef __cplusplus
 }
 #endif

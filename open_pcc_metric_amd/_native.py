@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("PCCM_LIB") or os.path.join(_HERE, "csrc", "libpccm.so
 OK, E_ARG, E_NODEV, E_HIP, E_OOM, E_STATE, E_RANGE = 0, -1, -2, -3, -4, -5, -6
 F32, F64 = 0, 1
 DIR_LEFT, DIR_RIGHT, DIR_SELF = 0, 1, 2
+PATH_REDUCE = 3          # Engine.last_path: the last reduction batch
 ENGINES = {"auto": 0, "brute": 1, "grid": 2}
 NORMAL_MODES = {"row": 0, "neighbour": 1}
 TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
@@ -38,7 +39,7 @@ SYMBOLS = (
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
     "pccm_color_transform", "pccm_lzf_decompress", "pccm_drop_caches", "pccm_graph_begin", "pccm_graph_end", "pccm_graph_launch", "pccm_graph_destroy",
     "pccm_sync",
-    "pccm_profile_enable", "pccm_profile_reset", "pccm_profile_get", "pccm_nn_stats",
+    "pccm_profile_enable", "pccm_profile_reset", "pccm_profile_get", "pccm_nn_stats", "pccm_nn_path", "pccm_grid_geometry",
 )
 
 COLOR_SCHEMES = {"rgb": 0, "ycc": 1, "yuv": 2}
@@ -142,6 +143,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_profile_reset.argtypes = [vp]
     lib.pccm_profile_get.argtypes = [vp, i32, dp, ctypes.POINTER(i64)]
     lib.pccm_nn_stats.argtypes = [vp, i32, ctypes.POINTER(i64)]
+    lib.pccm_nn_path.argtypes = [vp, i32, ctypes.c_char_p, i64, ctypes.POINTER(i64)]
+    lib.pccm_grid_geometry.argtypes = [vp, dp, dp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("pccm_last_error", "pccm_xvec_len", "pccm_cvec_len"):
@@ -635,6 +638,23 @@ class Engine:
         _check(self._lib.pccm_nn_stats(self._ctx, int(direction) | 0x10, out))      # PCCM_STATS_TAIL
         stats["tail_queries"] = int(out[0])
         return stats
+
+    def last_path(self, which: int) -> list:
+        """Kernels the last search of direction ``which`` (0, 1, 2) or the last reduction batch (``PATH_REDUCE``) enqueued, in
+        launch order, named as ``nm -C`` names their host stubs: ["k_grid_query_coop<false>", "k_grid_tail<pccm::Rec32, false>"]."""
+        n = ctypes.c_int64(0)
+        _check(self._lib.pccm_nn_path(self._ctx, int(which), None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(n.value + 1)
+        _check(self._lib.pccm_nn_path(self._ctx, int(which), buf, n.value + 1, ctypes.byref(n)))
+        text = buf.value.decode()
+        return text.split(";") if text else []
+
+    def grid_geometry(self):
+        """(org, h, dim) of the uniform grid the last grid-engine search ran on (pccm_grid_geometry)."""
+        org, h = (ctypes.c_double * 3)(), (ctypes.c_double * 3)()
+        dim = np.empty(3, dtype=np.int32)
+        _check(self._lib.pccm_grid_geometry(self._ctx, org, h, dim.ctypes.data_as(ctypes.c_void_p)))
+        return np.array(org[:]), np.array(h[:]), dim
 
     def tie_scan_queries(self, direction: int) -> int:
         """Queries of the last "mean" search of ``direction`` whose tie set the exact scan enumerated (PCCM_STATS_TIES)."""

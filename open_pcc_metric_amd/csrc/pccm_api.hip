@@ -1,5 +1,7 @@
 // C ABI of libpccm.so (include/pccm.h): context, ingest, nn dispatch, getters, reductions,
 // profiling.  Host-side only; kernels live in pccm_brute.hip / pccm_grid.hip / pccm_point.hip.
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -1062,6 +1064,9 @@ static int pick_engine(int engine)
 
 static int run_nn(pccm_ctx *ctx, int ndirs, const int *dirs, int engine)
 {
+    unsigned mask = 0;
+    for (int k = 0; k < ndirs; ++k) mask |= 1u << dirs[k];
+    PathScope path(ctx, mask);
     const bool automatic = engine == PCCM_ENGINE_AUTO && !getenv("PCCM_ENGINE");
     engine = pick_engine(engine);
     if (automatic && ctx->cloud[0].n > 0 && ctx->cloud[1].n > 0) {
@@ -1130,6 +1135,7 @@ static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx)
             return fail(PCCM_E_STATE, "matched rows are needed during graph capture: switch pccm_nn_want_idx on before the search");
         }
         const int dir = (int)(&res - ctx->nn);
+        PathScope path(ctx, 1u << dir);
         int rc = nn_grid(ctx, 1, &dir, /*force_idx=*/1);
         if (rc) return rc;
     }
@@ -1173,6 +1179,7 @@ static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb)
     if (want_nrm && (rc = ensure(ctx, t.nrm, n3))) return rc;
     if (want_rgb && (rc = ensure(ctx, t.rgb, n3))) return rc;
     t.gen = 0;
+    PathScope path(ctx, 1u << dir, /*keep=*/true);
     rc = tie_mean(ctx, dir, res.idx, res.d2, res.begin, ns, want_nrm ? se.nrm64 : nullptr, want_rgb ? se.rgb64 : nullptr, (double *)t.pos.p,
                   (int32_t *)t.k.p, (double *)t.nrm.p, (double *)t.rgb.p);
     if (rc) return rc;
@@ -1340,6 +1347,7 @@ int pccm_tie_exposure(pccm_ctx *ctx, int dir, int normal_mode, double out[8])
     if (rc) return rc;
     if (normal_mode >= 0 && (rc = check_normals(ctx, *it, *se, *res, normal_mode))) return rc;
     if ((rc = ensure_plain(ctx, *res, true))) return rc;
+    PathScope path(ctx, 1u << dir, /*keep=*/true);
     return tie_exposure(ctx, dir, *it, *se, *res, normal_mode, out);
 }
 
@@ -1583,6 +1591,8 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         int rc = ensure_plain(ctx, res, true);
         if (rc) return rc;
     }
+    const int path_kept = ctx->path_n[3];
+    PathScope path(ctx, 1u << 3);          // the batch's kernels: per-point columns (slot_prepare), point and unit jobs
     for (int k = 0; k < n; ++k) {
         if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
@@ -1595,7 +1605,10 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         s->pending = true;                 // so that slot_free/slot_find see it while the batch is assembled
         fresh[nfresh++] = s;
     }
-    if (nfresh == 0) return PCCM_OK;
+    if (nfresh == 0) {
+        ctx->path_n[3] = path_kept;        // no batch: the log still describes the last one
+        return PCCM_OK;
+    }
     int rc;
     if ((rc = launch_point_jobs(ctx, pj))) return rc;
     uint64_t seq = 0;
@@ -2115,6 +2128,59 @@ int pccm_profile_get(pccm_ctx *ctx, int kernel_class, double *ms_total, int64_t 
     if (rc) return rc;
     *ms_total = ctx->prof_ms[kernel_class];
     *launches = ctx->prof_n[kernel_class];
+    return PCCM_OK;
+}
+
+// "k_brick_query<false, 4, 2, 2176, false, 0, true>" for a kernel handle: its symbol demangled, without the return type, the
+// namespace and the parameter list -- how `nm -C` names the kernel's host stub after "__device_stub__"
+static std::string kernel_name(const void *k)
+{
+    Dl_info info;
+    if (!dladdr(k, &info) || !info.dli_sname || info.dli_saddr != k) return "?";
+    int st = 0;
+    char *dm = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st);
+    std::string s = st == 0 && dm ? dm : info.dli_sname;
+    free(dm);
+    if (s.compare(0, 5, "void ") == 0) s.erase(0, 5);
+    if (s.compare(0, 6, "pccm::") == 0) s.erase(0, 6);
+    int depth = 0;
+    for (size_t i = 0; i < s.size(); ++i) {
+        if (s[i] == '<') ++depth;
+        else if (s[i] == '>') --depth;
+        else if (s[i] == '(' && depth == 0) return s.substr(0, i);
+    }
+    return s;
+}
+
+int pccm_nn_path(pccm_ctx *ctx, int which, char *buf, int64_t cap, int64_t *len)
+{
+    CHECK_CTX(ctx);
+    if (which < 0 || which > PCCM_PATH_REDUCE || (cap > 0 && !buf) || cap < 0) return fail(PCCM_E_ARG, "bad argument");
+    std::string s;
+    for (int i = 0; i < ctx->path_n[which]; ++i) {
+        if (i) s += ';';
+        s += kernel_name(ctx->path[which][i]);
+    }
+    if (ctx->path_over[which]) s += ";...";
+    if (len) *len = (int64_t)s.size();
+    if (cap > 0) {
+        const size_t n = s.size() < (size_t)cap - 1 ? s.size() : (size_t)cap - 1;
+        memcpy(buf, s.data(), n);
+        buf[n] = 0;
+    }
+    return PCCM_OK;
+}
+
+int pccm_grid_geometry(pccm_ctx *ctx, double org[3], double h[3], int32_t dim[3])
+{
+    CHECK_CTX(ctx);
+    if (!org || !h || !dim) return fail(PCCM_E_ARG, "null pointer");
+    if (ctx->grid.ncells <= 0) return fail(PCCM_E_STATE, "no grid search has run");
+    for (int a = 0; a < 3; ++a) {
+        org[a] = ctx->grid.org[a];
+        h[a] = ctx->grid.h[a];
+        dim[a] = ctx->grid.dim[a];
+    }
     return PCCM_OK;
 }
 

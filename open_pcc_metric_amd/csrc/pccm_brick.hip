@@ -589,7 +589,7 @@ static void launch_plane(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g
         if (dev) {
             (void)hipMemsetAsync(dev, 0, slots * 8 * sizeof(unsigned long long), ctx->stream);
             bp.stamps = dev;
-            hipLaunchKernelGGL((k_brick_query<false, BY, BZ, PL, true>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+            PCCM_LAUNCH(ctx, (k_brick_query<false, BY, BZ, PL, true>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
             std::vector<unsigned long long> h(slots * 8);
             (void)hipMemcpyAsync(h.data(), dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
             (void)hipStreamSynchronize(ctx->stream);
@@ -614,27 +614,27 @@ static void launch_plane(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g
     }
     static const int ablate = [] { const char *e = getenv("PCCM_BRICK_ABLATE"); return e ? atoi(e) : 0; }();
     if (ablate && !self && BY == 4 && BZ == 2) {        // timing-only builds: results are wrong by construction
-        if (ablate == 1) hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 1>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-        else if (ablate == 2) hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 2>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-        else if (ablate == 4) hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 4>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-        else if (ablate == 8) hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 8>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-        else if (ablate == 16) hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 16>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-        else if (ablate == 32) hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 32>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-        else hipLaunchKernelGGL((k_brick_query<false, 4, 2, PL, false, 15>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        if (ablate == 1) PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 1>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        else if (ablate == 2) PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 2>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        else if (ablate == 4) PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 4>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        else if (ablate == 8) PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 8>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        else if (ablate == 16) PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 16>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        else if (ablate == 32) PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 32>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        else PCCM_LAUNCH(ctx, (k_brick_query<false, 4, 2, PL, false, 15>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
         return;
     }
 #endif
     static const bool v_free = [] { const char *e = PCCM_DIAG_ENV("PCCM_BRICK_V64"); return e && e[0] == '0'; }();
     if (v_free && !self) {     // A/B: no register cap
-        hipLaunchKernelGGL((k_brick_query_free<BY, BZ, PL>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+        PCCM_LAUNCH(ctx, (k_brick_query_free<BY, BZ, PL>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
         return;
     }
     // fp32-exact normals (file normals) or none fused: the kernel that carries the 16-byte word; fp64 rows (estimated normals) else
     bool n32 = true;
     for (int k = 0; k < jobs.njobs; ++k) n32 = n32 && (jobs.j[k].out.nrm == nullptr || jobs.j[k].out.nrm32 != nullptr);
-    if (self) hipLaunchKernelGGL((k_brick_query<true, BY, BZ, PL>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);     // (no normals in a self search)
-    else if (n32) hipLaunchKernelGGL((k_brick_query<false, BY, BZ, PL, false, 0, true>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
-    else hipLaunchKernelGGL((k_brick_query<false, BY, BZ, PL, false, 0, false>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+    if (self) PCCM_LAUNCH(ctx, (k_brick_query<true, BY, BZ, PL>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);     // (no normals in a self search)
+    else if (n32) PCCM_LAUNCH(ctx, (k_brick_query<false, BY, BZ, PL, false, 0, true>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
+    else PCCM_LAUNCH(ctx, (k_brick_query<false, BY, BZ, PL, false, 0, false>), grid, dim3(nt), lds, ctx->stream, jobs, g, bp);
 }
 
 template <int BY, int BZ>

@@ -242,13 +242,13 @@ static int scan_qt()
 }
 
 template <int QT>
-static void launch_k1(bool self, dim3 grid, hipStream_t st, const float *q32, int64_t qb, int64_t nq,
+static void launch_k1(pccm_ctx *ctx, bool self, dim3 grid, hipStream_t st, const float *q32, int64_t qb, int64_t nq,
                       const float4 *r32, int64_t ntiles, int tps, float *pb1, int32_t *pg, float *pb2)
 {
     if (self)
-        hipLaunchKernelGGL((k1_scan<QT, true>), grid, dim3(kScanThreads), 0, st, q32, qb, nq, r32, ntiles, tps, pb1, pg, pb2);
+        PCCM_LAUNCH(ctx, (k1_scan<QT, true>), grid, dim3(kScanThreads), 0, st, q32, qb, nq, r32, ntiles, tps, pb1, pg, pb2);
     else
-        hipLaunchKernelGGL((k1_scan<QT, false>), grid, dim3(kScanThreads), 0, st, q32, qb, nq, r32, ntiles, tps, pb1, pg, pb2);
+        PCCM_LAUNCH(ctx, (k1_scan<QT, false>), grid, dim3(kScanThreads), 0, st, q32, qb, nq, r32, ntiles, tps, pb1, pg, pb2);
 }
 
 // Exact rescan of the flagged queries of up to two results (counts on the device in res.nflag_dev[0]).
@@ -303,8 +303,8 @@ int launch_fallback(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Clo
     if (njobs == 1) jobs.j[1] = jobs.j[0];
     // enough workgroups to split a cloud finely; never more than there are queries to hand out one each
     dim3 grid((unsigned)(nqmax < cap ? nqmax : cap), (unsigned)njobs);
-    if (self) hipLaunchKernelGGL((k2b_fallback<true>), grid, dim3(256), 0, ctx->stream, jobs);
-    else hipLaunchKernelGGL((k2b_fallback<false>), grid, dim3(256), 0, ctx->stream, jobs);
+    if (self) PCCM_LAUNCH(ctx, (k2b_fallback<true>), grid, dim3(256), 0, ctx->stream, jobs);
+    else PCCM_LAUNCH(ctx, (k2b_fallback<false>), grid, dim3(256), 0, ctx->stream, jobs);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -339,8 +339,8 @@ int nn_brute(pccm_ctx *ctx, const Cloud &it, const Cloud &se, bool self, NNResul
     {
         ProfScope ps(ctx, PCCM_K_SCAN);
         dim3 grid((unsigned)qblocks, (unsigned)splits);
-        if (qt == 4) launch_k1<4>(self, grid, ctx->stream, (const float *)it.xyz32, res.begin, nq, se.xyz32, ntiles, tps, pb1, pg, pb2);
-        else launch_k1<8>(self, grid, ctx->stream, (const float *)it.xyz32, res.begin, nq, se.xyz32, ntiles, tps, pb1, pg, pb2);
+        if (qt == 4) launch_k1<4>(ctx, self, grid, ctx->stream, (const float *)it.xyz32, res.begin, nq, se.xyz32, ntiles, tps, pb1, pg, pb2);
+        else launch_k1<8>(ctx, self, grid, ctx->stream, (const float *)it.xyz32, res.begin, nq, se.xyz32, ntiles, tps, pb1, pg, pb2);
     }
     PCCM_HIP(hipGetLastError());
 
@@ -353,11 +353,11 @@ int nn_brute(pccm_ctx *ctx, const Cloud &it, const Cloud &se, bool self, NNResul
         const int64_t waves = (nq + 63) / 64;
         dim3 grid((unsigned)((waves + 3) / 4));
         if (self)
-            hipLaunchKernelGGL((k2_refine<true>), grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, nq, se.xyz64, se.n,
+            PCCM_LAUNCH(ctx, (k2_refine<true>), grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, nq, se.xyz64, se.n,
                                pb1, pg, pb2, (int)splits, slack, res.idx, res.d2, (int32_t *)res.flagged.p,
                                (float *)res.flag_thr.p, res.nflag_dev);
         else
-            hipLaunchKernelGGL((k2_refine<false>), grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, nq, se.xyz64, se.n,
+            PCCM_LAUNCH(ctx, (k2_refine<false>), grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, nq, se.xyz64, se.n,
                                pb1, pg, pb2, (int)splits, slack, res.idx, res.d2, (int32_t *)res.flagged.p,
                                (float *)res.flag_thr.p, res.nflag_dev);
     }

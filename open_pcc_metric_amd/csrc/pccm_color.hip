@@ -651,7 +651,7 @@ __global__ __launch_bounds__(256) void k_colors_from_u8(const unsigned char *__r
 int launch_colors_from_u8(pccm_ctx *ctx, const unsigned char *src, int64_t n3, double *out)
 {
     ProfScope ps(ctx, PCCM_K_INGEST);
-    hipLaunchKernelGGL(k_colors_from_u8, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, ctx->stream, src, n3, out);
+    PCCM_LAUNCH(ctx, k_colors_from_u8, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, ctx->stream, src, n3, out);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -664,10 +664,10 @@ int launch_color_rows(pccm_ctx *ctx, const double *own, const double *other, con
     ProfScope ps(ctx, PCCM_K_POINT);
     const dim3 grid((unsigned)((n + 255) / 256));
     if (own8 && other8)
-        hipLaunchKernelGGL(k_color_rows<true>, grid, dim3(256), 0, ctx->stream, own, other, own8, other8, rows, recs, n, n_other, scheme, scale, what, out,
+        PCCM_LAUNCH(ctx, k_color_rows<true>, grid, dim3(256), 0, ctx->stream, own, other, own8, other8, rows, recs, n, n_other, scheme, scale, what, out,
                            maxkeys, bad, other_q);
     else
-        hipLaunchKernelGGL(k_color_rows<false>, grid, dim3(256), 0, ctx->stream, own, other, own8, other8, rows, recs, n, n_other, scheme, scale, what, out,
+        PCCM_LAUNCH(ctx, k_color_rows<false>, grid, dim3(256), 0, ctx->stream, own, other, own8, other8, rows, recs, n, n_other, scheme, scale, what, out,
                            maxkeys, bad, other_q);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(256) void k_rgb8_pack(const unsigned char *__restri
 int launch_rgb8(pccm_ctx *ctx, Cloud &c, const unsigned char *bytes, unsigned int *flag)
 {
     ProfScope ps(ctx, PCCM_K_INGEST);
-    hipLaunchKernelGGL(k_rgb8_pack, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, bytes, (const double *)c.rgb64, c.n, c.rgb8, flag);
+    PCCM_LAUNCH(ctx, k_rgb8_pack, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, bytes, (const double *)c.rgb64, c.n, c.rgb8, flag);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -763,9 +763,9 @@ int launch_color_colsums(pccm_ctx *ctx, int njobs, const double *const cols[2], 
         ctx->colsum_configured = true;
     }
     dim3 grid((unsigned)most, 3 * njobs);
-    hipLaunchKernelGGL(k_colsum_approx, grid, dim3(kSumThreads), 0, ctx->stream, jobs);
-    hipLaunchKernelGGL(k_colsum_units, grid, dim3(kSumThreads), 0, ctx->stream, jobs);
-    hipLaunchKernelGGL(k_colsum_chain, dim3(3 * njobs), dim3(kSumThreads), dyn, ctx->stream, jobs);
+    PCCM_LAUNCH(ctx, k_colsum_approx, grid, dim3(kSumThreads), 0, ctx->stream, jobs);
+    PCCM_LAUNCH(ctx, k_colsum_units, grid, dim3(kSumThreads), 0, ctx->stream, jobs);
+    PCCM_LAUNCH(ctx, k_colsum_chain, dim3(3 * njobs), dim3(kSumThreads), dyn, ctx->stream, jobs);
     PCCM_HIP(hipGetLastError());
 #ifdef PCCM_DIAG
     if (getenv("PCCM_COLSUM_STAMP")) {

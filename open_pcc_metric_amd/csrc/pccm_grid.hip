@@ -754,8 +754,8 @@ static int measure_occupancy(pccm_ctx *ctx, const Cloud &c, double scale, Occupa
     unsigned long long *counter = (unsigned long long *)ctx->stats.p;
     PCCM_HIP(hipMemsetAsync(hist, 0, (size_t)(ncells + 1) * sizeof(uint32_t), ctx->stream));
     PCCM_HIP(hipMemsetAsync(counter, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_cell_hist, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, g, hist);
-    hipLaunchKernelGGL(k_count_occupied, dim3(1024), dim3(256), 0, ctx->stream, (const uint32_t *)hist, ncells, counter);
+    PCCM_LAUNCH(ctx, k_cell_hist, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, g, hist);
+    PCCM_LAUNCH(ctx, k_count_occupied, dim3(1024), dim3(256), 0, ctx->stream, (const uint32_t *)hist, ncells, counter);
     unsigned long long h[2] = {0, 0};
     PCCM_HIP(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
@@ -828,7 +828,7 @@ static int trim_box(pccm_ctx *ctx, bool &changed)
         for (int k = 0; k < 2; ++k) {
             const Cloud &c = ctx->cloud[k];
             if (c.n <= 0) continue;
-            hipLaunchKernelGGL(k_axis_hist, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, lo[0], lo[1],
+            PCCM_LAUNCH(ctx, k_axis_hist, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, lo[0], lo[1],
                                lo[2], iw[0], iw[1], iw[2], dh);
         }
         PCCM_HIP(hipMemcpyAsync(h.data(), dh, 3 * kTrimBins * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1190,10 +1190,10 @@ static int check_isolation(pccm_ctx *ctx)
         if (nq <= 0 || gr.n[1 - ii] <= 0) continue;
         dim3 grid((unsigned)((nq + 255) / 256));
         if (gr.rec32)
-            hipLaunchKernelGGL((k_count_isolated<Rec32>), grid, dim3(256), 0, ctx->stream,
+            PCCM_LAUNCH(ctx, (k_count_isolated<Rec32>), grid, dim3(256), 0, ctx->stream,
                                (const Rec32 *)gr.recs.p + (ii ? gr.n[0] : 0), nq, cs + (ii ? 0 : gr.ncells + 1), g, counter + ii);
         else
-            hipLaunchKernelGGL((k_count_isolated<GridRec>), grid, dim3(256), 0, ctx->stream,
+            PCCM_LAUNCH(ctx, (k_count_isolated<GridRec>), grid, dim3(256), 0, ctx->stream,
                                (const GridRec *)gr.recs.p + (ii ? gr.n[0] : 0), nq, cs + (ii ? 0 : gr.ncells + 1), g, counter + ii);
     }
     unsigned long long h[2] = {0, 0};
@@ -1245,8 +1245,8 @@ static int fused_mode(const pccm_ctx *ctx, int dir, const Cloud &it, const Cloud
 template <typename REC>
 static void launch_queries(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g, bool self, dim3 grid)
 {
-    if (self) hipLaunchKernelGGL((k_grid_query<REC, true>), grid, dim3(256), 0, ctx->stream, jobs, g);
-    else hipLaunchKernelGGL((k_grid_query<REC, false>), grid, dim3(256), 0, ctx->stream, jobs, g);
+    if (self) PCCM_LAUNCH(ctx, (k_grid_query<REC, true>), grid, dim3(256), 0, ctx->stream, jobs, g);
+    else PCCM_LAUNCH(ctx, (k_grid_query<REC, false>), grid, dim3(256), 0, ctx->stream, jobs, g);
 }
 
 // the one tail launch behind a ring-1 kernel: rings 2..3 for its tail lists, then the exact rescan of what is left (k_grid_tail)
@@ -1283,11 +1283,11 @@ static int launch_tail(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g, 
     ts.nap = 2;
     dim3 grid(ts.n_tail + ts.n_rescan * (uint32_t)jobs.njobs);
     if (rec32) {
-        if (self) hipLaunchKernelGGL((k_grid_tail<Rec32, true>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
-        else hipLaunchKernelGGL((k_grid_tail<Rec32, false>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
+        if (self) PCCM_LAUNCH(ctx, (k_grid_tail<Rec32, true>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
+        else PCCM_LAUNCH(ctx, (k_grid_tail<Rec32, false>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
     } else {
-        if (self) hipLaunchKernelGGL((k_grid_tail<GridRec, true>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
-        else hipLaunchKernelGGL((k_grid_tail<GridRec, false>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
+        if (self) PCCM_LAUNCH(ctx, (k_grid_tail<GridRec, true>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
+        else PCCM_LAUNCH(ctx, (k_grid_tail<GridRec, false>), grid, dim3(256), 0, ctx->stream, jobs, g, rj, ts);
     }
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
@@ -1517,8 +1517,8 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
                 if ((rc = launch_brick_query(ctx, jobs, g, self))) return rc;
             } else {
                 dim3 grid((unsigned)((chunks + 3) / 4));
-                if (self) hipLaunchKernelGGL((k_grid_query_coop<true>), grid, dim3(256), 0, ctx->stream, jobs, g);
-                else hipLaunchKernelGGL((k_grid_query_coop<false>), grid, dim3(256), 0, ctx->stream, jobs, g);
+                if (self) PCCM_LAUNCH(ctx, (k_grid_query_coop<true>), grid, dim3(256), 0, ctx->stream, jobs, g);
+                else PCCM_LAUNCH(ctx, (k_grid_query_coop<false>), grid, dim3(256), 0, ctx->stream, jobs, g);
             }
         } else {
             dim3 grid((unsigned)qblocks);
@@ -1679,8 +1679,8 @@ int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const
     J.normal_mode = normal_mode >= 0 ? normal_mode : PCCM_NORMAL_ROW;
     J.self = dir == PCCM_DIR_SELF;
     dim3 grid((unsigned)((ns + 255) / 256));
-    if (gr.rec32) hipLaunchKernelGGL((k_tie_exposure<Rec32>), grid, dim3(256), 0, ctx->stream, J, g, sums, counts);
-    else hipLaunchKernelGGL((k_tie_exposure<GridRec>), grid, dim3(256), 0, ctx->stream, J, g, sums, counts);
+    if (gr.rec32) PCCM_LAUNCH(ctx, (k_tie_exposure<Rec32>), grid, dim3(256), 0, ctx->stream, J, g, sums, counts);
+    else PCCM_LAUNCH(ctx, (k_tie_exposure<GridRec>), grid, dim3(256), 0, ctx->stream, J, g, sums, counts);
     PCCM_HIP(hipGetLastError());
     std::vector<double> hv(8 + 3 * nblk);
     double *h = hv.data();
@@ -1870,10 +1870,10 @@ int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64
     PCCM_HIP(hipMemsetAsync(J.list, 0, sizeof(uint32_t), ctx->stream));
     ProfScope ps(ctx, PCCM_K_POINT);
     dim3 grid((unsigned)((ns + 255) / 256));
-    if (gr.rec32) hipLaunchKernelGGL((k_tie_mean<Rec32>), grid, dim3(256), 0, ctx->stream, J, g);
-    else hipLaunchKernelGGL((k_tie_mean<GridRec>), grid, dim3(256), 0, ctx->stream, J, g);
+    if (gr.rec32) PCCM_LAUNCH(ctx, (k_tie_mean<Rec32>), grid, dim3(256), 0, ctx->stream, J, g);
+    else PCCM_LAUNCH(ctx, (k_tie_mean<GridRec>), grid, dim3(256), 0, ctx->stream, J, g);
     PCCM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_tie_mean_scan, dim3(256), dim3(256), 0, ctx->stream, J);      // (an empty list: every workgroup exits)
+    PCCM_LAUNCH(ctx, k_tie_mean_scan, dim3(256), dim3(256), 0, ctx->stream, J);      // (an empty list: every workgroup exits)
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

@@ -603,25 +603,25 @@ int sort_by_cell(pccm_ctx *ctx, const BuildJobs &jobs, const GridGeom &g, int64_
     const size_t lds_bins = (size_t)P.nbin * sizeof(uint32_t), lds_cells = ((size_t)1 << P.lg) * sizeof(uint32_t);
     if (P.ntiles > 0 && cur) {
         dim3 tg((unsigned)P.ntiles);
-        if (rec32) hipLaunchKernelGGL((k_bin_count<true, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
-        else hipLaunchKernelGGL((k_bin_count<false, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
-        if (rec32) hipLaunchKernelGGL((k_bin_scatter<Rec32, true, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (Rec32 *)ctx->g_tmp.p);
-        else hipLaunchKernelGGL((k_bin_scatter<GridRec, false, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (GridRec *)ctx->g_tmp.p);
+        if (rec32) PCCM_LAUNCH(ctx, (k_bin_count<true, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
+        else PCCM_LAUNCH(ctx, (k_bin_count<false, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
+        if (rec32) PCCM_LAUNCH(ctx, (k_bin_scatter<Rec32, true, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (Rec32 *)ctx->g_tmp.p);
+        else PCCM_LAUNCH(ctx, (k_bin_scatter<GridRec, false, true>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (GridRec *)ctx->g_tmp.p);
     } else if (P.ntiles > 0) {
         dim3 tg((unsigned)P.ntiles);
-        if (rec32) hipLaunchKernelGGL((k_bin_count<true, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
-        else hipLaunchKernelGGL((k_bin_count<false, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
-        hipLaunchKernelGGL(k_scan_lookback, dim3((unsigned)st), dim3(256), 0, ctx->stream, hist, P.hlen + 1, state, st);
-        if (rec32) hipLaunchKernelGGL((k_bin_scatter<Rec32, true, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (Rec32 *)ctx->g_tmp.p);
-        else hipLaunchKernelGGL((k_bin_scatter<GridRec, false, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (GridRec *)ctx->g_tmp.p);
+        if (rec32) PCCM_LAUNCH(ctx, (k_bin_count<true, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
+        else PCCM_LAUNCH(ctx, (k_bin_count<false, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, hist);
+        PCCM_LAUNCH(ctx, k_scan_lookback, dim3((unsigned)st), dim3(256), 0, ctx->stream, hist, P.hlen + 1, state, st);
+        if (rec32) PCCM_LAUNCH(ctx, (k_bin_scatter<Rec32, true, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (Rec32 *)ctx->g_tmp.p);
+        else PCCM_LAUNCH(ctx, (k_bin_scatter<GridRec, false, false>), tg, dim3(bin_threads), lds_bins, ctx->stream, P, g, (const uint32_t *)hist, (GridRec *)ctx->g_tmp.p);
     } else if (cur) {
         PCCM_HIP(hipMemsetAsync(P.bstart, 0, (size_t)(ncur + 1) * sizeof(uint32_t), ctx->stream));
     } else {
         PCCM_HIP(hipMemsetAsync(hist, 0, hist_bytes, ctx->stream));
     }
     dim3 bg((unsigned)(P.nbin * P.njobs));
-    if (rec32) hipLaunchKernelGGL((k_bin_sort<Rec32>), bg, dim3(256), lds_cells, ctx->stream, P, g, (const uint32_t *)hist, (const Rec32 *)ctx->g_tmp.p, (Rec32 *)recs);
-    else hipLaunchKernelGGL((k_bin_sort<GridRec>), bg, dim3(256), lds_cells, ctx->stream, P, g, (const uint32_t *)hist, (const GridRec *)ctx->g_tmp.p, (GridRec *)recs);
+    if (rec32) PCCM_LAUNCH(ctx, (k_bin_sort<Rec32>), bg, dim3(256), lds_cells, ctx->stream, P, g, (const uint32_t *)hist, (const Rec32 *)ctx->g_tmp.p, (Rec32 *)recs);
+    else PCCM_LAUNCH(ctx, (k_bin_sort<GridRec>), bg, dim3(256), lds_cells, ctx->stream, P, g, (const uint32_t *)hist, (const GridRec *)ctx->g_tmp.p, (GridRec *)recs);
     PCCM_HIP(hipGetLastError());
     ctx->bins_clean = true;                                // k_bin_sort has been queued: it leaves the cursors at zero
     return PCCM_OK;

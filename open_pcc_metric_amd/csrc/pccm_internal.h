@@ -291,6 +291,13 @@ struct pccm_ctx {
     std::vector<hipEvent_t> event_pool;
     double prof_ms[PCCM_K_COUNT] = {0};
     int64_t prof_n[PCCM_K_COUNT] = {0};
+    // path log (pccm_nn_path): the kernels the last search of each direction ([0..2]) and the last reduction batch ([3]) enqueued,
+    // as host kernel handles in launch order without repeats; noted by PCCM_LAUNCH into the logs of path_mask
+    static constexpr int kPathMax = 64;
+    const void *path[4][kPathMax] = {};
+    int path_n[4] = {0, 0, 0, 0};
+    bool path_over[4] = {false, false, false, false};   // a kernel did not fit: pccm_nn_path reports the list as incomplete
+    unsigned path_mask = 0;
 };
 
 namespace pccm {
@@ -307,6 +314,43 @@ int fail(int code, const char *fmt, ...);
 
 int ensure(pccm_ctx *ctx, DevBuf &b, size_t bytes);
 int grow(void **p, size_t &cap, size_t bytes);      // (re)allocate *p to hold `bytes`; keeps a buffer that is large enough
+
+// path log: note a kernel handle in every log of ctx->path_mask (host bookkeeping only: no GPU work, no synchronisation)
+inline void note_kernel(pccm_ctx *ctx, const void *k)
+{
+    for (int l = 0; l < 4; ++l) {
+        if (!(ctx->path_mask & (1u << l))) continue;
+        int i = 0;
+        while (i < ctx->path_n[l] && ctx->path[l][i] != k) ++i;
+        if (i < ctx->path_n[l]) continue;
+        if (i < pccm_ctx::kPathMax) ctx->path[l][ctx->path_n[l]++] = k;
+        else ctx->path_over[l] = true;
+    }
+}
+
+// hipLaunchKernelGGL that also notes the kernel in the path log
+#define PCCM_LAUNCH(ctx, kernel, ...)                                                   \
+    do {                                                                                \
+        ::pccm::note_kernel((ctx), reinterpret_cast<const void *>(&(kernel)));          \
+        hipLaunchKernelGGL(kernel, __VA_ARGS__);                                        \
+    } while (0)
+
+// while alive, launches are noted in the logs of `mask` (bit d: search of direction d, bit 3: reduction batch), which start
+// empty unless `keep` (work a search leaves for later -- tie means, tie exposure -- joins that search's log)
+struct PathScope {
+    pccm_ctx *ctx;
+    unsigned saved;
+    PathScope(pccm_ctx *c, unsigned mask, bool keep = false) : ctx(c), saved(c->path_mask)
+    {
+        for (int l = 0; l < 4; ++l)
+            if ((mask & (1u << l)) && !keep) {
+                ctx->path_n[l] = 0;
+                ctx->path_over[l] = false;
+            }
+        ctx->path_mask = mask;
+    }
+    ~PathScope() { ctx->path_mask = saved; }
+};
 
 struct ProfScope {   // records a HIP-event pair around a launch group when profiling is on
     pccm_ctx *ctx;

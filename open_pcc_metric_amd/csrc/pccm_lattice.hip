@@ -182,8 +182,8 @@ int launch_lattice_query(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g
     int64_t nqmax = 0;
     for (int k = 0; k < jobs.njobs; ++k) nqmax = jobs.j[k].nq > nqmax ? jobs.j[k].nq : nqmax;
     dim3 grid((unsigned)((nqmax + 255) / 256));
-    if (self) hipLaunchKernelGGL((k_lattice_query<true>), grid, dim3(256), 0, ctx->stream, jobs, g);
-    else hipLaunchKernelGGL((k_lattice_query<false>), grid, dim3(256), 0, ctx->stream, jobs, g);
+    if (self) PCCM_LAUNCH(ctx, (k_lattice_query<true>), grid, dim3(256), 0, ctx->stream, jobs, g);
+    else PCCM_LAUNCH(ctx, (k_lattice_query<false>), grid, dim3(256), 0, ctx->stream, jobs, g);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

@@ -454,14 +454,14 @@ int estimate_normals(pccm_ctx *ctx, int which, int k)
     const GridRec *crecs = (const GridRec *)gr.recs.p + (which ? gr.n[0] : 0);
     const int64_t qbase = 0;
     const int64_t wblocks = (c.n + 3) / 4;
-    hipLaunchKernelGGL(k_knn_cov_wave, dim3((unsigned)(wblocks < 16384 ? wblocks : 16384)), dim3(256), 0, ctx->stream,
+    PCCM_LAUNCH(ctx, k_knn_cov_wave, dim3((unsigned)(wblocks < 16384 ? wblocks : 16384)), dim3(256), 0, ctx->stream,
                        crecs, qbase, c.n, g, cs, k, cov, cnt, (uint32_t *)ctx->g_rank.p, todo_count);
-    hipLaunchKernelGGL(k_normals_from_cov, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)cov,
+    PCCM_LAUNCH(ctx, k_normals_from_cov, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)cov,
                        (const int32_t *)cnt, c.n, c.nrm64);
-    hipLaunchKernelGGL(k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, qbase, g, cs,
+    PCCM_LAUNCH(ctx, k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, qbase, g, cs,
                        (const double *)c.xyz64, k, c.nrm64, (const uint32_t *)ctx->g_rank.p, (const uint32_t *)todo_count,
                        (int32_t *)ctx->g_cell_of.p, open_count);
-    hipLaunchKernelGGL(k_knn_normals_full, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, k,
+    PCCM_LAUNCH(ctx, k_knn_normals_full, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, k,
                        (const int32_t *)ctx->g_cell_of.p, (const uint32_t *)open_count, c.nrm64);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_obb_frames(const double *__restrict__ v
 int launch_obb_frames(pccm_ctx *ctx, const double *verts, int64_t nv, const double *tri, int64_t nt, double *ext_out, double *vol_out)
 {
     ProfScope ps(ctx, PCCM_K_POINT);
-    hipLaunchKernelGGL(k_obb_frames, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, verts, nv, tri, nt, ext_out, vol_out);
+    PCCM_LAUNCH(ctx, k_obb_frames, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, verts, nv, tri, nt, ext_out, vol_out);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -155,7 +155,7 @@ int launch_extreme_rows(pccm_ctx *ctx, const double *x64, int64_t n, const float
 {
     ProfScope ps(ctx, PCCM_K_POINT);
     const int64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_extreme_rows, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, ctx->stream, x64, n, dirs, ndirs, best);
+    PCCM_LAUNCH(ctx, k_extreme_rows, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, ctx->stream, x64, n, dirs, ndirs, best);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -164,7 +164,7 @@ int launch_outside_planes(pccm_ctx *ctx, const double *x64, int64_t n, const dou
                           int32_t *rows_out, unsigned int *count)
 {
     ProfScope ps(ctx, PCCM_K_POINT);
-    hipLaunchKernelGGL(k_outside_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x64, n, planes, nplanes, margin,
+    PCCM_LAUNCH(ctx, k_outside_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x64, n, planes, nplanes, margin,
                        rows_out, count);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;

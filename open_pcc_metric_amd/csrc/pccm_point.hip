@@ -128,9 +128,9 @@ int launch_ingest_points(pccm_ctx *ctx, const void *src, int dtype, int64_t n, i
     const int64_t blocks = (n_pad + 255) / 256;
     dim3 grid((unsigned)(blocks < 256 ? blocks : 256));
     if (dtype == PCCM_F32)
-        hipLaunchKernelGGL((k_ingest_points<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n, n_pad, (float *)x32, x64, x32r, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_points<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n, n_pad, (float *)x32, x64, x32r, stats);
     else
-        hipLaunchKernelGGL((k_ingest_points<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n, n_pad, (float *)x32, x64, x32r, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_points<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n, n_pad, (float *)x32, x64, x32r, stats);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -141,9 +141,9 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
     const int64_t n3 = 3 * n;
     dim3 grid((unsigned)((n3 + 255) / 256));
     if (dtype == PCCM_F32)
-        hipLaunchKernelGGL((k_ingest_normals<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n3, out, out32, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_normals<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n3, out, out32, stats);
     else
-        hipLaunchKernelGGL((k_ingest_normals<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n3, out, out32, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_normals<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n3, out, out32, stats);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -191,7 +191,7 @@ int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const N
     if (ns <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_POINT);
     dim3 grid((unsigned)((ns + 255) / 256));
-    hipLaunchKernelGGL(k_point_metric, grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, ns, se.xyz64, res.idx,
+    PCCM_LAUNCH(ctx, k_point_metric, grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, ns, se.xyz64, res.idx,
                        se.nrm64, metric, normal_mode, out_val, out_err, c64, cn64);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
@@ -235,7 +235,7 @@ int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs)
     const int64_t total = jobs.off[jobs.njobs];
     if (total <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_POINT);
-    hipLaunchKernelGGL(k_point_jobs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, jobs);
+    PCCM_LAUNCH(ctx, k_point_jobs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, jobs);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -652,25 +652,25 @@ static void launch_unit_shape(pccm_ctx *ctx, const UnitJobs &jobs, int shape)
     const int64_t total = jobs.uoff[jobs.njobs] + jobs.toff[jobs.njobs];
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     switch (shape) {
-    case 1 * 4 + 1: hipLaunchKernelGGL((k_unit_lean<1, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 2 * 4 + 0: hipLaunchKernelGGL((k_unit_lean<2, 0>), grid, block, 0, ctx->stream, jobs); break;
-    case 2 * 4 + 1: hipLaunchKernelGGL((k_unit_lean<2, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 2 * 4 + 2: hipLaunchKernelGGL((k_unit_lean<2, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 4 * 4 + 0: hipLaunchKernelGGL((k_unit_lean<4, 0>), grid, block, 0, ctx->stream, jobs); break;
-    case 4 * 4 + 1: hipLaunchKernelGGL((k_unit_lean<4, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 4 * 4 + 2: hipLaunchKernelGGL((k_unit_lean<4, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 64 + 2 * 4 + 0: hipLaunchKernelGGL((k_unit_lean<2, 0, 1>), grid, block, 0, ctx->stream, jobs); break;      // matched records, fp32-exact normals
-    case 64 + 2 * 4 + 1: hipLaunchKernelGGL((k_unit_lean<2, 1, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 64 + 2 * 4 + 2: hipLaunchKernelGGL((k_unit_lean<2, 2, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 128 + 2 * 4 + 0: hipLaunchKernelGGL((k_unit_lean<2, 0, 2>), grid, block, 0, ctx->stream, jobs); break;     // ... fp64 normals
-    case 128 + 2 * 4 + 1: hipLaunchKernelGGL((k_unit_lean<2, 1, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 128 + 2 * 4 + 2: hipLaunchKernelGGL((k_unit_lean<2, 2, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 192 + 2 * 4 + 1: hipLaunchKernelGGL((k_unit_lean<2, 1, 3>), grid, block, 0, ctx->stream, jobs); break;     // ... no normals: distances only
-    case 256 + 2 * 4 + 0: hipLaunchKernelGGL((k_unit_lean<2, 0, 4>), grid, block, 0, ctx->stream, jobs); break;     // ... the matched row's normal, fp32-exact
-    case 256 + 2 * 4 + 2: hipLaunchKernelGGL((k_unit_lean<2, 2, 4>), grid, block, 0, ctx->stream, jobs); break;
-    case 320 + 2 * 4 + 0: hipLaunchKernelGGL((k_unit_lean<2, 0, 5>), grid, block, 0, ctx->stream, jobs); break;     // ... fp64
-    case 320 + 2 * 4 + 2: hipLaunchKernelGGL((k_unit_lean<2, 2, 5>), grid, block, 0, ctx->stream, jobs); break;
-    default: hipLaunchKernelGGL(k_unit_jobs, grid, block, 0, ctx->stream, jobs); break;      // signed projections (min / max of -0.0 and 0.0: fmin / fmax there), other shapes
+    case 1 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<1, 1>), grid, block, 0, ctx->stream, jobs); break;
+    case 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0>), grid, block, 0, ctx->stream, jobs); break;
+    case 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1>), grid, block, 0, ctx->stream, jobs); break;
+    case 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2>), grid, block, 0, ctx->stream, jobs); break;
+    case 4 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<4, 0>), grid, block, 0, ctx->stream, jobs); break;
+    case 4 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<4, 1>), grid, block, 0, ctx->stream, jobs); break;
+    case 4 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<4, 2>), grid, block, 0, ctx->stream, jobs); break;
+    case 64 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 1>), grid, block, 0, ctx->stream, jobs); break;      // matched records, fp32-exact normals
+    case 64 + 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1, 1>), grid, block, 0, ctx->stream, jobs); break;
+    case 64 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 1>), grid, block, 0, ctx->stream, jobs); break;
+    case 128 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 2>), grid, block, 0, ctx->stream, jobs); break;     // ... fp64 normals
+    case 128 + 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1, 2>), grid, block, 0, ctx->stream, jobs); break;
+    case 128 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 2>), grid, block, 0, ctx->stream, jobs); break;
+    case 192 + 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1, 3>), grid, block, 0, ctx->stream, jobs); break;     // ... no normals: distances only
+    case 256 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 4>), grid, block, 0, ctx->stream, jobs); break;     // ... the matched row's normal, fp32-exact
+    case 256 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 4>), grid, block, 0, ctx->stream, jobs); break;
+    case 320 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 5>), grid, block, 0, ctx->stream, jobs); break;     // ... fp64
+    case 320 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 5>), grid, block, 0, ctx->stream, jobs); break;
+    default: PCCM_LAUNCH(ctx, k_unit_jobs, grid, block, 0, ctx->stream, jobs); break;      // signed projections (min / max of -0.0 and 0.0: fmin / fmax there), other shapes
     }
 }
 
@@ -728,7 +728,7 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
     // the batch's completion, published behind its last launch.  The count the counter will reach is taken before the launch
     // is issued, so that a launch that fails can only make a waiter fall back to the event, never wake it early.
     *seq = ctx->capturing ? ++ctx->cap_batches : ++ctx->batches_issued;
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, ctx->stream, (unsigned long long *)ctx->done);
+    PCCM_LAUNCH(ctx, k_publish, dim3(1), dim3(64), 0, ctx->stream, (unsigned long long *)ctx->done);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -755,7 +755,7 @@ __global__ __launch_bounds__(256) void k_unpack(const double *__restrict__ rec, 
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2)
 {
     if (ns <= 0) return PCCM_OK;
-    hipLaunchKernelGGL(k_unpack, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, rec, stride, layout, q32, row0, ns, idx, d2);
+    PCCM_LAUNCH(ctx, k_unpack, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, rec, stride, layout, q32, row0, ns, idx, d2);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

@@ -473,8 +473,8 @@ __global__ __launch_bounds__(64) void k_vox_query(QueryJobs jobs, GridGeom g)
 int launch_vox_bricks(pccm_ctx *ctx, const VoxBuild &vb, const GridGeom &g)
 {
     dim3 grid((unsigned)((vb.ncells + kVoxTile - 1) / kVoxTile), (unsigned)vb.njobs);
-    hipLaunchKernelGGL(k_vox_bricks, grid, dim3(256), 0, ctx->stream, vb, g);
-    hipLaunchKernelGGL(k_vox_list, dim3(kVoxListWGs, (unsigned)vb.njobs), dim3(1024), 0, ctx->stream, vb);
+    PCCM_LAUNCH(ctx, k_vox_bricks, grid, dim3(256), 0, ctx->stream, vb, g);
+    PCCM_LAUNCH(ctx, k_vox_list, dim3(kVoxListWGs, (unsigned)vb.njobs), dim3(1024), 0, ctx->stream, vb);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -484,9 +484,9 @@ int launch_vox_query(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g, bo
     // one wave per occupied cell and turn, 32 waves per CU resident: a fixed grid walks the list (its length lives on the device)
     dim3 grid(8192u, (unsigned)jobs.njobs);
     if (self && rows) return fail(PCCM_E_STATE, "the self search with matched rows does not run on voxel bricks");
-    if (self) hipLaunchKernelGGL((k_vox_query<true, false>), grid, dim3(64), 0, ctx->stream, jobs, g);
-    else if (rows) hipLaunchKernelGGL((k_vox_query<false, true>), grid, dim3(64), 0, ctx->stream, jobs, g);
-    else hipLaunchKernelGGL((k_vox_query<false, false>), grid, dim3(64), 0, ctx->stream, jobs, g);
+    if (self) PCCM_LAUNCH(ctx, (k_vox_query<true, false>), grid, dim3(64), 0, ctx->stream, jobs, g);
+    else if (rows) PCCM_LAUNCH(ctx, (k_vox_query<false, true>), grid, dim3(64), 0, ctx->stream, jobs, g);
+    else PCCM_LAUNCH(ctx, (k_vox_query<false, false>), grid, dim3(64), 0, ctx->stream, jobs, g);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

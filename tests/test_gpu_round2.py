@@ -22,6 +22,14 @@ def engine():
     e.close()
 
 
+def _brick_served(engine, dirs):
+    """The LDS-brick kernel ran these searches (pccm_nn_path): what the tests below mean to exercise."""
+    for d in dirs:
+        path = engine.last_path(d)
+        assert any(k.startswith("k_brick_query<") for k in path), (d, path)
+        assert any(k.startswith("k_grid_tail<pccm::Rec32") for k in path), (d, path)
+
+
 def _unit(n, seed):
     g = np.random.default_rng(seed).standard_normal((n, 3), dtype=np.float32)
     return (g / np.linalg.norm(g, axis=1, keepdims=True)).astype(np.float32)
@@ -245,24 +253,49 @@ def test_chunk_vectors_of_four_ranks_give_the_unsharded_sums(engine):
     engine.set_shard(0, 1)
 
 
-def test_clumped_bricks_and_leftovers_stay_exact(engine, monkeypatch):
+_CLUMP_CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from open_pcc_metric_amd import _native as nat
+from oracle import oracle as orc
+rng = np.random.default_rng(12)
+a = rng.random((200_000, 3), dtype=np.float32)
+b = rng.random((200_000, 3), dtype=np.float32)
+a[:30_000] = 0.5 + 0.01 * rng.standard_normal((30_000, 3)).astype(np.float32)      # 15 % of A in one small clump
+b[:5_000] = 0.5 + 0.01 * rng.standard_normal((5_000, 3)).astype(np.float32)
+engine = nat.Engine(0)
+engine.set_cloud(0, a); engine.set_cloud(1, b)
+engine.nn_pair("grid"); engine.nn(2, "grid")
+for d in (0, 1, 2):
+    path = engine.last_path(d)
+    assert any(k.startswith("k_brick_query<") for k in path), (d, path)
+    assert any(k.startswith("k_grid_tail<pccm::Rec32") for k in path), (d, path)
+for d, (q, s, skip) in enumerate(((a, b, False), (b, a, False), (a, a, True))):
+    idx, d2 = engine.fetch_nn(d)
+    oi, od = orc.nn(q.astype(np.float64), s.astype(np.float64), skip_same_index=skip, method="kdtree")
+    assert np.array_equal(d2, od) and np.array_equal(idx, oi), d
+engine.close()
+print("clump ok")
+"""
+
+
+def test_clumped_bricks_and_leftovers_stay_exact():
     """The LDS-brick kernel hands bricks that exceed its LDS budget to the general kernels and loops over leftover queries
-    when a brick holds more than a workgroup: a dense clump inside uniform data exercises both."""
-    rng = np.random.default_rng(12)
-    a = rng.random((200_000, 3), dtype=np.float32)
-    b = rng.random((200_000, 3), dtype=np.float32)
-    a[:30_000] = 0.5 + 0.01 * rng.standard_normal((30_000, 3)).astype(np.float32)      # 15 % of A in one small clump
-    b[:5_000] = 0.5 + 0.01 * rng.standard_normal((5_000, 3)).astype(np.float32)
-    monkeypatch.setenv("PCCM_GRID_COOP", "1")                      # keep the brick kernel whatever the occupancy rule says
-    engine.set_cloud(0, a); engine.set_cloud(1, b)
-    engine.nn_pair("grid"); engine.nn(2, "grid")
-    for d, (q, s, skip) in enumerate(((a, b, False), (b, a, False), (a, a, True))):
-        idx, d2 = engine.fetch_nn(d)
-        oi, od = orc.nn(q.astype(np.float64), s.astype(np.float64), skip_same_index=skip, method="kdtree")
-        assert np.array_equal(d2, od) and np.array_equal(idx, oi)
+    when a brick holds more than a workgroup: a dense clump inside uniform data exercises both.  The clump also makes the
+    occupancy rule pick the per-thread kernel, so the brick kernel is forced -- in a child process, since the library
+    latches PCCM_GRID_COOP once per process."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", _CLUMP_CHILD, root], env=dict(os.environ, PCCM_GRID_COOP="1"), capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert "clump ok" in out.stdout
 
 
-def test_long_runs_inside_the_lds_budget_stay_exact(engine, monkeypatch):
+def test_long_runs_inside_the_lds_budget_stay_exact(engine):
     """A staged x-run of the brick kernel is copied 64 + 21 records at a time: thin dense lines along x inside uniform
     data give runs of a few hundred records in bricks whose total still fits the LDS budget (the clump test above overflows
     it instead).  Projections ride along (fp32-exact normals: the 16-byte gather)."""
@@ -277,12 +310,12 @@ def test_long_runs_inside_the_lds_budget_stay_exact(engine, monkeypatch):
             c[rows, 1] = np.float32(y) + np.float32(2e-4) * rng.standard_normal(1500).astype(np.float32)
             c[rows, 2] = np.float32(z) + np.float32(2e-4) * rng.standard_normal(1500).astype(np.float32)
     na, nb = _unit(n, 3), _unit(n, 4)
-    monkeypatch.setenv("PCCM_GRID_COOP", "1")
     engine.set_cloud(0, a); engine.set_cloud(1, b)
     engine.set_normals(0, na); engine.set_normals(1, nb)
     for d in (0, 1):
         engine.nn_fuse(d, "row")
     engine.nn_pair("grid"); engine.nn(2, "grid")
+    _brick_served(engine, (0, 1, 2))
     for d, (q, s, nrm, skip) in enumerate(((a, b, nb, False), (b, a, na, False), (a, a, None, True))):
         idx, d2 = engine.fetch_nn(d)
         oi, od = orc.nn(q.astype(np.float64), s.astype(np.float64), skip_same_index=skip, method="kdtree")
@@ -295,7 +328,7 @@ def test_long_runs_inside_the_lds_budget_stay_exact(engine, monkeypatch):
 
 @pytest.mark.parametrize("margin,note", [(0.012, "several thousand tails: more than one entry per wave at both ends of the wave range"),
                                          (0.05, "tens of thousands: the thread-per-query path")])
-def test_many_tail_queries_stay_exact(engine, monkeypatch, margin, note):
+def test_many_tail_queries_stay_exact(engine, margin, note):
     """Queries in a rim where the other cloud has no points cannot be settled by ring 1: they go through k_grid_tail
     (one wave per entry, the two directions' lists handed out from opposite ends) or, past 2^18 entries, through the
     per-thread search; a few fall through to the exact rescan.  Every row is still the oracle's."""
@@ -306,12 +339,12 @@ def test_many_tail_queries_stay_exact(engine, monkeypatch, margin, note):
     b[:, 2] = b[:, 2] * np.float32(1.0 + margin)                                               # ... and B out of A's along z only
     a[:, 2] = np.minimum(a[:, 2], np.float32(1.0))
     na, nb = _unit(n, 7), _unit(n, 8)
-    monkeypatch.setenv("PCCM_GRID_COOP", "1")
     engine.set_cloud(0, a); engine.set_cloud(1, b)
     engine.set_normals(0, na); engine.set_normals(1, nb)
     for d in (0, 1):
         engine.nn_fuse(d, "row")
     engine.nn_pair("grid")
+    _brick_served(engine, (0, 1))
     for d, (q, s, nrm) in enumerate(((a, b, nb), (b, a, na))):
         idx, d2 = engine.fetch_nn(d)
         oi, od = orc.nn(q.astype(np.float64), s.astype(np.float64), method="kdtree")
@@ -321,7 +354,7 @@ def test_many_tail_queries_stay_exact(engine, monkeypatch, margin, note):
         assert same_bits(engine.reduce_total(d, nat.METRIC_D2, "row")[0], np.sum(np.square(proj))), note
 
 
-def test_cloud_pair_report_identical_with_and_without_fusion(monkeypatch):
+def test_cloud_pair_report_identical_with_and_without_fusion():
     rng = np.random.default_rng(13)
     n = 120_000
     a, b = rng.random((n, 3), dtype=np.float32), rng.random((n, 3), dtype=np.float32)
@@ -330,7 +363,6 @@ def test_cloud_pair_report_identical_with_and_without_fusion(monkeypatch):
     with CloudPair(PointCloud(a, na), PointCloud(b, nb), extent=[1, 1, 1]) as pair:
         fused = MetricCalculator(pair).calculate(transform_options(opts)).as_dict()
         assert "point" not in {k for k in nat.KERNEL_CLASSES if pair._engine.profile_get(k)[1]}
-    monkeypatch.setenv("PCCM_NO_FUSE", "1")
     import subprocess, sys, json, os
     code = ("import numpy as np, json, sys; sys.path.insert(0, %r)\n"
             "from open_pcc_metric_amd.calculator import MetricCalculator\nfrom open_pcc_metric_amd.cloud_pair import CloudPair\n"
