@@ -66,6 +66,17 @@ extern "C" {
 #define PCCM_METRIC_D1 0   /* EuclideanDistance(point_to_plane=False): squared NN distance, metric.py:175-177 */
 #define PCCM_METRIC_D2 1   /* EuclideanDistance(point_to_plane=True): projection squared, metric.py:179 */
 #define PCCM_METRIC_PROJ 2 /* ErrorVector(point_to_plane=True): signed projection, metric.py:146-153 */
+/* Plane-to-plane angular similarity (Alexiou & Ebrahimi, ICME 2018) of directions 0 and 1 (the self search: PCCM_E_ARG).
+ * a = the iterating cloud's normal of row i, b = the searched cloud's normal of the MATCHED row nn(i) -- normal_mode does not
+ * apply and is ignored -- both fp64, every operation separately rounded (no FMA):
+ *   dot = (a0*b0 + a1*b1) + a2*b2,  na2 = (a0*a0 + a1*a1) + a2*a2,  nb2 likewise,  den = sqrt(na2 * nb2)
+ *   s   = 0                                    if den == 0 (a zero-length normal counts as perpendicular)
+ *   s   = 1 - (2 * acos(c)) / M_PI             otherwise, c = min(|dot| / den, 1)
+ * s is 1 for parallel and antiparallel normals (estimated normals are unoriented), 0 for perpendicular ones.  Under
+ * PCCM_TIES_MEAN the value of row i is the mean of s over its tie set, (((s_j1 + s_j2) + s_j3) + ...) / k (not s of the averaged
+ * normal: unoriented normals of opposite sign would cancel).  Both clouds need normals (PCCM_E_STATE otherwise).  Accepted by
+ * pccm_point_metric and every pccm_reduce* call; a plain column, reduced like D1. */
+#define PCCM_METRIC_ANGULAR 3
 
 /* kernel classes for pccm_profile_get() */
 #define PCCM_K_INGEST 0
@@ -209,7 +220,7 @@ int pccm_set_ties(pccm_ctx *ctx, int policy);
  * must have run under PCCM_TIES_MEAN (else PCCM_E_STATE). */
 int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
 
-/* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179. */
+/* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR ignores normal_mode. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
 /* Fused reduction of a per-point metric over the shard: the np.sum / np.max of

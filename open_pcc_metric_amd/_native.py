@@ -26,6 +26,7 @@ ENGINES = {"auto": 0, "brute": 1, "grid": 2}
 NORMAL_MODES = {"row": 0, "neighbour": 1}
 TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
+METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
 

@@ -14,8 +14,8 @@ import typing
 import pandas as pd
 
 from .cloud_pair import CloudPair
-from .metric import (AbstractMetric, BoundarySqrtDistances, EuclideanDistance, PrimaryMetric, SecondaryMetric,
-                     SymmetricMetric)
+from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, EuclideanDistance, PrimaryMetric,
+                     SecondaryMetric, SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -87,6 +87,8 @@ class MetricCalculator:
         if role == 1:
             if isinstance(metric, BoundarySqrtDistances):
                 wanted.append("boundary")
+            elif isinstance(metric, AngularSimilarities):
+                wanted.append(("angular", metric.is_left))
             (late if waits else early).append((metric, None, key))
         elif role == 2:
             if isinstance(metric, EuclideanDistance):

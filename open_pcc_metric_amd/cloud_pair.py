@@ -111,7 +111,9 @@ class DeviceColumn(_DeviceArray):
     ``"d1"``        squared NN distances (NeighbourDistances / D1 EuclideanDistance),
     ``"proj"``      signed point-to-plane projections (ErrorVector, point_to_plane=True),
     ``"d2"``        their squares (D2 EuclideanDistance),
-    ``"boundary"``  sqrt of the self-search distances (get_boundary_sqrt_distances).
+    ``"boundary"``  sqrt of the self-search distances (get_boundary_sqrt_distances),
+    ``"angular"``   plane-to-plane angular similarities (get_left/right_angular_similarities; include/pccm.h,
+                    PCCM_METRIC_ANGULAR: the own normal against the matched point's, ``normal_index`` does not apply).
     """
 
     def __init__(self, pair: "CloudPair", direction: int, kind: str):
@@ -120,7 +122,8 @@ class DeviceColumn(_DeviceArray):
         self._label = f"{kind}[dir={direction}]"
         self._red = None
 
-    _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2}
+    _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2,
+               "angular": nat.METRIC_ANGULAR}
 
     def _materialise(self) -> np.ndarray:
         p = self._pair
@@ -266,6 +269,7 @@ class CloudPair:
         self._colour_red = {}
         self._graph_id = None
         self._last_wanted = None
+        self._angular = False               # a report asked for the angular columns: the searches keep the matched rows
         self._extent = None if extent is None else np.asarray(extent, dtype=np.float64)
         self._coll = Collective(group)
         self._owns_engine = False
@@ -396,8 +400,9 @@ class CloudPair:
             eng.nn_fuse(direction, self.normal_index if self._normals_ready(other) and not mean else None)
         # the matched rows (cloud_pair.py:34-42) are only read by the colour metrics and the error-vector / neighbour
         # getters: clouds without colours leave them out of the result records (a getter that asks later still gets them)
+        # (and so do the angular columns, which compare each point's normal with its matched point's)
         if hasattr(eng, "nn_want_idx"):
-            eng.nn_want_idx(mean or any(_has_colors(c) for c in self.clouds))
+            eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or any(_has_colors(c) for c in self.clouds))
 
     def _colours_for_ties(self) -> None:
         """Under ``ties="mean"`` the colours go up before the searches, so that the one averaging pass per direction (pccm_set_ties)
@@ -664,6 +669,19 @@ class CloudPair:
             self._colour_red[key] = self._engine.color_reduce(direction, scheme, scale, self._colour_rows_arg(direction))
         return self._colour_red[key]
 
+    def _angular_column(self, direction: int) -> DeviceColumn:
+        """Plane-to-plane angular similarities of one direction: both clouds' normals (given, or estimated as for point-to-plane)."""
+        self._require_normals(0)
+        self._require_normals(1)
+        return DeviceColumn(self, direction, "angular")
+
+    def get_left_angular_similarities(self):
+        """Per point of the origin cloud: the angular similarity of its normal and its nearest reconstructed point's."""
+        return self._angular_column(nat.DIR_LEFT)
+
+    def get_right_angular_similarities(self):
+        return self._angular_column(nat.DIR_RIGHT)
+
     def get_left_neighbour_colors(self):
         """cloud_pair.py:120-121: the matched points' colours -- gathered on the device when asked for."""
         return DeviceColorRows(self, nat.DIR_LEFT, "neighbour")
@@ -674,7 +692,7 @@ class CloudPair:
     def prefetch_reductions(self, wanted, _remember: bool = True) -> None:
         """Enqueue the fused reductions a report is about to ask for, without waiting for any of them.
 
-        ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs and/or the string ``"boundary"``.
+        ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -695,6 +713,17 @@ class CloudPair:
                     eng.nn(nat.DIR_SELF, self.nn_engine)
                     self._self_done = True
                 requests.append((nat.DIR_SELF, nat.METRIC_D1))
+                continue
+            if item[0] == "angular":
+                try:
+                    self._require_normals(0)
+                    self._require_normals(1)
+                except ValueError:
+                    continue          # surfaces when the column is evaluated
+                if not self._angular:
+                    self._angular = True
+                    self._update_fusion()     # later searches keep the matched rows (this one's are recovered once)
+                requests.append((nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_ANGULAR))
                 continue
             is_left, p2p = item
             direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT

@@ -371,7 +371,7 @@ using namespace pccm;
 
 static void graph_free(GraphRec &g);
 static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx = true);
-static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb);
+static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb, bool want_ang = false);
 
 #define NOT_CAPTURING(ctx)                                                                          \
     do {                                                                                           \
@@ -468,8 +468,11 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int k = 0; k < 2; ++k) free_cloud(ctx->cloud[k]);
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
-                      &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync};
+                      &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
+                      &ctx->tie_list};
     for (DevBuf *b : bufs) free_buf(*b);
+    for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
+        for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
     for (auto &g : ctx->graphs) graph_free(g);
     for (auto &s : ctx->slots) {
         free_buf(s.val);
@@ -1151,25 +1154,31 @@ static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx)
 }
 
 // PCCM_TIES_MEAN: the virtual neighbours of the shard's rows of direction `dir` (0 or 1), made once per search and kept;
-// want_nrm / want_rgb: the averaged normals (the caller has checked them: check_normals) / colours too
-static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb)
+// want_nrm / want_rgb: the averaged normals (the caller has checked them: check_normals) / colours too; want_ang: the tie-set mean
+// of PCCM_METRIC_ANGULAR (the caller has checked both clouds' normals: check_angular)
+static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb, bool want_ang)
 {
     pccm_ctx::TieCols &t = ctx->tie[dir];
     NNResult &res = ctx->nn[dir];
     const Cloud &se = ctx->cloud[dir == PCCM_DIR_LEFT ? 1 : 0];
+    const Cloud &it = ctx->cloud[dir == PCCM_DIR_LEFT ? 0 : 1];
     // the colours the searched cloud has on the device ride along (one walk per direction and search, not one per consumer);
     // what is wanted but missing is not averaged (the consumers report the missing normals / colours themselves)
     const bool nrm_on = se.n_nrm == se.n && !se.nrm_deferred, rgb_on = se.n_rgb == se.n;
+    const bool ang_on = nrm_on && it.n_nrm == it.n && !it.nrm_deferred;
     want_nrm = want_nrm && nrm_on;
     want_rgb = want_rgb && rgb_on;
+    want_ang = want_ang && ang_on;
     const bool fresh = t.gen == ctx->nn_gen[dir];
     const bool have_nrm = fresh && t.nrm_gen == ctx->nrm_gen, have_rgb = fresh && t.rgb_gen == ctx->rgb_gen;
-    if (fresh && (!want_nrm || have_nrm) && (!want_rgb || have_rgb)) return PCCM_OK;
+    const bool have_ang = fresh && t.ang_gen == ctx->nrm_gen;
+    if (fresh && (!want_nrm || have_nrm) && (!want_rgb || have_rgb) && (!want_ang || have_ang)) return PCCM_OK;
     if (ctx->capturing) {
         ctx->capture_failed = true;
         return fail(PCCM_E_STATE, "PCCM_TIES_MEAN cannot be captured in a graph");
     }
     want_nrm = (want_nrm || have_nrm) && nrm_on;            // (averaged normals only where a neighbour-indexed projection asks)
+    want_ang = (want_ang || have_ang) && ang_on;            // (... and the angular column only where a report asks for it)
     want_rgb = rgb_on;
     int rc = ensure_plain(ctx, res, true);
     if (rc) return rc;
@@ -1178,10 +1187,12 @@ static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb)
     if ((rc = ensure(ctx, t.pos, n3)) || (rc = ensure(ctx, t.k, (size_t)(ns + 1) * sizeof(int32_t)))) return rc;   // (+ the scan count)
     if (want_nrm && (rc = ensure(ctx, t.nrm, n3))) return rc;
     if (want_rgb && (rc = ensure(ctx, t.rgb, n3))) return rc;
+    if (want_ang && (rc = ensure(ctx, t.ang, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
     t.gen = 0;
     PathScope path(ctx, 1u << dir, /*keep=*/true);
     rc = tie_mean(ctx, dir, res.idx, res.d2, res.begin, ns, want_nrm ? se.nrm64 : nullptr, want_rgb ? se.rgb64 : nullptr, (double *)t.pos.p,
-                  (int32_t *)t.k.p, (double *)t.nrm.p, (double *)t.rgb.p);
+                  (int32_t *)t.k.p, (double *)t.nrm.p, (double *)t.rgb.p, want_ang ? it.nrm64 : nullptr, want_ang ? se.nrm64 : nullptr,
+                  want_ang ? (double *)t.ang.p : nullptr);
     if (rc) return rc;
     // behind the k column: how many of these queries the pass left to the exact scan (pccm_nn_stats, PCCM_STATS_TIES)
     if (ns > 0) PCCM_HIP(hipMemcpyAsync((int32_t *)t.k.p + ns, ctx->tie_list.p, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
@@ -1189,6 +1200,7 @@ static int ensure_ties(pccm_ctx *ctx, int dir, bool want_nrm, bool want_rgb)
     t.gen = ctx->nn_gen[dir];
     t.nrm_gen = want_nrm ? ctx->nrm_gen : 0;
     t.rgb_gen = want_rgb ? ctx->rgb_gen : 0;
+    t.ang_gen = want_ang ? ctx->nrm_gen : 0;
     return PCCM_OK;
 }
 
@@ -1282,6 +1294,19 @@ static int check_normals(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const 
     return PCCM_OK;
 }
 
+// PCCM_METRIC_ANGULAR reads the normals of BOTH clouds (the iterating row's and the matched row's; normal_mode does not apply)
+static int check_angular(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se)
+{
+    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "angular similarity is not defined for the self search");
+    for (const Cloud *c : {&it, &se}) {      // announced normals (pccm_set_normals_deferred) cross PCIe now
+        int rcn = normals_ready(ctx, const_cast<Cloud &>(*c));
+        if (rcn) return rcn;
+    }
+    if (it.n_nrm <= 0 || se.n_nrm <= 0) return fail(PCCM_E_STATE, "angular similarity needs the normals of both clouds (pccm_set_normals)");
+    if (it.n_nrm != it.n || se.n_nrm != se.n) return fail(PCCM_E_ARG, "angular similarity needs one normal per point");
+    return PCCM_OK;
+}
+
 int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
 {
     CHECK_CTX(ctx);
@@ -1317,6 +1342,19 @@ static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode,
     *ns_out = ns;
     *it_out = it;
     *res_out = res;
+    if (metric == PCCM_METRIC_ANGULAR) {
+        if ((rc = check_angular(ctx, dir, *it, *se))) return rc;
+        if (res->ties == PCCM_TIES_MEAN) {                // the tie pass makes the column
+            if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
+            *dev = (const double *)ctx->tie[dir].ang.p;
+            return PCCM_OK;
+        }
+        if ((rc = ensure_plain(ctx, *res, true))) return rc;
+        if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
+        if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, PCCM_NORMAL_NEIGHBOUR, (double *)vb.p, nullptr))) return rc;
+        *dev = (const double *)vb.p;
+        return PCCM_OK;
+    }
     if ((rc = ensure_plain(ctx, *res, metric != PCCM_METRIC_D1))) return rc;
     if (metric == PCCM_METRIC_D1) {
         *dev = res->d2;
@@ -1429,6 +1467,30 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
             if ((rc = ensure_plain(ctx, *res, false))) return rc;
             dev = res->d2;
         }
+    } else if (metric == PCCM_METRIC_ANGULAR) {
+        // a plain column: made by the tie pass under PCCM_TIES_MEAN, else by a k_point_jobs job that reads the matched rows
+        // from the plain idx column or straight from matched records (prefetch_many has made sure one of them holds them)
+        if ((rc = check_angular(ctx, dir, *it, *se))) return rc;
+        if (res->ties == PCCM_TIES_MEAN) {
+            if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
+            dev = (const double *)ctx->tie[dir].ang.p;
+        } else {
+            const bool recs = !res->plain_valid && res->rec_valid && res->rec_layout == 1 && res->rec_stride == 2 && !res->no_rows;
+            if (!recs && (rc = ensure_plain(ctx, *res, true))) return rc;
+            if ((rc = ensure(ctx, s.val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
+            dev = (const double *)s.val.p;
+            if (ns > 0) {
+                if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane or angular columns per call");
+                PointJob &P = pj.j[pj.njobs];
+                P.q64 = it->xyz64; P.r64 = se->xyz64; P.nrm = se->nrm64; P.inrm = it->nrm64;
+                P.idx = recs ? nullptr : res->idx;
+                P.recs = recs ? (const float4 *)res->rec.p : nullptr;
+                P.c64 = P.cn64 = nullptr;
+                P.q_begin = res->begin; P.metric = metric; P.normal_mode = PCCM_NORMAL_NEIGHBOUR; P.val = (double *)s.val.p;
+                pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;
+                pj.njobs++;
+            }
+        }
     } else {
         if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
         if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
@@ -1449,7 +1511,8 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
                 if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane columns per call");
                 PointJob &P = pj.j[pj.njobs];
                 P.q64 = it->xyz64; P.r64 = se->xyz64; P.nrm = se->nrm64; P.idx = res->idx;
-                P.c64 = P.cn64 = nullptr;
+                P.c64 = P.cn64 = P.inrm = nullptr;
+                P.recs = nullptr;
                 if (res->ties == PCCM_TIES_MEAN) {
                     const bool nmean = normal_mode == PCCM_NORMAL_NEIGHBOUR;
                     if ((rc = ensure_ties(ctx, dir, nmean, false))) return rc;
@@ -1528,7 +1591,8 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
 static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, bool need_units = false)
 {
     for (auto &s : ctx->slots)
-        if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric && (metric == PCCM_METRIC_D1 || s.mode == normal_mode) &&
+        if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric &&
+            (metric == PCCM_METRIC_D1 || metric == PCCM_METRIC_ANGULAR || s.mode == normal_mode) &&
             s.gen == ctx->nn_gen[dir])
             return &s;
     return nullptr;
@@ -1580,10 +1644,41 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     // search needs the matched rows, and if the search left them out it is repeated (ensure_plain) -- with the rows, and
     // with the projection fused when the normals have arrived meanwhile.  Only then are the columns of this batch bound to
     // the records (a job bound earlier would read 16-byte records through a 32-byte stride).
+    // The angular column (normal_mode does not apply) needs the matched rows in any case: from the plain column or from matched
+    // records (NNOut::layout 1); records without them repeat the search here too.  Under PCCM_TIES_MEAN the tie pass makes it,
+    // together with the averaged normals a neighbour-indexed projection of the same batch wants: one walk per direction.
+    bool tie_ang[2] = {false, false}, tie_nrm[2] = {false, false};
+    for (int k = 0; k < n; ++k) {
+        if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
+        if (dirs[k] == PCCM_DIR_SELF) continue;
+        NNResult &res = ctx->nn[dirs[k]];
+        if (!res.valid || res.ties != PCCM_TIES_MEAN) continue;
+        if (metrics[k] == PCCM_METRIC_ANGULAR) tie_ang[dirs[k]] = true;
+        else if (metrics[k] != PCCM_METRIC_D1 && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
+    }
+    for (int d = 0; d < 2; ++d) {
+        if (!tie_ang[d] || slot_find(ctx, d, PCCM_METRIC_ANGULAR, 0, want_units)) continue;
+        const Cloud *it, *se;
+        NNResult *res;
+        int rc = need_nn(ctx, d, &it, &se, &res);
+        if (!rc) rc = check_angular(ctx, d, *it, *se);
+        if (rc) return rc;
+        if (tie_nrm[d] && check_normals(ctx, *it, *se, *res, PCCM_NORMAL_NEIGHBOUR) != PCCM_OK) tie_nrm[d] = false;   // (reported below)
+        if ((rc = ensure_ties(ctx, d, tie_nrm[d], false, true))) return rc;
+    }
     for (int k = 0; k < n; ++k) {
         if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (metrics[k] == PCCM_METRIC_D1 || dirs[k] == PCCM_DIR_SELF) continue;
         NNResult &res = ctx->nn[dirs[k]];
+        if (metrics[k] == PCCM_METRIC_ANGULAR) {
+            if (!res.valid || res.ties == PCCM_TIES_MEAN || res.plain_valid ||
+                (res.rec_valid && res.rec_layout == 1 && res.rec_stride == 2 && !res.no_rows))
+                continue;
+            if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
+            int rc = ensure_plain(ctx, res, true);
+            if (rc) return rc;
+            continue;
+        }
         const bool mean = res.valid && res.ties == PCCM_TIES_MEAN;      // (the virtual neighbours need the plain columns)
         if (!res.valid || (!res.rec_valid && !mean) ||
             (!mean && (res.fused_mode == normal_modes[k] || res.rec_stride == 4 || res.rec_layout == 1) && !res.no_rows)) continue;

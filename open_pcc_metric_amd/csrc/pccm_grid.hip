@@ -1720,14 +1720,22 @@ struct TieMeanJob {
     int64_t q_begin, ns, n_se;
     double *pos, *nrm, *rgb;    // [ns][3] outputs (nrm / rgb when snrm / srgb)
     int32_t *k;                 // [ns]
+    const double *inrm, *anrm;  // PCCM_METRIC_ANGULAR: iterating cloud's normals (by global row) against the searched cloud's ...
+    double *ang;                // ... -> [ns] the mean of the per-tie values, or null
     uint32_t *list;             // [0] queries for the scan, [1 ..] their indices
 };
 
 struct TieAcc {                 // sequential sums in ascending row order
-    double p[3] = {0, 0, 0}, n[3] = {0, 0, 0}, c[3] = {0, 0, 0};
+    double p[3] = {0, 0, 0}, n[3] = {0, 0, 0}, c[3] = {0, 0, 0}, s = 0;
+    const double *qn = nullptr; // the query's own normal (J.ang)
     int k = 0;
+    __device__ TieAcc(const TieMeanJob &J, int64_t row) : qn(J.ang ? J.inrm + 3 * row : nullptr) {}
     __device__ void add(const TieMeanJob &J, int64_t r)
     {
+        if (J.ang) {                // per tie, not of the averaged normal: unoriented normals of opposite sign would cancel
+            const double v = angular_similarity(qn, J.anrm + 3 * r);
+            s = k ? __dadd_rn(s, v) : v;
+        }
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const double v = J.s64[3 * r + a];
@@ -1746,6 +1754,7 @@ struct TieAcc {                 // sequential sums in ascending row order
             if (J.snrm) J.nrm[3 * i + a] = __ddiv_rn(n[a], dk);
             if (J.srgb) J.rgb[3 * i + a] = __ddiv_rn(c[a], dk);
         }
+        if (J.ang) J.ang[i] = __ddiv_rn(s, dk);
         J.k[i] = k;
     }
 };
@@ -1798,7 +1807,7 @@ __global__ __launch_bounds__(256) void k_tie_mean(TieMeanJob J, GridGeom g)
         J.list[1 + slot] = (uint32_t)i;
         return;
     }
-    TieAcc acc;
+    TieAcc acc(J, row);
     for (int t = 0; t < m; ++t) acc.add(J, rows[t]);
     acc.store(J, i);
 }
@@ -1814,7 +1823,7 @@ __global__ __launch_bounds__(256) void k_tie_mean_scan(TieMeanJob J)
         const int64_t row = J.q_begin + i;
         const double qx = J.q64[3 * row], qy = J.q64[3 * row + 1], qz = J.q64[3 * row + 2];
         const double d = tie_d2(J, i, qx, qy, qz);
-        TieAcc acc;
+        TieAcc acc(J, row);
         for (int64_t base = 0; base < J.n_se; base += 256) {
             const int64_t r = base + threadIdx.x;
             const bool hit = r < J.n_se && gdist64(qx, qy, qz, J.s64[3 * r], J.s64[3 * r + 1], J.s64[3 * r + 2]) == d;
@@ -1832,7 +1841,8 @@ __global__ __launch_bounds__(256) void k_tie_mean_scan(TieMeanJob J)
 }
 
 int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64_t q_begin, int64_t ns, const double *snrm,
-             const double *srgb, double *pos, int32_t *k, double *nrm, double *rgb)
+             const double *srgb, double *pos, int32_t *k, double *nrm, double *rgb, const double *inrm, const double *anrm,
+             double *ang)
 {
     if (dir != PCCM_DIR_LEFT && dir != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "ties are resolved for directions 0 and 1");
     if (ns <= 0) return PCCM_OK;
@@ -1866,6 +1876,9 @@ int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64
     J.nrm = nrm;
     J.rgb = rgb;
     J.k = k;
+    J.inrm = inrm;
+    J.anrm = anrm;
+    J.ang = (inrm && anrm) ? ang : nullptr;
     J.list = (uint32_t *)ctx->tie_list.p;
     PCCM_HIP(hipMemsetAsync(J.list, 0, sizeof(uint32_t), ctx->stream));
     ProfScope ps(ctx, PCCM_K_POINT);

@@ -235,8 +235,8 @@ struct pccm_ctx {
     // averaged normal and colour; valid for the search generation / colour upload / normals they were made from
     int ties = PCCM_TIES_PICK;
     struct TieCols {
-        pccm::DevBuf pos, nrm, rgb, k;
-        uint64_t gen = 0, rgb_gen = 0, nrm_gen = 0;   // 0: not made
+        pccm::DevBuf pos, nrm, rgb, k, ang;
+        uint64_t gen = 0, rgb_gen = 0, nrm_gen = 0, ang_gen = 0;   // 0: not made (ang: both clouds' normals, ctx->nrm_gen)
     } tie[2], tie_rows;                   // tie_rows: the whole iterating cloud, from caller-supplied rows (sharded colours)
     pccm::DevBuf tie_list;                // queries left to the exact scan (k_tie_mean_scan): [0] count, then shard rows
     uint64_t nrm_gen = 1;                 // bumped whenever any normals change
@@ -380,9 +380,12 @@ int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; 
 int estimate_normals(pccm_ctx *ctx, int which, int k);
 int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int normal_mode, double out[8]);
 // PCCM_TIES_MEAN producer: for the ns queries q_begin.. of direction dir (matched rows idx, squared distances d2 or null = formed
-// from idx) the ascending-row mean of all equidistant nearest points -> pos[ns][3], k[ns]; nrm / rgb likewise when snrm / srgb
+// from idx) the ascending-row mean of all equidistant nearest points -> pos[ns][3], k[ns]; nrm / rgb likewise when snrm / srgb;
+// ang[ns] when ang: the mean over the tie set of PCCM_METRIC_ANGULAR (the iterating cloud's normals inrm against the searched
+// cloud's anrm)
 int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64_t q_begin, int64_t ns, const double *snrm,
-             const double *srgb, double *pos, int32_t *k, double *nrm, double *rgb);
+             const double *srgb, double *pos, int32_t *k, double *nrm, double *rgb, const double *inrm = nullptr,
+             const double *anrm = nullptr, double *ang = nullptr);
 int check_device_errors(pccm_ctx *ctx);
 int normals_ready(pccm_ctx *ctx, Cloud &c);       // uploads normals announced by pccm_set_normals_deferred (no-op otherwise)           // PCCM_E_STATE when a kernel raised the context's device error word
 // exact rescan of the flagged queries of njobs <= 2 results (k2b_fallback)
@@ -412,9 +415,24 @@ struct RescanJobs {
     int njobs;
 };
 
-struct PointJob {               // one D2 / PROJ column (k_point_jobs)
+// PCCM_METRIC_ANGULAR of one pair of normals (include/pccm.h): every operation separately rounded, as NumPy's element-wise ops
+__device__ __forceinline__ double angular_similarity(const double *a, const double *b)
+{
+    const double dot = __dadd_rn(__dadd_rn(__dmul_rn(a[0], b[0]), __dmul_rn(a[1], b[1])), __dmul_rn(a[2], b[2]));
+    const double na2 = __dadd_rn(__dadd_rn(__dmul_rn(a[0], a[0]), __dmul_rn(a[1], a[1])), __dmul_rn(a[2], a[2]));
+    const double nb2 = __dadd_rn(__dadd_rn(__dmul_rn(b[0], b[0]), __dmul_rn(b[1], b[1])), __dmul_rn(b[2], b[2]));
+    const double den = __dsqrt_rn(__dmul_rn(na2, nb2));
+    if (den == 0.0) return 0.0;                                   // a zero-length normal: perpendicular
+    const double q = __ddiv_rn(fabs(dot), den);
+    const double c = q > 1.0 ? 1.0 : q;                           // np.minimum(q, 1.0) (a NaN stays NaN)
+    return __dsub_rn(1.0, __ddiv_rn(__dmul_rn(2.0, acos(c)), M_PI));
+}
+
+struct PointJob {               // one D2 / PROJ / ANGULAR column (k_point_jobs)
     const double *q64, *r64, *nrm;
     const double *c64, *cn64;   // PCCM_TIES_MEAN: per shard row the virtual neighbour / its averaged normal (null: gather via idx)
+    const double *inrm;         // PCCM_METRIC_ANGULAR: the iterating cloud's normals (nrm: the searched cloud's)
+    const float4 *recs;         // PCCM_METRIC_ANGULAR: matched records {x, y, z, row} (NNResult::rec_layout 1) instead of idx, or null
     const int32_t *idx;
     int64_t q_begin;
     int metric, normal_mode;
@@ -467,6 +485,7 @@ int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, cons
 // nothing was launched
 int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 
+// (PCCM_METRIC_ANGULAR: the pick's column from both clouds' normals; under PCCM_TIES_MEAN the tie pass makes it, tie_mean)
 int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,
                         int normal_mode, double *out_val /*[ns]*/, double *out_err /*[ns][3] or null*/,
                         const double *c64 = nullptr, const double *cn64 = nullptr);   // PCCM_TIES_MEAN columns (PointJob)

@@ -154,18 +154,24 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
 // The dot product is the FMA chain fma(e2,n2, fma(e1,n1, e0*n0)) that np.dot (OpenBLAS ddot)
 // evaluates on FMA-capable hosts; see oracle/pccm_oracle.c for how that was pinned.
 // HBM/gather bound: 24 (q) + 4 (idx) + 24 (r, gathered) + 24 (normal) + 8 (out) bytes per row.
+// PCCM_METRIC_ANGULAR (the pick's column): the own normal inrm[gi] against the matched row's nrm[j] -- 24 + 4 + 24 + 8 bytes.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_point_metric(const double *__restrict__ q64, int64_t q_begin, int64_t ns,
                                                       const double *__restrict__ r64,
                                                       const int32_t *__restrict__ idx,
                                                       const double *__restrict__ nrm, int metric, int normal_mode,
                                                       double *__restrict__ val, double *__restrict__ err,
-                                                      const double *__restrict__ c64, const double *__restrict__ cn64)
+                                                      const double *__restrict__ c64, const double *__restrict__ cn64,
+                                                      const double *__restrict__ inrm)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= ns) return;
     const int64_t gi = q_begin + i;
     const int64_t j = idx[i];
+    if (metric == PCCM_METRIC_ANGULAR) {
+        val[i] = angular_similarity(inrm + 3 * gi, nrm + 3 * j);
+        return;
+    }
     const double *r = c64 ? c64 + 3 * i : r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
     const double ex = __dsub_rn(q64[3 * gi], r[0]);
     const double ey = __dsub_rn(q64[3 * gi + 1], r[1]);
@@ -192,7 +198,7 @@ int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const N
     ProfScope ps(ctx, PCCM_K_POINT);
     dim3 grid((unsigned)((ns + 255) / 256));
     PCCM_LAUNCH(ctx, k_point_metric, grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, ns, se.xyz64, res.idx,
-                       se.nrm64, metric, normal_mode, out_val, out_err, c64, cn64);
+                       se.nrm64, metric, normal_mode, out_val, out_err, c64, cn64, it.nrm64);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -203,8 +209,8 @@ int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const N
 // pairwise-sum leaf, so that np.sum's tree can be finished bit for bit (pccm_finish_sum / pccm_reduce_total).
 // ------------------------------------------------------------------------------------------
 // ---- batched forms: several columns per launch, results written straight into pinned host memory ------
-// A report needs up to four columns (D1/D2 x left/right).  One k_point_jobs launch evaluates all D2
-// columns, one k_unit_jobs launch reduces all columns and stores the per-unit sums/min/max and the raw
+// A report needs up to four columns (D1/D2 x left/right).  One k_point_jobs launch evaluates all D2 (and the pick's
+// PCCM_METRIC_ANGULAR) columns, one k_unit_jobs launch reduces all columns and stores the per-unit sums/min/max and the raw
 // tail values directly into the slots' pinned host buffers (device-visible), so there is no copy node
 // and no extra launch per column.
 __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
@@ -218,6 +224,11 @@ __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
     const PointJob &J = jobs.j[jb];
     const int64_t i = i0 - jobs.off[jb];
     const int64_t gi = J.q_begin + i;
+    if (J.metric == PCCM_METRIC_ANGULAR) {             // the own normal against the matched row's: 24 + 4 (or 16) + 24 + 8 bytes
+        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
+        J.val[i] = angular_similarity(J.inrm + 3 * gi, J.nrm + 3 * j);
+        return;
+    }
     const int64_t j = J.idx[i];
     const double *r = J.c64 ? J.c64 + 3 * i : J.r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
     const double ex = __dsub_rn(J.q64[3 * gi], r[0]);

@@ -1,7 +1,7 @@
 """Command line -- same flags and report text as ``python -m open_pcc_metric`` (handler.py:4-71).
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
-                                  [--point-to-plane] [--csv]
+                                  [--point-to-plane] [--plane-to-plane] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -11,7 +11,9 @@ on the order of exact ties, which nanoflann decides by traversal -- cloud_pair.p
 (pick = the smallest row of several equidistant nearest neighbours; mean = their mean, which makes the point-to-plane and
 colour rows independent of the order of the points; D1 rows are the same either way).  Files without normals get them estimated on the GPU when
 --point-to-plane asks for them (k = 30 covariance normals, as Open3D's estimate_normals does at
-cloud_pair.py:61-64).  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+cloud_pair.py:61-64).  ``--plane-to-plane`` (no counterpart in the reference) adds the angular similarity rows of Alexiou &
+Ebrahimi (ICME 2018) after all others; they compare each point's normal with its matched point's, so they too estimate the
+normals files lack.  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -27,6 +29,10 @@ import click
               help="Report hausdorff metric as well. If --point-to-plane is provided, "
                    "then hausdorff point-to-plane would be reported too")
 @click.option("--point-to-plane", required=False, is_flag=True, help="Report point-to-plane distance as well.")
+@click.option("--plane-to-plane", required=False, is_flag=True,
+              help="Report plane-to-plane angular similarity as well (1: parallel or antiparallel normals, 0: perpendicular), "
+                   "after all other rows; with --hausdorff also its worst point.  Compares each point's normal with its matched "
+                   "point's normal: --normal-index does not apply.  Normals missing from a file are estimated.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -40,14 +46,15 @@ import click
 @click.option("--ties", type=click.Choice(["pick", "mean"]), default="pick", show_default=True,
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
-def cli(ocloud, pcloud, color, hausdorff, point_to_plane, csv, device, engine, normal_index, extent, tie_exposure, ties) -> None:
+def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, csv, device, engine, normal_index, extent, tie_exposure,
+        ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
     from .options import CalculateOptions, transform_options
 
     ocloud_cloud = read_point_cloud(ocloud)
-    options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane)
+    options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane)
     cloud_pair = None
     for path in pcloud:
         pcloud_cloud = read_point_cloud(path)

@@ -118,6 +118,13 @@ class NeighbourColors(PrimaryMetric, DirectionalMetric):         # metric.py:115
                            cloud_pair.get_right_neighbour_colors)
 
 
+class AngularSimilarities(PrimaryMetric, DirectionalMetric):     # no counterpart in the reference (options.py: plane_to_plane)
+    """Per point of the iterating cloud, the angular similarity of its normal and its matched neighbour's (include/pccm.h,
+    PCCM_METRIC_ANGULAR): 1 - 2 acos(min(|a . b| / (|a| |b|), 1)) / pi, 0 for a zero-length normal."""
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, cloud_pair.get_left_angular_similarities, cloud_pair.get_right_angular_similarities)
+
+
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, cloud_pair: CloudPair) -> None:
@@ -209,6 +216,30 @@ class GeoHausdorffDistance(_OverEuclidean):                      # metric.py:353
         column = euclidean_distance.value
         fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
         self.value = fused()[2] if fused is not None else np.max(column, axis=0)
+
+
+class _OverAngular(SecondaryMetric, DirectionalMetric):
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"angular_similarities": AngularSimilarities(is_left=self.is_left)}
+
+
+class AngularSimilarity(_OverAngular):
+    """Plane-to-plane similarity of one direction: the mean of the per-point values (sum / n, NumPy's pairwise sum)."""
+    _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+    def calculate(self, angular_similarities: AngularSimilarities) -> None:
+        column = angular_similarities.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
+        total = fused()[0] if fused is not None else None
+        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+
+
+class MinAngularSimilarity(_OverAngular):
+    """The worst point of one direction (reported with hausdorff)."""
+    _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+    def calculate(self, angular_similarities: AngularSimilarities) -> None:
+        column = angular_similarities.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.min would dispatch to, called directly
+        self.value = fused()[1] if fused is not None else np.min(column, axis=0)
 
 
 def _peak_of(cloud_extent):

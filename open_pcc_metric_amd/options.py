@@ -8,21 +8,28 @@ of the CLI report, so it is part of the contract:
   point_to_plane         GeoMSE L/R/sym, GeoPSNR L/R/sym with point_to_plane=True   (options.py:84-104)
   hausdorff              Hausdorff L/R/sym, HausdorffPSNR L/R/sym (D1)              (options.py:106-138)
   hausdorff & p2plane    Hausdorff L/R, HausdorffPSNR L/R, then both symmetric rows (options.py:140-172)
+
+and, with ``plane_to_plane`` (no counterpart in the reference: the angular similarity of Alexiou & Ebrahimi, ICME 2018), after
+every row above:
+
+  plane_to_plane         AngularSimilarity L/R/sym
+  plane_to_plane & hd    MinAngularSimilarity L/R/sym
 """
 from __future__ import annotations
 
 import typing
 
-from .metric import (AbstractMetric, ColorMSE, ColorPSNR, GeoHausdorffDistance, GeoHausdorffDistancePSNR,
-                     GeoMSE, GeoPSNR, MaxSqrtDistance, MinSqrtDistance, SymmetricMetric)
+from .metric import (AbstractMetric, AngularSimilarity, ColorMSE, ColorPSNR, GeoHausdorffDistance, GeoHausdorffDistancePSNR,
+                     GeoMSE, GeoPSNR, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance, SymmetricMetric)
 
 
 class CalculateOptions:
     def __init__(self, color: typing.Optional[str] = None, hausdorff: bool = False,
-                 point_to_plane: bool = False):
+                 point_to_plane: bool = False, plane_to_plane: bool = False):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
+        self.plane_to_plane = plane_to_plane
 
 
 def _sides(cls, **kw):
@@ -51,4 +58,9 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
         kw = dict(point_to_plane=True)
         metrics += (_sides(GeoHausdorffDistance, **kw) + _sides(GeoHausdorffDistancePSNR, **kw)
                     + [_sym(GeoHausdorffDistance, False, **kw), _sym(GeoHausdorffDistancePSNR, True, **kw)])
+    if getattr(options, "plane_to_plane", False):
+        # higher is better: the symmetric rows report the smaller side
+        metrics += _sides(AngularSimilarity) + [_sym(AngularSimilarity, True)]
+        if options.hausdorff:
+            metrics += _sides(MinAngularSimilarity) + [_sym(MinAngularSimilarity, True)]
     return metrics
