@@ -77,6 +77,16 @@ extern "C" {
  * normal: unoriented normals of opposite sign would cancel).  Both clouds need normals (PCCM_E_STATE otherwise).  Accepted by
  * pccm_point_metric and every pccm_reduce* call; a plain column, reduced like D1. */
 #define PCCM_METRIC_ANGULAR 3
+/* PointSSIM similarity (Alexiou & Ebrahimi, ICME Workshops 2020) of one attribute, directions 0 and 1 (the self search:
+ * PCCM_E_ARG).  F = the feature columns pccm_ssim_features made, a = F_it(i), b = F_se(nn(i)) of the MATCHED row (normal_mode
+ * does not apply and is ignored), every operation separately rounded:
+ *   s = 1 - |a - b| / (max(|a|, |b|) + 2^-52)
+ * PCCM_E_STATE unless both clouds hold that attribute's features at the same k, and under PCCM_TIES_MEAN.  Accepted by
+ * pccm_point_metric and every pccm_reduce* call; a plain column, reduced like D1. */
+#define PCCM_METRIC_SSIM_GEOMETRY 4
+#define PCCM_METRIC_SSIM_NORMAL 5
+#define PCCM_METRIC_SSIM_CURVATURE 6
+#define PCCM_METRIC_SSIM_COLOR 7
 
 /* kernel classes for pccm_profile_get() */
 #define PCCM_K_INGEST 0
@@ -140,6 +150,24 @@ int pccm_set_io_staged(pccm_ctx *ctx, int on);
  * magnitude is positive.  The normals stay on the device; pccm_get_normals copies [n][3] doubles out. */
 int pccm_estimate_normals(pccm_ctx *ctx, int which, int knn);
 int pccm_get_normals(pccm_ctx *ctx, int which, double *out);
+
+/* PointSSIM features ("PointSSIM") of cloud `which`: per point p, N_k(p) = the k points of the same cloud first
+ * in ascending (d2, row) order (p itself included; all of them when the cloud has fewer than k), and per attribute the variance
+ * with divisor m - 1 of m values over N_k(p), fp64, sums left to right in neighbourhood order, every operation separately rounded:
+ *   PCCM_SSIM_GEOMETRY   distances sqrt(d2(p, q_j)), j >= 1
+ *   PCCM_SSIM_NORMAL     PCCM_METRIC_ANGULAR of n_p and n_{q_j}, j >= 1 (needs the cloud's normals)
+ *   PCCM_SSIM_CURVATURE  c(q_j) = lambda_min / trace of the covariance of N_k(q_j) (0 for a zero trace), j >= 0
+ *   PCCM_SSIM_COLOR      the luma of q_j (first row of transform_colors' "ycc" matrix), j >= 0 (needs the cloud's colours)
+ * F = 0 when m < 2.  attrs: a mask of PCCM_SSIM_*; k in 2..64.  The columns stay with the cloud in HBM until its points, normals
+ * or colours change; a call whose attributes are already there at the same k does no work (*built = 0, else 1; built may be
+ * null).  PCCM_E_STATE when the normals or colours the mask needs are absent. */
+#define PCCM_SSIM_GEOMETRY 1
+#define PCCM_SSIM_NORMAL 2
+#define PCCM_SSIM_CURVATURE 4
+#define PCCM_SSIM_COLOR 8
+int pccm_ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built);
+/* one feature column (attr: a single PCCM_SSIM_* flag) of cloud `which`: n doubles */
+int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out);
 
 /* Query-axis shard of this context: rank r of `world` owns, in every direction, the rows
  * [begin, end) of the iterating cloud returned by pccm_shard_range (boundaries are multiples
@@ -220,7 +248,8 @@ int pccm_set_ties(pccm_ctx *ctx, int policy);
  * must have run under PCCM_TIES_MEAN (else PCCM_E_STATE). */
 int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
 
-/* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR ignores normal_mode. */
+/* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR and
+ * PCCM_METRIC_SSIM_* ignore normal_mode. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
 /* Fused reduction of a per-point metric over the shard: the np.sum / np.max of

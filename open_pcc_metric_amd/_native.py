@@ -27,13 +27,17 @@ NORMAL_MODES = {"row": 0, "neighbour": 1}
 TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
 METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
+# PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
+SSIM_ATTRS = {"geometry": 1, "normal": 2, "curvature": 4, "color": 8}
+METRIC_SSIM = {"geometry": 4, "normal": 5, "curvature": 6, "color": 7}
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
 
 # every symbol include/pccm.h declares (tests check that the library exports all of them)
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
-    "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
+    "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals",
+    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
@@ -100,6 +104,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_set_shard_dir.argtypes = [vp, i32, i32, i32]
     lib.pccm_estimate_normals.argtypes = [vp, i32, i32]
     lib.pccm_get_normals.argtypes = [vp, i32, vp]
+    lib.pccm_ssim_features.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i32)]
+    lib.pccm_get_ssim_features.argtypes = [vp, i32, i32, vp]
     lib.pccm_shard_range.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.pccm_nn.argtypes = [vp, i32, i32]
     lib.pccm_nn_pair.argtypes = [vp, i32]
@@ -462,6 +468,21 @@ class Engine:
     def get_normals(self, which: int) -> np.ndarray:
         out = np.empty((self._n[which], 3), dtype=np.float64)
         _check(self._lib.pccm_get_normals(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def ssim_features(self, which: int, k: int, attrs) -> bool:
+        """Build (or find) cloud ``which``'s PointSSIM feature columns for the attribute names ``attrs`` in HBM; True when work
+        was done (pccm_ssim_features)."""
+        mask = 0
+        for a in attrs:
+            mask |= SSIM_ATTRS[a]
+        built = ctypes.c_int32()
+        _check(self._lib.pccm_ssim_features(self._ctx, int(which), int(k), mask, ctypes.byref(built)))
+        return bool(built.value)
+
+    def get_ssim_features(self, which: int, attr: str) -> np.ndarray:
+        out = np.empty(self._n[which], dtype=np.float64)
+        _check(self._lib.pccm_get_ssim_features(self._ctx, int(which), SSIM_ATTRS[attr], out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def set_shard(self, rank: int, world: int) -> None:

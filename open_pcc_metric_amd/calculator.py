@@ -15,7 +15,7 @@ import pandas as pd
 
 from .cloud_pair import CloudPair
 from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, EuclideanDistance, PrimaryMetric,
-                     SecondaryMetric, SymmetricMetric)
+                     SecondaryMetric, SSIMSimilarities, SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -89,6 +89,8 @@ class MetricCalculator:
                 wanted.append("boundary")
             elif isinstance(metric, AngularSimilarities):
                 wanted.append(("angular", metric.is_left))
+            elif isinstance(metric, SSIMSimilarities):
+                wanted.append(("ssim", metric.attribute, metric.is_left, metric.k))
             (late if waits else early).append((metric, None, key))
         elif role == 2:
             if isinstance(metric, EuclideanDistance):

@@ -113,7 +113,9 @@ class DeviceColumn(_DeviceArray):
     ``"d2"``        their squares (D2 EuclideanDistance),
     ``"boundary"``  sqrt of the self-search distances (get_boundary_sqrt_distances),
     ``"angular"``   plane-to-plane angular similarities (get_left/right_angular_similarities; include/pccm.h,
-                    PCCM_METRIC_ANGULAR: the own normal against the matched point's, ``normal_index`` does not apply).
+                    PCCM_METRIC_ANGULAR: the own normal against the matched point's, ``normal_index`` does not apply),
+    ``"ssim:<attribute>"``  PointSSIM similarities of one attribute (get_left/right_ssim_similarities; PCCM_METRIC_SSIM_*: the
+                    own feature against the matched point's, at the neighbourhood size the pair's features were built with).
     """
 
     def __init__(self, pair: "CloudPair", direction: int, kind: str):
@@ -123,7 +125,7 @@ class DeviceColumn(_DeviceArray):
         self._red = None
 
     _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2,
-               "angular": nat.METRIC_ANGULAR}
+               "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}}
 
     def _materialise(self) -> np.ndarray:
         p = self._pair
@@ -165,6 +167,18 @@ class DeviceColumn(_DeviceArray):
         if ufunc is np.square and method == "__call__" and not kwargs and self._kind == "proj":
             return DeviceColumn(self._pair, self._dir, "d2")     # metric.py:179 stays on the GPU
         return NotImplemented
+
+
+class DeviceFeatures(_DeviceArray):
+    """One cloud's PointSSIM feature column of one attribute (get_ssim_features), copied from HBM when asked for."""
+
+    def __init__(self, pair: "CloudPair", which: int, attribute: str):
+        self._pair, self._which, self._attribute = pair, which, attribute
+        self.shape = (pair._engine.n_iter(nat.DIR_LEFT if which == 0 else nat.DIR_RIGHT),)
+        self._label = f"ssim features[{attribute}, cloud {which}]"
+
+    def _materialise(self) -> np.ndarray:
+        return self._pair._engine.get_ssim_features(self._which, self._attribute)
 
 
 class DeviceRows(_DeviceArray):
@@ -270,6 +284,7 @@ class CloudPair:
         self._graph_id = None
         self._last_wanted = None
         self._angular = False               # a report asked for the angular columns: the searches keep the matched rows
+        self._ssim = False                  # ... or for PointSSIM columns (likewise)
         self._extent = None if extent is None else np.asarray(extent, dtype=np.float64)
         self._coll = Collective(group)
         self._owns_engine = False
@@ -402,7 +417,8 @@ class CloudPair:
         # getters: clouds without colours leave them out of the result records (a getter that asks later still gets them)
         # (and so do the angular columns, which compare each point's normal with its matched point's)
         if hasattr(eng, "nn_want_idx"):
-            eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or any(_has_colors(c) for c in self.clouds))
+            eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or self.__dict__.get("_ssim", False)
+                            or any(_has_colors(c) for c in self.clouds))
 
     def _colours_for_ties(self) -> None:
         """Under ``ties="mean"`` the colours go up before the searches, so that the one averaging pass per direction (pccm_set_ties)
@@ -682,6 +698,54 @@ class CloudPair:
     def get_right_angular_similarities(self):
         return self._angular_column(nat.DIR_RIGHT)
 
+    # -- PointSSIM ("PointSSIM") ------------------------------------------------------------------------------
+    def _check_ssim(self, attributes, k: int) -> None:
+        """The ValueErrors of CalculateOptions and options.check_point_ssim, for this pair -- raised before any GPU work of a
+        report."""
+        from .options import CalculateOptions, check_point_ssim
+        check_point_ssim(CalculateOptions(point_ssim=attributes, ssim_neighbours=k), *self.clouds,
+                         estimate_normals=self._estimate_normals, ties=self.ties,
+                         group=self._coll.group if self._coll.sharded else None)
+
+    def _ensure_ssim(self, attributes, k: int) -> None:
+        """Both clouds' feature columns of ``attributes`` at neighbourhood size ``k``, built in HBM where missing
+        (pccm_ssim_features; the origin cloud's survive with_reconst), and the matched rows kept by later searches."""
+        attributes = tuple(attributes)
+        self._check_ssim(attributes, k)
+        if "normal" in attributes:
+            self._require_normals(0)
+            self._require_normals(1)
+        if "color" in attributes:
+            self._ensure_colours()
+        built = False
+        for which in (0, 1):
+            built = self._engine.ssim_features(which, int(k), attributes) or built
+        if built:                                         # totals of earlier features are stale
+            self._totals = {key: v for key, v in self._totals.items() if key[1] not in nat.METRIC_SSIM.values()}
+        if not self._ssim:
+            self._ssim = True
+            self._update_fusion()     # later searches keep the matched rows (this one's are recovered once)
+
+    def get_ssim_features(self, which: int, attribute: str, k: int = 12):
+        """Per point of cloud ``which`` (0 origin, 1 reconstructed): its PointSSIM feature of ``attribute`` over its k
+        nearest points (fp64; a device column, copied to the host when asked for)."""
+        if which not in (0, 1):
+            raise ValueError("which must be 0 or 1")
+        self._ensure_ssim((attribute,), k)
+        return DeviceFeatures(self, which, attribute)
+
+    def _ssim_column(self, direction: int, attribute: str, k: int) -> DeviceColumn:
+        self._ensure_ssim((attribute,), k)
+        return DeviceColumn(self, direction, f"ssim:{attribute}")
+
+    def get_left_ssim_similarities(self, attribute: str, k: int = 12):
+        """Per point of the origin cloud: the PointSSIM similarity of its ``attribute`` feature and its nearest reconstructed
+        point's."""
+        return self._ssim_column(nat.DIR_LEFT, attribute, k)
+
+    def get_right_ssim_similarities(self, attribute: str, k: int = 12):
+        return self._ssim_column(nat.DIR_RIGHT, attribute, k)
+
     def get_left_neighbour_colors(self):
         """cloud_pair.py:120-121: the matched points' colours -- gathered on the device when asked for."""
         return DeviceColorRows(self, nat.DIR_LEFT, "neighbour")
@@ -692,7 +756,8 @@ class CloudPair:
     def prefetch_reductions(self, wanted, _remember: bool = True) -> None:
         """Enqueue the fused reductions a report is about to ask for, without waiting for any of them.
 
-        ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)`` and/or the string ``"boundary"``.
+        ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``
+        and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -704,8 +769,21 @@ class CloudPair:
                 eng.graph_destroy(self._graph_id)             # a different report: capture anew next time
                 self._graph_id = None
             self._last_wanted = wanted
-        requests = []
+        # PointSSIM: every check first (ValueError before any GPU work of the report), then the features -- built here, eagerly
+        # and outside any graph capture, the first time a report asks for them; found in HBM every time after that
+        ssim_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "ssim"]
+        by_k = {}
+        for _, attribute, _, k in ssim_items:
+            by_k.setdefault(k, []).append(attribute)
+        for k, attributes in by_k.items():
+            self._check_ssim(attributes, k)
+        for k, attributes in by_k.items():
+            self._ensure_ssim(sorted(set(attributes)), k)
+        requests, ssim_requests = [], []
         for item in wanted:
+            if item in ssim_items:
+                ssim_requests.append((nat.DIR_LEFT if item[2] else nat.DIR_RIGHT, nat.METRIC_SSIM[item[1]]))
+                continue
             if item == "boundary":
                 if self._self_done and (nat.DIR_SELF, nat.METRIC_D1) in self._totals:
                     continue                              # inherited with the origin cloud (with_reconst): nothing to reduce again
@@ -741,12 +819,15 @@ class CloudPair:
                     continue      # row-indexed normals out of range (the WHOLE cloud decides, so that every rank of a
                     #               sharded pair agrees): surfaces, on every rank, where the reference raises
                 requests.append((direction, nat.METRIC_D2))
-        self._xchg_wanted = list(requests)
+        self._xchg_wanted = list(requests) + ssim_requests
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
             eng.reduce_prefetch_many(requests[:8], self.normal_index)
+            for b in range(0, len(ssim_requests), 4):     # (at most four matched-row columns per batch: k_point_jobs)
+                eng.reduce_prefetch_many(ssim_requests[b:b + 4], self.normal_index)
         else:
+            requests = requests + ssim_requests
             for direction, metric in requests:
                 eng.reduce_prefetch(direction, metric, self.normal_index)
 

@@ -138,6 +138,10 @@ static void free_cloud(Cloud &c)
     if (c.rgb64) (void)hipFree(c.rgb64);
     if (c.rgb8) (void)hipFree(c.rgb8);
     if (c.sp) (void)hipFree(c.sp);
+    if (c.ssim64) (void)hipFree(c.ssim64);
+    c.ssim64 = nullptr;
+    c.cap_ssim = 0;
+    c.ssim_attrs = c.ssim_k = 0;
     c.sp = nullptr;
     c.cap_sp = 0;
     c.sp_valid = false;
@@ -161,6 +165,7 @@ static void drop_cloud(Cloud &c)
     c.nrm_host = nullptr;
     c.sp_valid = c.sp_tried = false;
     c.rgb8_valid = false;
+    c.ssim_attrs = c.ssim_k = 0;
 }
 
 static void free_nn(NNResult &r)
@@ -312,6 +317,7 @@ static int upload(pccm_ctx *ctx, const void *src, size_t bytes, int on_device, c
 static int ingest_normals(pccm_ctx *ctx, Cloud &c, int which, const void *nrm, int64_t n, int dtype, int on_device, hipStream_t st, DevBuf &stage)
 {
     ctx->nrm_gen++;                                      // (averaged normals of PCCM_TIES_MEAN are stale)
+    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
     const size_t esz = dtype == PCCM_F32 ? 4 : 8;
     const void *dsrc = nrm;
     if (!on_device) {
@@ -469,7 +475,7 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->tie_list};
+                      &ctx->ssim_scratch,                      &ctx->tie_list};
     for (DevBuf *b : bufs) free_buf(*b);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
@@ -566,6 +572,7 @@ int pccm_set_normals(pccm_ctx *ctx, int which, const void *nrm, int64_t n, int d
     c.n_nrm = 0;
     c.nrm_exact32 = false;
     c.nrm_deferred = false;
+    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
     c.nrm_host = nullptr;
     int rc = grow((void **)&c.nrm64, c.cap_nrm, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
@@ -585,6 +592,7 @@ int pccm_set_normals_deferred(pccm_ctx *ctx, int which, const void *nrm, int64_t
     for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;
     ctx->epoch++;
     c.nrm_exact32 = false;
+    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
     int rc = grow((void **)&c.nrm64, c.cap_nrm, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
     if ((rc = grow((void **)&c.nrm32, c.cap_nrm32, (size_t)n * sizeof(float4)))) return rc;
@@ -646,6 +654,7 @@ int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dt
     if (n != c.n) return fail(PCCM_E_ARG, "cloud %d has %lld points but %lld colours", which, (long long)c.n, (long long)n);
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     c.n_rgb = 0;
+    c.ssim_attrs &= ~PCCM_SSIM_COLOR;
     ctx->rgb_gen++;
     int rc = grow((void **)&c.rgb64, c.cap_rgb, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
@@ -680,6 +689,7 @@ int pccm_set_colors_u8(pccm_ctx *ctx, int which, const unsigned char *rgb, int64
     if (n != c.n) return fail(PCCM_E_ARG, "cloud %d has %lld points but %lld colours", which, (long long)c.n, (long long)n);
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     c.n_rgb = 0;
+    c.ssim_attrs &= ~PCCM_SSIM_COLOR;
     ctx->rgb_gen++;
     int rc = grow((void **)&c.rgb64, c.cap_rgb, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
@@ -957,6 +967,39 @@ int pccm_get_normals(pccm_ctx *ctx, int which, double *out)
     { int rcn = normals_ready(ctx, c); if (rcn) return rcn; }
     if (c.n_nrm <= 0) return fail(PCCM_E_STATE, "cloud %d has no normals", which);
     { int rcd = d2h(ctx, out, c.nrm64, (size_t)c.n_nrm * 3 * sizeof(double)); if (rcd) return rcd; }
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
+}
+
+int pccm_ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
+{
+    CHECK_CTX(ctx);
+    if (built) *built = 0;
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (k < 2 || k > 64) return fail(PCCM_E_ARG, "PointSSIM neighbourhoods have 2..64 points, not %d", k);
+    if (attrs <= 0 || attrs > 15) return fail(PCCM_E_ARG, "bad PointSSIM attribute mask %d", attrs);
+    Cloud &c = ctx->cloud[which];
+    if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    if (attrs & PCCM_SSIM_NORMAL) {
+        if (!ctx->capturing) { int rcn = normals_ready(ctx, c); if (rcn) return rcn; }
+        if (c.n_nrm != c.n || c.nrm_deferred) return fail(PCCM_E_STATE, "PointSSIM normal features need the normals of cloud %d", which);
+    }
+    if ((attrs & PCCM_SSIM_COLOR) && c.n_rgb != c.n) return fail(PCCM_E_STATE, "PointSSIM colour features need the colours of cloud %d", which);
+    return ssim_features(ctx, which, k, attrs, built);    // (what is there already needs no work, and may be asked for while capturing)
+}
+
+int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    if (attr != PCCM_SSIM_GEOMETRY && attr != PCCM_SSIM_NORMAL && attr != PCCM_SSIM_CURVATURE && attr != PCCM_SSIM_COLOR)
+        return fail(PCCM_E_ARG, "one PointSSIM attribute expected, not %d", attr);
+    const Cloud &c = ctx->cloud[which];
+    if (!(c.ssim_attrs & attr)) return fail(PCCM_E_STATE, "cloud %d has no PointSSIM features of attribute %d", which, attr);
+    const int a = attr == PCCM_SSIM_GEOMETRY ? 0 : attr == PCCM_SSIM_NORMAL ? 1 : attr == PCCM_SSIM_CURVATURE ? 2 : 3;
+    { int rcd = d2h(ctx, out, c.ssim64 + (size_t)a * c.n, (size_t)c.n * sizeof(double)); if (rcd) return rcd; }
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     return PCCM_OK;
 }
@@ -1307,6 +1350,29 @@ static int check_angular(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &s
     return PCCM_OK;
 }
 
+// PCCM_METRIC_SSIM_*: both clouds' feature columns of the attribute, made at the same k (pccm_ssim_features)
+static int check_ssim(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int metric)
+{
+    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "PointSSIM similarity is not defined for the self search");
+    if (res.ties == PCCM_TIES_MEAN) return fail(PCCM_E_STATE, "PointSSIM similarity is not defined under PCCM_TIES_MEAN");
+    const int bit = 1 << (metric - PCCM_METRIC_SSIM_GEOMETRY);
+    if (!(it.ssim_attrs & bit) || !(se.ssim_attrs & bit) || it.ssim_k != se.ssim_k)
+        return fail(PCCM_E_STATE, "PointSSIM similarity needs both clouds' features at the same k (pccm_ssim_features)");
+    return PCCM_OK;
+}
+
+// the feature column of a PCCM_METRIC_SSIM_* metric
+static const double *ssim_column(const Cloud &c, int metric)
+{
+    return c.ssim64 + (size_t)(metric - PCCM_METRIC_SSIM_GEOMETRY) * c.n;
+}
+
+// columns that compare a row with its matched row (PCCM_METRIC_ANGULAR, PCCM_METRIC_SSIM_*): normal_mode does not apply
+static bool matched_column(int metric)
+{
+    return metric == PCCM_METRIC_ANGULAR || is_ssim_metric(metric);
+}
+
 int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
 {
     CHECK_CTX(ctx);
@@ -1349,6 +1415,14 @@ static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode,
             *dev = (const double *)ctx->tie[dir].ang.p;
             return PCCM_OK;
         }
+        if ((rc = ensure_plain(ctx, *res, true))) return rc;
+        if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
+        if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, PCCM_NORMAL_NEIGHBOUR, (double *)vb.p, nullptr))) return rc;
+        *dev = (const double *)vb.p;
+        return PCCM_OK;
+    }
+    if (is_ssim_metric(metric)) {
+        if ((rc = check_ssim(ctx, dir, *it, *se, *res, metric))) return rc;
         if ((rc = ensure_plain(ctx, *res, true))) return rc;
         if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
         if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, PCCM_NORMAL_NEIGHBOUR, (double *)vb.p, nullptr))) return rc;
@@ -1467,10 +1541,12 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
             if ((rc = ensure_plain(ctx, *res, false))) return rc;
             dev = res->d2;
         }
-    } else if (metric == PCCM_METRIC_ANGULAR) {
+    } else if (matched_column(metric)) {
         // a plain column: made by the tie pass under PCCM_TIES_MEAN, else by a k_point_jobs job that reads the matched rows
         // from the plain idx column or straight from matched records (prefetch_many has made sure one of them holds them)
-        if ((rc = check_angular(ctx, dir, *it, *se))) return rc;
+        // (PCCM_METRIC_SSIM_*: the same job on the two clouds' feature columns instead of their normals)
+        const bool ssim = is_ssim_metric(metric);
+        if ((rc = ssim ? check_ssim(ctx, dir, *it, *se, *res, metric) : check_angular(ctx, dir, *it, *se))) return rc;
         if (res->ties == PCCM_TIES_MEAN) {
             if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
             dev = (const double *)ctx->tie[dir].ang.p;
@@ -1480,9 +1556,11 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
             if ((rc = ensure(ctx, s.val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
             dev = (const double *)s.val.p;
             if (ns > 0) {
-                if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane or angular columns per call");
+                if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane, angular or PointSSIM columns per call");
                 PointJob &P = pj.j[pj.njobs];
-                P.q64 = it->xyz64; P.r64 = se->xyz64; P.nrm = se->nrm64; P.inrm = it->nrm64;
+                P.q64 = it->xyz64; P.r64 = se->xyz64;
+                P.nrm = ssim ? ssim_column(*se, metric) : se->nrm64;
+                P.inrm = ssim ? ssim_column(*it, metric) : it->nrm64;
                 P.idx = recs ? nullptr : res->idx;
                 P.recs = recs ? (const float4 *)res->rec.p : nullptr;
                 P.c64 = P.cn64 = nullptr;
@@ -1592,7 +1670,7 @@ static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode
 {
     for (auto &s : ctx->slots)
         if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric &&
-            (metric == PCCM_METRIC_D1 || metric == PCCM_METRIC_ANGULAR || s.mode == normal_mode) &&
+            (metric == PCCM_METRIC_D1 || matched_column(metric) || s.mode == normal_mode) &&
             s.gen == ctx->nn_gen[dir])
             return &s;
     return nullptr;
@@ -1670,7 +1748,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (metrics[k] == PCCM_METRIC_D1 || dirs[k] == PCCM_DIR_SELF) continue;
         NNResult &res = ctx->nn[dirs[k]];
-        if (metrics[k] == PCCM_METRIC_ANGULAR) {
+        if (matched_column(metrics[k])) {
             if (!res.valid || res.ties == PCCM_TIES_MEAN || res.plain_valid ||
                 (res.rec_valid && res.rec_layout == 1 && res.rec_stride == 2 && !res.no_rows))
                 continue;
@@ -1692,7 +1770,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
         ReduceSlot *s = slot_free(ctx, fresh, nfresh);
-        if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 8 live columns in one batch");
+        if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 16 live columns in one batch");
         if (s->pending && !ctx->capturing && s->wait_ev) { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
         s->pending = false;
         int rc = slot_prepare(ctx, *s, dirs[k], metrics[k], normal_modes[k], want_units, pj, uj);

@@ -74,6 +74,11 @@ struct Cloud {
     double maxabs = 0.0;
     double bb_min[3] = {0, 0, 0}, bb_max[3] = {0, 0, 0};   // bounding box (fp64 coordinates)
     uint64_t version = 0;       // bumped by pccm_set_cloud (grid caches key on it)
+    // PointSSIM features (pccm_ssim_features): [4][n] fp64 columns by attribute bit (geometry, normal, curvature, colour), valid for
+    // the attributes in ssim_attrs at neighbourhood size ssim_k; a bit is cleared when what it was made from changes
+    double *ssim64 = nullptr;
+    size_t cap_ssim = 0;
+    int ssim_attrs = 0, ssim_k = 0;
     double solo_scale = 1.0;    // cell-edge factor of a grid over this cloud alone (grid_ensure_solo), decided for ...
     uint64_t solo_scale_version = ~0ull;   // ... this version of the cloud
 };
@@ -243,6 +248,7 @@ struct pccm_ctx {
     // scratch
     pccm::DevBuf part_b1, part_g, part_b2, val, stats, staging, counters;
     pccm::DevBuf rescan_part;             // k2b_fallback's split regime: partial minima per (query, workgroup)
+    pccm::DevBuf ssim_scratch;            // pccm_ssim_features: neighbour rows [n][k] + curvatures [n]
     pccm::DevBuf tail_sync;               // k_grid_tail: retired-entry counts + ticket, for the normal and the self pass
     bool tail_sync_clean = false;
     pccm::DevBuf color_cols, color_idx;   // colour pass: squares as three columns / caller-supplied neighbour rows
@@ -277,7 +283,7 @@ struct pccm_ctx {
     bool bins_clean = false;   // the build's bin cursors (head of g_bins) are zero on the stream
     int want_idx = 1;                      // pccm_nn_want_idx: searches store the matched row with every result
     int fuse_mode[3] = {-1, -1, -1};       // pccm_nn_fuse: normal mode of the D2 projection fused into the search, per direction
-    pccm::ReduceSlot slots[8];
+    pccm::ReduceSlot slots[16];           // (a report with every PointSSIM row holds up to 15 columns at once)
     uint64_t nn_gen[3] = {1, 1, 1};
     // hipGraph capture of a step (pccm_graph_*): epoch changes whenever inputs, shard or any device
     // buffer a captured kernel may reference changes, which invalidates every recorded graph
@@ -378,6 +384,7 @@ int spatial_order(pccm_ctx *ctx, Cloud &c);      // fills Cloud::sp (ingest; no-
 int grid_decide(pccm_ctx *ctx, bool *hostile);   // geometry decision for the current pair (cached per pair)
 int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; isolation verdict (cached per pair)
 int estimate_normals(pccm_ctx *ctx, int which, int k);
+int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built);   // the checks are pccm_ssim_features'
 int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int normal_mode, double out[8]);
 // PCCM_TIES_MEAN producer: for the ns queries q_begin.. of direction dir (matched rows idx, squared distances d2 or null = formed
 // from idx) the ascending-row mean of all equidistant nearest points -> pos[ns][3], k[ns]; nrm / rgb likewise when snrm / srgb;
@@ -428,11 +435,25 @@ __device__ __forceinline__ double angular_similarity(const double *a, const doub
     return __dsub_rn(1.0, __ddiv_rn(__dmul_rn(2.0, acos(c)), M_PI));
 }
 
+// PCCM_METRIC_SSIM_*: a point's feature a against its matched point's b (include/pccm.h), every operation separately rounded
+__device__ __forceinline__ double ssim_similarity(double a, double b)
+{
+    const double num = fabs(__dsub_rn(a, b));
+    const double den = __dadd_rn(fmax(fabs(a), fabs(b)), 0x1.0p-52);
+    return __dsub_rn(1.0, __ddiv_rn(num, den));
+}
+
+__host__ __device__ __forceinline__ bool is_ssim_metric(int metric)
+{
+    return metric >= PCCM_METRIC_SSIM_GEOMETRY && metric <= PCCM_METRIC_SSIM_COLOR;
+}
+
 struct PointJob {               // one D2 / PROJ / ANGULAR column (k_point_jobs)
     const double *q64, *r64, *nrm;
     const double *c64, *cn64;   // PCCM_TIES_MEAN: per shard row the virtual neighbour / its averaged normal (null: gather via idx)
-    const double *inrm;         // PCCM_METRIC_ANGULAR: the iterating cloud's normals (nrm: the searched cloud's)
-    const float4 *recs;         // PCCM_METRIC_ANGULAR: matched records {x, y, z, row} (NNResult::rec_layout 1) instead of idx, or null
+    const double *inrm;         // PCCM_METRIC_ANGULAR: the iterating cloud's normals (nrm: the searched cloud's); PCCM_METRIC_SSIM_*:
+                                // the iterating cloud's feature column (nrm: the searched cloud's)
+    const float4 *recs;         // PCCM_METRIC_ANGULAR / SSIM_*: matched records {x, y, z, row} (NNResult::rec_layout 1) instead of idx, or null
     const int32_t *idx;
     int64_t q_begin;
     int metric, normal_mode;

@@ -155,6 +155,7 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
 // evaluates on FMA-capable hosts; see oracle/pccm_oracle.c for how that was pinned.
 // HBM/gather bound: 24 (q) + 4 (idx) + 24 (r, gathered) + 24 (normal) + 8 (out) bytes per row.
 // PCCM_METRIC_ANGULAR (the pick's column): the own normal inrm[gi] against the matched row's nrm[j] -- 24 + 4 + 24 + 8 bytes.
+// PCCM_METRIC_SSIM_*: inrm / nrm are the two clouds' feature columns, the own feature against the matched row's -- 8 + 4 + 8 + 8.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_point_metric(const double *__restrict__ q64, int64_t q_begin, int64_t ns,
                                                       const double *__restrict__ r64,
@@ -170,6 +171,10 @@ __global__ __launch_bounds__(256) void k_point_metric(const double *__restrict__
     const int64_t j = idx[i];
     if (metric == PCCM_METRIC_ANGULAR) {
         val[i] = angular_similarity(inrm + 3 * gi, nrm + 3 * j);
+        return;
+    }
+    if (is_ssim_metric(metric)) {
+        val[i] = ssim_similarity(inrm[gi], nrm[j]);
         return;
     }
     const double *r = c64 ? c64 + 3 * i : r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
@@ -198,7 +203,9 @@ int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const N
     ProfScope ps(ctx, PCCM_K_POINT);
     dim3 grid((unsigned)((ns + 255) / 256));
     PCCM_LAUNCH(ctx, k_point_metric, grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, ns, se.xyz64, res.idx,
-                       se.nrm64, metric, normal_mode, out_val, out_err, c64, cn64, it.nrm64);
+                       is_ssim_metric(metric) ? se.ssim64 + (size_t)(metric - PCCM_METRIC_SSIM_GEOMETRY) * se.n : se.nrm64, metric,
+                       normal_mode, out_val, out_err, c64, cn64,
+                       is_ssim_metric(metric) ? it.ssim64 + (size_t)(metric - PCCM_METRIC_SSIM_GEOMETRY) * it.n : it.nrm64);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -227,6 +234,11 @@ __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
     if (J.metric == PCCM_METRIC_ANGULAR) {             // the own normal against the matched row's: 24 + 4 (or 16) + 24 + 8 bytes
         const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
         J.val[i] = angular_similarity(J.inrm + 3 * gi, J.nrm + 3 * j);
+        return;
+    }
+    if (is_ssim_metric(J.metric)) {                    // the own feature against the matched row's: 8 + 4 (or 16) + 8 + 8 bytes
+        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
+        J.val[i] = ssim_similarity(J.inrm[gi], J.nrm[j]);
         return;
     }
     const int64_t j = J.idx[i];

@@ -1,7 +1,7 @@
 """Command line -- same flags and report text as ``python -m open_pcc_metric`` (handler.py:4-71).
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
-                                  [--point-to-plane] [--plane-to-plane] [--csv]
+                                  [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -13,7 +13,9 @@ colour rows independent of the order of the points; D1 rows are the same either 
 --point-to-plane asks for them (k = 30 covariance normals, as Open3D's estimate_normals does at
 cloud_pair.py:61-64).  ``--plane-to-plane`` (no counterpart in the reference) adds the angular similarity rows of Alexiou &
 Ebrahimi (ICME 2018) after all others; they compare each point's normal with its matched point's, so they too estimate the
-normals files lack.  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+normals files lack.  ``--point-ssim geometry|normal|curvature|color`` (repeatable; no counterpart in the reference) adds the
+PointSSIM rows of Alexiou & Ebrahimi (ICME Workshops 2020) after those, over neighbourhoods of ``--ssim-neighbours`` points
+("PointSSIM").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -33,6 +35,12 @@ import click
               help="Report plane-to-plane angular similarity as well (1: parallel or antiparallel normals, 0: perpendicular), "
                    "after all other rows; with --hausdorff also its worst point.  Compares each point's normal with its matched "
                    "point's normal: --normal-index does not apply.  Normals missing from a file are estimated.")
+@click.option("--point-ssim", "point_ssim", type=click.Choice(["geometry", "normal", "curvature", "color"]), multiple=True,
+              help="Report the PointSSIM structural similarity of this attribute as well (may be repeated), after all other "
+                   "rows: 1 - |F_A - F_B| / max(|F_A|, |F_B|) of each point's neighbourhood variance and its matched point's, "
+                   "averaged.  Normals missing from a file are estimated; color needs colours in both files.")
+@click.option("--ssim-neighbours", "ssim_neighbours", type=click.IntRange(2, 64), default=12, show_default=True,
+              help="Points per PointSSIM neighbourhood (the point itself included).")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -46,18 +54,20 @@ import click
 @click.option("--ties", type=click.Choice(["pick", "mean"]), default="pick", show_default=True,
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
-def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, csv, device, engine, normal_index, extent, tie_exposure,
-        ties) -> None:
+def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, csv, device, engine,
+        normal_index, extent, tie_exposure, ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import CalculateOptions, transform_options
+    from .options import CalculateOptions, check_point_ssim, transform_options
 
     ocloud_cloud = read_point_cloud(ocloud)
-    options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane)
+    options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
+                               point_ssim=point_ssim, ssim_neighbours=ssim_neighbours)
     cloud_pair = None
     for path in pcloud:
         pcloud_cloud = read_point_cloud(path)
+        check_point_ssim(options, ocloud_cloud, pcloud_cloud, ties=ties)       # (before the GPU context, for every processed cloud)
         if cloud_pair is None:
             # (clouds read from files are freed while the GPU context works on -- with several decoded clouds, when the next one
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)

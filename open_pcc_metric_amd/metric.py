@@ -125,6 +125,21 @@ class AngularSimilarities(PrimaryMetric, DirectionalMetric):     # no counterpar
         self.value = _side(self, cloud_pair.get_left_angular_similarities, cloud_pair.get_right_angular_similarities)
 
 
+class SSIMSimilarities(PrimaryMetric, DirectionalMetric):        # no counterpart in the reference (options.py: point_ssim)
+    """Per point of the iterating cloud, the PointSSIM similarity of one attribute's feature and its matched point's
+    (include/pccm.h, PCCM_METRIC_SSIM_*): 1 - |a - b| / (max(|a|, |b|) + 2^-52)."""
+    def __init__(self, is_left: bool, attribute: str, k: int = 12):
+        super().__init__(is_left)
+        self.attribute, self.k = attribute, int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.attribute, self.is_left, self.k)
+
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, lambda: cloud_pair.get_left_ssim_similarities(self.attribute, self.k),
+                           lambda: cloud_pair.get_right_ssim_similarities(self.attribute, self.k))
+
+
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, cloud_pair: CloudPair) -> None:
@@ -240,6 +255,52 @@ class MinAngularSimilarity(_OverAngular):
         column = angular_similarities.value
         fused = getattr(column, "_reduced", None)             # a device column: what np.min would dispatch to, called directly
         self.value = fused()[1] if fused is not None else np.min(column, axis=0)
+
+
+class _PointSSIM(SecondaryMetric, DirectionalMetric):
+    """PointSSIM of one attribute and direction (Alexiou & Ebrahimi, ICME Workshops 2020; INTEGRATION.md, "PointSSIM"): the
+    mean of the per-point similarities (sum / n, NumPy's pairwise sum)."""
+    attribute: str
+    _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+
+    def __init__(self, is_left: bool, k: int = 12):
+        super().__init__(is_left)
+        self.k = int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.k)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"ssim_similarities": SSIMSimilarities(is_left=self.is_left, attribute=self.attribute, k=self.k)}
+
+    def calculate(self, ssim_similarities: SSIMSimilarities) -> None:
+        column = ssim_similarities.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
+        total = fused()[0] if fused is not None else None
+        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+
+
+class GeometrySSIM(_PointSSIM):
+    """Variance of the distances to the k - 1 nearest other points."""
+    attribute = "geometry"
+
+
+class NormalSSIM(_PointSSIM):
+    """Variance of the angular similarities of the normals of the k - 1 nearest other points with the point's own."""
+    attribute = "normal"
+
+
+class CurvatureSSIM(_PointSSIM):
+    """Variance of the curvatures (smallest eigenvalue / trace of the k-NN covariance) over the neighbourhood."""
+    attribute = "curvature"
+
+
+class ColorSSIM(_PointSSIM):
+    """Variance of the luma (BT.709 "ycc" Y) over the neighbourhood."""
+    attribute = "color"
+
+
+SSIM_CLASSES = {"geometry": GeometrySSIM, "normal": NormalSSIM, "curvature": CurvatureSSIM, "color": ColorSSIM}
 
 
 def _peak_of(cloud_extent):

@@ -14,22 +14,66 @@ every row above:
 
   plane_to_plane         AngularSimilarity L/R/sym
   plane_to_plane & hd    MinAngularSimilarity L/R/sym
+
+and, with ``point_ssim`` (no counterpart in the reference: PointSSIM, Alexiou & Ebrahimi, ICME Workshops 2020), after every row
+above and in this order whatever order the caller gave:
+
+  geometry               GeometrySSIM L/R/sym
+  normal                 NormalSSIM L/R/sym
+  curvature              CurvatureSSIM L/R/sym
+  color                  ColorSSIM L/R/sym
 """
 from __future__ import annotations
 
 import typing
 
-from .metric import (AbstractMetric, AngularSimilarity, ColorMSE, ColorPSNR, GeoHausdorffDistance, GeoHausdorffDistancePSNR,
-                     GeoMSE, GeoPSNR, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance, SymmetricMetric)
+from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMSE, ColorPSNR, GeoHausdorffDistance,
+                     GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
+                     SymmetricMetric)
+
+SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
+SSIM_MIN_K, SSIM_MAX_K = 2, 64
 
 
 class CalculateOptions:
     def __init__(self, color: typing.Optional[str] = None, hausdorff: bool = False,
-                 point_to_plane: bool = False, plane_to_plane: bool = False):
+                 point_to_plane: bool = False, plane_to_plane: bool = False,
+                 point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
         self.plane_to_plane = plane_to_plane
+        if isinstance(point_ssim, str):
+            point_ssim = (point_ssim,)
+        wanted = set(point_ssim or ())
+        unknown = sorted(str(a) for a in wanted - set(SSIM_ATTRIBUTES))
+        if unknown:
+            raise ValueError(f"unknown PointSSIM attribute(s) {', '.join(map(repr, unknown))}: "
+                             f"choose from {', '.join(SSIM_ATTRIBUTES)}")
+        if isinstance(ssim_neighbours, bool) or int(ssim_neighbours) != ssim_neighbours \
+                or not SSIM_MIN_K <= int(ssim_neighbours) <= SSIM_MAX_K:
+            raise ValueError(f"ssim_neighbours must be an integer in {SSIM_MIN_K}..{SSIM_MAX_K}, not {ssim_neighbours!r}")
+        self.point_ssim = tuple(a for a in SSIM_ATTRIBUTES if a in wanted)
+        self.ssim_neighbours = int(ssim_neighbours)
+
+
+def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
+                     ties: str = "pick", group=None) -> None:
+    """Raise ``ValueError`` when the PointSSIM rows ``options`` asks for cannot be computed for this pair -- before any GPU
+    context exists (the command line calls it before it makes the pair; CloudPair checks the same before any GPU work)."""
+    attrs = getattr(options, "point_ssim", ())
+    if not attrs:
+        return
+    if ties != "pick":
+        raise ValueError("PointSSIM rows are not defined for ties='mean'")
+    if group is not None:
+        raise ValueError("PointSSIM rows are not available for sharded pairs (group=)")
+    from .cloud_pair import _has_colors, _has_normals
+    clouds = (origin_cloud, reconst_cloud)
+    if "color" in attrs and not all(_has_colors(c) for c in clouds):
+        raise ValueError("ColorSSIM needs the colours of both clouds")
+    if "normal" in attrs and not estimate_normals and not all(_has_normals(c) for c in clouds):
+        raise ValueError("NormalSSIM needs the normals of both clouds (or estimate_normals=True)")
 
 
 def _sides(cls, **kw):
@@ -63,4 +107,9 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
         metrics += _sides(AngularSimilarity) + [_sym(AngularSimilarity, True)]
         if options.hausdorff:
             metrics += _sides(MinAngularSimilarity) + [_sym(MinAngularSimilarity, True)]
+    for attribute in SSIM_ATTRIBUTES:
+        if attribute in (getattr(options, "point_ssim", None) or ()):
+            # higher is better: the symmetric rows report the smaller side
+            cls, kw = SSIM_CLASSES[attribute], dict(k=getattr(options, "ssim_neighbours", 12))
+            metrics += _sides(cls, **kw) + [_sym(cls, True, **kw)]
     return metrics
