@@ -174,7 +174,7 @@ static void free_nn(NNResult &r)
     free_buf(r.flag_thr);
     free_buf(r.tail);
     free_buf(r.rec);
-    r.rec_valid = r.plain_valid = false;
+    r.form = NNForm{};
     if (r.idx) (void)hipFree(r.idx);
     if (r.d2) (void)hipFree(r.d2);
     r.idx = nullptr;
@@ -741,7 +741,7 @@ static int color_operands(pccm_ctx *ctx, int dir, int scheme, const int32_t *row
         if (!res.valid) return fail(PCCM_E_STATE, "run pccm_nn for direction %d first", dir);
         if (res.begin != 0 || res.end != it.n)
             return fail(PCCM_E_STATE, "the search of direction %d was sharded: pass the gathered neighbour rows", dir);
-        if (!res.plain_valid && res.rec_valid && res.rec_layout == 1 && res.rec_stride == 2 && !res.no_rows) {
+        if (res.form.matched_in_place()) {
             *drows = nullptr;
             *drecs = (const float4 *)res.rec.p;
         } else {
@@ -1080,10 +1080,7 @@ static int prepare_nn(pccm_ctx *ctx, int dir, int *trivial)
         int rc2 = ensure(ctx, res.rec, (size_t)(ns > 0 ? ns : 1) * sizeof(double4));   // 32-byte result records (grid engine)
         if (rc2) return rc2;
     }
-    res.rec_valid = false;
-    res.no_rows = false;
-    res.plain_valid = res.plain_d2_valid = ns <= 0;          // an empty shard has nothing to unpack
-    res.fused_mode = -1;
+    res.form = ns <= 0 ? NNForm::columns() : NNForm{};      // an empty shard has nothing to unpack
     res.ties = dir == PCCM_DIR_SELF ? PCCM_TIES_PICK : ctx->ties;
     res.stats[0] = res.stats[1] = res.stats[2] = 0;
     *trivial = 0;
@@ -1094,7 +1091,7 @@ static int prepare_nn(pccm_ctx *ctx, int dir, int *trivial)
             PCCM_HIP(hipMemsetAsync(res.d2, 0, (size_t)ns * sizeof(double), ctx->stream));
         }
         PCCM_HIP(hipMemsetAsync(res.nflag_dev, 0, 2 * sizeof(uint32_t), ctx->stream));
-        res.plain_valid = res.plain_d2_valid = true;
+        res.form = NNForm::columns();
         *trivial = 1;
     }
     return PCCM_OK;
@@ -1136,7 +1133,7 @@ static int run_nn(pccm_ctx *ctx, int ndirs, const int *dirs, int engine)
         for (int k = 0; k < ntodo; ++k) {
             const Cloud *it, *se;
             if ((rc = dir_clouds(ctx, todo[k], &it, &se))) return rc;
-            ctx->nn[todo[k]].plain_valid = ctx->nn[todo[k]].plain_d2_valid = true;   // the brute-force engine writes the plain columns
+            ctx->nn[todo[k]].form = NNForm::columns();            // the brute-force engine writes the plain columns
             if ((rc = nn_brute(ctx, *it, *se, todo[k] == PCCM_DIR_SELF, ctx->nn[todo[k]]))) return rc;
         }
     }
@@ -1171,28 +1168,26 @@ static int need_nn(pccm_ctx *ctx, int dir, const Cloud **it, const Cloud **se, N
 // wants columns (getters, colour kernels, the separate point kernel)
 static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx)
 {
-    if (res.plain_valid || (!need_idx && res.plain_d2_valid)) return PCCM_OK;
-    if (!res.rec_valid) return fail(PCCM_E_STATE, "no nearest-neighbour result to read");
-    if (need_idx && ((res.rec_stride != 4 && res.rec_layout != 1) || res.no_rows)) {   // (matched records carry the row, the voxel-brick search's excepted)
+    if (res.form.plain_ready(need_idx)) return PCCM_OK;
+    if (!res.form.has_records()) return fail(PCCM_E_STATE, "no nearest-neighbour result to read");
+    const int dir = (int)(&res - ctx->nn);
+    if (need_idx && res.form.rows_need_repeat()) {
         // the search ran without the matched rows (pccm_nn_want_idx off) and now somebody asks for them: run it again
         // for this direction with the rows on -- same results, 32-byte records; the clouds and the grid are resident
         if (ctx->capturing) {
             ctx->capture_failed = true;
             return fail(PCCM_E_STATE, "matched rows are needed during graph capture: switch pccm_nn_want_idx on before the search");
         }
-        const int dir = (int)(&res - ctx->nn);
         PathScope path(ctx, 1u << dir);
         int rc = nn_grid(ctx, 1, &dir, /*force_idx=*/1);
         if (rc) return rc;
     }
-    const bool rows = (res.rec_stride == 4 || res.rec_layout == 1) && !res.no_rows;
-    const int udir = (int)(&res - ctx->nn);
-    const Cloud &uit = ctx->cloud[udir == PCCM_DIR_RIGHT ? 1 : 0];
-    int rc = launch_unpack(ctx, (const double *)res.rec.p, res.rec_stride, res.rec_layout, uit.xyz32r, res.begin, res.end - res.begin,
+    const bool rows = res.form.has_rows();
+    const Cloud &uit = ctx->cloud[dir == PCCM_DIR_RIGHT ? 1 : 0];
+    int rc = launch_unpack(ctx, (const double *)res.rec.p, res.form.stride(), res.form.layout(), uit.xyz32r, res.begin, res.end - res.begin,
                            rows ? res.idx : nullptr, res.d2);
     if (rc) return rc;
-    res.plain_d2_valid = true;
-    res.plain_valid = rows;
+    res.form.plain = rows ? NNForm::kPlainAll : NNForm::kPlainD2;
     return PCCM_OK;
 }
 
@@ -1519,6 +1514,58 @@ static int wait_slot(pccm_ctx *ctx, const ReduceSlot *s)
     return PCCM_OK;
 }
 
+// Where a reduction column is read from (given the form and tie policy of the direction's search), and what has to happen before
+// it can be bound.  slot_prepare binds from the first answer; prefetch_many acts on the second for every request before binding
+// any: a repeated search rewrites the records, and a column bound to them earlier would read them through the wrong stride.
+struct ColumnSource {
+    enum From {
+        kRecords,         // a field of the result records: off (0: squared distance, 1: projection), square, defer (UnitJob)
+        kPlainD2,         // the plain d2 column (no records: the engine wrote the plain columns)
+        kPointJob,        // a k_point_jobs job that reads the matched rows from the plain idx column, or from matched records (recs)
+        kTieColumn,       // the tie pass's column (PCCM_TIES_MEAN)
+    } from = kPointJob;
+    // the plain columns: none needed or they are there; the binder unpacks them; or they come before any column of the batch is
+    // bound.  Which columns the binder unpacks (an unfused projection over stride-4 records) is today's split: it decides which
+    // pccm_nn_path log lists the k_unpack -- the binder's joins the batch's log (PCCM_PATH_REDUCE), the first pass runs before it
+    enum Prep { kReady, kBinderUnpacks, kPlainFirst } prep = kReady;
+    int off = 0, square = 0, defer = 0;
+    bool recs = false;
+};
+
+static ColumnSource column_source(const pccm_ctx *ctx, int dir, int metric, int normal_mode)
+{
+    const NNResult &res = ctx->nn[dir];
+    const NNForm &f = res.form;
+    const bool mean = res.ties == PCCM_TIES_MEAN;
+    ColumnSource c;
+    if (!res.valid) return c;                              // (slot_prepare reports what is missing)
+    if (metric == PCCM_METRIC_D1) {
+        c.from = f.has_records() ? ColumnSource::kRecords : ColumnSource::kPlainD2;
+        if (f.layout() == 1) c.defer = 3;                  // matched records: the reduction forms the distance (NNOut::layout)
+        return c;
+    }
+    if (dir == PCCM_DIR_SELF) return c;
+    if (matched_column(metric)) {                          // the matched rows in place, or from the plain idx column
+        if (mean) c.from = ColumnSource::kTieColumn;
+        else if (f.matched_in_place()) c.recs = true;
+        else if (!f.plain_ready(true)) c.prep = ColumnSource::kPlainFirst;
+        return c;
+    }
+    if (!mean && f.holds_projection(normal_mode)) {       // (under PCCM_TIES_MEAN the records hold the pick's projection)
+        c.from = ColumnSource::kRecords;
+        c.off = 1;
+        c.square = metric == PCCM_METRIC_D2 ? 1 : 0;       // metric.py:179: the square of the stored projection
+        // ... which the reduction forms itself from a matched record (NNOut::layout): with the normal of the query's row
+        // (streamed) or of the matched row the record carries (gathered: what a separate point pass would gather too)
+        if (f.layout() == 1)
+            c.defer = (ctx->cloud[dir == PCCM_DIR_LEFT ? 1 : 0].nrm_exact32 ? 1 : 2) + (normal_mode == PCCM_NORMAL_NEIGHBOUR ? 3 : 0);
+        return c;
+    }
+    if (!f.plain_ready(true))                              // (the virtual neighbours of PCCM_TIES_MEAN need them too)
+        c.prep = mean || f.rows_need_repeat() ? ColumnSource::kPlainFirst : ColumnSource::kBinderUnpacks;
+    return c;
+}
+
 // bookkeeping + buffers of one slot; the kernels are launched for all new slots together (slots_launch)
 static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int normal_mode, bool want_units, PointJobs &pj,
                         UnitJobs &uj)
@@ -1528,80 +1575,51 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     int rc = need_nn(ctx, dir, &it, &se, &res);
     if (rc) return rc;
     const int64_t ns = res->end - res->begin;
-    // where the column lives: a field of the grid engine's 32-byte result records (squared distance, or the signed
-    // projection fused into the search by pccm_nn_fuse), or a plain column (brute-force engine; unfused projection)
-    const double *dev = nullptr;
-    int stride = 1, square = 0, defer = 0;
-    if (metric == PCCM_METRIC_D1) {
-        if (res->rec_valid) {
-            dev = (const double *)res->rec.p;
-            stride = res->rec_stride;
-            if (res->rec_layout == 1) defer = 3;             // matched records: the reduction forms the distance (NNOut::layout)
-        } else {
-            if ((rc = ensure_plain(ctx, *res, false))) return rc;
-            dev = res->d2;
-        }
-    } else if (matched_column(metric)) {
-        // a plain column: made by the tie pass under PCCM_TIES_MEAN, else by a k_point_jobs job that reads the matched rows
-        // from the plain idx column or straight from matched records (prefetch_many has made sure one of them holds them)
-        // (PCCM_METRIC_SSIM_*: the same job on the two clouds' feature columns instead of their normals)
-        const bool ssim = is_ssim_metric(metric);
+    const bool matched = matched_column(metric), ssim = is_ssim_metric(metric);
+    if (matched) {
         if ((rc = ssim ? check_ssim(ctx, dir, *it, *se, *res, metric) : check_angular(ctx, dir, *it, *se))) return rc;
-        if (res->ties == PCCM_TIES_MEAN) {
-            if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
-            dev = (const double *)ctx->tie[dir].ang.p;
-        } else {
-            const bool recs = !res->plain_valid && res->rec_valid && res->rec_layout == 1 && res->rec_stride == 2 && !res->no_rows;
-            if (!recs && (rc = ensure_plain(ctx, *res, true))) return rc;
-            if ((rc = ensure(ctx, s.val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
-            dev = (const double *)s.val.p;
-            if (ns > 0) {
-                if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane, angular or PointSSIM columns per call");
-                PointJob &P = pj.j[pj.njobs];
-                P.q64 = it->xyz64; P.r64 = se->xyz64;
-                P.nrm = ssim ? ssim_column(*se, metric) : se->nrm64;
-                P.inrm = ssim ? ssim_column(*it, metric) : it->nrm64;
-                P.idx = recs ? nullptr : res->idx;
-                P.recs = recs ? (const float4 *)res->rec.p : nullptr;
-                P.c64 = P.cn64 = nullptr;
-                P.q_begin = res->begin; P.metric = metric; P.normal_mode = PCCM_NORMAL_NEIGHBOUR; P.val = (double *)s.val.p;
-                pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;
-                pj.njobs++;
-            }
-        }
-    } else {
+    } else if (metric != PCCM_METRIC_D1) {
         if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
         if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
         if ((rc = check_normals(ctx, *it, *se, *res, normal_mode))) return rc;
-        if (res->rec_valid && !res->no_rows && res->ties != PCCM_TIES_MEAN &&      // (the records hold the pick's projection)
-            (res->fused_mode == normal_mode || (res->rec_layout == 1 && (normal_mode == PCCM_NORMAL_ROW || normal_mode == PCCM_NORMAL_NEIGHBOUR)))) {
-            dev = (const double *)res->rec.p + 1;
-            stride = res->rec_stride;
-            square = metric == PCCM_METRIC_D2 ? 1 : 0;       // metric.py:179: the square of the stored projection
-            // ... which this reduction forms itself from a matched record (NNOut::layout): with the normal of the query's row
-            // (streamed) or of the matched row the record carries (gathered: what a separate point pass would gather too)
-            if (res->rec_layout == 1) defer = (se->nrm_exact32 ? 1 : 2) + (normal_mode == PCCM_NORMAL_NEIGHBOUR ? 3 : 0);
-        } else {
-            if ((rc = ensure_plain(ctx, *res))) return rc;
-            if ((rc = ensure(ctx, s.val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
-            dev = (const double *)s.val.p;
-            if (ns > 0) {
-                if (pj.njobs >= 4) return fail(PCCM_E_ARG, "at most four unfused point-to-plane columns per call");
-                PointJob &P = pj.j[pj.njobs];
-                P.q64 = it->xyz64; P.r64 = se->xyz64; P.nrm = se->nrm64; P.idx = res->idx;
-                P.c64 = P.cn64 = P.inrm = nullptr;
-                P.recs = nullptr;
-                if (res->ties == PCCM_TIES_MEAN) {
-                    const bool nmean = normal_mode == PCCM_NORMAL_NEIGHBOUR;
-                    if ((rc = ensure_ties(ctx, dir, nmean, false))) return rc;
-                    P.c64 = (const double *)ctx->tie[dir].pos.p;
-                    if (nmean) P.cn64 = (const double *)ctx->tie[dir].nrm.p;
-                }
-                P.q_begin = res->begin; P.metric = metric; P.normal_mode = normal_mode; P.val = (double *)s.val.p;
-                pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;
-                pj.njobs++;
+    }
+    const ColumnSource src = column_source(ctx, dir, metric, normal_mode);
+    const double *dev = (const double *)res->rec.p;
+    int stride = 1;
+    switch (src.from) {
+    case ColumnSource::kRecords: stride = res->form.stride(); break;
+    case ColumnSource::kPlainD2: dev = res->d2; break;
+    case ColumnSource::kTieColumn:
+        if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
+        dev = (const double *)ctx->tie[dir].ang.p;
+        break;
+    case ColumnSource::kPointJob:
+        // (PCCM_METRIC_SSIM_*: the angular column's job on the two clouds' feature columns instead of their normals)
+        if (src.prep != ColumnSource::kReady && (rc = ensure_plain(ctx, *res, true))) return rc;
+        if ((rc = ensure(ctx, s.val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
+        dev = (const double *)s.val.p;
+        if (ns > 0) {
+            if (pj.njobs >= 4)
+                return fail(PCCM_E_ARG, matched ? "at most four unfused point-to-plane, angular or PointSSIM columns per call"
+                                                : "at most four unfused point-to-plane columns per call");
+            PointJob &P = pj.j[pj.njobs];
+            P.q64 = it->xyz64; P.r64 = se->xyz64;
+            P.nrm = ssim ? ssim_column(*se, metric) : se->nrm64;
+            P.inrm = !matched ? nullptr : ssim ? ssim_column(*it, metric) : it->nrm64;
+            P.idx = src.recs ? nullptr : res->idx;
+            P.recs = src.recs ? (const float4 *)res->rec.p : nullptr;
+            P.c64 = P.cn64 = nullptr;
+            if (!matched && res->ties == PCCM_TIES_MEAN) {
+                const bool nmean = normal_mode == PCCM_NORMAL_NEIGHBOUR;
+                if ((rc = ensure_ties(ctx, dir, nmean, false))) return rc;
+                P.c64 = (const double *)ctx->tie[dir].pos.p;
+                if (nmean) P.cn64 = (const double *)ctx->tie[dir].nrm.p;
             }
+            P.q_begin = res->begin; P.metric = metric; P.normal_mode = matched ? PCCM_NORMAL_NEIGHBOUR : normal_mode; P.val = (double *)s.val.p;
+            pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;
+            pj.njobs++;
         }
+        break;
     }
     s.dir = dir; s.metric = metric; s.mode = normal_mode;
     s.gen = ctx->nn_gen[dir];
@@ -1627,13 +1645,12 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     if (!s.ev) PCCM_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
     if (s.nunits > 0) {
         UnitCol col;
-        col.off = (stride >= 2 && metric != PCCM_METRIC_D1) ? 1 : 0;
-        col.square = square;
+        col.off = src.off;
+        col.square = src.square;
         col.out_units = want_units ? s.host : nullptr;
         col.out_blocks = s.host + 3 * s.nunits;
         col.out_tail = s.host + 3 * s.nunits + 3 * s.nblocks;
         // a second column over the same result records rides along with the job that already reads them
-        const double *base = stride >= 2 ? (const double *)res->rec.p : dev;
         UnitJob *host_job = nullptr;
         static const bool merge = [] {
             const char *e = PCCM_DIAG_ENV("PCCM_REDUCE_MERGE");
@@ -1641,18 +1658,18 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         }();
         if (stride >= 2 && merge)
             for (int k = 0; k < uj.njobs; ++k)
-                if (uj.j[k].stride >= 2 && uj.j[k].val == base && uj.j[k].ncols == 1 &&
-                    (uj.j[k].defer == defer || uj.j[k].defer == 3 || defer == 3))      // (one normal per job: row- and neighbour-indexed D2 do not share one)
+                if (uj.j[k].stride >= 2 && uj.j[k].val == dev && uj.j[k].ncols == 1 &&
+                    (uj.j[k].defer == src.defer || uj.j[k].defer == 3 || src.defer == 3))      // (one normal per job: row- and neighbour-indexed D2 do not share one)
                     host_job = &uj.j[k];
         if (host_job) {
             host_job->c[1] = col;
             host_job->ncols = 2;
-            if (defer && defer != 3 && (host_job->defer == 0 || host_job->defer == 3)) host_job->defer = defer;   // (3: distances only so far)
+            if (src.defer && src.defer != 3 && (host_job->defer == 0 || host_job->defer == 3)) host_job->defer = src.defer;   // (3: distances only so far)
         } else {
             if (uj.njobs >= 8) return fail(PCCM_E_ARG, "too many columns in one reduction batch");
             UnitJob &U = uj.j[uj.njobs];
-            U.val = base; U.stride = stride; U.ncols = 1;
-            U.defer = defer; U.nrm64 = se->nrm64; U.nrm32 = se->nrm32; U.nrm_rows = se->n_nrm; U.q32 = it->xyz32r; U.row0 = res->begin;
+            U.val = dev; U.stride = stride; U.ncols = 1;
+            U.defer = src.defer; U.nrm64 = se->nrm64; U.nrm32 = se->nrm32; U.nrm_rows = se->n_nrm; U.q32 = it->xyz32r; U.row0 = res->begin;
             U.c[0] = col; U.c[1] = col;
             U.ns = ns; U.nunits = s.nunits;
             U.tail_first = s.t0 - res->begin; U.tail_n = s.tail_n;
@@ -1716,18 +1733,17 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     UnitJobs uj;
     pj.njobs = 0; pj.off[0] = 0;
     uj.njobs = 0; uj.uoff[0] = 0; uj.toff[0] = 0;
+    for (int k = 0; k < n; ++k)
+        if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
     ReduceSlot *fresh[8];
     int nfresh = 0;
-    // first, whatever may change the layout of a direction's result records: a projection that was not fused into the
-    // search needs the matched rows, and if the search left them out it is repeated (ensure_plain) -- with the rows, and
-    // with the projection fused when the normals have arrived meanwhile.  Only then are the columns of this batch bound to
-    // the records (a job bound earlier would read 16-byte records through a 32-byte stride).
-    // The angular column (normal_mode does not apply) needs the matched rows in any case: from the plain column or from matched
-    // records (NNOut::layout 1); records without them repeat the search here too.  Under PCCM_TIES_MEAN the tie pass makes it,
-    // together with the averaged normals a neighbour-indexed projection of the same batch wants: one walk per direction.
+    // first, whatever may change the layout of a direction's result records: a column that needs the plain columns before
+    // the batch is bound (column_source) gets them now -- when the search left the matched rows out it is repeated
+    // (ensure_plain), with the rows, and with the projection fused when the normals have arrived meanwhile.  Only then are the
+    // columns of this batch bound to the records.  Under PCCM_TIES_MEAN the tie pass makes the angular column, together with
+    // the averaged normals a neighbour-indexed projection of the same batch wants: one walk per direction.
     bool tie_ang[2] = {false, false}, tie_nrm[2] = {false, false};
     for (int k = 0; k < n; ++k) {
-        if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (dirs[k] == PCCM_DIR_SELF) continue;
         NNResult &res = ctx->nn[dirs[k]];
         if (!res.valid || res.ties != PCCM_TIES_MEAN) continue;
@@ -1745,29 +1761,15 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         if ((rc = ensure_ties(ctx, d, tie_nrm[d], false, true))) return rc;
     }
     for (int k = 0; k < n; ++k) {
-        if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
-        if (metrics[k] == PCCM_METRIC_D1 || dirs[k] == PCCM_DIR_SELF) continue;
-        NNResult &res = ctx->nn[dirs[k]];
-        if (matched_column(metrics[k])) {
-            if (!res.valid || res.ties == PCCM_TIES_MEAN || res.plain_valid ||
-                (res.rec_valid && res.rec_layout == 1 && res.rec_stride == 2 && !res.no_rows))
-                continue;
-            if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
-            int rc = ensure_plain(ctx, res, true);
-            if (rc) return rc;
+        if (column_source(ctx, dirs[k], metrics[k], normal_modes[k]).prep != ColumnSource::kPlainFirst ||
+            slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units))
             continue;
-        }
-        const bool mean = res.valid && res.ties == PCCM_TIES_MEAN;      // (the virtual neighbours need the plain columns)
-        if (!res.valid || (!res.rec_valid && !mean) ||
-            (!mean && (res.fused_mode == normal_modes[k] || res.rec_stride == 4 || res.rec_layout == 1) && !res.no_rows)) continue;
-        if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
-        int rc = ensure_plain(ctx, res, true);
+        int rc = ensure_plain(ctx, ctx->nn[dirs[k]], true);
         if (rc) return rc;
     }
     const int path_kept = ctx->path_n[3];
     PathScope path(ctx, 1u << 3);          // the batch's kernels: per-point columns (slot_prepare), point and unit jobs
     for (int k = 0; k < n; ++k) {
-        if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
         ReduceSlot *s = slot_free(ctx, fresh, nfresh);
         if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 16 live columns in one batch");
@@ -1809,22 +1811,32 @@ int pccm_reduce_prefetch(pccm_ctx *ctx, int dir, int metric, int normal_mode)
     return pccm_reduce_prefetch_many(ctx, 1, &dir, &metric, &normal_mode);
 }
 
+// the slot of one column, enqueued when nobody has, once its numbers are on the host (units: with the per-leaf results)
+static int take_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, bool units, ReduceSlot **out)
+{
+    if (dir < 0 || dir > 2) return fail(PCCM_E_ARG, "bad direction %d", dir);
+    ReduceSlot *s = slot_find(ctx, dir, metric, normal_mode, units);
+    if (!s) {
+        int rc = prefetch_many(ctx, 1, &dir, &metric, &normal_mode, units);
+        if (rc) return rc;
+        s = slot_find(ctx, dir, metric, normal_mode, units);
+        if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
+    }
+    int rc = wait_slot(ctx, s);
+    if (!rc) rc = check_device_errors(ctx);
+    if (rc) return rc;
+    s->pending = false;
+    *out = s;
+    return PCCM_OK;
+}
+
 int pccm_reduce(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *xvec, double *minmax)
 {
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
     if (!xvec || !minmax) return fail(PCCM_E_ARG, "null pointer");
-    if (dir < 0 || dir > 2) return fail(PCCM_E_ARG, "bad direction %d", dir);
-    ReduceSlot *s = slot_find(ctx, dir, metric, normal_mode, true);
-    if (!s) {
-        int rc = prefetch_many(ctx, 1, &dir, &metric, &normal_mode, true);
-        if (rc) return rc;
-        s = slot_find(ctx, dir, metric, normal_mode, true);
-        if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
-    }
-    { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
-    { int rce = check_device_errors(ctx); if (rce) return rce; }
-    s->pending = false;
+    ReduceSlot *s;
+    { int rc = take_slot(ctx, dir, metric, normal_mode, true, &s); if (rc) return rc; }
     const int64_t n = s->n_iter;
     const int64_t xlen = pccm_xvec_len(n);
     memset(xvec, 0, (size_t)xlen * sizeof(double));
@@ -1875,17 +1887,8 @@ int pccm_finish_sum(const double *xvec, int64_t n_iter, double *sum)
 // = (tree of its first 32 leaves) + (tree of its last 32 leaves), and the GPU already finished both halves (begin = 0 here)
 static int total_from_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, double out[3])
 {
-    if (dir < 0 || dir > 2) return fail(PCCM_E_ARG, "bad direction %d", dir);
-    ReduceSlot *s = slot_find(ctx, dir, metric, normal_mode);
-    if (!s) {
-        int rc = pccm_reduce_prefetch(ctx, dir, metric, normal_mode);
-        if (rc) return rc;
-        s = slot_find(ctx, dir, metric, normal_mode);
-        if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
-    }
-    { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
-    { int rce = check_device_errors(ctx); if (rce) return rce; }
-    s->pending = false;
+    ReduceSlot *s;
+    { int rc = take_slot(ctx, dir, metric, normal_mode, false, &s); if (rc) return rc; }
     const int64_t n = s->n_iter, nunits = s->nunits, nblocks = s->nblocks;
     const int64_t nfull = n / kChunk;
     const double *bsum = s->host + 3 * nunits, *bmin = bsum + nblocks, *bmax = bsum + 2 * nblocks;
@@ -1921,17 +1924,8 @@ int64_t pccm_cvec_len(int64_t n_iter)
 // halves of the chunk's pairwise tree) + the raw values of the last, partial chunk; zero elsewhere
 static int chunks_from_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *cvec, double minmax[2])
 {
-    if (dir < 0 || dir > 2) return fail(PCCM_E_ARG, "bad direction %d", dir);
-    ReduceSlot *s = slot_find(ctx, dir, metric, normal_mode);
-    if (!s) {
-        int rc = prefetch_many(ctx, 1, &dir, &metric, &normal_mode, false);
-        if (rc) return rc;
-        s = slot_find(ctx, dir, metric, normal_mode);
-        if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
-    }
-    { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
-    { int rce = check_device_errors(ctx); if (rce) return rce; }
-    s->pending = false;
+    ReduceSlot *s;
+    { int rc = take_slot(ctx, dir, metric, normal_mode, false, &s); if (rc) return rc; }
     const int64_t n = s->n_iter, nunits = s->nunits, nblocks = s->nblocks;
     const int64_t nfull = n / kChunk, full_rows = nfull * kChunk;
     memset(cvec, 0, (size_t)pccm_cvec_len(n) * sizeof(double));
@@ -2108,13 +2102,7 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
         if (op.kind == 1) {
             ctx->nn_gen[op.dir]++;
             ctx->nn[op.dir].valid = true;
-            ctx->nn[op.dir].rec_valid = op.rec_valid;
-            ctx->nn[op.dir].plain_valid = op.plain_valid;
-            ctx->nn[op.dir].fused_mode = op.fused_mode;
-            ctx->nn[op.dir].rec_stride = op.rec_stride;
-            ctx->nn[op.dir].rec_layout = op.rec_layout;
-            ctx->nn[op.dir].no_rows = op.no_rows;
-            ctx->nn[op.dir].plain_d2_valid = op.plain_valid;
+            ctx->nn[op.dir].form = op.form;
         } else if (op.kind == 2) {
             ReduceSlot &s = ctx->slots[op.slot];
             if (s.pending && s.gen == ctx->nn_gen[s.dir] && s.wait_ev) {      // still in use by someone else
@@ -2180,14 +2168,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     }
     g.ops = ctx->cap_ops;
     for (auto &op : g.ops)
-        if (op.kind == 1) {                                // the state the captured sequence leaves behind
-            op.rec_valid = ctx->nn[op.dir].rec_valid;
-            op.plain_valid = ctx->nn[op.dir].plain_valid;
-            op.fused_mode = ctx->nn[op.dir].fused_mode;
-            op.rec_stride = ctx->nn[op.dir].rec_stride;
-            op.rec_layout = ctx->nn[op.dir].rec_layout;
-            op.no_rows = ctx->nn[op.dir].no_rows;
-        }
+        if (op.kind == 1) op.form = ctx->nn[op.dir].form;  // the state the captured sequence leaves behind
     g.epoch = ctx->epoch;
     g.batches = ctx->cap_batches;
     g.valid = true;

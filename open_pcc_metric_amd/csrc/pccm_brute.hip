@@ -274,12 +274,12 @@ int rescan_jobs(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Cloud *
         J.nflag = res.nflag_dev;
         J.idx_out = res.idx;
         J.d2_out = res.d2;
-        // the grid engine's results are 32-byte records (nn_grid set rec_valid for this run); the brute engine writes columns
-        J.rec_out = res.rec_valid ? (double *)res.rec.p : nullptr;
-        J.rec_stride = res.rec_stride;
-        J.rec_layout = res.rec_valid ? res.rec_layout : 0;
-        J.nrm = (res.rec_valid && res.fused_mode >= 0) ? se.nrm64 : nullptr;
-        J.normal_mode = res.fused_mode >= 0 ? res.fused_mode : PCCM_NORMAL_ROW;
+        // the grid engine's results are result records (nn_grid set the form for this run); the brute engine writes columns
+        J.rec_out = res.form.has_records() ? (double *)res.rec.p : nullptr;
+        J.rec_stride = res.form.stride();
+        J.rec_layout = res.form.layout();
+        J.nrm = (res.form.has_records() && res.form.fused >= 0) ? se.nrm64 : nullptr;
+        J.normal_mode = res.form.fused >= 0 ? res.form.fused : PCCM_NORMAL_ROW;
         J.part_d = (double *)ctx->rescan_part.p + (size_t)k * kSplitMax * cap;
         J.part_j = (int32_t *)((double *)ctx->rescan_part.p + (size_t)2 * kSplitMax * cap) + (size_t)k * kSplitMax * cap;
         J.ticket = (uint32_t *)ctx->counters.p + 8 + k + (self ? 2 : 0);

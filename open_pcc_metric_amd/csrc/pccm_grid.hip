@@ -1416,27 +1416,23 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
         J.slack32 = exact ? 0.0 : maxabs * 0x1.0p-20;
         int fm = fused_mode(ctx, dir, it, se);
         if (gr.vox && fm == PCCM_NORMAL_NEIGHBOUR) fm = -1;    // matched records carry no projection: the point kernel forms it from the rows
-        res.rec_stride = (ctx->want_idx || force_idx) ? 4 : 2;
         // fp32-exact pairs, and no neighbour-indexed projection to fuse: the searches leave the matched record itself (16 bytes,
         // one store) and the reductions form distance and row-indexed projection from rows and normals they read in row order
         // (NNOut::layout).  PCCM_DEFER=0: the searches form both themselves, as in round 2 (A/B runs)
         static const bool defer_off = [] { const char *e = getenv("PCCM_DEFER"); return e && e[0] == '0'; }();
         const bool defer = gr.vox || (!defer_off && gr.rec32 && fm != PCCM_NORMAL_NEIGHBOUR);
-        if (defer) res.rec_stride = 2;
-        else if (fm >= 0 && (rc = normals_ready(ctx, ctx->cloud[si]))) return rc;     // the search itself projects: announced normals cross PCIe now
-        res.rec_layout = defer ? 1 : 0;
-        res.no_rows = gr.vox && !(gr.vox_rows && want_vox == 2 && dir != PCCM_DIR_SELF);
+        if (!defer && fm >= 0 && (rc = normals_ready(ctx, ctx->cloud[si]))) return rc;     // the search itself projects: announced normals cross PCIe now
+        NNForm::Recs recs = (ctx->want_idx || force_idx) ? NNForm::kPairRows : NNForm::kPair;
+        if (defer) recs = gr.vox && !(gr.vox_rows && want_vox == 2 && dir != PCCM_DIR_SELF) ? NNForm::kMatchedNoRows : NNForm::kMatched;
+        res.form = {recs, NNForm::kNoPlain, fm};
         J.out.rec = (double *)res.rec.p;
-        J.out.stride = res.rec_stride;
+        J.out.stride = res.form.stride();
         J.out.nrm = fm >= 0 ? se.nrm64 : nullptr;
         static const bool nrm32_off = [] { const char *e = getenv("PCCM_NRM32"); return e && e[0] == '0'; }();
         J.out.nrm32 = (fm >= 0 && se.nrm_exact32 && !nrm32_off) ? se.nrm32 : nullptr;
         J.out.row_base = res.begin;
         J.out.normal_mode = fm >= 0 ? fm : PCCM_NORMAL_ROW;
-        J.out.layout = res.rec_layout;
-        res.fused_mode = fm;
-        res.rec_valid = true;
-        res.plain_valid = res.plain_d2_valid = false;
+        J.out.layout = res.form.layout();
         J.tail = res.tail.p;
         J.counters = res.nflag_dev;                         // [0] full rescans, [1] tail length
         if ((rc = ensure(ctx, res.flagged, (size_t)nq * sizeof(int32_t)))) return rc;

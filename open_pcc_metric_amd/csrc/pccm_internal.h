@@ -88,21 +88,44 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// Where the last search of a direction left its results: one value that holds only what the engines produce (a stride-4
+// matched record, or a row that no record carries, cannot be written down); stride and layout are the kernels' view of it.
+struct NNForm {
+    enum Recs {
+        kNone,            // no result records: the plain columns hold the results (brute-force engine, trivial self search,
+                          // empty shard), or -- before a search -- nothing does
+        kPairRows,        // layout 0, stride 4: {d2, projection, row, -}
+        kPair,            // layout 0, stride 2: {d2, projection} (pccm_nn_want_idx off)
+        kMatched,         // layout 1, stride 2: the matched record {rx, ry, rz, row}; the reductions form distance and projection
+        kMatchedNoRows,   // ... whose row word is void (voxel-brick search): good for distances only
+    } recs = kNone;
+    enum Plain { kNoPlain, kPlainD2, kPlainAll } plain = kNoPlain;   // unpacked into d2 / idx: nothing, d2 alone, both
+    int fused = -1;               // normal mode of the projection fused into the search, -1: none
+
+    static NNForm columns() { return {kNone, kPlainAll, -1}; }
+    bool has_records() const { return recs != kNone; }
+    int stride() const { return recs == kPairRows ? 4 : 2; }                       // doubles per record
+    int layout() const { return recs == kMatched || recs == kMatchedNoRows ? 1 : 0; }
+    bool has_rows() const { return recs == kPairRows || recs == kMatched; }        // the records carry the matched row ...
+    bool rows_need_repeat() const { return has_records() && !has_rows(); }         // ... or who wants it repeats the search
+    bool plain_ready(bool need_idx) const { return plain == kPlainAll || (!need_idx && plain == kPlainD2); }
+    bool matched_in_place() const { return recs == kMatched && plain != kPlainAll; }   // the rows are read out of the records
+    // the records hold the projection of normal mode m: fused into the search, or formed from matched records by the reduction
+    bool holds_projection(int m) const
+    {
+        if (recs == kMatched) return m == PCCM_NORMAL_ROW || m == PCCM_NORMAL_NEIGHBOUR;
+        return (recs == kPairRows || recs == kPair) && fused == m;
+    }
+};
+
 struct NNResult {
     bool valid = false;
     int64_t begin = 0, end = 0; // shard rows of the iterating cloud
     int32_t *idx = nullptr;     // [end-begin]   plain columns: written by the brute-force engine, or unpacked from `rec`
     double *d2 = nullptr;       // [end-begin]   on demand (ensure_plain)
     int64_t cap = 0;
-    DevBuf rec;                 // [end-begin] 32-byte result records {d2, projection, row, -} (grid engine; NNOut in pccm_grid.h)
-    bool rec_valid = false;     // `rec` holds the last run's results
-    bool plain_valid = false;   // idx / d2 hold them
-    bool plain_d2_valid = false;   // d2 alone does (unpacked from records that carry no row)
-    int fused_mode = -1;        // normal mode of the projection stored in `rec`, -1: not fused
-    int rec_stride = 4;         // doubles per record: 4 = with the matched row, 2 = {d2, projection} only (pccm_nn_want_idx off)
-    int rec_layout = 0;         // 0: {d2, projection[, row, -]}; 1 (stride 2): the matched record {rx, ry, rz, row}: distance and
-                                //    row-indexed projection are formed by the reduction that reads the records (NNOut::layout)
-    bool no_rows = false;       // layout 1 records whose row word is void (voxel-brick search): good for distances only
+    DevBuf rec;                 // [end-begin] result records of up to 32 bytes (grid engine; NNOut in pccm_grid.h)
+    NNForm form;                // what `rec`, idx and d2 hold of the last run's results
     int ties = PCCM_TIES_PICK;  // pccm_set_ties policy the search ran under (consumers read the virtual neighbours under MEAN)
     int64_t stats[3] = {0, 0, 0};
     uint32_t *nflag_dev = nullptr;  // device counters of the last run: [0] fallback queries, [1] grid tail length
@@ -194,9 +217,7 @@ struct ProfSpan {
 struct GraphOp {               // host-side effect of one captured call, replayed by pccm_graph_launch
     int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot)
     int dir = 0, slot = -1;
-    bool rec_valid = false, plain_valid = false;   // kind 1: where the direction's results live once the graph has run
-    int fused_mode = -1, rec_stride = 4, rec_layout = 0;
-    bool no_rows = false;
+    NNForm form;               // kind 1: where the direction's results live once the graph has run
     ReduceSlot snap;           // kind 2: the slot's bookkeeping at capture time (pointers are not owned)
 };
 
@@ -409,8 +430,8 @@ struct RescanJob {              // flagged queries of one result (k2b_fallback)
     int32_t *idx_out;           // plain outputs (brute-force engine) ...
     double *d2_out;
     double *rec_out;            // ... or result records with the projection fused (grid engine), when non-null
-    int rec_stride;             // doubles per record (NNResult::rec_stride)
-    int rec_layout;             // NNResult::rec_layout
+    int rec_stride;             // doubles per record (NNForm::stride)
+    int rec_layout;             // NNForm::layout
     const double *nrm;          // normals for the fused projection, or null
     int normal_mode;
     double *part_d;             // split regime: [kSplitMax][gridDim.x] partial minima
@@ -453,7 +474,7 @@ struct PointJob {               // one D2 / PROJ / ANGULAR column (k_point_jobs)
     const double *c64, *cn64;   // PCCM_TIES_MEAN: per shard row the virtual neighbour / its averaged normal (null: gather via idx)
     const double *inrm;         // PCCM_METRIC_ANGULAR: the iterating cloud's normals (nrm: the searched cloud's); PCCM_METRIC_SSIM_*:
                                 // the iterating cloud's feature column (nrm: the searched cloud's)
-    const float4 *recs;         // PCCM_METRIC_ANGULAR / SSIM_*: matched records {x, y, z, row} (NNResult::rec_layout 1) instead of idx, or null
+    const float4 *recs;         // PCCM_METRIC_ANGULAR / SSIM_*: matched records {x, y, z, row} (NNForm::layout 1) instead of idx, or null
     const int32_t *idx;
     int64_t q_begin;
     int metric, normal_mode;
