@@ -280,6 +280,24 @@ int pccm_reduce_total(pccm_ctx *ctx, int dir, int metric, int normal_mode, doubl
  * of one per column -- the np.sum / np.max of every GeoMSE / GeoHausdorffDistance row (metric.py:226-228, 366). */
 int pccm_reduce_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, double *out);
 
+/* Ranked (generalized) Hausdorff distance: the ks[i]-th smallest element (1-based; nearest rank, equal elements count
+ * separately) of the column GeoHausdorffDistance.calculate takes the np.max of (metric.py:353-366) -- PCCM_METRIC_D1 or
+ * PCCM_METRIC_D2 of direction 0 or 1, under the context's tie policy.  out[i] is an element of the column, bit for bit
+ * np.partition(column, k - 1)[k - 1]; k = n_iter gives the np.max pccm_reduce_total reports.  The column is ranked in HBM by
+ * the kernel that reduces it, from the values that reduction forms: a most-significant-bits-first radix select over the
+ * order keys of the doubles (bit pattern with the sign flipped, negative values inverted -- the columns here hold no negative
+ * value, no -0.0 and no NaN, the keys order any finite column), 11 bits per launch; no column and no per-row scratch is
+ * allocated or copied.  n <= 8 selections per call, like a reduction batch.
+ *   pccm_select_prefetch_many  enqueues the launches (and the columns' reductions where nobody has); capturable into a
+ *                              hipGraph between pccm_graph_begin / pccm_graph_end like pccm_reduce_prefetch.
+ *   pccm_select_many           consumes them (enqueuing first what nobody prefetched) and waits once.
+ * PCCM_E_ARG: PCCM_DIR_SELF, any other metric, k < 1 or k > n_iter, a cloud of 2^32 rows or more (counts are 32 bits wide);
+ * PCCM_E_STATE: no search result yet, a sharded context; PCCM_METRIC_D2 without the normals it needs: PCCM_E_STATE /
+ * PCCM_E_RANGE exactly where pccm_reduce_total gives them. */
+int pccm_select_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks);
+int pccm_select_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks,
+                     double *out /*[n]*/);
+
 /* Sharded contexts whose rows start and end on whole 8192-row chunks (pccm_set_shard / pccm_set_shard_dir do that
  * whenever every rank can have a chunk): the exchange vector shrinks to ONE number per chunk -- NumPy adds the
  * chunks of a column one after the other, and the GPU has finished each chunk's pairwise tree -- plus the raw values
@@ -366,11 +384,11 @@ int pccm_color_transform(const double *rgb, int64_t n, int scheme, double *out);
 int pccm_drop_caches(pccm_ctx *ctx);
 
 /* hipGraph capture.  Between pccm_graph_begin() and pccm_graph_end() only pccm_drop_caches(),
- * pccm_nn() and pccm_reduce_prefetch() may be called; they are recorded on the context's stream
- * instead of executed.  The same sequence must have run once before (capture cannot allocate).
+ * pccm_nn(), pccm_reduce_prefetch[_many]() and pccm_select_prefetch_many() may be called; they are recorded on the
+ * context's stream instead of executed.  The same sequence must have run once before (capture cannot allocate).
  * pccm_graph_end() instantiates the graph, runs it once and returns its id; pccm_graph_launch()
  * replays the whole sequence -- kernels and host-side bookkeeping -- with a single launch, after which
- * pccm_reduce()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
+ * pccm_reduce()/pccm_select_many()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
  * clouds, normals, shard or any buffer it references change.  One report over resident clouds is
  * ~45 small launches, which an eager host cannot issue as fast as the GPU retires them. */
 int pccm_graph_begin(pccm_ctx *ctx);

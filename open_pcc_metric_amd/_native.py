@@ -39,7 +39,7 @@ SYMBOLS = (
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals",
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
-    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
+    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
     "pccm_color_transform", "pccm_lzf_decompress", "pccm_drop_caches", "pccm_graph_begin", "pccm_graph_end", "pccm_graph_launch", "pccm_graph_destroy",
@@ -126,6 +126,9 @@ def load() -> ctypes.CDLL:
     lib.pccm_finish_sum.argtypes = [vp, i64, dp]
     lib.pccm_reduce_total.argtypes = [vp, i32, i32, i32, dp]
     lib.pccm_reduce_total_many.argtypes = [vp, i32, ip, ip, ip, dp]
+    lp = ctypes.POINTER(i64)
+    lib.pccm_select_prefetch_many.argtypes = [vp, i32, ip, ip, ip, lp]
+    lib.pccm_select_many.argtypes = [vp, i32, ip, ip, ip, lp, dp]
     lib.pccm_cvec_len.argtypes = [i64]
     lib.pccm_cvec_len.restype = i64
     lib.pccm_reduce_chunks_many.argtypes = [vp, i32, ip, ip, ip, dp, dp]
@@ -599,6 +602,28 @@ class Engine:
         _check(self._lib.pccm_reduce_total_many(self._ctx, k, arr(*[int(r[0]) for r in requests]), arr(*[int(r[1]) for r in requests]),
                                                 arr(*_modes(normal_mode, k)), out))
         return [(np.float64(out[3 * i]), np.float64(out[3 * i + 1]), np.float64(out[3 * i + 2])) for i in range(k)]
+
+    def _select_args(self, requests, normal_mode):
+        k = len(requests)
+        arr = ctypes.c_int * k
+        return (k, arr(*[int(r[0]) for r in requests]), arr(*[int(r[1]) for r in requests]), arr(*_modes(normal_mode, k)),
+                (ctypes.c_int64 * k)(*[int(r[2]) for r in requests]))
+
+    def select_prefetch_many(self, requests, normal_mode: str = "row") -> None:
+        """``requests``: up to 8 ``(direction, metric, k)``: enqueue the selection of the k-th smallest element (1-based) of each
+        D1 / D2 column without waiting (pccm_select_prefetch_many); a later select_many() consumes them."""
+        if requests:
+            _check(self._lib.pccm_select_prefetch_many(self._ctx, *self._select_args(requests, normal_mode)))
+
+    def select_many(self, requests, normal_mode: str = "row"):
+        """-> the k-th smallest element of each of up to 8 columns ``(direction, metric, k)``, ranked in HBM (pccm_select_many):
+        bit for bit ``np.partition(column, k - 1)[k - 1]``."""
+        if not requests:
+            return []
+        args = self._select_args(requests, normal_mode)
+        out = (ctypes.c_double * args[0])()
+        _check(self._lib.pccm_select_many(self._ctx, *args, out))
+        return [np.float64(v) for v in out]
 
     def reduce_chunks_many(self, requests, normal_mode: str = "row"):
         """-> (one float64 array holding the chunk vectors of up to 8 columns ``(direction, metric)`` one after the other,

@@ -14,8 +14,8 @@ import typing
 import pandas as pd
 
 from .cloud_pair import CloudPair
-from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, EuclideanDistance, PrimaryMetric,
-                     SecondaryMetric, SSIMSimilarities, SymmetricMetric)
+from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, EuclideanDistance,
+                     GeoRankedHausdorffDistance, PrimaryMetric, SecondaryMetric, SSIMSimilarities, SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -33,10 +33,12 @@ class CalculateResult:
     def as_df(self) -> pd.DataFrame:
         rows: typing.Dict[str, list] = {c: [] for c in _COLUMNS}
         for m in self._metrics:
-            if isinstance(m, SymmetricMetric):
-                label = type(m.metrics[0]).__name__ + "(symmetric)"
-            else:
-                label = type(m).__name__
+            inner = m.metrics[0] if isinstance(m, SymmetricMetric) else m
+            label = type(inner).__name__
+            if getattr(inner, "rank", None) is not None:        # ranked Hausdorff rows: one block per rank
+                label += f"[{inner.rank!r}]"
+            if inner is not m:
+                label += "(symmetric)"
             rows["label"].append(label)
             rows["is_left"].append(getattr(m, "is_left", ""))
             rows["point-to-plane"].append(getattr(m, "point_to_plane", ""))
@@ -95,6 +97,8 @@ class MetricCalculator:
         elif role == 2:
             if isinstance(metric, EuclideanDistance):
                 wanted.append((metric.is_left, metric.point_to_plane))
+            elif isinstance(metric, GeoRankedHausdorffDistance):
+                wanted.append(("ranked", metric.is_left, metric.point_to_plane, metric.rank))
             resolved = {}
             for name, dep in metric._get_dependencies().items():
                 resolved[name], _, dep_waits = self._visit(dep, early, late, planned, wanted)

@@ -152,6 +152,18 @@ class DeviceColumn(_DeviceArray):
             self._red = (total, np.float64(mn), np.float64(mx))
         return self._red
 
+    def ranked(self, k: int):
+        """The k-th smallest element (1-based) of the column: ``np.partition(column, k - 1)[k - 1]``, selected in HBM when the
+        engine can (pccm_select_many: D1 and D2 columns) -- no column leaves the GPU then."""
+        k = int(k)
+        if not 1 <= k <= self.shape[0]:
+            raise ValueError(f"rank {k} outside 1..{self.shape[0]}")
+        if self._kind in ("d1", "d2"):
+            value = self._pair._selected(self._dir, self._METRIC[self._kind], k)
+            if value is not None:
+                return value
+        return np.partition(np.asarray(self), k - 1)[k - 1]
+
     def _fused_function(self, func, args, kwargs):
         which = _REDUCERS.get(func)
         if which is None or len(args) != 1 or args[0] is not self:
@@ -279,6 +291,7 @@ class CloudPair:
         self._estimate_normals, self._normals_knn = bool(estimate_normals), int(normals_knn)
         self._estimated = [False, False]
         self._xchg, self._xchg_wanted = {}, []
+        self._selections, self._sel_wanted = {}, []
         self._colours_on_device = [False, False]
         self._colour_red = {}
         self._graph_id = None
@@ -362,6 +375,7 @@ class CloudPair:
         new._estimated = [self._estimated[0], False]
         new._colours_on_device = [self._colours_on_device[0], False]
         new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
+        new._selections, new._sel_wanted = {}, []
         new._graph_id, new._last_wanted = None, None
         keep_self = bool(self.__dict__.get("_self_done")) and bool(getattr(eng, "keeps_self_search", False))
         self_total = self.__dict__.get("_totals", {}).get((nat.DIR_SELF, nat.METRIC_D1)) if keep_self else None
@@ -433,6 +447,7 @@ class CloudPair:
         self._idx_cache = {}
         self._xchg = {}
         self._totals = {}
+        self._selections = {}
         self._colour_red = {}
         if self._use_graph and self._last_wanted is not None and hasattr(eng, "graph_begin"):
             wants_self = "boundary" in self._last_wanted
@@ -551,6 +566,26 @@ class CloudPair:
             if key not in self._totals:
                 self._totals[key] = eng.reduce_total(direction, metric, self.normal_index)
         return self._totals[key]
+
+    def _check_ranked(self) -> None:
+        """options.check_hausdorff_rank for this pair: ValueError before any GPU work of a report."""
+        if self._coll.sharded:
+            raise ValueError("ranked Hausdorff rows are not available for sharded pairs (group=)")
+
+    def _selected(self, direction: int, metric: int, k: int):
+        """The k-th smallest element of a whole D1 / D2 column, selected on the GPU.  The first selection a report asks for
+        brings every selection the report enqueued (prefetch_reductions) back in one call per eight.  None: this engine has no
+        selection (a test double): the caller ranks the materialised column."""
+        self._check_ranked()
+        eng = self._engine
+        if not hasattr(eng, "select_many"):
+            return None
+        key = (direction, metric, k)
+        if key not in self._selections:
+            batch = next((b for b in _selection_batches(self._sel_wanted) if key in b), [key])
+            for q, v in zip(batch, eng.select_many(batch, self.normal_index)):
+                self._selections[q] = v
+        return self._selections[key]
 
     def tie_exposure(self, is_left: bool = True, point_to_plane: bool = True) -> dict:
         """Opt-in diagnostic (not part of any report): how far the order of EXACT ties can move the point-to-plane MSE.
@@ -756,8 +791,8 @@ class CloudPair:
     def prefetch_reductions(self, wanted, _remember: bool = True) -> None:
         """Enqueue the fused reductions a report is about to ask for, without waiting for any of them.
 
-        ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``
-        and/or the string ``"boundary"``.
+        ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
+        ``("ranked", is_left, point_to_plane, rank)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -779,8 +814,13 @@ class CloudPair:
             self._check_ssim(attributes, k)
         for k, attributes in by_k.items():
             self._ensure_ssim(sorted(set(attributes)), k)
-        requests, ssim_requests = [], []
+        ranked_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "ranked"]
+        if ranked_items:
+            self._check_ranked()
+        requests, ssim_requests, selections = [], [], []
         for item in wanted:
+            if item in ranked_items:
+                continue              # (below: their columns are requests of their own, EuclideanDistance's)
             if item in ssim_items:
                 ssim_requests.append((nat.DIR_LEFT if item[2] else nat.DIR_RIGHT, nat.METRIC_SSIM[item[1]]))
                 continue
@@ -819,13 +859,25 @@ class CloudPair:
                     continue      # row-indexed normals out of range (the WHOLE cloud decides, so that every rank of a
                     #               sharded pair agrees): surfaces, on every rank, where the reference raises
                 requests.append((direction, nat.METRIC_D2))
+        # ranked Hausdorff rows: the selections of every column this report reduces (a column that was left out above -- no
+        # normals, row-indexed normals out of range -- surfaces when the row is evaluated), by column, then rank
+        from .metric import rank_index
+        for _, is_left, p2p, rank in ranked_items:
+            direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
+            column = (direction, nat.METRIC_D2 if p2p else nat.METRIC_D1)
+            if column in requests:
+                selections.append(column + (rank_index(rank, eng.n_iter(direction)),))
         self._xchg_wanted = list(requests) + ssim_requests
+        self._sel_wanted = sorted(set(selections))
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
             eng.reduce_prefetch_many(requests[:8], self.normal_index)
             for b in range(0, len(ssim_requests), 4):     # (at most four matched-row columns per batch: k_point_jobs)
                 eng.reduce_prefetch_many(ssim_requests[b:b + 4], self.normal_index)
+            if hasattr(eng, "select_prefetch_many"):
+                for batch in _selection_batches(self._sel_wanted):
+                    eng.select_prefetch_many(batch, self.normal_index)
         else:
             requests = requests + ssim_requests
             for direction, metric in requests:
@@ -835,6 +887,23 @@ class CloudPair:
     def point_to_plane_column(self, is_left: bool) -> DeviceColumn:
         self._require_normals(1 if is_left else 0)
         return DeviceColumn(self, nat.DIR_LEFT if is_left else nat.DIR_RIGHT, "proj")
+
+
+def _selection_batches(selections, cap: int = 8):
+    """Sorted ``(direction, metric, k)`` selections in batches of at most ``cap`` (pccm_select_many's limit) that keep the ranks
+    of a column together: every pass of a batch streams each of its columns once, whatever the number of ranks."""
+    batches, current = [], []
+    for column in sorted({q[:2] for q in selections}):
+        ranks = [q for q in selections if q[:2] == column]
+        for at in range(0, len(ranks), cap):
+            part = ranks[at:at + cap]
+            if current and len(current) + len(part) > cap:
+                batches.append(current)
+                current = []
+            current = current + part
+    if current:
+        batches.append(current)
+    return batches
 
 
 def _has_normals(cloud) -> bool:

@@ -68,6 +68,7 @@ int check_device_errors(pccm_ctx *ctx)
     if (!e) return PCCM_OK;
     for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
     for (auto &s : ctx->slots) s.pending = false;
+    for (auto &q : ctx->sel_slots) q.pending = false;
     return fail(PCCM_E_STATE, "a search kernel reported an inconsistent state (device error word 0x%x: %s%s): the results of this search were "
                               "dropped, run it again", e, (e & 1u) ? "the tail launch's wait for its own workgroups ran out; " : "",
                 (e & 2u) ? "a voxel brick contradicts its cell start" : "");
@@ -442,6 +443,10 @@ int pccm_ctx_create(int device, void *hip_stream, pccm_ctx **out)
         rc = fail(PCCM_E_OOM, "hipHostMalloc of the completion counter failed");
     }
     if (!rc) *ctx->done = 0;
+    if (!rc && hipHostMalloc((void **)&ctx->sel_host, pccm_ctx::kSelSlots * sizeof(double), hipHostMallocCoherent) != hipSuccess) {
+        ctx->sel_host = nullptr;
+        rc = fail(PCCM_E_OOM, "hipHostMalloc of the selection results failed");
+    }
     if (!rc && hipEventCreateWithFlags(&ctx->batch_ev, hipEventDisableTiming) != hipSuccess) rc = fail(PCCM_E_HIP, "hipEventCreate failed");
     if (!rc) rc = ensure(ctx, ctx->stats, 32 * sizeof(unsigned long long));      // [0..9] the main stream's scratch, [12..14] the copy stream's, [16..22] colour reduction of the other direction
     if (!rc && hipMemsetAsync(ctx->counters.p, 0, 16 * sizeof(uint32_t), ctx->stream) != hipSuccess)
@@ -471,11 +476,13 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     ctx->host_err = nullptr;
     if (ctx->done) (void)hipHostFree(ctx->done);
     ctx->done = nullptr;
+    if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
+    ctx->sel_host = nullptr;
     for (int k = 0; k < 2; ++k) free_cloud(ctx->cloud[k]);
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->ssim_scratch,                      &ctx->tie_list};
+                      &ctx->ssim_scratch,                      &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
     for (DevBuf *b : bufs) free_buf(*b);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
@@ -1490,10 +1497,9 @@ int64_t pccm_xvec_len(int64_t n_iter)
 // counter once they are (k_publish, pccm_point.hip), and the host watches that word -- the runtime's event completion path
 // wakes a waiting thread ~13 us after the kernel ends.  The spin is bounded: past kSpinBound, or for a
 // slot the counter does not cover (wait_seq 0), the batch event says it, and reports a fault or a hang as a HIP error.
-static int wait_slot(pccm_ctx *ctx, const ReduceSlot *s)
+static int wait_batch(pccm_ctx *ctx, uint64_t want, hipEvent_t wait_ev)
 {
     constexpr auto kSpinBound = std::chrono::milliseconds(2);
-    const uint64_t want = s->wait_seq;
     if (ctx->wait_mode == PCCM_WAIT_SPIN && want) {
         const auto t0 = std::chrono::steady_clock::now();
         for (unsigned k = 0;; ++k) {
@@ -1503,16 +1509,18 @@ static int wait_slot(pccm_ctx *ctx, const ReduceSlot *s)
         }
     }
 #ifdef PCCM_DIAG
-    if (ctx->wait_mode == 2 && s->wait_ev) {
+    if (ctx->wait_mode == 2 && wait_ev) {
         hipError_t e;
-        while ((e = hipEventQuery(s->wait_ev)) == hipErrorNotReady) __builtin_ia32_pause();
+        while ((e = hipEventQuery(wait_ev)) == hipErrorNotReady) __builtin_ia32_pause();
         PCCM_HIP(e);
         return PCCM_OK;
     }
 #endif
-    if (s->wait_ev) PCCM_HIP(hipEventSynchronize(s->wait_ev));
+    if (wait_ev) PCCM_HIP(hipEventSynchronize(wait_ev));
     return PCCM_OK;
 }
+
+static int wait_slot(pccm_ctx *ctx, const ReduceSlot *s) { return wait_batch(ctx, s->wait_seq, s->wait_ev); }
 
 // Where a reduction column is read from (given the form and tie policy of the direction's search), and what has to happen before
 // it can be bound.  slot_prepare binds from the first answer; prefetch_many acts on the second for every request before binding
@@ -1627,6 +1635,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     s.nunits = ns > 0 ? (ns + kLeaf - 1) / kLeaf : 0;
     s.nblocks = (s.nunits + 31) / 32;
     s.has_units = want_units;
+    s.has_job = false;
     const int64_t nfull = it->n / kChunk, full_rows = nfull * kChunk;
     s.t0 = res->begin > full_rows ? res->begin : full_rows;
     s.tail_n = s.t0 < res->end ? res->end - s.t0 : 0;
@@ -1650,6 +1659,15 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         col.out_units = want_units ? s.host : nullptr;
         col.out_blocks = s.host + 3 * s.nunits;
         col.out_tail = s.host + 3 * s.nunits + 3 * s.nblocks;
+        // the column as a job of its own (what a selection of this column ranks: pccm_select_prefetch_many)
+        UnitJob &U = s.job;
+        U.val = dev; U.stride = stride; U.ncols = 1;
+        U.defer = src.defer; U.nrm64 = se->nrm64; U.nrm32 = se->nrm32; U.nrm_rows = se->n_nrm; U.q32 = it->xyz32r; U.row0 = res->begin;
+        U.c[0] = col; U.c[1] = col;
+        U.ns = ns; U.nunits = s.nunits;
+        U.tail_first = s.t0 - res->begin; U.tail_n = s.tail_n;
+        U.nblocks = s.nblocks;
+        s.has_job = true;
         // a second column over the same result records rides along with the job that already reads them
         UnitJob *host_job = nullptr;
         static const bool merge = [] {
@@ -1667,13 +1685,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
             if (src.defer && src.defer != 3 && (host_job->defer == 0 || host_job->defer == 3)) host_job->defer = src.defer;   // (3: distances only so far)
         } else {
             if (uj.njobs >= 8) return fail(PCCM_E_ARG, "too many columns in one reduction batch");
-            UnitJob &U = uj.j[uj.njobs];
-            U.val = dev; U.stride = stride; U.ncols = 1;
-            U.defer = src.defer; U.nrm64 = se->nrm64; U.nrm32 = se->nrm32; U.nrm_rows = se->n_nrm; U.q32 = it->xyz32r; U.row0 = res->begin;
-            U.c[0] = col; U.c[1] = col;
-            U.ns = ns; U.nunits = s.nunits;
-            U.tail_first = s.t0 - res->begin; U.tail_n = s.tail_n;
-            U.nblocks = s.nblocks;
+            uj.j[uj.njobs] = s.job;
             const int64_t lanes = (s.nunits * 8 + 255) / 256 * 256;
             uj.uoff[uj.njobs + 1] = uj.uoff[uj.njobs] + lanes;
             uj.toff[uj.njobs + 1] = uj.toff[uj.njobs] + s.tail_n;
@@ -2004,6 +2016,157 @@ int pccm_reduce_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *met
     return PCCM_OK;
 }
 
+// ---- selections: the k-th smallest element of a column (include/pccm.h) ------------------------------------------------------
+static SelectSlot *sel_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, int64_t k)
+{
+    for (auto &q : ctx->sel_slots)
+        if (q.pending && q.dir == dir && q.metric == metric && q.k == k && (metric == PCCM_METRIC_D1 || q.mode == normal_mode) &&
+            q.gen == ctx->nn_gen[dir])
+            return &q;
+    return nullptr;
+}
+
+static int select_check(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
+{
+    if (n < 0 || n > kSelMax || (n > 0 && (!dirs || !metrics || !normal_modes || !ks))) return fail(PCCM_E_ARG, "1..8 requests expected");
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "%s needs the whole columns on this GPU (world = 1)", who);
+    for (int i = 0; i < n; ++i) {
+        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "selections rank directions 0 and 1, not %d", dirs[i]);
+        if (metrics[i] != PCCM_METRIC_D1 && metrics[i] != PCCM_METRIC_D2)
+            return fail(PCCM_E_ARG, "selections rank PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", metrics[i]);
+        const Cloud *it, *se;
+        NNResult *res;
+        int rc = need_nn(ctx, dirs[i], &it, &se, &res);
+        if (rc) return rc;
+        if (it->n >= ((int64_t)1 << 32)) return fail(PCCM_E_ARG, "selections count rows in 32 bits: columns of 2^32 rows or more are not supported");
+        if (ks[i] < 1 || ks[i] > it->n) return fail(PCCM_E_ARG, "rank %lld outside 1..%lld", (long long)ks[i], (long long)it->n);
+    }
+    return PCCM_OK;
+}
+
+static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
+{
+    // what is not enqueued yet, by column; a column's reduction is enqueued first when nobody has: the selection ranks the
+    // column as that reduction's job describes it
+    int todo[kSelMax], ntodo = 0, cd[kSelMax], cm[kSelMax], cmode[kSelMax], col_of[kSelMax], ncols = 0;
+    for (int i = 0; i < n; ++i) {
+        if (sel_find(ctx, dirs[i], metrics[i], normal_modes[i], ks[i])) continue;
+        bool dup = false;
+        for (int j = 0; j < ntodo; ++j)
+            dup = dup || (dirs[todo[j]] == dirs[i] && metrics[todo[j]] == metrics[i] && ks[todo[j]] == ks[i] &&
+                          (metrics[i] == PCCM_METRIC_D1 || normal_modes[todo[j]] == normal_modes[i]));
+        if (dup) continue;
+        int c = 0;
+        while (c < ncols && !(cd[c] == dirs[i] && cm[c] == metrics[i] && (metrics[i] == PCCM_METRIC_D1 || cmode[c] == normal_modes[i]))) ++c;
+        if (c == ncols) { cd[c] = dirs[i]; cm[c] = metrics[i]; cmode[c] = normal_modes[i]; ncols++; }
+        col_of[ntodo] = c;
+        todo[ntodo++] = i;
+    }
+    if (ntodo == 0) return PCCM_OK;
+    int rc = ensure(ctx, ctx->sel_hist, (size_t)kSelPasses * kSelMax * kSelBins * sizeof(uint32_t));
+    if (!rc) rc = ensure(ctx, ctx->sel_state, (size_t)kSelPasses * kSelMax * sizeof(SelState));
+    if (!rc) rc = prefetch_many(ctx, ncols, cd, cm, cmode, false);
+    if (rc) return rc;
+    const ReduceSlot *cslot[kSelMax];
+    for (int c = 0; c < ncols; ++c) {
+        cslot[c] = slot_find(ctx, cd[c], cm[c], cmode[c]);
+        if (!cslot[c] || !cslot[c]->has_job) return fail(PCCM_E_STATE, "reduction slot lost");
+    }
+    SelectSlot *fresh[kSelMax];
+    int nfresh = 0;
+    bool placed[kSelMax] = {};
+    PathScope path(ctx, 1u << 3, true);            // the selection's launches join the log of the column's reduction batch
+    for (int left = ntodo; left > 0;) {            // rounds of at most kSelPerCol selections per column (two at the most)
+        UnitJobs uj;
+        uj.njobs = 0;
+        for (int k = 0; k < 9; ++k) uj.uoff[k] = uj.toff[k] = 0;
+        UnitSelect &S = uj.sel;
+        S.hist = (uint32_t *)ctx->sel_hist.p;
+        S.state = (SelState *)ctx->sel_state.p;
+        for (int c = 0; c < ncols; ++c) {
+            int taken = 0;
+            for (int j = 0; j < ntodo && taken < kSelPerCol; ++j) {
+                if (placed[j] || col_of[j] != c) continue;
+                SelectSlot *q = nullptr;
+                for (auto &cand : ctx->sel_slots)
+                    if (!q && (!cand.pending || cand.gen != ctx->nn_gen[cand.dir])) q = &cand;
+                for (auto &cand : ctx->sel_slots) {               // failing that, one that is not of this call: its result is given up
+                    bool mine = false;
+                    for (int f = 0; f < nfresh; ++f) mine = mine || fresh[f] == &cand;
+                    if (!q && !mine) q = &cand;
+                }
+                if (!q) return fail(PCCM_E_STATE, "no free selection slot");
+                if (q->pending && !ctx->capturing && q->wait_ev && (rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
+                const int i = todo[j];
+                q->dir = dirs[i]; q->metric = metrics[i]; q->mode = normal_modes[i]; q->k = ks[i];
+                q->gen = ctx->nn_gen[dirs[i]];
+                q->pending = true;
+                fresh[nfresh++] = q;
+                if (taken == 0) {
+                    uj.j[uj.njobs] = cslot[c]->job;
+                    S.sfirst[uj.njobs] = S.nsel;
+                    uj.njobs++;
+                }
+                S.k[S.nsel] = (unsigned long long)ks[i];
+                S.out[S.nsel] = ctx->sel_host + (q - ctx->sel_slots);
+                S.nsel++;
+                placed[j] = true;
+                taken++;
+                left--;
+            }
+        }
+        for (int k = uj.njobs; k < 9; ++k) S.sfirst[k] = S.nsel;
+        for (int k = uj.njobs; k < 8; ++k) uj.j[k] = uj.j[0];
+        if ((rc = launch_unit_select(ctx, uj))) return rc;
+    }
+    uint64_t seq = 0;
+    if ((rc = launch_publish(ctx, &seq))) return rc;
+    for (int f = 0; f < nfresh; ++f) {
+        SelectSlot &q = *fresh[f];
+        q.wait_seq = seq;                          // (while capturing: the batch's ordinal in the captured sequence)
+        q.wait_ev = ctx->capturing ? nullptr : ctx->batch_ev;
+        if (ctx->capturing) {
+            GraphOp op;
+            op.kind = 3;
+            op.dir = q.dir;
+            op.slot = (int)(&q - ctx->sel_slots);
+            op.ssnap = q;
+            ctx->cap_ops.push_back(op);
+        }
+    }
+    if (!ctx->capturing) PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
+    return PCCM_OK;
+}
+
+int pccm_select_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
+{
+    CHECK_CTX(ctx);
+    int rc = select_check(ctx, "pccm_select_prefetch_many", n, dirs, metrics, normal_modes, ks);
+    if (rc) return rc;
+    return select_prefetch(ctx, n, dirs, metrics, normal_modes, ks);
+}
+
+int pccm_select_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (n > 0 && !out) return fail(PCCM_E_ARG, "null pointer");
+    int rc = select_check(ctx, "pccm_select_many", n, dirs, metrics, normal_modes, ks);
+    if (!rc) rc = select_prefetch(ctx, n, dirs, metrics, normal_modes, ks);      // whatever is not enqueued yet, in one batch
+    if (rc) return rc;
+    SelectSlot *got[kSelMax];
+    for (int i = 0; i < n; ++i) {
+        SelectSlot *q = sel_find(ctx, dirs[i], metrics[i], normal_modes[i], ks[i]);
+        if (!q) return fail(PCCM_E_STATE, "selection slot lost");
+        if ((rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
+        if ((rc = check_device_errors(ctx))) return rc;
+        out[i] = ctx->sel_host[q - ctx->sel_slots];
+        got[i] = q;
+    }
+    for (int i = 0; i < n; ++i) got[i]->pending = false;
+    return PCCM_OK;
+}
+
 // Host helper for the colour metrics (metric.py:261-290): out[r] = M * rgb[r] for the BT.709 "ycc" (1) or
 // the "yuv" (2) matrix.  The reference maps every row with np.matmul(M, c); on the authoring host
 // (NumPy 2.2.6 / OpenBLAS dgemv) that evaluates each component as fma(m2*c2, fma(m0*c0, m1*c1)) -- pinned
@@ -2113,10 +2276,22 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
             s.n_iter = op.snap.n_iter; s.begin = op.snap.begin; s.end = op.snap.end;
             s.nunits = op.snap.nunits; s.nblocks = op.snap.nblocks; s.has_units = op.snap.has_units;
             s.t0 = op.snap.t0; s.tail_n = op.snap.tail_n;
+            s.has_job = op.snap.has_job; s.job = op.snap.job;
             s.gen = ctx->nn_gen[s.dir];
             s.pending = true;
             s.wait_ev = ctx->batch_ev;
             s.wait_seq = op.snap.wait_seq ? ctx->batches_issued + op.snap.wait_seq : 0;
+        } else if (op.kind == 3) {
+            SelectSlot &q = ctx->sel_slots[op.slot];
+            if (q.pending && q.gen == ctx->nn_gen[q.dir] && q.wait_ev) {       // still in use by someone else
+                int rcw = wait_batch(ctx, q.wait_seq, q.wait_ev);
+                if (rcw) return rcw;
+            }
+            q = op.ssnap;
+            q.gen = ctx->nn_gen[q.dir];
+            q.pending = true;
+            q.wait_ev = ctx->batch_ev;
+            q.wait_seq = op.ssnap.wait_seq ? ctx->batches_issued + op.ssnap.wait_seq : 0;
         }
     }
     ctx->batches_issued += g.batches;                            // before the launch: a failed one only delays a waiter
@@ -2132,6 +2307,7 @@ int pccm_graph_begin(pccm_ctx *ctx)
     if (ctx->ties != PCCM_TIES_PICK) return fail(PCCM_E_STATE, "searches under PCCM_TIES_MEAN run eagerly: no graph capture");
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     for (auto &s : ctx->slots) s.pending = false;      // nothing outside the graph may be half-consumed
+    for (auto &q : ctx->sel_slots) q.pending = false;
     ctx->cap_ops.clear();
     ctx->cap_batches = 0;
     ctx->capture_failed = false;
@@ -2154,6 +2330,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
         // whatever the captured calls recorded on the host never ran on the GPU
         for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
         for (auto &s : ctx->slots) s.pending = false;
+    for (auto &q : ctx->sel_slots) q.pending = false;
         grid_invalidate(ctx);
         return fail(PCCM_E_STATE, "graph capture failed (%s); the context is usable, results were invalidated",
                     e != hipSuccess ? hipGetErrorString(e) : "a captured call reported an error");
@@ -2163,6 +2340,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
         (void)hipGraphDestroy(g.graph);
         for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
         for (auto &s : ctx->slots) s.pending = false;
+    for (auto &q : ctx->sel_slots) q.pending = false;
         grid_invalidate(ctx);
         return fail(PCCM_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     }
@@ -2177,6 +2355,9 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
         if (op.kind == 2) {
             ctx->slots[op.slot].wait_ev = ctx->batch_ev;
             ctx->slots[op.slot].wait_seq = op.snap.wait_seq ? ctx->batches_issued + op.snap.wait_seq : 0;
+        } else if (op.kind == 3) {
+            ctx->sel_slots[op.slot].wait_ev = ctx->batch_ev;
+            ctx->sel_slots[op.slot].wait_seq = op.ssnap.wait_seq ? ctx->batches_issued + op.ssnap.wait_seq : 0;
         }
     ctx->batches_issued += g.batches;
     PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
@@ -2237,6 +2418,7 @@ int pccm_ctx_reset(pccm_ctx *ctx)
     }
     for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
     for (auto &s : ctx->slots) s.pending = false;
+    for (auto &q : ctx->sel_slots) q.pending = false;
     for (auto &g : ctx->graphs) graph_free(g);
     ctx->graphs.clear();
     ctx->epoch++;

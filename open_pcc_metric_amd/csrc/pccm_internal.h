@@ -193,12 +193,41 @@ struct Grid {                    // one geometry, both clouds (grid engine)
                                    // rank among the set bits of the cell's brick
 };
 
+struct UnitCol {                // one column reduced from a job's array
+    int off;                    // field of the 32-byte result record (0: squared distance, 1: projection); 0 for plain columns
+    int square;                 // reduce value^2 (the D2 column from the records' signed projection; metric.py:179)
+    double *out_units;          // pinned host memory [3][nunits] per-leaf sum/min/max, or null
+    double *out_blocks;         // pinned host memory [3][nblocks] per-32-leaf tree sum/min/max
+    double *out_tail;           // pinned host memory [tail_n]
+};
+struct UnitJob {                // one per-point array to reduce (k_unit_jobs): up to two columns per pass
+    const double *val;          // plain column (stride 1) or the result records (stride 2 or 4 doubles)
+    int stride;
+    // records of layout 1 (the matched record {rx, ry, rz, row}, 16 bytes): field 0 = the squared distance to row row0 + i of the
+    // iterating cloud (q32), field 1 = err . normal[row0 + i] (metric.py:146-153), both formed here -- the rows and the searched
+    // cloud's row-indexed normals are read in row order, i.e. coalesced, where the search would have gathered the normal
+    int defer;                  // 0: no; 1: normals as 16-byte fp32-exact words (nrm32); 2: as fp64 rows (nrm64); 3: no normals (field 0 only);
+                                // 4 / 5: as 1 / 2 with the normal of the MATCHED row (the record's row: --normal-index neighbour)
+    int64_t nrm_rows;           // rows of the searched cloud's normals (bounds the gather of 4 / 5)
+    const double *nrm64;
+    const float4 *nrm32;
+    const float4 *q32;          // iterating cloud, one fp32 word per row (Cloud::xyz32r)
+    int64_t row0;               // row of the cloud the shard's first record belongs to
+    int ncols;
+    UnitCol c[2];
+    int64_t ns, nunits;
+    int64_t tail_first, tail_n; // rows [tail_first, tail_first + tail_n) are copied out raw
+    int64_t nblocks;            // ceil(nunits / 32)
+};
+
 struct ReduceSlot {            // one enqueued reduction (pccm_reduce_prefetch / pccm_reduce)
     bool pending = false;
     int dir = 0, metric = 0, mode = 0;
     uint64_t gen = 0;          // nn generation of `dir` it was computed from
     int64_t n_iter = 0, begin = 0, end = 0, nunits = 0, nblocks = 0, t0 = 0, tail_n = 0;
     bool has_units = false;    // per-leaf results were written (needed by pccm_reduce's exchange vector)
+    bool has_job = false;      // job below describes the column (pccm_select_*: a selection ranks what the reduction reduced)
+    UnitJob job;               // the column as a one-column k_unit_jobs job, as bound when the reduction was enqueued
     DevBuf val;
     double *host = nullptr;    // pinned: [3][nunits] leaf sums/min/max | [3][nblocks] half-chunk trees | tail_n raw values
     size_t host_cap = 0;
@@ -209,16 +238,26 @@ struct ReduceSlot {            // one enqueued reduction (pccm_reduce_prefetch /
                                     // in a GraphOp's snapshot: the batch's ordinal within the captured sequence)
 };
 
+struct SelectSlot {            // one enqueued selection (pccm_select_prefetch_many / pccm_select_many)
+    bool pending = false;
+    int dir = 0, metric = 0, mode = 0;
+    int64_t k = 0;
+    uint64_t gen = 0;          // nn generation of `dir` it was computed from
+    hipEvent_t wait_ev = nullptr;
+    uint64_t wait_seq = 0;     // as ReduceSlot's
+};
+
 struct ProfSpan {
     hipEvent_t a, b;
     int cls;
 };
 
 struct GraphOp {               // host-side effect of one captured call, replayed by pccm_graph_launch
-    int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot)
+    int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch(slot)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
     ReduceSlot snap;           // kind 2: the slot's bookkeeping at capture time (pointers are not owned)
+    SelectSlot ssnap;          // kind 3: likewise for a selection slot
 };
 
 struct GraphRec {
@@ -305,6 +344,12 @@ struct pccm_ctx {
     int want_idx = 1;                      // pccm_nn_want_idx: searches store the matched row with every result
     int fuse_mode[3] = {-1, -1, -1};       // pccm_nn_fuse: normal mode of the D2 projection fused into the search, per direction
     pccm::ReduceSlot slots[16];           // (a report with every PointSSIM row holds up to 15 columns at once)
+    // selections (pccm_select_*): slot s answers into sel_host[s] (host-coherent pinned memory); the histograms and pass states
+    // are sized once per context
+    static constexpr int kSelSlots = 32;
+    pccm::SelectSlot sel_slots[kSelSlots];
+    double *sel_host = nullptr;
+    pccm::DevBuf sel_hist, sel_state;
     uint64_t nn_gen[3] = {1, 1, 1};
     // hipGraph capture of a step (pccm_graph_*): epoch changes whenever inputs, shard or any device
     // buffer a captured kernel may reference changes, which invalidates every recorded graph
@@ -485,37 +530,35 @@ struct PointJobs {
     int njobs;
     int64_t off[5];             // prefix sums of the jobs' row counts
 };
-struct UnitCol {                // one column reduced from a job's array
-    int off;                    // field of the 32-byte result record (0: squared distance, 1: projection); 0 for plain columns
-    int square;                 // reduce value^2 (the D2 column from the records' signed projection; metric.py:179)
-    double *out_units;          // pinned host memory [3][nunits] per-leaf sum/min/max, or null
-    double *out_blocks;         // pinned host memory [3][nblocks] per-32-leaf tree sum/min/max
-    double *out_tail;           // pinned host memory [tail_n]
+// Selection mode of k_unit_jobs (pccm_select_*): the k-th smallest value of a job's column 0, by a radix select over the order
+// keys of the values unit_load / unit_pick form -- the values the reduction mode reduces.  kSelBits key bits per launch from the
+// top down; launch p histograms the rows whose higher bits equal the prefix that launches 0..p-1 settled, and the launch boundary
+// is the only synchronisation: every workgroup of launch p derives that prefix for itself from launch p-1's counts.
+constexpr int kSelBits = 11, kSelBins = 1 << kSelBits;
+constexpr int kSelPasses = 6;       // 6 x 11 >= 64 (the last pass holds the 9 lowest bits)
+constexpr int kSelMax = 8;          // selections per launch sequence ...
+constexpr int kSelPerCol = 4;       // ... of which at most this many rank one column (one 8 KB LDS histogram each)
+constexpr size_t kSelLds = (size_t)kSelPerCol * kSelBins * sizeof(uint32_t) + 256;   // LDS of the selection mode
+struct SelState {
+    unsigned long long prefix;  // the settled high bits of the key (zero below them)
+    unsigned long long k;       // rank among the rows that share them (1-based)
 };
-struct UnitJob {                // one per-point array to reduce (k_unit_jobs): up to two columns per pass
-    const double *val;          // plain column (stride 1) or the result records (stride 2 or 4 doubles)
-    int stride;
-    // records of layout 1 (the matched record {rx, ry, rz, row}, 16 bytes): field 0 = the squared distance to row row0 + i of the
-    // iterating cloud (q32), field 1 = err . normal[row0 + i] (metric.py:146-153), both formed here -- the rows and the searched
-    // cloud's row-indexed normals are read in row order, i.e. coalesced, where the search would have gathered the normal
-    int defer;                  // 0: no; 1: normals as 16-byte fp32-exact words (nrm32); 2: as fp64 rows (nrm64); 3: no normals (field 0 only);
-                                // 4 / 5: as 1 / 2 with the normal of the MATCHED row (the record's row: --normal-index neighbour)
-    int64_t nrm_rows;           // rows of the searched cloud's normals (bounds the gather of 4 / 5)
-    const double *nrm64;
-    const float4 *nrm32;
-    const float4 *q32;          // iterating cloud, one fp32 word per row (Cloud::xyz32r)
-    int64_t row0;               // row of the cloud the shard's first record belongs to
-    int ncols;
-    UnitCol c[2];
-    int64_t ns, nunits;
-    int64_t tail_first, tail_n; // rows [tail_first, tail_first + tail_n) are copied out raw
-    int64_t nblocks;            // ceil(nunits / 32)
+struct UnitSelect {
+    int pass = 0;               // 0: a reduction launch.  1..kSelPasses: histogram pass `pass - 1`; kSelPasses + 1: resolve and store
+    int nsel = 0;
+    int sfirst[9] = {};         // selections sfirst[j] .. sfirst[j + 1] - 1 rank column 0 of job j
+    int boff[9] = {};           // prefix sums of the jobs' workgroups in a histogram pass
+    unsigned long long k[kSelMax] = {};   // 1-based ranks
+    double *out[kSelMax] = {};  // pinned host memory: one double per selection
+    uint32_t *hist = nullptr;   // [kSelPasses][kSelMax][kSelBins], zeroed on the stream before pass 0
+    SelState *state = nullptr;  // [kSelPasses][kSelMax]: what pass p matched and ranked by (written by pass p, read by pass p + 1)
 };
 struct UnitJobs {
     UnitJob j[8];
     int njobs;
     int64_t uoff[9];            // prefix sums of 8 * nunits, each rounded up to a multiple of 256
     int64_t toff[9];            // prefix sums of tail_n
+    UnitSelect sel;             // sel.pass != 0: a selection launch (uoff / toff are not read)
 };
 // the rescan jobs of njobs <= 2 results (scratch allocated), for k2b_fallback or the rescan half of k_grid_tail
 int rescan_jobs(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Cloud *const *ses, NNResult *const *ress, bool self, RescanJobs *out);
@@ -526,6 +569,9 @@ int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, cons
 // *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when
 // nothing was launched
 int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
+// the selection launches of jobs.sel (memset of the histograms, kSelPasses histogram passes, resolve); nothing is published
+int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs);
+int launch_publish(pccm_ctx *ctx, uint64_t *seq);     // k_publish behind whatever the stream holds; *seq as for launch_unit_jobs
 
 // (PCCM_METRIC_ANGULAR: the pick's column from both clouds' normals; under PCCM_TIES_MEAN the tie pass makes it, tie_mean)
 int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,

@@ -345,9 +345,162 @@ __device__ __forceinline__ void unit_pick(const UnitView &J, double v[2])       
     if (J.sq1) v[1] = __dmul_rn(v[1], v[1]);
 }
 
+
+// ---- selection mode (UnitSelect, pccm_internal.h) ---------------------------------------------------------------------------
+// The k-th smallest value of a job's column 0.  Keys: order_key of the value -- every value a report ranks is a square or a
+// sum of squares (non-negative, never -0.0, never NaN), for which the plain bit pattern would order too; the sign-flip keeps the
+// mode right for a column that does hold negative values.  Counts are 32 bits wide: the host refuses columns of 2^32 rows or more.
+__device__ __forceinline__ int sel_shift(int p) { return p >= kSelPasses - 1 ? 0 : 64 - kSelBits * (p + 1); }
+
+__device__ __forceinline__ double sel_value(unsigned long long key)         // inverse of order_key
+{
+    const unsigned long long b = (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key;
+    return __longlong_as_double((long long)b);
+}
+
+// What pass p (1..kSelPasses; kSelPasses: the resolve launch) matches and ranks by, for the m <= kSelPerCol selections s0.. of
+// one job: from what pass p - 1 matched by (SelState; {0, k} for pass 0) and its counts -- the bin that holds the k-th row
+// extends the prefix, the rows in the bins below it leave the rank.  Selections whose prefixes were equal in pass p - 1 shared
+// one histogram, the first one's.  Every workgroup computes the same numbers; 256 threads, 8 bins each.
+__device__ __forceinline__ void sel_derive(const UnitSelect &S, int p, int s0, int m, uint32_t *wsum, SelState *cur)
+{
+    unsigned long long ppre[kSelPerCol], pk[kSelPerCol];
+#pragma unroll
+    for (int r = 0; r < kSelPerCol; ++r) {
+        ppre[r] = 0;
+        pk[r] = 0;
+        if (r < m) {
+            if (p == 1) pk[r] = S.k[s0 + r];
+            else { const SelState st = S.state[(p - 1) * kSelMax + s0 + r]; ppre[r] = st.prefix; pk[r] = st.k; }
+        }
+    }
+    const int t = threadIdx.x, w = t >> 6;
+#pragma unroll
+    for (int r = 0; r < kSelPerCol; ++r) {
+        if (r >= m) break;                                      // (uniform)
+        int lead = r;
+#pragma unroll
+        for (int r2 = r - 1; r2 >= 0; --r2)
+            if (ppre[r2] == ppre[r]) lead = r2;
+        const uint32_t *h = S.hist + ((size_t)(p - 1) * kSelMax + s0 + lead) * kSelBins + 8 * t;
+        const uint4 a = *reinterpret_cast<const uint4 *>(h), b = *reinterpret_cast<const uint4 *>(h + 4);
+        const uint32_t c[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        uint32_t tsum = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) tsum += c[j];
+        uint32_t incl = tsum;                                   // (sums stay below 2^32: they count rows of one column)
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(incl, off);
+            if ((t & 63) >= off) incl += o;
+        }
+        if ((t & 63) == 63) wsum[w] = incl;
+        if (t == 0) cur[r] = SelState{ppre[r], pk[r]};          // (never kept: some bin holds the k-th row)
+        __syncthreads();
+        unsigned long long run = incl - tsum;
+        for (int j = 0; j < w; ++j) run += wsum[j];
+        const unsigned long long kk = pk[r];
+        if (run < kk && kk <= run + tsum) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (run < kk && kk <= run + c[j])
+                    cur[r] = SelState{ppre[r] | ((unsigned long long)(8 * t + j) << sel_shift(p - 1)), kk - run};
+                run += c[j];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void unit_select(const UnitJobs &jobs, unsigned char *smem)
+{
+    const UnitSelect &S = jobs.sel;
+    uint32_t *lh = reinterpret_cast<uint32_t *>(smem);                                  // [kSelPerCol][kSelBins]
+    SelState *cur = reinterpret_cast<SelState *>(smem + (size_t)kSelPerCol * kSelBins * sizeof(uint32_t));     // [kSelPerCol]
+    uint32_t *wsum = reinterpret_cast<uint32_t *>(cur + kSelPerCol);                    // [4]
+    const int p = S.pass - 1;
+    const int t = threadIdx.x;
+    if (p >= kSelPasses) {                                      // resolve: one workgroup, job after job
+        for (int jb = 0; jb < jobs.njobs; ++jb) {
+            const int s0 = S.sfirst[jb], m = S.sfirst[jb + 1] - s0;
+            sel_derive(S, kSelPasses, s0, m, wsum, cur);
+            for (int r = 0; r < m; ++r)
+                if (t == r) *S.out[s0 + r] = sel_value(cur[r].prefix);     // after the last pass the prefix is the whole key
+            __syncthreads();
+        }
+        return;
+    }
+    int jb = 0;
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        if (k < jobs.njobs && (int)blockIdx.x >= S.boff[k]) jb = k;
+    jb = __builtin_amdgcn_readfirstlane(jb);
+    const int s0 = S.sfirst[jb], m = S.sfirst[jb + 1] - s0;
+    const int blk = (int)blockIdx.x - S.boff[jb], nblk = S.boff[jb + 1] - S.boff[jb];
+    unsigned long long cpre[kSelPerCol];
+    bool own[kSelPerCol];                                       // the selection has a histogram of its own in this pass
+    if (p > 0) sel_derive(S, p, s0, m, wsum, cur);
+#pragma unroll
+    for (int r = 0; r < kSelPerCol; ++r) {
+        cpre[r] = (p > 0 && r < m) ? cur[r].prefix : 0ull;
+        own[r] = r < m;
+#pragma unroll
+        for (int r2 = 0; r2 < r; ++r2)
+            if (cpre[r2] == cpre[r]) own[r] = false;
+    }
+    if (p > 0 && blk == 0 && t < m) S.state[p * kSelMax + s0 + t] = cur[t];
+    for (int b = t; b < m * kSelBins; b += 256) lh[b] = 0u;
+    __syncthreads();
+    const UnitView V = unit_view(jobs.j[jb]);
+    const int64_t ns = jobs.j[jb].ns;
+    const int sh = sel_shift(p), above = p > 0 ? sel_shift(p - 1) : 0;
+    const unsigned mask = p == kSelPasses - 1 ? (1u << (64 - kSelBits * (kSelPasses - 1))) - 1u : (unsigned)kSelBins - 1u;
+    auto count = [&](double v) {
+        const unsigned long long key = order_key(v);
+        const unsigned bin = (unsigned)(key >> sh) & mask;
+#pragma unroll
+        for (int r = 0; r < kSelPerCol; ++r)
+            if (own[r] && (p == 0 || ((key ^ cpre[r]) >> above) == 0ull)) atomicAdd(&lh[r * kSelBins + bin], 1u);
+    };
+    const int64_t step = (int64_t)nblk * 256;
+    int64_t i = (int64_t)blk * 256 + t;
+    for (; i + 3 * step < ns; i += 4 * step) {                  // four independent loads in flight
+        double v[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) unit_load(V, i + j * step, v[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unit_pick(V, v[j]);
+            count(v[j][0]);
+        }
+    }
+    for (; i < ns; i += step) {
+        double v[2];
+        unit_load(V, i, v);
+        unit_pick(V, v);
+        count(v[0]);
+    }
+    __syncthreads();
+    // integer adds commute: the global counts do not depend on the order the workgroups arrive in
+#pragma unroll
+    for (int r = 0; r < kSelPerCol; ++r) {
+        if (!own[r]) continue;
+        uint32_t *g = S.hist + ((size_t)p * kSelMax + s0 + r) * kSelBins;
+        for (int b = t; b < kSelBins; b += 256) {
+            const uint32_t c = lh[r * kSelBins + b];
+            if (c) atomicAdd(&g[b], c);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
 {
     __shared__ double ls[2][32], lmn[2][32], lmx[2][32];
+    __shared__ __attribute__((aligned(16))) unsigned char sel_smem[kSelLds];      // selection launches only
+    if (jobs.sel.pass) {                                   // block-uniform (a kernel argument)
+        unit_select(jobs, sel_smem);
+        return;
+    }
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t unit_threads = jobs.uoff[jobs.njobs];
     if (t < unit_threads) {                                // block-uniform: jobs start at multiples of 256 lanes
@@ -418,8 +571,9 @@ __global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
             }
         }
         if (k == 0) {
-            for (int c = 0; c < ncols; ++c) {
-                double *ou = J.c[c].out_units;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {                  // (constant bounds: r / mn / mx stay in registers)
+                double *ou = c < ncols ? J.c[c].out_units : nullptr;
                 if (live && ou) {                          // per-leaf results: the sharded exchange needs them
                     ou[u] = r[c];
                     ou[J.nunits + u] = mn[c];
@@ -468,7 +622,9 @@ __global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
     double v[2];
     unit_load(V, J.tail_first + e, v);
     unit_pick(V, v);
-    for (int c = 0; c < J.ncols; ++c) J.c[c].out_tail[e] = v[c];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        if (c < J.ncols) J.c[c].out_tail[e] = v[c];
 }
 
 // The same reduction with the jobs' shape fixed at compile time (every report's jobs share one shape): record stride and
@@ -748,10 +904,41 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
             launch_unit_shape(ctx, sub, shape[first_of[g]]);
         }
     }
-    // the batch's completion, published behind its last launch.  The count the counter will reach is taken before the launch
-    // is issued, so that a launch that fails can only make a waiter fall back to the event, never wake it early.
+    return launch_publish(ctx, seq);
+}
+
+// the batch's completion, published behind its last launch.  The count the counter will reach is taken before the launch
+// is issued, so that a launch that fails can only make a waiter fall back to the event, never wake it early.
+int launch_publish(pccm_ctx *ctx, uint64_t *seq)
+{
     *seq = ctx->capturing ? ++ctx->cap_batches : ++ctx->batches_issued;
     PCCM_LAUNCH(ctx, k_publish, dim3(1), dim3(64), 0, ctx->stream, (unsigned long long *)ctx->done);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+// The selections of jobs.sel: the histograms zeroed on the stream, one launch per radix pass (each reads the counts of the one
+// before: the launch boundary is the only synchronisation), one workgroup that resolves the values into pinned host memory.
+int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs)
+{
+    UnitSelect &S = jobs.sel;
+    if (S.nsel <= 0) return PCCM_OK;
+    ProfScope ps(ctx, PCCM_K_REDUCE);
+    int nb = 0;
+    for (int k = 0; k < 8; ++k) {
+        S.boff[k] = nb;
+        if (k < jobs.njobs) {                 // 4096 rows per workgroup, at most one workgroup per CU and job
+            const int64_t want = (jobs.j[k].ns + 4095) / 4096;
+            nb += (int)(want < 1 ? 1 : want > 256 ? 256 : want);
+        }
+    }
+    S.boff[8] = nb;
+    PCCM_HIP(hipMemsetAsync(S.hist, 0, (size_t)kSelPasses * kSelMax * kSelBins * sizeof(uint32_t), ctx->stream));
+    for (int p = 0; p <= kSelPasses; ++p) {
+        S.pass = p + 1;
+        PCCM_LAUNCH(ctx, k_unit_jobs, dim3(p < kSelPasses ? (unsigned)nb : 1u), dim3(256), 0, ctx->stream, jobs);
+    }
+    S.pass = 0;
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

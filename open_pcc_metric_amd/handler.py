@@ -1,7 +1,7 @@
 """Command line -- same flags and report text as ``python -m open_pcc_metric`` (handler.py:4-71).
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
-                                  [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--csv]
+                                  [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -15,7 +15,10 @@ cloud_pair.py:61-64).  ``--plane-to-plane`` (no counterpart in the reference) ad
 Ebrahimi (ICME 2018) after all others; they compare each point's normal with its matched point's, so they too estimate the
 normals files lack.  ``--point-ssim geometry|normal|curvature|color`` (repeatable; no counterpart in the reference) adds the
 PointSSIM rows of Alexiou & Ebrahimi (ICME Workshops 2020) after those, over neighbourhoods of ``--ssim-neighbours`` points
-("PointSSIM").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+("PointSSIM").  ``--hausdorff-rank R`` (repeatable, R in (0, 1]; no counterpart in the reference) adds the ranked
+(generalized) Hausdorff rows of Javaheri et al. (QoMEX 2020) after all others: the ceil(R n)-th smallest squared distance of
+each direction and its PSNR, for D1 and -- with ``--point-to-plane`` -- D2, selected on the GPU; independent of ``--hausdorff``,
+whose rows are those of R = 1 ("Ranked Hausdorff").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -41,6 +44,10 @@ import click
                    "averaged.  Normals missing from a file are estimated; color needs colours in both files.")
 @click.option("--ssim-neighbours", "ssim_neighbours", type=click.IntRange(2, 64), default=12, show_default=True,
               help="Points per PointSSIM neighbourhood (the point itself included).")
+@click.option("--hausdorff-rank", "hausdorff_rank", type=float, multiple=True,
+              help="Report the ranked (generalized) Hausdorff distance at this rank in (0, 1] as well (may be repeated, at most 4), "
+                   "after all other rows: the ceil(R n)-th smallest squared distance of each direction and its PSNR (0.95: the "
+                   "distance 95 % of the points stay within; 1: the Hausdorff rows); with --point-to-plane for D2 too.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -54,16 +61,20 @@ import click
 @click.option("--ties", type=click.Choice(["pick", "mean"]), default="pick", show_default=True,
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
-def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, csv, device, engine,
-        normal_index, extent, tie_exposure, ties) -> None:
+def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank, csv, device,
+        engine, normal_index, extent, tie_exposure, ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import CalculateOptions, check_point_ssim, transform_options
+    from .options import CalculateOptions, check_hausdorff_rank, check_point_ssim, transform_options
 
+    try:                                       # (a bad rank: before any file is read and any GPU context exists)
+        options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
+                                   point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None)
+    except ValueError as exc:
+        raise click.UsageError(str(exc))
+    check_hausdorff_rank(options)
     ocloud_cloud = read_point_cloud(ocloud)
-    options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
-                               point_ssim=point_ssim, ssim_neighbours=ssim_neighbours)
     cloud_pair = None
     for path in pcloud:
         pcloud_cloud = read_point_cloud(path)

@@ -14,6 +14,7 @@ NumPy itself.
 from __future__ import annotations
 
 import abc
+import fractions
 import math
 import typing
 
@@ -233,6 +234,33 @@ class GeoHausdorffDistance(_OverEuclidean):                      # metric.py:353
         self.value = fused()[2] if fused is not None else np.max(column, axis=0)
 
 
+def rank_index(rank: float, n: int) -> int:
+    """Nearest-rank index of ``rank`` in (0, 1] over ``n`` points: k = max(1, ceil(R * n)), 1-based, where R is the decimal
+    number ``repr(float(rank))`` spells, taken as an exact fraction -- the number the user typed, not the binary double next to
+    it (ceil(0.07 * 100) is 8 in fp64 and 7 here)."""
+    return max(1, math.ceil(fractions.Fraction(repr(float(rank))) * int(n)))
+
+
+class GeoRankedHausdorffDistance(_OverEuclidean):                # no counterpart in the reference (options.py: hausdorff_rank)
+    """Ranked (generalized) Hausdorff distance of one direction (Javaheri et al., QoMEX 2020; INTEGRATION.md, "Ranked
+    Hausdorff"): the rank_index(rank, n)-th smallest element of the column GeoHausdorffDistance takes the maximum of -- a
+    SQUARED distance like it, and equal to it bit for bit at rank 1."""
+    _pccm_waits = True      # reads a selection back from the GPU: the calculator evaluates these last
+
+    def __init__(self, is_left: bool, point_to_plane: bool, rank: float):
+        super().__init__(is_left, point_to_plane)
+        self.rank = float(rank)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.point_to_plane, self.rank)
+
+    def calculate(self, euclidean_distance: EuclideanDistance) -> None:
+        column = euclidean_distance.value
+        k = rank_index(self.rank, column.shape[0])
+        ranked = getattr(column, "ranked", None)              # a device column: selected in HBM
+        self.value = ranked(k) if ranked is not None else np.partition(np.asarray(column), k - 1)[k - 1]
+
+
 class _OverAngular(SecondaryMetric, DirectionalMetric):
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         return {"angular_similarities": AngularSimilarities(is_left=self.is_left)}
@@ -333,6 +361,24 @@ class GeoHausdorffDistancePSNR(SecondaryMetric, PointToPlaneable):   # metric.py
 
     def calculate(self, max_sqrt: MaxSqrtDistance, hausdorff_distance: GeoHausdorffDistance) -> None:
         self.value = _psnr(max_sqrt.value, hausdorff_distance.value)
+
+
+class GeoRankedHausdorffDistancePSNR(SecondaryMetric, PointToPlaneable):
+    """GeoHausdorffDistancePSNR's expression (metric.py:369-386) with the ranked value."""
+    def __init__(self, is_left: bool, point_to_plane: bool, rank: float):
+        super().__init__(is_left, point_to_plane)
+        self.rank = float(rank)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.point_to_plane, self.rank)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"max_sqrt": MaxSqrtDistance(),
+                "ranked_distance": GeoRankedHausdorffDistance(is_left=self.is_left, point_to_plane=self.point_to_plane,
+                                                              rank=self.rank)}
+
+    def calculate(self, max_sqrt: MaxSqrtDistance, ranked_distance: GeoRankedHausdorffDistance) -> None:
+        self.value = _psnr(max_sqrt.value, ranked_distance.value)
 
 
 # --------------------------------------------------------------------------- colour secondaries

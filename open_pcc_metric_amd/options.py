@@ -22,23 +22,54 @@ above and in this order whatever order the caller gave:
   normal                 NormalSSIM L/R/sym
   curvature              CurvatureSSIM L/R/sym
   color                  ColorSSIM L/R/sym
+
+and, with ``hausdorff_rank`` (no counterpart in the reference: the generalized Hausdorff distance of Javaheri et al., QoMEX 2020),
+after every row above, for each rank in ascending order:
+
+  rank r                 RankedHausdorff L/R/sym, RankedHausdorffPSNR L/R/sym (D1)
+  rank r & p2plane       the same six with point_to_plane=True
 """
 from __future__ import annotations
 
 import typing
 
+import math
+import numbers
+
 from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMSE, ColorPSNR, GeoHausdorffDistance,
-                     GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
-                     SymmetricMetric)
+                     GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR,
+                     MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance, SymmetricMetric)
 
 SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
+MAX_HAUSDORFF_RANKS = 4
+
+
+def _hausdorff_ranks(value) -> typing.Tuple[float, ...]:
+    """``hausdorff_rank`` as a sorted tuple of distinct floats in (0, 1]; ValueError for anything else."""
+    if value is None:
+        return ()
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"hausdorff_rank must be a number or an iterable of numbers in (0, 1], not {value!r}")
+    items = [value] if isinstance(value, numbers.Real) else list(value) if hasattr(value, "__iter__") else [value]
+    ranks = set()
+    for r in items:
+        if isinstance(r, (bool,)) or type(r).__name__ == "bool_" or not isinstance(r, numbers.Real):
+            raise ValueError(f"hausdorff_rank: {r!r} is not a number in (0, 1]")
+        f = float(r)
+        if math.isnan(f) or not 0.0 < f <= 1.0:
+            raise ValueError(f"hausdorff_rank: {r!r} is not in (0, 1]")
+        ranks.add(f)
+    if len(ranks) > MAX_HAUSDORFF_RANKS:
+        raise ValueError(f"hausdorff_rank: at most {MAX_HAUSDORFF_RANKS} ranks per report, not {len(ranks)}")
+    return tuple(sorted(ranks))
 
 
 class CalculateOptions:
     def __init__(self, color: typing.Optional[str] = None, hausdorff: bool = False,
                  point_to_plane: bool = False, plane_to_plane: bool = False,
-                 point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12):
+                 point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
+                 hausdorff_rank=None):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -55,6 +86,7 @@ class CalculateOptions:
             raise ValueError(f"ssim_neighbours must be an integer in {SSIM_MIN_K}..{SSIM_MAX_K}, not {ssim_neighbours!r}")
         self.point_ssim = tuple(a for a in SSIM_ATTRIBUTES if a in wanted)
         self.ssim_neighbours = int(ssim_neighbours)
+        self.hausdorff_rank = _hausdorff_ranks(hausdorff_rank)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -74,6 +106,14 @@ def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, 
         raise ValueError("ColorSSIM needs the colours of both clouds")
     if "normal" in attrs and not estimate_normals and not all(_has_normals(c) for c in clouds):
         raise ValueError("NormalSSIM needs the normals of both clouds (or estimate_normals=True)")
+
+
+def check_hausdorff_rank(options: CalculateOptions, *, group=None) -> None:
+    """Raise ``ValueError`` when the ranked Hausdorff rows ``options`` asks for cannot be computed for this pair -- before any
+    GPU work (the command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).
+    A sharded pair would have to exchange the per-pass histograms across its ranks: not built."""
+    if getattr(options, "hausdorff_rank", ()) and group is not None:
+        raise ValueError("ranked Hausdorff rows are not available for sharded pairs (group=)")
 
 
 def _sides(cls, **kw):
@@ -112,4 +152,8 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
             # higher is better: the symmetric rows report the smaller side
             cls, kw = SSIM_CLASSES[attribute], dict(k=getattr(options, "ssim_neighbours", 12))
             metrics += _sides(cls, **kw) + [_sym(cls, True, **kw)]
+    for rank in getattr(options, "hausdorff_rank", None) or ():
+        for point_to_plane in (False, True) if options.point_to_plane else (False,):
+            metrics += _error_then_psnr(GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR,
+                                        point_to_plane=point_to_plane, rank=rank)
     return metrics
