@@ -87,6 +87,11 @@ extern "C" {
 #define PCCM_METRIC_SSIM_NORMAL 5
 #define PCCM_METRIC_SSIM_CURVATURE 6
 #define PCCM_METRIC_SSIM_COLOR 7
+/* Point-to-distribution value M (pccm_p2d_build) of directions 0 and 1 (the self search: PCCM_E_ARG): the stored column of the
+ * direction, which depends on neither the matched rows nor the tie policy; normal_mode is ignored.  PCCM_E_STATE while the
+ * columns are not built.  Accepted by pccm_point_metric and every pccm_reduce* call; a plain column, reduced like D1 (the
+ * direction needs a search result, like every reduction: the slot takes its row range and generation from it). */
+#define PCCM_METRIC_P2D 8
 
 /* kernel classes for pccm_profile_get() */
 #define PCCM_K_INGEST 0
@@ -169,6 +174,27 @@ int pccm_ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built);
 /* one feature column (attr: a single PCCM_SSIM_* flag) of cloud `which`: n doubles */
 int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out);
 
+/* Point-to-distribution columns ("Point-to-distribution"; after Javaheri et al., IEEE SPL 2020) of directions 0
+ * and 1: n_A and n_B doubles in HBM.  Direction A -> B, per point p of A, fp64, every operation separately rounded, sums left
+ * to right in the order written:
+ *   N    = the k points of B first in ascending (d2, row) order, d2 = ((dx*dx) + (dy*dy)) + dz*dz, d = p - q; all of B when it
+ *          has fewer than k points; kk = |N|, q_0, q_1, ... in that order (an exact k-NN search of A's points in B's cells)
+ *   e_j  = q_j - p;  S1_a = sum_j e_j,a;  S2_ab = sum_j (e_j,a * e_j,b);  m_a = S1_a / kk;  C_ab = S2_ab / kk - m_a * m_b
+ *   t    = (C00 + C11) + C22;  lam = t * 2^-10;  c_aa = C_aa + lam, off-diagonal c_ab = C_ab   (a ridge relative to the trace: flat
+ *          neighbourhoods stay invertible, M stays invariant under uniform scaling, cond(c) <= 3 * 2^10 + 1)
+ *   f00 = c11*c22 - c12*c12, f01 = c02*c12 - c01*c22, f02 = c01*c12 - c02*c11, f11 = c00*c22 - c02*c02, f12 = c01*c02 - c00*c12,
+ *   f22 = c00*c11 - c01*c01;  det = (c00*f00 + c01*f01) + c02*f02;  v_a = (f_a0*m0 + f_a1*m1) + f_a2*m2;
+ *   quad = (m0*v0 + m1*v1) + m2*v2;  M(p) = sqrt(max(quad / det, 0))
+ *   !(t > 0) or !(det > 0) (all of N is one location):  M(p) = 0 when m0 == m1 == m2 == 0, +inf otherwise
+ * k in 4..64 (PCCM_E_ARG).  Needs both clouds and no search result; PCCM_E_STATE for a missing cloud, a sharded context, or a
+ * build during graph capture.  A call that finds the columns at the same k does no work (*built = 0, else 1; built may be null)
+ * and is allowed during capture.  New points in either cloud drop both columns.  A build makes pending reductions of directions
+ * 0 and 1 stale and, when a column moves, captured graphs too.  The pair's grid is rebuilt (as by pccm_ssim_features). */
+int pccm_p2d_build(pccm_ctx *ctx, int k, int *built);
+/* the neighbourhoods behind direction dir's column: out[n][k] rows of the searched cloud in ascending (d2, row) order (entries
+ * from count[i] on are -1), count[n].  Searches again (the build keeps no lists); PCCM_E_STATE while the columns are not built. */
+int pccm_get_p2d_neighbours(pccm_ctx *ctx, int dir, int32_t *out, int32_t *count);
+
 /* Query-axis shard of this context: rank r of `world` owns, in every direction, the rows
  * [begin, end) of the iterating cloud returned by pccm_shard_range (boundaries are multiples
  * of 8192 rows -- whole chunks of NumPy's sum: pccm_reduce_chunks_many -- when the cloud has a chunk for every rank,
@@ -249,7 +275,7 @@ int pccm_set_ties(pccm_ctx *ctx, int policy);
 int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
 
 /* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR and
- * PCCM_METRIC_SSIM_* ignore normal_mode. */
+ * PCCM_METRIC_SSIM_* and PCCM_METRIC_P2D ignore normal_mode. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
 /* Fused reduction of a per-point metric over the shard: the np.sum / np.max of

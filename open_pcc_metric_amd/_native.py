@@ -30,6 +30,7 @@ METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does n
 # PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
 SSIM_ATTRS = {"geometry": 1, "normal": 2, "curvature": 4, "color": 8}
 METRIC_SSIM = {"geometry": 4, "normal": 5, "curvature": 6, "color": 7}
+METRIC_P2D = 8           # point-to-distribution (Mahalanobis) column of a direction (pccm_p2d_build; normal_mode does not apply)
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
 
@@ -37,7 +38,7 @@ KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals",
-    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
+    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_get_p2d_neighbours", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
@@ -106,6 +107,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_get_normals.argtypes = [vp, i32, vp]
     lib.pccm_ssim_features.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_ssim_features.argtypes = [vp, i32, i32, vp]
+    lib.pccm_p2d_build.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    lib.pccm_get_p2d_neighbours.argtypes = [vp, i32, vp, vp]
     lib.pccm_shard_range.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.pccm_nn.argtypes = [vp, i32, i32]
     lib.pccm_nn_pair.argtypes = [vp, i32]
@@ -330,6 +333,7 @@ class Engine:
                                          ctypes.byref(self._ctx)))
         self.device = int(device)
         self._n = [0, 0]
+        self._p2d_k = 0               # neighbourhood size of the point-to-distribution columns in HBM (0: none)
 
     def close(self) -> None:
         if getattr(self, "_ctx", None) and self._ctx.value:
@@ -346,12 +350,14 @@ class Engine:
         """Forget clouds, shard, graphs and profile; keep the device allocations (pccm_ctx_reset)."""
         _check(self._lib.pccm_ctx_reset(self._ctx))
         self._n = [0, 0]
+        self._p2d_k = 0
 
     # -- inputs ---------------------------------------------------------------------------
     def set_cloud(self, which: int, points) -> None:
         ptr, n, dt, dev, keep = _as_rows(points, "points")
         _check(self._lib.pccm_set_cloud(self._ctx, int(which), ptr, n, dt, dev))
         self._n[which] = n
+        self._p2d_k = 0               # (new points in either cloud drop both columns)
 
     def set_normals(self, which: int, normals) -> None:
         ptr, n, dt, dev, keep = _as_rows(normals, "normals")
@@ -487,6 +493,26 @@ class Engine:
         out = np.empty(self._n[which], dtype=np.float64)
         _check(self._lib.pccm_get_ssim_features(self._ctx, int(which), SSIM_ATTRS[attr], out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    def p2d_build(self, k: int) -> bool:
+        """Build (or find) the point-to-distribution columns of both directions at neighbourhood size ``k`` in HBM; True when
+        work was done (pccm_p2d_build)."""
+        built = ctypes.c_int32()
+        _check(self._lib.pccm_p2d_build(self._ctx, int(k), ctypes.byref(built)))
+        self._p2d_k = int(k)
+        return bool(built.value)
+
+    def get_p2d_neighbours(self, direction: int):
+        """-> (rows, counts): per point of the iterating cloud of ``direction`` the rows of its neighbours in the other cloud, in
+        ascending (d2, row) order ((n, k) int32, -1 beyond the count), and how many there are (pccm_get_p2d_neighbours)."""
+        if not self._p2d_k:
+            raise PccmStateError("no point-to-distribution columns (p2d_build)")
+        n = self.n_iter(direction)
+        rows = np.empty((n, self._p2d_k), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int32)
+        _check(self._lib.pccm_get_p2d_neighbours(self._ctx, int(direction), rows.ctypes.data_as(ctypes.c_void_p),
+                                                 counts.ctypes.data_as(ctypes.c_void_p)))
+        return rows, counts
 
     def set_shard(self, rank: int, world: int) -> None:
         _check(self._lib.pccm_set_shard(self._ctx, int(rank), int(world)))

@@ -15,7 +15,8 @@ import pandas as pd
 
 from .cloud_pair import CloudPair
 from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, EuclideanDistance,
-                     GeoRankedHausdorffDistance, PrimaryMetric, SecondaryMetric, SSIMSimilarities, SymmetricMetric)
+                     GeoRankedHausdorffDistance, MahalanobisDistances, PrimaryMetric, SecondaryMetric, SSIMSimilarities,
+                     SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -93,6 +94,8 @@ class MetricCalculator:
                 wanted.append(("angular", metric.is_left))
             elif isinstance(metric, SSIMSimilarities):
                 wanted.append(("ssim", metric.attribute, metric.is_left, metric.k))
+            elif isinstance(metric, MahalanobisDistances):
+                wanted.append(("p2d", metric.is_left, metric.k))
             (late if waits else early).append((metric, None, key))
         elif role == 2:
             if isinstance(metric, EuclideanDistance):

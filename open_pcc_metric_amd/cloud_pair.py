@@ -115,7 +115,9 @@ class DeviceColumn(_DeviceArray):
     ``"angular"``   plane-to-plane angular similarities (get_left/right_angular_similarities; include/pccm.h,
                     PCCM_METRIC_ANGULAR: the own normal against the matched point's, ``normal_index`` does not apply),
     ``"ssim:<attribute>"``  PointSSIM similarities of one attribute (get_left/right_ssim_similarities; PCCM_METRIC_SSIM_*: the
-                    own feature against the matched point's, at the neighbourhood size the pair's features were built with).
+                    own feature against the matched point's, at the neighbourhood size the pair's features were built with),
+    ``"p2d"``       point-to-distribution (Mahalanobis) distances (get_left/right_mahalanobis_distances; PCCM_METRIC_P2D: the
+                    direction's stored column, at the neighbourhood size the pair's columns were built with).
     """
 
     def __init__(self, pair: "CloudPair", direction: int, kind: str):
@@ -125,7 +127,7 @@ class DeviceColumn(_DeviceArray):
         self._red = None
 
     _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2,
-               "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}}
+               "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}, "p2d": nat.METRIC_P2D}
 
     def _materialise(self) -> np.ndarray:
         p = self._pair
@@ -781,6 +783,38 @@ class CloudPair:
     def get_right_ssim_similarities(self, attribute: str, k: int = 12):
         return self._ssim_column(nat.DIR_RIGHT, attribute, k)
 
+    # -- point-to-distribution ("Point-to-distribution") ------------------------------------------------------
+    def _check_p2d(self, k: int) -> None:
+        """The ValueErrors of CalculateOptions and options.check_point_to_distribution, for this pair -- raised before any GPU
+        work of a report."""
+        from .options import CalculateOptions, check_point_to_distribution
+        check_point_to_distribution(CalculateOptions(point_to_distribution=True, p2d_neighbours=k),
+                                    group=self._coll.group if self._coll.sharded else None)
+
+    def _ensure_p2d(self, k: int) -> None:
+        """Both directions' columns at neighbourhood size ``k``, built in HBM where missing (pccm_p2d_build: new points in
+        either cloud -- with_reconst -- drop them, so the next report builds both again)."""
+        self._check_p2d(k)
+        if not hasattr(self._engine, "p2d_build"):
+            raise ValueError("this engine has no point-to-distribution columns")
+        built = self._engine.p2d_build(int(k))
+        if built or self.__dict__.get("_p2d_k") != int(k):    # totals of earlier columns are stale
+            self._totals = {key: v for key, v in self._totals.items() if key[1] != nat.METRIC_P2D}
+        self._p2d_k = int(k)
+
+    def _p2d_column(self, direction: int, k: int) -> DeviceColumn:
+        self._ensure_p2d(k)
+        return DeviceColumn(self, direction, "p2d")
+
+    def get_left_mahalanobis_distances(self, k: int = 30):
+        """Per point of the origin cloud: its Mahalanobis distance to the distribution of its k nearest reconstructed points
+        (fp64; a device column: ``np.asarray`` fetches it, ``np.sum`` / ``np.max`` reduce it on the GPU).  The tie policy of the
+        1-NN searches does not enter it."""
+        return self._p2d_column(nat.DIR_LEFT, k)
+
+    def get_right_mahalanobis_distances(self, k: int = 30):
+        return self._p2d_column(nat.DIR_RIGHT, k)
+
     def get_left_neighbour_colors(self):
         """cloud_pair.py:120-121: the matched points' colours -- gathered on the device when asked for."""
         return DeviceColorRows(self, nat.DIR_LEFT, "neighbour")
@@ -792,7 +826,7 @@ class CloudPair:
         """Enqueue the fused reductions a report is about to ask for, without waiting for any of them.
 
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
-        ``("ranked", is_left, point_to_plane, rank)`` and/or the string ``"boundary"``.
+        ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -817,10 +851,17 @@ class CloudPair:
         ranked_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "ranked"]
         if ranked_items:
             self._check_ranked()
+        # point-to-distribution: the check, then the columns -- built here like the features, eagerly and outside any capture
+        p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "p2d"]
+        for k in sorted({item[2] for item in p2d_items}):
+            self._check_p2d(k)
+        for k in sorted({item[2] for item in p2d_items}):
+            self._ensure_p2d(k)
         requests, ssim_requests, selections = [], [], []
+        p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_P2D) for item in p2d_items]
         for item in wanted:
-            if item in ranked_items:
-                continue              # (below: their columns are requests of their own, EuclideanDistance's)
+            if item in ranked_items or item in p2d_items:
+                continue              # (ranked: their columns are requests of their own, EuclideanDistance's)
             if item in ssim_items:
                 ssim_requests.append((nat.DIR_LEFT if item[2] else nat.DIR_RIGHT, nat.METRIC_SSIM[item[1]]))
                 continue
@@ -867,19 +908,22 @@ class CloudPair:
             column = (direction, nat.METRIC_D2 if p2p else nat.METRIC_D1)
             if column in requests:
                 selections.append(column + (rank_index(rank, eng.n_iter(direction)),))
-        self._xchg_wanted = list(requests) + ssim_requests
+        self._xchg_wanted = list(requests) + ssim_requests + p2d_requests
         self._sel_wanted = sorted(set(selections))
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
-            eng.reduce_prefetch_many(requests[:8], self.normal_index)
+            ride = len(requests) + len(p2d_requests) <= 8     # (stored columns: they join the first batch when it has room)
+            eng.reduce_prefetch_many((requests + p2d_requests if ride else requests)[:8], self.normal_index)
             for b in range(0, len(ssim_requests), 4):     # (at most four matched-row columns per batch: k_point_jobs)
                 eng.reduce_prefetch_many(ssim_requests[b:b + 4], self.normal_index)
+            if not ride:
+                eng.reduce_prefetch_many(p2d_requests, self.normal_index)
             if hasattr(eng, "select_prefetch_many"):
                 for batch in _selection_batches(self._sel_wanted):
                     eng.select_prefetch_many(batch, self.normal_index)
         else:
-            requests = requests + ssim_requests
+            requests = requests + ssim_requests + p2d_requests
             for direction, metric in requests:
                 eng.reduce_prefetch(direction, metric, self.normal_index)
 

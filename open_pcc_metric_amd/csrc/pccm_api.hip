@@ -479,6 +479,12 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
     ctx->sel_host = nullptr;
     for (int k = 0; k < 2; ++k) free_cloud(ctx->cloud[k]);
+    for (int d = 0; d < 2; ++d) {
+        if (ctx->p2d64[d]) (void)hipFree(ctx->p2d64[d]);
+        ctx->p2d64[d] = nullptr;
+        ctx->cap_p2d[d] = 0;
+    }
+    ctx->p2d_k = 0;
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
@@ -515,6 +521,7 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     Cloud &c = ctx->cloud[which];
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     drop_cloud(c);                                   // its normals and colours go with it
+    ctx->p2d_k = 0;                                  // (both point-to-distribution columns depend on either cloud)
     // (a new cloud 1 leaves the self search of cloud 0 -- cloud_pair.py:108-109 -- as valid as it was: one reference cloud
     // against several decoded ones, BASELINE configs[4], keeps it, see CloudPair.with_reconst)
     for (int d = 0; d < 3; ++d) {
@@ -1011,6 +1018,34 @@ int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out)
     return PCCM_OK;
 }
 
+int pccm_p2d_build(pccm_ctx *ctx, int k, int *built)
+{
+    CHECK_CTX(ctx);
+    if (built) *built = 0;
+    if (k < 4 || k > 64) return fail(PCCM_E_ARG, "point-to-distribution neighbourhoods have 4..64 points, not %d", k);
+    for (int which = 0; which < 2; ++which)
+        if (ctx->cloud[which].n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "point-to-distribution columns need whole clouds on this GPU (world = 1)");
+    return p2d_build(ctx, k, built);                   // (what is there already needs no work, and may be asked for while capturing)
+}
+
+int pccm_get_p2d_neighbours(pccm_ctx *ctx, int dir, int32_t *out, int32_t *count)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (dir != PCCM_DIR_LEFT && dir != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "point-to-distribution exists for directions 0 and 1");
+    if (!out || !count) return fail(PCCM_E_ARG, "null pointer");
+    if (ctx->p2d_k <= 0) return fail(PCCM_E_STATE, "no point-to-distribution columns (pccm_p2d_build)");
+    const int64_t n = ctx->cloud[dir].n;
+    const int32_t *nbr, *cnt;
+    int rc = p2d_neighbours(ctx, dir, ctx->p2d_k, &nbr, &cnt);
+    if (rc) return rc;
+    if ((rc = d2h(ctx, out, nbr, (size_t)n * ctx->p2d_k * sizeof(int32_t)))) return rc;
+    if ((rc = d2h(ctx, count, cnt, (size_t)n * sizeof(int32_t)))) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
+}
+
 int pccm_set_shard(pccm_ctx *ctx, int rank, int world)
 {
     CHECK_CTX(ctx);
@@ -1375,6 +1410,14 @@ static bool matched_column(int metric)
     return metric == PCCM_METRIC_ANGULAR || is_ssim_metric(metric);
 }
 
+// PCCM_METRIC_P2D: the stored column of the direction (pccm_p2d_build); neither the matched rows nor normal_mode enter it
+static int check_p2d(pccm_ctx *ctx, int dir)
+{
+    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-distribution is not defined for the self search");
+    if (ctx->p2d_k <= 0) return fail(PCCM_E_STATE, "point-to-distribution columns are not built (pccm_p2d_build)");
+    return PCCM_OK;
+}
+
 int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
 {
     CHECK_CTX(ctx);
@@ -1421,6 +1464,11 @@ static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode,
         if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
         if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, PCCM_NORMAL_NEIGHBOUR, (double *)vb.p, nullptr))) return rc;
         *dev = (const double *)vb.p;
+        return PCCM_OK;
+    }
+    if (metric == PCCM_METRIC_P2D) {
+        if ((rc = check_p2d(ctx, dir))) return rc;
+        *dev = ctx->p2d64[dir] + res->begin;
         return PCCM_OK;
     }
     if (is_ssim_metric(metric)) {
@@ -1531,6 +1579,7 @@ struct ColumnSource {
         kPlainD2,         // the plain d2 column (no records: the engine wrote the plain columns)
         kPointJob,        // a k_point_jobs job that reads the matched rows from the plain idx column, or from matched records (recs)
         kTieColumn,       // the tie pass's column (PCCM_TIES_MEAN)
+        kStored,          // a stride-1 column kept with the context (PCCM_METRIC_P2D: pccm_p2d_build)
     } from = kPointJob;
     // the plain columns: none needed or they are there; the binder unpacks them; or they come before any column of the batch is
     // bound.  Which columns the binder unpacks (an unfused projection over stride-4 records) is today's split: it decides which
@@ -1553,6 +1602,10 @@ static ColumnSource column_source(const pccm_ctx *ctx, int dir, int metric, int 
         return c;
     }
     if (dir == PCCM_DIR_SELF) return c;
+    if (metric == PCCM_METRIC_P2D) {
+        c.from = ColumnSource::kStored;
+        return c;
+    }
     if (matched_column(metric)) {                          // the matched rows in place, or from the plain idx column
         if (mean) c.from = ColumnSource::kTieColumn;
         else if (f.matched_in_place()) c.recs = true;
@@ -1586,6 +1639,8 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     const bool matched = matched_column(metric), ssim = is_ssim_metric(metric);
     if (matched) {
         if ((rc = ssim ? check_ssim(ctx, dir, *it, *se, *res, metric) : check_angular(ctx, dir, *it, *se))) return rc;
+    } else if (metric == PCCM_METRIC_P2D) {
+        if ((rc = check_p2d(ctx, dir))) return rc;
     } else if (metric != PCCM_METRIC_D1) {
         if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
         if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
@@ -1601,6 +1656,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
         dev = (const double *)ctx->tie[dir].ang.p;
         break;
+    case ColumnSource::kStored: dev = ctx->p2d64[dir] + res->begin; break;
     case ColumnSource::kPointJob:
         // (PCCM_METRIC_SSIM_*: the angular column's job on the two clouds' feature columns instead of their normals)
         if (src.prep != ColumnSource::kReady && (rc = ensure_plain(ctx, *res, true))) return rc;
@@ -1699,7 +1755,7 @@ static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode
 {
     for (auto &s : ctx->slots)
         if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric &&
-            (metric == PCCM_METRIC_D1 || matched_column(metric) || s.mode == normal_mode) &&
+            (metric == PCCM_METRIC_D1 || metric == PCCM_METRIC_P2D || matched_column(metric) || s.mode == normal_mode) &&
             s.gen == ctx->nn_gen[dir])
             return &s;
     return nullptr;
@@ -1760,7 +1816,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         NNResult &res = ctx->nn[dirs[k]];
         if (!res.valid || res.ties != PCCM_TIES_MEAN) continue;
         if (metrics[k] == PCCM_METRIC_ANGULAR) tie_ang[dirs[k]] = true;
-        else if (metrics[k] != PCCM_METRIC_D1 && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
+        else if (metrics[k] != PCCM_METRIC_D1 && metrics[k] != PCCM_METRIC_P2D && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
     }
     for (int d = 0; d < 2; ++d) {
         if (!tie_ang[d] || slot_find(ctx, d, PCCM_METRIC_ANGULAR, 0, want_units)) continue;
@@ -1784,7 +1840,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     for (int k = 0; k < n; ++k) {
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
         ReduceSlot *s = slot_free(ctx, fresh, nfresh);
-        if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 16 live columns in one batch");
+        if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 24 live columns in one batch");
         if (s->pending && !ctx->capturing && s->wait_ev) { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
         s->pending = false;
         int rc = slot_prepare(ctx, *s, dirs[k], metrics[k], normal_modes[k], want_units, pj, uj);
@@ -2412,6 +2468,7 @@ int pccm_ctx_reset(pccm_ctx *ctx)
         drop_cloud(ctx->cloud[k]);
         ctx->cloud[k].version++;
     }
+    ctx->p2d_k = 0;
     for (int d = 0; d < 3; ++d) {
         ctx->shard_rank[d] = 0;
         ctx->shard_world[d] = 1;

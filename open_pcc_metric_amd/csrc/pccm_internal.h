@@ -308,7 +308,12 @@ struct pccm_ctx {
     // scratch
     pccm::DevBuf part_b1, part_g, part_b2, val, stats, staging, counters;
     pccm::DevBuf rescan_part;             // k2b_fallback's split regime: partial minima per (query, workgroup)
-    pccm::DevBuf ssim_scratch;            // pccm_ssim_features: neighbour rows [n][k] + curvatures [n]
+    pccm::DevBuf ssim_scratch;            // pccm_ssim_features: neighbour rows [n][k] + curvatures [n]; pccm_p2d_build: neighbour rows [n][k]
+    // point-to-distribution columns (pccm_p2d_build): M of every point of cloud d against the other cloud's k nearest points, valid
+    // for neighbourhood size p2d_k (0: not built; new points in either cloud drop both)
+    double *p2d64[2] = {nullptr, nullptr};
+    size_t cap_p2d[2] = {0, 0};
+    int p2d_k = 0;
     pccm::DevBuf tail_sync;               // k_grid_tail: retired-entry counts + ticket, for the normal and the self pass
     bool tail_sync_clean = false;
     pccm::DevBuf color_cols, color_idx;   // colour pass: squares as three columns / caller-supplied neighbour rows
@@ -343,7 +348,7 @@ struct pccm_ctx {
     bool bins_clean = false;   // the build's bin cursors (head of g_bins) are zero on the stream
     int want_idx = 1;                      // pccm_nn_want_idx: searches store the matched row with every result
     int fuse_mode[3] = {-1, -1, -1};       // pccm_nn_fuse: normal mode of the D2 projection fused into the search, per direction
-    pccm::ReduceSlot slots[16];           // (a report with every PointSSIM row holds up to 15 columns at once)
+    pccm::ReduceSlot slots[24];           // (a report with every PointSSIM and point-to-distribution row holds up to 17 columns at once)
     // selections (pccm_select_*): slot s answers into sel_host[s] (host-coherent pinned memory); the histograms and pass states
     // are sized once per context
     static constexpr int kSelSlots = 32;
@@ -451,6 +456,8 @@ int grid_decide(pccm_ctx *ctx, bool *hostile);   // geometry decision for the cu
 int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; isolation verdict (cached per pair)
 int estimate_normals(pccm_ctx *ctx, int which, int k);
 int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built);   // the checks are pccm_ssim_features'
+int p2d_build(pccm_ctx *ctx, int k, int *built);                             // the checks are pccm_p2d_build's
+int p2d_neighbours(pccm_ctx *ctx, int dir, int k, const int32_t **nbr, const int32_t **cnt);   // device lists [n][k], [n]
 int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int normal_mode, double out[8]);
 // PCCM_TIES_MEAN producer: for the ns queries q_begin.. of direction dir (matched rows idx, squared distances d2 or null = formed
 // from idx) the ascending-row mean of all equidistant nearest points -> pos[ns][3], k[ns]; nrm / rgb likewise when snrm / srgb;
@@ -509,6 +516,7 @@ __device__ __forceinline__ double ssim_similarity(double a, double b)
     return __dsub_rn(1.0, __ddiv_rn(num, den));
 }
 
+// (PCCM_METRIC_P2D is a stored column: pccm_api.hip binds it, no point kernel sees it)
 __host__ __device__ __forceinline__ bool is_ssim_metric(int metric)
 {
     return metric >= PCCM_METRIC_SSIM_GEOMETRY && metric <= PCCM_METRIC_SSIM_COLOR;

@@ -24,6 +24,15 @@
 // normal.  k_normals_from_cov then runs again: for the curvature of every point (mode 1) and for the features (mode 2), both from
 // the neighbour lists -- the covariance behind a curvature is summed in neighbourhood order, not in the search's order (which
 // follows the grid, and so the other cloud of the pair), so that a cloud's features do not depend on the pair it is in.
+//
+// Point-to-distribution (pccm_p2d_build, INTEGRATION.md "Point-to-distribution") runs the three searches ACROSS the clouds: the
+// queries are the points of one cloud (query_at), the candidates the cells of the other.  A query's cell comes from its
+// coordinates through ncell_coord, which clamps, so a query may lie outside the searched cloud's grid.  The stop rule stays a
+// valid lower bound: L only counts a face of the cube [c-r, c+r]^3 that is not a face of the grid, and on every axis the query
+// lies between the two faces of its cube or beyond the one that is the grid's (where no point of the searched cloud can be: the
+// grid's boundary cells hold everything that clamps into them).  A point outside the cube is beyond a counted face, at least
+// (face - q) - slack away along that axis, exactly as for a query inside the grid.  k_normals_from_cov (mode 3) then forms the
+// Mahalanobis distance of every query to its neighbours' distribution from the neighbour lists.
 #include "pccm_internal.h"
 
 namespace pccm {
@@ -52,6 +61,21 @@ __device__ __forceinline__ double nd2(double qx, double qy, double qz, double rx
     d = __dadd_rn(d, __dmul_rn(dy, dy));
     d = __dadd_rn(d, __dmul_rn(dz, dz));
     return d;
+}
+
+// The query a search thread or wave works on: record t of `qrecs` (cell-sorted records: the searched cloud's own slice, or the
+// other cloud's slice of the pair's grid), or -- qrecs null -- row t of `qx64` (a cloud that is not in the searched grid)
+__device__ __forceinline__ void query_at(const GridRec *__restrict__ qrecs, const double *__restrict__ qx64, int64_t t, double &qx,
+                                         double &qy, double &qz, int &qrow)
+{
+    if (qrecs) {
+        const double4 qa = *reinterpret_cast<const double4 *>(&qrecs[t]);
+        qx = qa.x; qy = qa.y; qz = qa.z;
+        qrow = (int)(__double_as_longlong(qa.w) & 0xffffffffll);
+    } else {
+        qx = qx64[3 * t]; qy = qx64[3 * t + 1]; qz = qx64[3 * t + 2];
+        qrow = (int)t;
+    }
 }
 
 // sorted insertion of (d, row) into the k best kept in ascending (d, row) order
@@ -144,7 +168,9 @@ __device__ __forceinline__ void ssim_neighbours_out(const int *bi, int cnt, int 
 
 // one thread per point (in cell-sorted order); rings 0..kKnnMaxRing
 // `todo` / `todo_count`: positions (within this cloud's slice) the wave kernel handed on; the threads stride over them
-__global__ __launch_bounds__(256) void k_knn_normals(const GridRec *__restrict__ recs, int64_t qbase, KnnGeom g,
+// `qrecs` / `qx64`: where the queries are read (query_at); `recs`, `cell_start`, `x64`: the searched cloud
+__global__ __launch_bounds__(256) void k_knn_normals(const GridRec *__restrict__ recs, const GridRec *__restrict__ qrecs,
+                                                     const double *__restrict__ qx64, KnnGeom g,
                                                      const uint32_t *__restrict__ cell_start, const double *__restrict__ x64,
                                                      int k, double *__restrict__ nrm_out, const uint32_t *__restrict__ todo,
                                                      const uint32_t *__restrict__ todo_count, int32_t *__restrict__ open_list,
@@ -154,9 +180,9 @@ __global__ __launch_bounds__(256) void k_knn_normals(const GridRec *__restrict__
   const int64_t n = *todo_count;
   for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n; u += (int64_t)gridDim.x * 256) {
     const int64_t t = todo[u];
-    const double4 qa = *reinterpret_cast<const double4 *>(&recs[qbase + t]);   // this cloud's slice of the combined array
-    const double qx = qa.x, qy = qa.y, qz = qa.z;
-    const int qrow = (int)(__double_as_longlong(qa.w) & 0xffffffffll);
+    double qx, qy, qz;
+    int qrow;
+    query_at(qrecs, qx64, t, qx, qy, qz, qrow);
     const int dimx = g.dim[0], dimy = g.dim[1], dimz = g.dim[2];
     const int cx = ncell_coord(qx, g.org[0], g.inv_h[0], dimx);
     const int cy = ncell_coord(qy, g.org[1], g.inv_h[1], dimy);
@@ -235,7 +261,8 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict__ recs, int64_t qbase, int64_t n, KnnGeom g,
+__global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict__ recs, const GridRec *__restrict__ qrecs,
+                                                      const double *__restrict__ qx64, int64_t n, KnnGeom g,
                                                       const uint32_t *__restrict__ cell_start, int k,
                                                       double *__restrict__ cov_out /*[n][6] by row*/, int32_t *__restrict__ cnt_out,
                                                       uint32_t *__restrict__ todo, uint32_t *__restrict__ todo_count,
@@ -247,9 +274,9 @@ __global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict_
     const int dimx = g.dim[0], dimy = g.dim[1], dimz = g.dim[2];
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t t = (int64_t)blockIdx.x * 4 + w; t < n; t += nwaves) {
-        const double4 qa = *reinterpret_cast<const double4 *>(&recs[qbase + t]);          // wave-uniform
-        const double qx = qa.x, qy = qa.y, qz = qa.z;
-        const int qrow = (int)(__double_as_longlong(qa.w) & 0xffffffffll);
+        double qx, qy, qz;                                                                  // wave-uniform
+        int qrow;
+        query_at(qrecs, qx64, t, qx, qy, qz, qrow);
         const int cx = ncell_coord(qx, g.org[0], g.inv_h[0], dimx);
         const int cy = ncell_coord(qy, g.org[1], g.inv_h[1], dimy);
         const int cz = ncell_coord(qz, g.org[2], g.inv_h[2], dimz);
@@ -454,20 +481,63 @@ __device__ __forceinline__ double ssim_value(int a, int64_t p, int64_t q, const 
     return fma(0.0722, c[2], fma(0.2126, c[0], __dmul_rn(0.7152, c[1])));
 }
 
+// Point-to-distribution value of query i (include/pccm.h, pccm_p2d_build): the Mahalanobis distance from the query p to the
+// distribution of its cnt neighbours `row` (rows of x64, ascending (d2, row)).  Moments of e_j = q_j - p summed left to right in
+// neighbourhood order, population covariance, a ridge of 2^-10 of the trace on the diagonal, the quadratic form by cofactors.
+// Every operation is rounded separately, in the order INTEGRATION.md writes it: a NumPy restatement gives the same bits.
+__device__ __forceinline__ double p2d_value(const double *__restrict__ x64, const double *__restrict__ q64, int64_t i,
+                                            const int32_t *__restrict__ row, int cnt)
+{
+    const double px = q64[3 * i], py = q64[3 * i + 1], pz = q64[3 * i + 2];
+    double s0 = 0, s1 = 0, s2 = 0, s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const double *q = x64 + 3 * (int64_t)row[j];
+        const double e0 = __dsub_rn(q[0], px), e1 = __dsub_rn(q[1], py), e2 = __dsub_rn(q[2], pz);
+        s0 = __dadd_rn(s0, e0); s1 = __dadd_rn(s1, e1); s2 = __dadd_rn(s2, e2);
+        s00 = __dadd_rn(s00, __dmul_rn(e0, e0)); s01 = __dadd_rn(s01, __dmul_rn(e0, e1)); s02 = __dadd_rn(s02, __dmul_rn(e0, e2));
+        s11 = __dadd_rn(s11, __dmul_rn(e1, e1)); s12 = __dadd_rn(s12, __dmul_rn(e1, e2)); s22 = __dadd_rn(s22, __dmul_rn(e2, e2));
+    }
+    const double kk = (double)cnt;
+    const double m0 = __ddiv_rn(s0, kk), m1 = __ddiv_rn(s1, kk), m2 = __ddiv_rn(s2, kk);
+    const double C00 = __dsub_rn(__ddiv_rn(s00, kk), __dmul_rn(m0, m0)), c01 = __dsub_rn(__ddiv_rn(s01, kk), __dmul_rn(m0, m1));
+    const double c02 = __dsub_rn(__ddiv_rn(s02, kk), __dmul_rn(m0, m2)), C11 = __dsub_rn(__ddiv_rn(s11, kk), __dmul_rn(m1, m1));
+    const double c12 = __dsub_rn(__ddiv_rn(s12, kk), __dmul_rn(m1, m2)), C22 = __dsub_rn(__ddiv_rn(s22, kk), __dmul_rn(m2, m2));
+    const double t = __dadd_rn(__dadd_rn(C00, C11), C22);
+    const double lam = __dmul_rn(t, 0x1.0p-10);
+    const double c00 = __dadd_rn(C00, lam), c11 = __dadd_rn(C11, lam), c22 = __dadd_rn(C22, lam);
+    const double f00 = __dsub_rn(__dmul_rn(c11, c22), __dmul_rn(c12, c12)), f01 = __dsub_rn(__dmul_rn(c02, c12), __dmul_rn(c01, c22));
+    const double f02 = __dsub_rn(__dmul_rn(c01, c12), __dmul_rn(c02, c11)), f11 = __dsub_rn(__dmul_rn(c00, c22), __dmul_rn(c02, c02));
+    const double f12 = __dsub_rn(__dmul_rn(c01, c02), __dmul_rn(c00, c12)), f22 = __dsub_rn(__dmul_rn(c00, c11), __dmul_rn(c01, c01));
+    const double det = __dadd_rn(__dadd_rn(__dmul_rn(c00, f00), __dmul_rn(c01, f01)), __dmul_rn(c02, f02));
+    if (!(t > 0.0) || !(det > 0.0)) return (m0 == 0.0 && m1 == 0.0 && m2 == 0.0) ? 0.0 : INFINITY;
+    const double v0 = __dadd_rn(__dadd_rn(__dmul_rn(f00, m0), __dmul_rn(f01, m1)), __dmul_rn(f02, m2));
+    const double v1 = __dadd_rn(__dadd_rn(__dmul_rn(f01, m0), __dmul_rn(f11, m1)), __dmul_rn(f12, m2));
+    const double v2 = __dadd_rn(__dadd_rn(__dmul_rn(f02, m0), __dmul_rn(f12, m1)), __dmul_rn(f22, m2));
+    const double quad = __dadd_rn(__dadd_rn(__dmul_rn(m0, v0), __dmul_rn(m1, v1)), __dmul_rn(m2, v2));
+    const double r = __ddiv_rn(quad, det);
+    return __dsqrt_rn(r > 0.0 ? r : 0.0);
+}
+
 // mode 0: normals from the covariances (the per-thread kernels write their own: cnt < 0)
 // mode 1 (PointSSIM): curvature of every point -> curv[n], from the neighbour lists nbr[n][k] (cnt[i] entries)
 // mode 2 (PointSSIM): the features of the attributes in `attrs` -> feat[a][n], from the neighbour lists nbr[n][k] (cnt[i] entries):
 //   m values v_j over N_k(p), mu = (sum v_j) / m, F = (sum (v_j - mu)^2) / (m - 1), F = 0 for m < 2; left-to-right sums, every
 //   operation separately rounded.  Geometry and normal skip q_0 (the point itself).  The values are formed twice (two passes)
 //   instead of being kept: up to 64 of them per thread would live in scratch memory.
+// mode 3 (point-to-distribution): p2d_value of every query i (row i of q64) -> nrm_out[n], from its neighbour list nbr[n][k] of rows
+//   of x64 (cnt[i] entries)
 __global__ __launch_bounds__(256) void k_normals_from_cov(const double *__restrict__ cov, const int32_t *__restrict__ cnt, int64_t n,
                                                           double *__restrict__ nrm_out, int mode, const int32_t *__restrict__ nbr, int k,
                                                           const double *__restrict__ x64, const double *__restrict__ nrm64,
                                                           const double *__restrict__ rgb64, double *__restrict__ curv,
-                                                          double *__restrict__ feat, int attrs)
+                                                          double *__restrict__ feat, int attrs, const double *__restrict__ q64)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (mode == 3) {
+        nrm_out[i] = p2d_value(x64, q64, i, nbr + i * k, cnt[i]);
+        return;
+    }
     if (mode == 1) {
         curv[i] = curvature_of(x64, i, nbr + i * k, cnt[i]);
         return;
@@ -507,7 +577,8 @@ __global__ __launch_bounds__(256) void k_normals_from_cov(const double *__restri
 
 // isolated points: exact k-NN by a full scan, one workgroup per point.  Every thread keeps the k best of its
 // stride; the k global best are then extracted one by one with a workgroup-wide lexicographic minimum.
-__global__ __launch_bounds__(256) void k_knn_normals_full(const double *__restrict__ x64, int64_t n, int k,
+// (`qx64`: the queries' cloud -- the scanned cloud itself, or the other one for a search across the clouds)
+__global__ __launch_bounds__(256) void k_knn_normals_full(const double *__restrict__ x64, const double *__restrict__ qx64, int64_t n, int k,
                                                           const int32_t *__restrict__ open_list,
                                                           const uint32_t *__restrict__ open_count,
                                                           double *__restrict__ nrm_out, int32_t *__restrict__ nbr_out,
@@ -520,7 +591,7 @@ __global__ __launch_bounds__(256) void k_knn_normals_full(const double *__restri
     const uint32_t count = *open_count;
     for (uint32_t f = blockIdx.x; f < count; f += gridDim.x) {
         const int qrow = open_list[f];
-        const double qx = x64[3 * (int64_t)qrow], qy = x64[3 * (int64_t)qrow + 1], qz = x64[3 * (int64_t)qrow + 2];
+        const double qx = qx64[3 * (int64_t)qrow], qy = qx64[3 * (int64_t)qrow + 1], qz = qx64[3 * (int64_t)qrow + 2];
         double bd[kKnnMax];
         int bi[kKnnMax];
         int cnt = 0;
@@ -551,8 +622,11 @@ __global__ __launch_bounds__(256) void k_knn_normals_full(const double *__restri
     }
 }
 
-// the grid both k-NN searches of cloud `which` run on, its cell starts and records (shared by estimate_normals and ssim_features)
-static int knn_setup(pccm_ctx *ctx, int which, KnnGeom &g, const uint32_t *&cs, const GridRec *&crecs)
+// the grid the k-NN searches of cloud `which` run on, its cell starts and records (shared by estimate_normals, ssim_features and
+// the point-to-distribution search).  `qrecs` (the search across the clouds): the OTHER cloud's cell-sorted records when both
+// clouds sit in the pair's grid -- queries taken in that order walk the same cells wave after wave -- or null when `which` has
+// cells of its own, which only sort `which`
+static int knn_setup(pccm_ctx *ctx, int which, KnnGeom &g, const uint32_t *&cs, const GridRec *&crecs, const GridRec **qrecs = nullptr)
 {
     const Cloud &c = ctx->cloud[which];
     int rc;
@@ -560,9 +634,10 @@ static int knn_setup(pccm_ctx *ctx, int which, KnnGeom &g, const uint32_t *&cs, 
     // one of similar size, hopeless for a much sparser one (a low rate of a codec: k = 30 neighbours then lie six rings out), which
     // gets cells of its own (grid_ensure_solo: a few histogram passes, cached with the cloud)
     const Cloud &other = ctx->cloud[1 - which];
-    if (other.n > 2 * c.n) {
+    const bool solo = other.n > 2 * c.n;
+    if (solo) {
         if ((rc = grid_ensure_solo(ctx, which))) return rc;
-    } else if ((rc = grid_ensure(ctx, true, 1 << which))) return rc;
+    } else if ((rc = grid_ensure(ctx, true, qrecs ? 3 : 1 << which))) return rc;
     const Grid &gr = ctx->grid;
     for (int a = 0; a < 3; ++a) {
         g.dim[a] = gr.dim[a];
@@ -574,6 +649,7 @@ static int knn_setup(pccm_ctx *ctx, int which, KnnGeom &g, const uint32_t *&cs, 
     // cell_start holds positions relative to the cloud's first record
     cs = (const uint32_t *)gr.cell_start.p + (which ? gr.ncells + 1 : 0);
     crecs = (const GridRec *)gr.recs.p + (which ? gr.n[0] : 0);
+    if (qrecs) *qrecs = solo ? nullptr : (const GridRec *)gr.recs.p + (which ? 0 : gr.n[0]);
     return PCCM_OK;
 }
 
@@ -591,6 +667,22 @@ static int knn_scratch(pccm_ctx *ctx, int64_t n, double **cov, int32_t **cnt, ui
     *cov = (double *)ctx->val.p;
     *cnt = (int32_t *)(*cov + 6 * n);
     return PCCM_OK;
+}
+
+// the three searches in neighbour-list mode: for each of the nq queries (qrecs / qx64: query_at; q64: their cloud's rows, which
+// the full scan reads) its k nearest points of the searched cloud (crecs, cs, s64, ns points) -> nbr[nq][k], cnt[nq] by query row
+static void launch_knn_lists(pccm_ctx *ctx, const GridRec *crecs, const uint32_t *cs, const KnnGeom &g, const double *s64, int64_t ns,
+                             const GridRec *qrecs, const double *qx64, const double *q64, int64_t nq, int k, double *cov, int32_t *cnt,
+                             uint32_t *open_count, uint32_t *todo_count, int32_t *nbr)
+{
+    const int64_t wblocks = (nq + 3) / 4;
+    PCCM_LAUNCH(ctx, k_knn_cov_wave, dim3((unsigned)(wblocks < 16384 ? wblocks : 16384)), dim3(256), 0, ctx->stream,
+                       crecs, qrecs, qx64, nq, g, cs, k, cov, cnt, (uint32_t *)ctx->g_rank.p, todo_count, nbr);
+    PCCM_LAUNCH(ctx, k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, qrecs, qx64, g, cs,
+                       s64, k, (double *)nullptr, (const uint32_t *)ctx->g_rank.p, (const uint32_t *)todo_count,
+                       (int32_t *)ctx->g_cell_of.p, open_count, nbr, cnt);
+    PCCM_LAUNCH(ctx, k_knn_normals_full, dim3(512), dim3(256), 0, ctx->stream, s64, q64, ns, k,
+                       (const int32_t *)ctx->g_cell_of.p, (const uint32_t *)open_count, (double *)nullptr, nbr, cnt);
 }
 
 int estimate_normals(pccm_ctx *ctx, int which, int k)
@@ -616,18 +708,19 @@ int estimate_normals(pccm_ctx *ctx, int which, int k)
     int32_t *cnt;
     uint32_t *open_count, *todo_count;
     if ((rc = knn_scratch(ctx, c.n, &cov, &cnt, &open_count, &todo_count))) return rc;
-    const int64_t qbase = 0;
     const int64_t wblocks = (c.n + 3) / 4;
     PCCM_LAUNCH(ctx, k_knn_cov_wave, dim3((unsigned)(wblocks < 16384 ? wblocks : 16384)), dim3(256), 0, ctx->stream,
-                       crecs, qbase, c.n, g, cs, k, cov, cnt, (uint32_t *)ctx->g_rank.p, todo_count, (int32_t *)nullptr);
+                       crecs, crecs, (const double *)nullptr, c.n, g, cs, k, cov, cnt, (uint32_t *)ctx->g_rank.p, todo_count,
+                       (int32_t *)nullptr);
     PCCM_LAUNCH(ctx, k_normals_from_cov, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)cov,
                        (const int32_t *)cnt, c.n, c.nrm64, 0, (const int32_t *)nullptr, k, (const double *)nullptr,
-                       (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr, 0);
-    PCCM_LAUNCH(ctx, k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, qbase, g, cs,
+                       (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr, 0,
+                       (const double *)nullptr);
+    PCCM_LAUNCH(ctx, k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, crecs, (const double *)nullptr, g, cs,
                        (const double *)c.xyz64, k, c.nrm64, (const uint32_t *)ctx->g_rank.p, (const uint32_t *)todo_count,
                        (int32_t *)ctx->g_cell_of.p, open_count, (int32_t *)nullptr, (int32_t *)nullptr);
-    PCCM_LAUNCH(ctx, k_knn_normals_full, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, k,
-                       (const int32_t *)ctx->g_cell_of.p, (const uint32_t *)open_count, c.nrm64, (int32_t *)nullptr,
+    PCCM_LAUNCH(ctx, k_knn_normals_full, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, (const double *)c.xyz64,
+                       c.n, k, (const int32_t *)ctx->g_cell_of.p, (const uint32_t *)open_count, c.nrm64, (int32_t *)nullptr,
                        (int32_t *)nullptr);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
@@ -665,31 +758,94 @@ int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
     if ((rc = ensure(ctx, ctx->ssim_scratch, nbr_words * sizeof(int32_t) + (size_t)c.n * sizeof(double)))) return rc;
     int32_t *nbr = (int32_t *)ctx->ssim_scratch.p;
     double *curv = (double *)(nbr + nbr_words);
-    const int64_t qbase = 0;
-    const int64_t wblocks = (c.n + 3) / 4;
     const dim3 pgrid((unsigned)((c.n + 255) / 256));
-    PCCM_LAUNCH(ctx, k_knn_cov_wave, dim3((unsigned)(wblocks < 16384 ? wblocks : 16384)), dim3(256), 0, ctx->stream,
-                       crecs, qbase, c.n, g, cs, k, cov, cnt, (uint32_t *)ctx->g_rank.p, todo_count, nbr);
-    PCCM_LAUNCH(ctx, k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, qbase, g, cs,
-                       (const double *)c.xyz64, k, (double *)nullptr, (const uint32_t *)ctx->g_rank.p, (const uint32_t *)todo_count,
-                       (int32_t *)ctx->g_cell_of.p, open_count, nbr, cnt);
-    PCCM_LAUNCH(ctx, k_knn_normals_full, dim3(512), dim3(256), 0, ctx->stream, (const double *)c.xyz64, c.n, k,
-                       (const int32_t *)ctx->g_cell_of.p, (const uint32_t *)open_count, (double *)nullptr, nbr, cnt);
+    launch_knn_lists(ctx, crecs, cs, g, c.xyz64, c.n, crecs, nullptr, c.xyz64, c.n, k, cov, cnt, open_count, todo_count, nbr);
     if (attrs & PCCM_SSIM_CURVATURE)
         PCCM_LAUNCH(ctx, k_normals_from_cov, pgrid, dim3(256), 0, ctx->stream, (const double *)nullptr, (const int32_t *)cnt, c.n,
                            (double *)nullptr, 1, (const int32_t *)nbr, k, (const double *)c.xyz64, (const double *)nullptr,
-                           (const double *)nullptr, curv, (double *)nullptr, 0);
+                           (const double *)nullptr, curv, (double *)nullptr, 0, (const double *)nullptr);
     // one launch per attribute: at 1M points and k = 12 the four attributes take 2.25 ms in one launch, 1.99 ms in four
     for (int a = 0; a < 4; ++a)
         if (attrs & (1 << a))
             PCCM_LAUNCH(ctx, k_normals_from_cov, pgrid, dim3(256), 0, ctx->stream, (const double *)nullptr, (const int32_t *)cnt, c.n,
                                (double *)nullptr, 2, (const int32_t *)nbr, k, (const double *)c.xyz64,
                                (const double *)((attrs & PCCM_SSIM_NORMAL) ? c.nrm64 : nullptr),
-                               (const double *)((attrs & PCCM_SSIM_COLOR) ? c.rgb64 : nullptr), curv, c.ssim64, 1 << a);
+                               (const double *)((attrs & PCCM_SSIM_COLOR) ? c.rgb64 : nullptr), curv, c.ssim64, 1 << a,
+                               (const double *)nullptr);
     PCCM_HIP(hipGetLastError());
     c.ssim_k = k;
     c.ssim_attrs = attrs;
     if (built) *built = 1;
+    return PCCM_OK;
+}
+
+// Point-to-distribution: the k nearest points of the OTHER cloud for every point of cloud `dir` (direction dir: cloud dir's points
+// are the queries), as neighbour lists nbr[n][k] / cnt[n] in ctx->ssim_scratch / ctx->val.  The grid is the one knn_setup picks for
+// the searched cloud; the chain wave -> per-thread -> full scan is the same-cloud searches', and so is the exactness.
+static int p2d_search(pccm_ctx *ctx, int dir, int k, int32_t **nbr_out, int32_t **cnt_out)
+{
+    const Cloud &a = ctx->cloud[dir], &b = ctx->cloud[1 - dir];
+    int rc;
+    KnnGeom g;
+    const uint32_t *cs;
+    const GridRec *crecs, *qrecs;
+    if ((rc = knn_setup(ctx, 1 - dir, g, cs, crecs, &qrecs))) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    double *cov;
+    int32_t *cnt;
+    uint32_t *open_count, *todo_count;
+    if ((rc = knn_scratch(ctx, a.n, &cov, &cnt, &open_count, &todo_count))) return rc;
+    if ((rc = ensure(ctx, ctx->ssim_scratch, (size_t)a.n * k * sizeof(int32_t)))) return rc;
+    int32_t *nbr = (int32_t *)ctx->ssim_scratch.p;
+    launch_knn_lists(ctx, crecs, cs, g, b.xyz64, b.n, qrecs, a.xyz64, a.xyz64, a.n, k, cov, cnt, open_count, todo_count, nbr);
+    PCCM_HIP(hipGetLastError());
+    *nbr_out = nbr;
+    *cnt_out = cnt;
+    return PCCM_OK;
+}
+
+// pccm_p2d_build has checked k, the clouds and the context's state
+int p2d_build(pccm_ctx *ctx, int k, int *built)
+{
+    if (built) *built = 0;
+    if (ctx->p2d_k == k) return PCCM_OK;
+    if (ctx->capturing) {
+        ctx->capture_failed = true;
+        return fail(PCCM_E_STATE, "point-to-distribution columns are built before graph capture");
+    }
+    int rc;
+    ctx->p2d_k = 0;
+    for (int d = 0; d < 2; ++d) ctx->nn_gen[d]++;       // pending point-to-distribution reductions would read stale columns
+    for (int d = 0; d < 2; ++d) {
+        const Cloud &a = ctx->cloud[d], &b = ctx->cloud[1 - d];
+        const double *before = ctx->p2d64[d];
+        PCCM_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = grow((void **)&ctx->p2d64[d], ctx->cap_p2d[d], (size_t)a.n * sizeof(double)))) return rc;
+        if (ctx->p2d64[d] != before) ctx->epoch++;          // (graphs that read the old column are stale)
+        int32_t *nbr, *cnt;
+        if ((rc = p2d_search(ctx, d, k, &nbr, &cnt))) return rc;
+        PCCM_LAUNCH(ctx, k_normals_from_cov, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)nullptr,
+                           (const int32_t *)cnt, a.n, ctx->p2d64[d], 3, (const int32_t *)nbr, k, (const double *)b.xyz64,
+                           (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr, 0,
+                           (const double *)a.xyz64);
+        PCCM_HIP(hipGetLastError());
+    }
+    ctx->p2d_k = k;
+    if (built) *built = 1;
+    return PCCM_OK;
+}
+
+// the neighbour lists of direction dir, in HBM until the next k-NN search (a search of its own: the build keeps no lists)
+int p2d_neighbours(pccm_ctx *ctx, int dir, int k, const int32_t **nbr_out, const int32_t **cnt_out)
+{
+    const Cloud &a = ctx->cloud[dir];
+    int rc;
+    if ((rc = ensure(ctx, ctx->ssim_scratch, (size_t)a.n * k * sizeof(int32_t)))) return rc;
+    PCCM_HIP(hipMemsetAsync(ctx->ssim_scratch.p, 0xff, (size_t)a.n * k * sizeof(int32_t), ctx->stream));   // unused entries: -1
+    int32_t *nbr, *cnt;
+    if ((rc = p2d_search(ctx, dir, k, &nbr, &cnt))) return rc;
+    *nbr_out = nbr;
+    *cnt_out = cnt;
     return PCCM_OK;
 }
 

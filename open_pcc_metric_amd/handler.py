@@ -1,7 +1,8 @@
 """Command line -- same flags and report text as ``python -m open_pcc_metric`` (handler.py:4-71).
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
-                                  [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...] [--csv]
+                                  [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
+                                  [--point-to-distribution] [--p2d-neighbours K] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -18,7 +19,10 @@ PointSSIM rows of Alexiou & Ebrahimi (ICME Workshops 2020) after those, over nei
 ("PointSSIM").  ``--hausdorff-rank R`` (repeatable, R in (0, 1]; no counterpart in the reference) adds the ranked
 (generalized) Hausdorff rows of Javaheri et al. (QoMEX 2020) after all others: the ceil(R n)-th smallest squared distance of
 each direction and its PSNR, for D1 and -- with ``--point-to-plane`` -- D2, selected on the GPU; independent of ``--hausdorff``,
-whose rows are those of R = 1 ("Ranked Hausdorff").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+whose rows are those of R = 1 ("Ranked Hausdorff").  ``--point-to-distribution`` (no counterpart in the reference)
+adds, after all others, the point-to-distribution rows after Javaheri et al. (IEEE SPL 2020): the mean -- with ``--hausdorff``
+also the maximum -- Mahalanobis distance of each point to the distribution of its ``--p2d-neighbours`` nearest points in the other
+cloud ("Point-to-distribution").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -48,6 +52,12 @@ import click
               help="Report the ranked (generalized) Hausdorff distance at this rank in (0, 1] as well (may be repeated, at most 4), "
                    "after all other rows: the ceil(R n)-th smallest squared distance of each direction and its PSNR (0.95: the "
                    "distance 95 % of the points stay within; 1: the Hausdorff rows); with --point-to-plane for D2 too.")
+@click.option("--point-to-distribution", "point_to_distribution", required=False, is_flag=True,
+              help="Report the point-to-distribution metric as well, after all other rows: the Mahalanobis distance of each point "
+                   "to the mean and covariance of its nearest points in the other cloud, averaged (lower is better, "
+                   "dimensionless); with --hausdorff also its worst point.  Does not depend on --ties.")
+@click.option("--p2d-neighbours", "p2d_neighbours", type=click.IntRange(4, 64), default=30, show_default=True,
+              help="Points of the other cloud per point-to-distribution neighbourhood.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -61,19 +71,22 @@ import click
 @click.option("--ties", type=click.Choice(["pick", "mean"]), default="pick", show_default=True,
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
-def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank, csv, device,
-        engine, normal_index, extent, tie_exposure, ties) -> None:
+def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
+        point_to_distribution, p2d_neighbours, csv, device, engine, normal_index, extent, tie_exposure, ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import CalculateOptions, check_hausdorff_rank, check_point_ssim, transform_options
+    from .options import (CalculateOptions, check_hausdorff_rank, check_point_ssim, check_point_to_distribution,
+                          transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
         options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
-                                   point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None)
+                                   point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None,
+                                   point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours)
     except ValueError as exc:
         raise click.UsageError(str(exc))
     check_hausdorff_rank(options)
+    check_point_to_distribution(options)
     ocloud_cloud = read_point_cloud(ocloud)
     cloud_pair = None
     for path in pcloud:

@@ -141,6 +141,21 @@ class SSIMSimilarities(PrimaryMetric, DirectionalMetric):        # no counterpar
                            lambda: cloud_pair.get_right_ssim_similarities(self.attribute, self.k))
 
 
+class MahalanobisDistances(PrimaryMetric, DirectionalMetric):    # no counterpart in the reference (options.py: point_to_distribution)
+    """Per point of the iterating cloud, its Mahalanobis distance to the distribution (mean and ridged covariance) of its k
+    nearest points in the OTHER cloud (include/pccm.h, pccm_p2d_build; INTEGRATION.md, "Point-to-distribution")."""
+    def __init__(self, is_left: bool, k: int = 30):
+        super().__init__(is_left)
+        self.k = int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.k)
+
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, lambda: cloud_pair.get_left_mahalanobis_distances(self.k),
+                           lambda: cloud_pair.get_right_mahalanobis_distances(self.k))
+
+
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, cloud_pair: CloudPair) -> None:
@@ -326,6 +341,39 @@ class CurvatureSSIM(_PointSSIM):
 class ColorSSIM(_PointSSIM):
     """Variance of the luma (BT.709 "ycc" Y) over the neighbourhood."""
     attribute = "color"
+
+
+class _OverMahalanobis(SecondaryMetric, DirectionalMetric):
+    _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+
+    def __init__(self, is_left: bool, k: int = 30):
+        super().__init__(is_left)
+        self.k = int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.k)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"mahalanobis_distances": MahalanobisDistances(is_left=self.is_left, k=self.k)}
+
+
+class MahalanobisDistance(_OverMahalanobis):
+    """Point-to-distribution metric of one direction (after Javaheri et al., IEEE SPL 2020): the mean of the per-point
+    Mahalanobis distances (sum / n, NumPy's pairwise sum).  Dimensionless; inf when a point's neighbourhood is one location the
+    point is not at."""
+    def calculate(self, mahalanobis_distances: MahalanobisDistances) -> None:
+        column = mahalanobis_distances.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
+        total = fused()[0] if fused is not None else None
+        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+
+
+class MaxMahalanobisDistance(_OverMahalanobis):
+    """The worst point of one direction (reported with hausdorff)."""
+    def calculate(self, mahalanobis_distances: MahalanobisDistances) -> None:
+        column = mahalanobis_distances.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
+        self.value = fused()[2] if fused is not None else np.max(column, axis=0)
 
 
 SSIM_CLASSES = {"geometry": GeometrySSIM, "normal": NormalSSIM, "curvature": CurvatureSSIM, "color": ColorSSIM}

@@ -28,6 +28,12 @@ after every row above, for each rank in ascending order:
 
   rank r                 RankedHausdorff L/R/sym, RankedHausdorffPSNR L/R/sym (D1)
   rank r & p2plane       the same six with point_to_plane=True
+
+and, with ``point_to_distribution`` (no counterpart in the reference: the Mahalanobis point-to-distribution metric of Javaheri et
+al., IEEE SPL 2020), after every row above, ranked Hausdorff rows included:
+
+  point_to_distribution        MahalanobisDistance L/R/sym
+  point_to_distribution & hd   MaxMahalanobisDistance L/R/sym
 """
 from __future__ import annotations
 
@@ -38,11 +44,13 @@ import numbers
 
 from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMSE, ColorPSNR, GeoHausdorffDistance,
                      GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR,
-                     MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance, SymmetricMetric)
+                     MahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
+                     SymmetricMetric)
 
 SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
 MAX_HAUSDORFF_RANKS = 4
+P2D_MIN_K, P2D_MAX_K = 4, 64
 
 
 def _hausdorff_ranks(value) -> typing.Tuple[float, ...]:
@@ -69,7 +77,7 @@ class CalculateOptions:
     def __init__(self, color: typing.Optional[str] = None, hausdorff: bool = False,
                  point_to_plane: bool = False, plane_to_plane: bool = False,
                  point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
-                 hausdorff_rank=None):
+                 hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -87,6 +95,11 @@ class CalculateOptions:
         self.point_ssim = tuple(a for a in SSIM_ATTRIBUTES if a in wanted)
         self.ssim_neighbours = int(ssim_neighbours)
         self.hausdorff_rank = _hausdorff_ranks(hausdorff_rank)
+        if isinstance(p2d_neighbours, bool) or type(p2d_neighbours).__name__ == "bool_" or not isinstance(p2d_neighbours, numbers.Real) \
+                or int(p2d_neighbours) != p2d_neighbours or not P2D_MIN_K <= int(p2d_neighbours) <= P2D_MAX_K:
+            raise ValueError(f"p2d_neighbours must be an integer in {P2D_MIN_K}..{P2D_MAX_K}, not {p2d_neighbours!r}")
+        self.point_to_distribution = bool(point_to_distribution)
+        self.p2d_neighbours = int(p2d_neighbours)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -114,6 +127,14 @@ def check_hausdorff_rank(options: CalculateOptions, *, group=None) -> None:
     A sharded pair would have to exchange the per-pass histograms across its ranks: not built."""
     if getattr(options, "hausdorff_rank", ()) and group is not None:
         raise ValueError("ranked Hausdorff rows are not available for sharded pairs (group=)")
+
+
+def check_point_to_distribution(options: CalculateOptions, *, group=None) -> None:
+    """Raise ``ValueError`` when the point-to-distribution rows ``options`` asks for cannot be computed for this pair -- before
+    any GPU work (the command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).
+    The columns need both whole clouds on one GPU: a sharded pair is out of scope."""
+    if getattr(options, "point_to_distribution", False) and group is not None:
+        raise ValueError("point-to-distribution rows are not available for sharded pairs (group=)")
 
 
 def _sides(cls, **kw):
@@ -156,4 +177,10 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
         for point_to_plane in (False, True) if options.point_to_plane else (False,):
             metrics += _error_then_psnr(GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR,
                                         point_to_plane=point_to_plane, rank=rank)
+    if getattr(options, "point_to_distribution", False):
+        # lower is better: the symmetric rows report the larger side
+        kw = dict(k=getattr(options, "p2d_neighbours", 30))
+        metrics += _sides(MahalanobisDistance, **kw) + [_sym(MahalanobisDistance, False, **kw)]
+        if options.hausdorff:
+            metrics += _sides(MaxMahalanobisDistance, **kw) + [_sym(MaxMahalanobisDistance, False, **kw)]
     return metrics

@@ -1,0 +1,434 @@
+"""Point-to-distribution rows on the GPU ("Point-to-distribution"; include/pccm.h, pccm_p2d_build /
+PCCM_METRIC_P2D; CalculateOptions(point_to_distribution=True)).
+
+The yardstick is the NumPy restatement of tests/p2d_reference.py.  Neighbour lists, per-point columns and pooled rows must equal
+it bit for bit: every step of the metric is separately rounded, so a neighbour taken out of (d2, row) order, a wrong tie at the
+k-th distance, an FMA or a reordered sum changes them.  No tolerance anywhere in this file."""
+import ctypes
+import functools
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+from click.testing import CliRunner
+
+from open_pcc_metric_amd import _native as nat
+from open_pcc_metric_amd.calculator import MetricCalculator
+from open_pcc_metric_amd.cloud_pair import CloudPair
+from open_pcc_metric_amd.handler import cli
+from open_pcc_metric_amd.io import read_point_cloud, write_point_cloud
+from open_pcc_metric_amd.options import CalculateOptions, transform_options
+from open_pcc_metric_amd.point_cloud import PointCloud
+from open_pcc_metric_amd.sequence import evaluate_pairs
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import p2d_reference as ref  # noqa: E402
+
+MEAN, MAX = "MahalanobisDistance", "MaxMahalanobisDistance"
+EXTENT = [1.0, 1.0, 1.0]
+
+
+def pair_of(a, b, **kw):
+    return CloudPair(PointCloud(a), PointCloud(b), extent=EXTENT, **kw)
+
+
+def report(pair, k=30, p2d=True, **kw):
+    opts = CalculateOptions(point_to_distribution=p2d, p2d_neighbours=k, **kw)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return MetricCalculator(pair).calculate(transform_options(opts)).as_dict()
+
+
+def bits(res):
+    return {key: np.asarray(v, dtype=np.float64).tobytes() for key, v in res.items()}
+
+
+def assert_same(got, want):
+    got = np.ascontiguousarray(got, dtype=np.float64)
+    want = np.ascontiguousarray(want, dtype=np.float64)
+    assert got.shape == want.shape
+    bad = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
+    assert bad.size == 0, f"{bad.size} rows differ, first {bad[:5]}: {got[bad[:5]]} vs {want[bad[:5]]}"
+
+
+def same_bits(value, want):
+    return np.float64(value).tobytes() == np.float64(want).tobytes()
+
+
+def check_pair(pair, a, b, k, nbr=None):
+    """Neighbour lists, columns and pooled rows of both directions of `pair` against the restatement."""
+    res = report(pair, k, hausdorff=True)
+    cols = {}
+    for is_left, p, q in ((True, a, b), (False, b, a)):
+        direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
+        want_nbr = ref.knn_rows(p, q, k) if nbr is None else nbr[is_left]
+        kk = want_nbr.shape[1]
+        rows, counts = pair._engine.get_p2d_neighbours(direction)
+        assert rows.shape == (len(p), k) and np.all(counts == kk)
+        bad = np.flatnonzero(np.any(rows[:, :kk] != want_nbr, axis=1))
+        assert bad.size == 0, f"{bad.size} neighbour lists differ, first {bad[:3]}: {rows[bad[:3]]} vs {want_nbr[bad[:3]]}"
+        assert np.all(rows[:, kk:] == -1)
+        want = ref.mahalanobis(p, q, k, nbr=want_nbr)
+        getter = pair.get_left_mahalanobis_distances if is_left else pair.get_right_mahalanobis_distances
+        column = getter(k)
+        assert_same(np.asarray(column), want)
+        with np.errstate(invalid="ignore"):
+            assert same_bits(np.sum(column), np.sum(want)) and same_bits(np.max(column), np.max(want))
+            assert same_bits(res[(MEAN, is_left, k)], np.mean(want))
+        assert same_bits(res[(MAX, is_left, k)], np.max(want))
+        cols[is_left] = want
+    for cls, pool in ((MEAN, np.mean), (MAX, np.max)):
+        left, right = pool(cols[True]), pool(cols[False])
+        assert same_bits(res[("SymmetricMetric", cls, True, k, cls, False, k)], right if right > left else left)
+    return cols
+
+
+@functools.lru_cache(maxsize=None)
+def family(name):
+    """(a, b, brute-force neighbour rows of both directions at k = 64): the first k columns are the rows at any smaller k."""
+    a, b = ref.FAMILIES[name]()
+    return a, b, {True: ref.knn_rows(a, b, 64), False: ref.knn_rows(b, a, 64)}
+
+
+# ---- every family, every stage of the search ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [4, 30, 64])
+@pytest.mark.parametrize("name", sorted(ref.FAMILIES))
+def test_neighbours_columns_and_rows_are_bit_exact(name, k):
+    a, b, rows = family(name)
+    with pair_of(a, b) as pair:
+        cols = check_pair(pair, a, b, k, nbr={side: r[:, :k] for side, r in rows.items()})
+    if name == "lattice":                                        # the data has what it is here for: ties at the k-th distance
+        d2 = np.sort(ref.sq_dist(a[:50, None, :], b[None, :, :]), axis=1)
+        assert np.any(d2[:, k - 1] == d2[:, k])
+    if name == "planes":                                         # ... singular covariances, which the ridge keeps finite
+        assert np.all(np.isfinite(cols[True])) and np.all(np.isfinite(cols[False]))
+    if name == "b_smaller_than_k":
+        assert len(b) < k
+
+
+@pytest.mark.parametrize("engine", ["grid", "brute"])
+def test_partly_overlapping_boxes_under_either_engine(engine):
+    a, b, rows = family("overlap")
+    with pair_of(a, b, nn_engine=engine) as pair:
+        check_pair(pair, a, b, 30, nbr={side: r[:, :30] for side, r in rows.items()})
+
+
+def _constant(name):
+    src = open(os.path.join(ROOT, "open_pcc_metric_amd", "csrc", "pccm_normals.hip")).read()
+    return int(re.search(rf"constexpr int {name} = (\d+);", src).group(1))
+
+
+def _settles(q, b, cells_b, org, h, dim, k, rings):
+    """Does the searches' stop rule settle query q within `rings` rings of the grid (org, h, dim)?  (The rule of k_knn_normals,
+    restated: the k-th best distance inside the cube against the nearest face of the cube that is not a face of the grid.)"""
+    c = np.clip(np.floor((q - org) / h), 0, dim - 1).astype(np.int64)
+    slack = (np.abs(org) + (dim + 2) * h) * 2.0 ** -48
+    for r in range(rings + 1):
+        inside = np.all(np.abs(cells_b - c) <= r, axis=1)
+        L = np.inf
+        for x in range(3):
+            if c[x] - r > 0:
+                L = min(L, (q[x] - (org[x] + (c[x] - r) * h[x])) - slack[x])
+            if c[x] + r < dim[x] - 1:
+                L = min(L, ((org[x] + (c[x] + r + 1) * h[x]) - q[x]) - slack[x])
+        if L == np.inf:
+            return True
+        d2 = np.sort(ref.sq_dist(q[None, :], b[inside]))
+        if len(d2) >= k and L > 0 and d2[k - 1] < L * L * (1.0 - 2.0 ** -30):
+            return True
+    return False
+
+
+def test_the_staged_case_reaches_every_stage():
+    """The data of FAMILIES["staged"] against the constants of pccm_normals.hip and the grid the search ran on: some queries have
+    more than kWCap candidates in their first cube (the wave search hands them to the per-thread search), some are still open
+    after kKnnMaxRing rings (the full scan), and most settle in the wave search."""
+    wcap, max_ring = _constant("kWCap"), _constant("kKnnMaxRing")
+    a, b = ref.FAMILIES["staged"]()
+    k = 30
+    with pair_of(a, b) as pair:
+        report(pair, k)
+        pair._engine.get_p2d_neighbours(nat.DIR_LEFT)            # (the grid of the left direction is the last one built)
+        org, h, dim = pair._engine.grid_geometry()
+    dim = dim.astype(np.int64)
+    cells_b = np.clip(np.floor((b - org) / h), 0, dim - 1).astype(np.int64)
+    centre = np.array([0.5, 0.5, 0.5])
+    near = a[np.linalg.norm(a - centre, axis=1) < 2e-3]
+    far = a[a[:, 2] > 5.0]
+    assert len(near) >= 30 and len(far) >= 20
+    crowded = 0
+    for q in near:
+        c = np.clip(np.floor((q - org) / h), 0, dim - 1).astype(np.int64)
+        crowded += int(np.sum(np.all(np.abs(cells_b - c) <= 2, axis=1)) > wcap)
+    assert crowded >= 30                                          # more than kWCap candidates within the first cube
+    open_after = sum(not _settles(q, b, cells_b, org, h, dim, k, max_ring) for q in far)
+    assert open_after >= 20                                       # nothing settles them within kKnnMaxRing rings
+    rng = np.random.default_rng(0)
+    plain = a[(a[:, 2] <= 1.0) & (np.linalg.norm(a - centre, axis=1) > 0.2)]
+    sample = plain[rng.integers(0, len(plain), 40)]
+    assert sum(_settles(q, b, cells_b, org, h, dim, k, 3) for q in sample) >= 20
+
+
+def test_two_hundred_thousand_points_each():
+    """A 200k-point pair against a blocked brute-force restatement: every (query, candidate) distance is formed, block by block
+    (on the GPU through torch, one element-wise op at a time), the k + 8 smallest per query go to the host, where the order is
+    decided in NumPy by the exact (d2, row) and the cut below the candidates is checked to be strict."""
+    import torch
+    rng = np.random.default_rng(61)
+    n, k = 200_000, 30
+    a, b = rng.random((n, 3)), rng.random((n, 3))
+
+    def blocked_rows(p, q, block=1024, extra=8):
+        qt = torch.from_numpy(q).to("cuda")
+        out = np.empty((len(p), k), dtype=np.int64)
+        for s in range(0, len(p), block):
+            pt = torch.from_numpy(p[s:s + block]).to("cuda")
+            d2 = None
+            for x in range(3):
+                d = pt[:, None, x] - qt[None, :, x]
+                d = d * d
+                d2 = d if d2 is None else d2 + d
+            cand = torch.topk(d2, k + extra, dim=1, largest=False).indices.cpu().numpy()
+            cd2 = ref.sq_dist(p[s:s + block, None, :], q[cand])
+            order = np.lexsort((cand, cd2), axis=-1)
+            cd2 = np.take_along_axis(cd2, order, axis=-1)
+            assert np.all(cd2[:, k - 1] < cd2[:, -1])            # nothing outside the candidates can belong to the first k
+            out[s:s + block] = np.take_along_axis(cand, order, axis=-1)[:, :k]
+        return out
+
+    nbr = {True: blocked_rows(a, b), False: blocked_rows(b, a)}
+    torch.cuda.synchronize()
+    with pair_of(a, b) as pair:
+        check_pair(pair, a, b, k, nbr=nbr)
+
+
+@pytest.mark.parametrize("name", ["uniform", "lattice", "georeferenced", "a_large"])
+def test_scaling_by_eight_leaves_every_bit(name):
+    a, b = ref.FAMILIES[name]()
+    with pair_of(a, b) as pair:
+        report(pair, 30)
+        want = [np.asarray(pair.get_left_mahalanobis_distances()), np.asarray(pair.get_right_mahalanobis_distances())]
+        rows = [pair._engine.get_p2d_neighbours(d)[0] for d in (nat.DIR_LEFT, nat.DIR_RIGHT)]
+    with pair_of(a * 8.0, b * 8.0) as pair:
+        report(pair, 30)
+        assert_same(np.asarray(pair.get_left_mahalanobis_distances()), want[0])
+        assert_same(np.asarray(pair.get_right_mahalanobis_distances()), want[1])
+        for d in (nat.DIR_LEFT, nat.DIR_RIGHT):                   # the grid changes, the neighbours must not
+            assert np.array_equal(pair._engine.get_p2d_neighbours(d)[0], rows[d])
+
+
+# ---- the rows beside the others -------------------------------------------------------------------------------------------------
+def coloured_surfaces(n, seed):
+    from test_gpu_pointssim import surface
+    return surface(n, seed), surface(n, seed + 1)               # (equal sizes: row-indexed point-to-plane normals are legal)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_earlier_rows_do_not_move(use_graph):
+    a, b = coloured_surfaces(5000, 121)
+    kw = dict(color="ycc", hausdorff=True, point_to_plane=True, hausdorff_rank=(0.5, 0.95))
+    with CloudPair(a, b, extent=EXTENT, use_graph=use_graph) as pair:
+        before = report(pair, p2d=False, **kw)                   # D1 / D2 rows before the build ...
+        built = pair._engine.p2d_build(30)
+        assert built is True
+        after = report(pair, p2d=False, **kw)                    # ... and after it
+        assert list(after) == list(before) and bits(after) == bits(before)
+        for _ in range(3 if use_graph else 1):
+            if use_graph:
+                pair.recompute()                                  # (captured with the new rows the second time, replayed the third)
+            both = report(pair, **kw)
+            assert list(both)[:len(before)] == list(before)          # the same rows in the same order, then the new ones
+            assert {k: v for k, v in bits(both).items() if k in before} == bits(before)
+            assert len(both) == len(before) + 6
+        if use_graph:
+            assert pair._graph_id is not None
+        assert bits(report(pair, p2d=False, **kw)) == bits(before)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_every_option_at_once_equals_each_alone(use_graph):
+    a, b = coloured_surfaces(5000, 131)
+    attrs = ["geometry", "normal", "curvature", "color"]
+    alone = [dict(color="ycc", hausdorff=True), dict(point_to_plane=True, hausdorff=True), dict(plane_to_plane=True, hausdorff=True),
+             dict(point_ssim=attrs), dict(hausdorff_rank=(0.5, 0.95), point_to_plane=True),
+             dict(point_to_distribution=True, hausdorff=True)]
+    want = {}
+    for kw in alone:
+        with CloudPair(a, b, extent=EXTENT) as single:
+            with np.errstate(divide="ignore"):
+                want.update(bits(MetricCalculator(single).calculate(transform_options(CalculateOptions(**kw))).as_dict()))
+    everything = dict(color="ycc", hausdorff=True, point_to_plane=True, plane_to_plane=True, point_ssim=attrs,
+                      hausdorff_rank=(0.5, 0.95))
+    with CloudPair(a, b, extent=EXTENT, use_graph=use_graph) as pair:
+        for _ in range(3 if use_graph else 1):
+            got = bits(report(pair, **everything))
+            assert set(got) == set(want)
+            bad = [key for key in want if got[key] != want[key]]
+            assert not bad, bad
+            pair.recompute()
+        if use_graph:
+            assert pair._graph_id is not None
+
+
+def test_ties_mean_gives_the_same_rows():
+    a, b = ref.FAMILIES["lattice"]()
+    with pair_of(a, b) as pick:
+        want = report(pick, 30, hausdorff=True)
+    with pair_of(a, b, ties="mean") as mean:
+        got = report(mean, 30, hausdorff=True)
+        check_pair(mean, a, b, 30)
+    new = [key for key in want if "Mahalanobis" in str(key)]
+    assert len(new) == 6
+    for key in new:
+        assert same_bits(got[key], want[key])
+
+
+def test_replay_gives_the_eager_bits_and_builds_once():
+    a, b = ref.FAMILIES["surface"]()
+    with pair_of(a, b) as eager:
+        want = bits(report(eager, 30, hausdorff=True))
+    with pair_of(a, b, use_graph=True) as pair:
+        assert bits(report(pair, 30, hausdorff=True)) == want
+        for _ in range(3):
+            pair.recompute()
+            assert pair._engine.p2d_build(30) is False           # the columns are found, not built again
+            assert bits(report(pair, 30, hausdorff=True)) == want
+        assert pair._graph_id is not None
+        assert pair._engine.p2d_build(12) is True                # another k: built again, the graph is stale or recaptured
+        other = report(pair, 12, hausdorff=True)
+    with pair_of(a, b) as eager:
+        assert bits(report(eager, 12, hausdorff=True)) == bits(other)
+
+
+def test_with_reconst_and_evaluate_pairs_match_fresh_pairs():
+    a = ref.surface(4000, 141)
+    recs = [ref.surface(3000 + 400 * s, 142 + s) for s in range(3)]
+    fresh = []
+    for b in recs:
+        with pair_of(a, b) as single:
+            fresh.append(bits(report(single, 30, hausdorff=True)))
+    with pair_of(a, recs[0]) as pair:
+        assert bits(report(pair, 30, hausdorff=True)) == fresh[0]
+        cur = pair
+        for b, want in zip(recs[1:], fresh[1:]):
+            cur = cur.with_reconst(PointCloud(b))
+            with pytest.raises(nat.PccmStateError):               # new points: both columns went with them
+                cur._engine.point_metric(nat.DIR_LEFT, nat.METRIC_P2D)
+            assert bits(report(cur, 30, hausdorff=True)) == want
+            check_pair(cur, a, b, 30)
+        cur.close()
+    opts = CalculateOptions(hausdorff=True, point_to_distribution=True)
+    with np.errstate(divide="ignore"):
+        seq = evaluate_pairs([(PointCloud(a), PointCloud(b)) for b in recs], opts, extent=EXTENT)
+    assert [bits(r) for r in seq] == fresh
+
+
+def test_command_line(tmp_path):
+    a, b, c = ref.surface(3000, 151), ref.surface(2500, 152), ref.surface(2600, 153)
+    pa, pb, pc = (str(tmp_path / f"{name}.ply") for name in "abc")
+    for path, x in ((pa, a), (pb, b), (pc, c)):
+        write_point_cloud(path, PointCloud(x), coord_dtype="float")
+    ra, rb, rc = read_point_cloud(pa), read_point_cloud(pb), read_point_cloud(pc)
+    args = ["--ocloud", pa, "--pcloud", pb, "--pcloud", pc, "--hausdorff", "--point-to-distribution", "--p2d-neighbours", "10",
+            "--extent", "1", "1", "1"]
+    out = CliRunner().invoke(cli, args)
+    assert out.exit_code == 0, out.output
+    opts = CalculateOptions(hausdorff=True, point_to_distribution=True, p2d_neighbours=10)
+    texts, csvs = [], []
+    for r in (rb, rc):
+        with CloudPair(ra, r, extent=EXTENT) as pair:
+            with np.errstate(divide="ignore"):
+                df = MetricCalculator(pair).calculate(transform_options(opts)).as_df()
+            texts.append(df.to_string())
+            csvs.append(df.to_csv())
+    assert out.output == texts[0] + "\n" + texts[1] + "\n"
+    for label in ("MahalanobisDistance", "MahalanobisDistance(symmetric)", "MaxMahalanobisDistance", "MaxMahalanobisDistance(symmetric)"):
+        assert label in texts[0]
+    out = CliRunner().invoke(cli, args + ["--csv"])
+    assert out.exit_code == 0 and out.output == csvs[0] + "\n" + csvs[1] + "\n"
+    plain = CliRunner().invoke(cli, ["--ocloud", pa, "--pcloud", pb, "--hausdorff", "--extent", "1", "1", "1"])
+    assert plain.exit_code == 0 and "Mahalanobis" not in plain.output
+    for bad in ("3", "65", "many"):
+        out = CliRunner().invoke(cli, ["--ocloud", pa, "--pcloud", pb, "--point-to-distribution", "--p2d-neighbours", bad])
+        assert out.exit_code == 2
+
+
+def test_sharded_pairs_are_refused_before_any_gpu_work():
+    a, b = ref.FAMILIES["uniform"]()
+    lib = nat.load()
+    with pair_of(a, b) as pair:
+        class Peers:                                              # what Collective(group) says of a group with two ranks
+            sharded, group, rank, world = True, object(), 0, 2
+        mine = pair._coll
+        pair._coll = Peers()
+        try:
+            with pytest.raises(ValueError, match="sharded"):
+                pair.get_left_mahalanobis_distances()
+            with pytest.raises(ValueError, match="sharded"):
+                pair.prefetch_reductions([("p2d", True, 30)])
+        finally:
+            pair._coll = mine
+        out, cnt = np.empty((len(a), 30), dtype=np.int32), np.empty(len(a), dtype=np.int32)
+        rc = lib.pccm_get_p2d_neighbours(pair._engine._ctx, 0, out.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p))
+        assert rc == nat.E_STATE                                  # nothing was built
+
+
+def test_c_calls_and_their_error_codes():
+    a, b = ref.FAMILIES["uniform"]()
+    lib = nat.load()
+    eng = nat.Engine(0)
+    P2D = nat.METRIC_P2D
+    try:
+        built = ctypes.c_int32(7)
+        eng.set_cloud(0, a)
+        assert lib.pccm_p2d_build(eng._ctx, 30, ctypes.byref(built)) == nat.E_STATE and built.value == 0     # cloud 1 is missing
+        eng.set_cloud(1, b)
+        for k in (3, 65, 0, -4):
+            assert lib.pccm_p2d_build(eng._ctx, k, ctypes.byref(built)) == nat.E_ARG
+        out, cnt = np.empty((len(a), 30), dtype=np.int32), np.empty(len(a), dtype=np.int32)
+        args = (out.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p))
+        assert lib.pccm_get_p2d_neighbours(eng._ctx, 0, *args) == nat.E_STATE                                # not built
+        assert lib.pccm_p2d_build(eng._ctx, 30, ctypes.byref(built)) == nat.OK and built.value == 1          # no search result needed
+        assert lib.pccm_p2d_build(eng._ctx, 30, ctypes.byref(built)) == nat.OK and built.value == 0
+        assert lib.pccm_p2d_build(eng._ctx, 30, None) == nat.OK
+        assert lib.pccm_get_p2d_neighbours(eng._ctx, 2, *args) == nat.E_ARG
+        assert lib.pccm_get_p2d_neighbours(eng._ctx, 0, None, None) == nat.E_ARG
+        assert lib.pccm_get_p2d_neighbours(eng._ctx, 0, *args) == nat.OK
+        assert np.array_equal(out, ref.knn_rows(a, b, 30)) and np.all(cnt == 30)
+        with pytest.raises(nat.PccmStateError):                   # a reduction needs the direction's search result, like any other
+            eng.reduce_total(nat.DIR_LEFT, P2D)
+        eng.nn_pair("auto")
+        want = {nat.DIR_LEFT: ref.mahalanobis(a, b, 30), nat.DIR_RIGHT: ref.mahalanobis(b, a, 30)}
+        for d in (nat.DIR_LEFT, nat.DIR_RIGHT):
+            for mode in ("row", "neighbour"):                     # normal_mode is ignored
+                assert_same(eng.point_metric(d, P2D, mode), want[d])
+            s, mn, mx = eng.reduce_total(d, P2D)
+            assert same_bits(s, np.sum(want[d])) and mn == np.min(want[d]) and mx == np.max(want[d])
+            xvec, mn, mx = eng.reduce(d, P2D)
+            assert same_bits(eng.finish_sum(xvec, len(want[d])), np.sum(want[d])) and mx == np.max(want[d])
+        many = eng.reduce_total_many([(nat.DIR_LEFT, P2D), (nat.DIR_RIGHT, nat.METRIC_D1), (nat.DIR_RIGHT, P2D)])
+        assert same_bits(many[0][0], np.sum(want[nat.DIR_LEFT])) and same_bits(many[2][0], np.sum(want[nat.DIR_RIGHT]))
+        eng.nn(nat.DIR_SELF, "auto")
+        with pytest.raises(ValueError):                           # PCCM_E_ARG: not defined for the self search
+            eng.point_metric(nat.DIR_SELF, P2D)
+        with pytest.raises(ValueError):
+            eng.reduce_total(nat.DIR_SELF, P2D)
+        eng.graph_begin()                                         # another k would have to build during capture
+        assert lib.pccm_p2d_build(eng._ctx, 30, ctypes.byref(built)) == nat.OK and built.value == 0
+        assert lib.pccm_p2d_build(eng._ctx, 12, ctypes.byref(built)) == nat.E_STATE
+        eng.graph_abort()
+        eng.nn_pair("auto")
+        assert_same(eng.point_metric(nat.DIR_LEFT, P2D), want[nat.DIR_LEFT])      # the columns at k = 30 are still there
+        eng.set_cloud(1, b)                                       # new points in either cloud: both columns go
+        eng.nn_pair("auto")
+        for d in (nat.DIR_LEFT, nat.DIR_RIGHT):
+            with pytest.raises(nat.PccmStateError):
+                eng.point_metric(d, P2D)
+        eng.set_shard(0, 2)
+        assert lib.pccm_p2d_build(eng._ctx, 30, ctypes.byref(built)) == nat.E_STATE                          # a sharded context
+    finally:
+        eng.close()
