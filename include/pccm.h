@@ -92,6 +92,10 @@ extern "C" {
  * columns are not built.  Accepted by pccm_point_metric and every pccm_reduce* call; a plain column, reduced like D1 (the
  * direction needs a search result, like every reduction: the slot takes its row range and generation from it). */
 #define PCCM_METRIC_P2D 8
+/* The colour value M_Y and the joint value M_J of pccm_p2d_build_attrs (PCCM_P2D_COLOR): stored columns exactly like
+ * PCCM_METRIC_P2D, with the same rules; PCCM_E_STATE while they are not built (a geometry-only build, or new colours since). */
+#define PCCM_METRIC_P2D_COLOR 9
+#define PCCM_METRIC_P2D_JOINT 10
 
 /* kernel classes for pccm_profile_get() */
 #define PCCM_K_INGEST 0
@@ -191,6 +195,25 @@ int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out);
  * and is allowed during capture.  New points in either cloud drop both columns.  A build makes pending reductions of directions
  * 0 and 1 stale and, when a column moves, captured graphs too.  The pair's grid is rebuilt (as by pccm_ssim_features). */
 int pccm_p2d_build(pccm_ctx *ctx, int k, int *built);
+/* What pccm_p2d_build_attrs builds (bit flags).  The geometry column is always built; PCCM_P2D_COLOR stands for the colour
+ * column and the joint column together. */
+#define PCCM_P2D_GEOMETRY 1
+#define PCCM_P2D_COLOR 2
+/* pccm_p2d_build with a choice of columns (pccm_p2d_build(ctx, k, built) is attrs = PCCM_P2D_GEOMETRY).  PCCM_P2D_COLOR adds, per
+ * direction, the colour and the joint column ("Point-to-distribution: colour and joint"; after Javaheri et al.,
+ * IEEE MMSP 2021) over exactly the neighbourhood N of the geometry column.  Direction A -> B, p = row i of A, fp64, every
+ * operation separately rounded, sums from 0.0 left to right in neighbourhood order:
+ *   y(c) = fma(0.0722, c_b, fma(0.2126, c_r, 0.7152 * c_g))   (the luma of PCCM_SSIM_COLOR)
+ *   e_j  = y(rgb_B[q_j]) - y(rgb_A[i]);  S1 = sum_j e_j;  S2 = sum_j (e_j * e_j);  m = S1 / kk;  V = S2 / kk - m * m
+ *   v    = max(V, 0) + 2^-20;  M_Y(p) = |m| / sqrt(v)  (always finite);  M_J(p) = sqrt(M_G(p) * M_G(p) + M_Y(p) * M_Y(p)),
+ *   M_G the geometry column's value (+inf propagates).
+ * PCCM_E_ARG for a bad k or unknown attrs bits; PCCM_E_STATE as pccm_p2d_build, and when PCCM_P2D_COLOR is asked for and either
+ * cloud has no colours.  A call that finds all requested columns at the same k does no work (*built = 0) and is allowed during
+ * capture; one that finds the geometry columns but not the colour columns it asks for builds those (*built = 1) and leaves the
+ * geometry columns as they are.  One build runs one k-NN search per direction, whatever the attrs.  New points in either cloud
+ * drop all columns; pccm_set_colors / pccm_set_colors_u8 on either cloud drop the colour and joint columns of both directions and
+ * keep the geometry columns. */
+int pccm_p2d_build_attrs(pccm_ctx *ctx, int k, int attrs, int *built);
 /* the neighbourhoods behind direction dir's column: out[n][k] rows of the searched cloud in ascending (d2, row) order (entries
  * from count[i] on are -1), count[n].  Searches again (the build keeps no lists); PCCM_E_STATE while the columns are not built. */
 int pccm_get_p2d_neighbours(pccm_ctx *ctx, int dir, int32_t *out, int32_t *count);
@@ -275,7 +298,7 @@ int pccm_set_ties(pccm_ctx *ctx, int policy);
 int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
 
 /* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR and
- * PCCM_METRIC_SSIM_* and PCCM_METRIC_P2D ignore normal_mode. */
+ * PCCM_METRIC_SSIM_* and PCCM_METRIC_P2D* ignore normal_mode. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
 /* Fused reduction of a per-point metric over the shard: the np.sum / np.max of

@@ -31,6 +31,9 @@ METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does n
 SSIM_ATTRS = {"geometry": 1, "normal": 2, "curvature": 4, "color": 8}
 METRIC_SSIM = {"geometry": 4, "normal": 5, "curvature": 6, "color": 7}
 METRIC_P2D = 8           # point-to-distribution (Mahalanobis) column of a direction (pccm_p2d_build; normal_mode does not apply)
+METRIC_P2D_COLOR = 9     # ... its colour (luma) column and
+METRIC_P2D_JOINT = 10    # ... its joint geometry-and-colour column (pccm_p2d_build_attrs with P2D_COLOR)
+P2D_GEOMETRY, P2D_COLOR = 1, 2      # PCCM_P2D_*: what pccm_p2d_build_attrs builds (P2D_COLOR: the colour and the joint column)
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
 
@@ -38,7 +41,7 @@ KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals",
-    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_get_p2d_neighbours", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
+    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
@@ -108,6 +111,7 @@ def load() -> ctypes.CDLL:
     lib.pccm_ssim_features.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_ssim_features.argtypes = [vp, i32, i32, vp]
     lib.pccm_p2d_build.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    lib.pccm_p2d_build_attrs.argtypes = [vp, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_p2d_neighbours.argtypes = [vp, i32, vp, vp]
     lib.pccm_shard_range.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.pccm_nn.argtypes = [vp, i32, i32]
@@ -494,11 +498,12 @@ class Engine:
         _check(self._lib.pccm_get_ssim_features(self._ctx, int(which), SSIM_ATTRS[attr], out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def p2d_build(self, k: int) -> bool:
+    def p2d_build(self, k: int, attrs: int = P2D_GEOMETRY) -> bool:
         """Build (or find) the point-to-distribution columns of both directions at neighbourhood size ``k`` in HBM; True when
-        work was done (pccm_p2d_build)."""
+        work was done (pccm_p2d_build_attrs).  ``attrs``: P2D_GEOMETRY, or P2D_GEOMETRY | P2D_COLOR for the colour and joint
+        columns as well (both clouds' colours must be on the device)."""
         built = ctypes.c_int32()
-        _check(self._lib.pccm_p2d_build(self._ctx, int(k), ctypes.byref(built)))
+        _check(self._lib.pccm_p2d_build_attrs(self._ctx, int(k), int(attrs), ctypes.byref(built)))
         self._p2d_k = int(k)
         return bool(built.value)
 

@@ -14,9 +14,9 @@ import typing
 import pandas as pd
 
 from .cloud_pair import CloudPair
-from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, EuclideanDistance,
-                     GeoRankedHausdorffDistance, MahalanobisDistances, PrimaryMetric, SecondaryMetric, SSIMSimilarities,
-                     SymmetricMetric)
+from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, ColorMahalanobisDistances, EuclideanDistance,
+                     GeoRankedHausdorffDistance, JointMahalanobisDistances, MahalanobisDistances, PrimaryMetric, SecondaryMetric,
+                     SSIMSimilarities, SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -94,6 +94,10 @@ class MetricCalculator:
                 wanted.append(("angular", metric.is_left))
             elif isinstance(metric, SSIMSimilarities):
                 wanted.append(("ssim", metric.attribute, metric.is_left, metric.k))
+            elif isinstance(metric, ColorMahalanobisDistances):
+                wanted.append(("p2d_color", metric.is_left, metric.k))
+            elif isinstance(metric, JointMahalanobisDistances):
+                wanted.append(("p2d_joint", metric.is_left, metric.k))
             elif isinstance(metric, MahalanobisDistances):
                 wanted.append(("p2d", metric.is_left, metric.k))
             (late if waits else early).append((metric, None, key))

@@ -117,7 +117,9 @@ class DeviceColumn(_DeviceArray):
     ``"ssim:<attribute>"``  PointSSIM similarities of one attribute (get_left/right_ssim_similarities; PCCM_METRIC_SSIM_*: the
                     own feature against the matched point's, at the neighbourhood size the pair's features were built with),
     ``"p2d"``       point-to-distribution (Mahalanobis) distances (get_left/right_mahalanobis_distances; PCCM_METRIC_P2D: the
-                    direction's stored column, at the neighbourhood size the pair's columns were built with).
+                    direction's stored column, at the neighbourhood size the pair's columns were built with),
+    ``"p2d_color"`` / ``"p2d_joint"``  its colour and joint columns (get_left/right_color_mahalanobis_distances,
+                    get_left/right_joint_mahalanobis_distances; PCCM_METRIC_P2D_COLOR / PCCM_METRIC_P2D_JOINT).
     """
 
     def __init__(self, pair: "CloudPair", direction: int, kind: str):
@@ -127,7 +129,8 @@ class DeviceColumn(_DeviceArray):
         self._red = None
 
     _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2,
-               "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}, "p2d": nat.METRIC_P2D}
+               "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}, "p2d": nat.METRIC_P2D,
+               "p2d_color": nat.METRIC_P2D_COLOR, "p2d_joint": nat.METRIC_P2D_JOINT}
 
     def _materialise(self) -> np.ndarray:
         p = self._pair
@@ -784,27 +787,34 @@ class CloudPair:
         return self._ssim_column(nat.DIR_RIGHT, attribute, k)
 
     # -- point-to-distribution ("Point-to-distribution") ------------------------------------------------------
-    def _check_p2d(self, k: int) -> None:
-        """The ValueErrors of CalculateOptions and options.check_point_to_distribution, for this pair -- raised before any GPU
-        work of a report."""
-        from .options import CalculateOptions, check_point_to_distribution
-        check_point_to_distribution(CalculateOptions(point_to_distribution=True, p2d_neighbours=k),
-                                    group=self._coll.group if self._coll.sharded else None)
+    _P2D_METRICS = (nat.METRIC_P2D, nat.METRIC_P2D_COLOR, nat.METRIC_P2D_JOINT)
 
-    def _ensure_p2d(self, k: int) -> None:
-        """Both directions' columns at neighbourhood size ``k``, built in HBM where missing (pccm_p2d_build: new points in
-        either cloud -- with_reconst -- drop them, so the next report builds both again)."""
-        self._check_p2d(k)
+    def _check_p2d(self, k: int, color: bool = False) -> None:
+        """The ValueErrors of CalculateOptions, options.check_point_to_distribution and -- ``color`` -- options.check_p2d_color,
+        for this pair -- raised before any GPU work of a report."""
+        from .options import CalculateOptions, check_p2d_color, check_point_to_distribution
+        options = CalculateOptions(point_to_distribution=True, p2d_neighbours=k, p2d_color=color)
+        group = self._coll.group if self._coll.sharded else None
+        check_point_to_distribution(options, group=group)
+        check_p2d_color(options, *self.clouds, group=group)
+
+    def _ensure_p2d(self, k: int, color: bool = False) -> None:
+        """Both directions' columns at neighbourhood size ``k`` -- ``color``: the colour and joint columns too -- built in HBM
+        where missing (pccm_p2d_build_attrs: new points in either cloud -- with_reconst -- drop them, so the next report builds
+        them again; new colours drop the colour and joint columns).  Both clouds' colours go up before a build that reads them."""
+        self._check_p2d(k, color)
         if not hasattr(self._engine, "p2d_build"):
             raise ValueError("this engine has no point-to-distribution columns")
-        built = self._engine.p2d_build(int(k))
+        if color:
+            self._ensure_colours()
+        built = self._engine.p2d_build(int(k), nat.P2D_GEOMETRY | (nat.P2D_COLOR if color else 0))
         if built or self.__dict__.get("_p2d_k") != int(k):    # totals of earlier columns are stale
-            self._totals = {key: v for key, v in self._totals.items() if key[1] != nat.METRIC_P2D}
+            self._totals = {key: v for key, v in self._totals.items() if key[1] not in self._P2D_METRICS}
         self._p2d_k = int(k)
 
-    def _p2d_column(self, direction: int, k: int) -> DeviceColumn:
-        self._ensure_p2d(k)
-        return DeviceColumn(self, direction, "p2d")
+    def _p2d_column(self, direction: int, k: int, kind: str = "p2d") -> DeviceColumn:
+        self._ensure_p2d(k, color=kind != "p2d")
+        return DeviceColumn(self, direction, kind)
 
     def get_left_mahalanobis_distances(self, k: int = 30):
         """Per point of the origin cloud: its Mahalanobis distance to the distribution of its k nearest reconstructed points
@@ -814,6 +824,23 @@ class CloudPair:
 
     def get_right_mahalanobis_distances(self, k: int = 30):
         return self._p2d_column(nat.DIR_RIGHT, k)
+
+    def get_left_color_mahalanobis_distances(self, k: int = 30):
+        """Per point of the origin cloud: the distance of its luma to the luma distribution of its k nearest reconstructed
+        points -- the neighbourhood of get_left_mahalanobis_distances -- in ridged standard deviations (fp64, always finite; a
+        device column).  Both clouds need colours."""
+        return self._p2d_column(nat.DIR_LEFT, k, "p2d_color")
+
+    def get_right_color_mahalanobis_distances(self, k: int = 30):
+        return self._p2d_column(nat.DIR_RIGHT, k, "p2d_color")
+
+    def get_left_joint_mahalanobis_distances(self, k: int = 30):
+        """Per point of the origin cloud: sqrt(M_G^2 + M_Y^2) of its geometry and colour point-to-distribution values (inf
+        where the geometry value is)."""
+        return self._p2d_column(nat.DIR_LEFT, k, "p2d_joint")
+
+    def get_right_joint_mahalanobis_distances(self, k: int = 30):
+        return self._p2d_column(nat.DIR_RIGHT, k, "p2d_joint")
 
     def get_left_neighbour_colors(self):
         """cloud_pair.py:120-121: the matched points' colours -- gathered on the device when asked for."""
@@ -826,7 +853,8 @@ class CloudPair:
         """Enqueue the fused reductions a report is about to ask for, without waiting for any of them.
 
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
-        ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)`` and/or the string ``"boundary"``.
+        ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
+        ``("p2d_joint", is_left, k)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -852,13 +880,15 @@ class CloudPair:
         if ranked_items:
             self._check_ranked()
         # point-to-distribution: the check, then the columns -- built here like the features, eagerly and outside any capture
-        p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "p2d"]
-        for k in sorted({item[2] for item in p2d_items}):
-            self._check_p2d(k)
-        for k in sorted({item[2] for item in p2d_items}):
-            self._ensure_p2d(k)
+        # (one build per neighbourhood size, with the union of what the report needs at that size)
+        p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] in ("p2d", "p2d_color", "p2d_joint")]
+        p2d_color = {k: any(item[0] != "p2d" for item in p2d_items if item[2] == k) for k in sorted({item[2] for item in p2d_items})}
+        for k, color in p2d_color.items():
+            self._check_p2d(k, color)
+        for k, color in p2d_color.items():
+            self._ensure_p2d(k, color)
         requests, ssim_requests, selections = [], [], []
-        p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_P2D) for item in p2d_items]
+        p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, DeviceColumn._METRIC[item[0]]) for item in p2d_items]
         for item in wanted:
             if item in ranked_items or item in p2d_items:
                 continue              # (ranked: their columns are requests of their own, EuclideanDistance's)

@@ -483,8 +483,14 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
         if (ctx->p2d64[d]) (void)hipFree(ctx->p2d64[d]);
         ctx->p2d64[d] = nullptr;
         ctx->cap_p2d[d] = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (ctx->p2d_cj64[d][c]) (void)hipFree(ctx->p2d_cj64[d][c]);
+            ctx->p2d_cj64[d][c] = nullptr;
+            ctx->cap_p2d_cj[d][c] = 0;
+        }
     }
     ctx->p2d_k = 0;
+    ctx->p2d_color = false;
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
@@ -522,6 +528,7 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     drop_cloud(c);                                   // its normals and colours go with it
     ctx->p2d_k = 0;                                  // (both point-to-distribution columns depend on either cloud)
+    ctx->p2d_color = false;
     // (a new cloud 1 leaves the self search of cloud 0 -- cloud_pair.py:108-109 -- as valid as it was: one reference cloud
     // against several decoded ones, BASELINE configs[4], keeps it, see CloudPair.with_reconst)
     for (int d = 0; d < 3; ++d) {
@@ -656,6 +663,14 @@ int pccm_flush_uploads(pccm_ctx *ctx)
     return PCCM_OK;
 }
 
+// new colours in either cloud: the colour and joint point-to-distribution columns of both directions go, the geometry columns stay
+static void drop_p2d_color(pccm_ctx *ctx)
+{
+    if (!ctx->p2d_color) return;
+    ctx->p2d_color = false;
+    for (int d = 0; d < 2; ++d) ctx->nn_gen[d]++;      // pending reductions of those columns used the old colours
+}
+
 int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dtype, int on_device)
 {
     CHECK_CTX(ctx);
@@ -669,6 +684,7 @@ int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dt
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     c.n_rgb = 0;
     c.ssim_attrs &= ~PCCM_SSIM_COLOR;
+    drop_p2d_color(ctx);
     ctx->rgb_gen++;
     int rc = grow((void **)&c.rgb64, c.cap_rgb, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
@@ -704,6 +720,7 @@ int pccm_set_colors_u8(pccm_ctx *ctx, int which, const unsigned char *rgb, int64
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     c.n_rgb = 0;
     c.ssim_attrs &= ~PCCM_SSIM_COLOR;
+    drop_p2d_color(ctx);
     ctx->rgb_gen++;
     int rc = grow((void **)&c.rgb64, c.cap_rgb, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
@@ -1018,15 +1035,25 @@ int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out)
     return PCCM_OK;
 }
 
-int pccm_p2d_build(pccm_ctx *ctx, int k, int *built)
+int pccm_p2d_build_attrs(pccm_ctx *ctx, int k, int attrs, int *built)
 {
     CHECK_CTX(ctx);
     if (built) *built = 0;
     if (k < 4 || k > 64) return fail(PCCM_E_ARG, "point-to-distribution neighbourhoods have 4..64 points, not %d", k);
+    if (attrs & ~(PCCM_P2D_GEOMETRY | PCCM_P2D_COLOR)) return fail(PCCM_E_ARG, "unknown point-to-distribution attributes 0x%x", attrs);
     for (int which = 0; which < 2; ++which)
         if (ctx->cloud[which].n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
     if (ctx->sharded()) return fail(PCCM_E_STATE, "point-to-distribution columns need whole clouds on this GPU (world = 1)");
-    return p2d_build(ctx, k, built);                   // (what is there already needs no work, and may be asked for while capturing)
+    if (attrs & PCCM_P2D_COLOR)
+        for (int which = 0; which < 2; ++which)
+            if (ctx->cloud[which].n_rgb != ctx->cloud[which].n)
+                return fail(PCCM_E_STATE, "cloud %d has no colours (PCCM_P2D_COLOR)", which);
+    return p2d_build(ctx, k, attrs, built);            // (what is there already needs no work, and may be asked for while capturing)
+}
+
+int pccm_p2d_build(pccm_ctx *ctx, int k, int *built)
+{
+    return pccm_p2d_build_attrs(ctx, k, PCCM_P2D_GEOMETRY, built);
 }
 
 int pccm_get_p2d_neighbours(pccm_ctx *ctx, int dir, int32_t *out, int32_t *count)
@@ -1410,12 +1437,19 @@ static bool matched_column(int metric)
     return metric == PCCM_METRIC_ANGULAR || is_ssim_metric(metric);
 }
 
-// PCCM_METRIC_P2D: the stored column of the direction (pccm_p2d_build); neither the matched rows nor normal_mode enter it
-static int check_p2d(pccm_ctx *ctx, int dir)
+// PCCM_METRIC_P2D*: a stored column of the direction (pccm_p2d_build_attrs); neither the matched rows nor normal_mode enter it
+static int check_p2d(pccm_ctx *ctx, int dir, int metric)
 {
     if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-distribution is not defined for the self search");
     if (ctx->p2d_k <= 0) return fail(PCCM_E_STATE, "point-to-distribution columns are not built (pccm_p2d_build)");
+    if (metric != PCCM_METRIC_P2D && !ctx->p2d_color)
+        return fail(PCCM_E_STATE, "point-to-distribution colour columns are not built (pccm_p2d_build_attrs, PCCM_P2D_COLOR)");
     return PCCM_OK;
+}
+
+static const double *p2d_column(const pccm_ctx *ctx, int dir, int metric)
+{
+    return metric == PCCM_METRIC_P2D ? ctx->p2d64[dir] : ctx->p2d_cj64[dir][metric - PCCM_METRIC_P2D_COLOR];
 }
 
 int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
@@ -1466,9 +1500,9 @@ static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode,
         *dev = (const double *)vb.p;
         return PCCM_OK;
     }
-    if (metric == PCCM_METRIC_P2D) {
-        if ((rc = check_p2d(ctx, dir))) return rc;
-        *dev = ctx->p2d64[dir] + res->begin;
+    if (is_p2d_metric(metric)) {
+        if ((rc = check_p2d(ctx, dir, metric))) return rc;
+        *dev = p2d_column(ctx, dir, metric) + res->begin;
         return PCCM_OK;
     }
     if (is_ssim_metric(metric)) {
@@ -1579,7 +1613,7 @@ struct ColumnSource {
         kPlainD2,         // the plain d2 column (no records: the engine wrote the plain columns)
         kPointJob,        // a k_point_jobs job that reads the matched rows from the plain idx column, or from matched records (recs)
         kTieColumn,       // the tie pass's column (PCCM_TIES_MEAN)
-        kStored,          // a stride-1 column kept with the context (PCCM_METRIC_P2D: pccm_p2d_build)
+        kStored,          // a stride-1 column kept with the context (PCCM_METRIC_P2D*: pccm_p2d_build_attrs)
     } from = kPointJob;
     // the plain columns: none needed or they are there; the binder unpacks them; or they come before any column of the batch is
     // bound.  Which columns the binder unpacks (an unfused projection over stride-4 records) is today's split: it decides which
@@ -1602,7 +1636,7 @@ static ColumnSource column_source(const pccm_ctx *ctx, int dir, int metric, int 
         return c;
     }
     if (dir == PCCM_DIR_SELF) return c;
-    if (metric == PCCM_METRIC_P2D) {
+    if (is_p2d_metric(metric)) {
         c.from = ColumnSource::kStored;
         return c;
     }
@@ -1639,8 +1673,8 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     const bool matched = matched_column(metric), ssim = is_ssim_metric(metric);
     if (matched) {
         if ((rc = ssim ? check_ssim(ctx, dir, *it, *se, *res, metric) : check_angular(ctx, dir, *it, *se))) return rc;
-    } else if (metric == PCCM_METRIC_P2D) {
-        if ((rc = check_p2d(ctx, dir))) return rc;
+    } else if (is_p2d_metric(metric)) {
+        if ((rc = check_p2d(ctx, dir, metric))) return rc;
     } else if (metric != PCCM_METRIC_D1) {
         if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
         if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
@@ -1656,7 +1690,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
         dev = (const double *)ctx->tie[dir].ang.p;
         break;
-    case ColumnSource::kStored: dev = ctx->p2d64[dir] + res->begin; break;
+    case ColumnSource::kStored: dev = p2d_column(ctx, dir, metric) + res->begin; break;
     case ColumnSource::kPointJob:
         // (PCCM_METRIC_SSIM_*: the angular column's job on the two clouds' feature columns instead of their normals)
         if (src.prep != ColumnSource::kReady && (rc = ensure_plain(ctx, *res, true))) return rc;
@@ -1755,7 +1789,7 @@ static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode
 {
     for (auto &s : ctx->slots)
         if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric &&
-            (metric == PCCM_METRIC_D1 || metric == PCCM_METRIC_P2D || matched_column(metric) || s.mode == normal_mode) &&
+            (metric == PCCM_METRIC_D1 || is_p2d_metric(metric) || matched_column(metric) || s.mode == normal_mode) &&
             s.gen == ctx->nn_gen[dir])
             return &s;
     return nullptr;
@@ -1816,7 +1850,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         NNResult &res = ctx->nn[dirs[k]];
         if (!res.valid || res.ties != PCCM_TIES_MEAN) continue;
         if (metrics[k] == PCCM_METRIC_ANGULAR) tie_ang[dirs[k]] = true;
-        else if (metrics[k] != PCCM_METRIC_D1 && metrics[k] != PCCM_METRIC_P2D && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
+        else if (metrics[k] != PCCM_METRIC_D1 && !is_p2d_metric(metrics[k]) && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
     }
     for (int d = 0; d < 2; ++d) {
         if (!tie_ang[d] || slot_find(ctx, d, PCCM_METRIC_ANGULAR, 0, want_units)) continue;
@@ -2469,6 +2503,7 @@ int pccm_ctx_reset(pccm_ctx *ctx)
         ctx->cloud[k].version++;
     }
     ctx->p2d_k = 0;
+    ctx->p2d_color = false;
     for (int d = 0; d < 3; ++d) {
         ctx->shard_rank[d] = 0;
         ctx->shard_world[d] = 1;

@@ -314,6 +314,11 @@ struct pccm_ctx {
     double *p2d64[2] = {nullptr, nullptr};
     size_t cap_p2d[2] = {0, 0};
     int p2d_k = 0;
+    // ... and their colour [0] and joint [1] columns per direction (PCCM_P2D_COLOR), valid while p2d_color is set (then at p2d_k):
+    // new colours in either cloud drop these and keep the geometry columns
+    double *p2d_cj64[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    size_t cap_p2d_cj[2][2] = {{0, 0}, {0, 0}};
+    bool p2d_color = false;
     pccm::DevBuf tail_sync;               // k_grid_tail: retired-entry counts + ticket, for the normal and the self pass
     bool tail_sync_clean = false;
     pccm::DevBuf color_cols, color_idx;   // colour pass: squares as three columns / caller-supplied neighbour rows
@@ -348,7 +353,7 @@ struct pccm_ctx {
     bool bins_clean = false;   // the build's bin cursors (head of g_bins) are zero on the stream
     int want_idx = 1;                      // pccm_nn_want_idx: searches store the matched row with every result
     int fuse_mode[3] = {-1, -1, -1};       // pccm_nn_fuse: normal mode of the D2 projection fused into the search, per direction
-    pccm::ReduceSlot slots[24];           // (a report with every PointSSIM and point-to-distribution row holds up to 17 columns at once)
+    pccm::ReduceSlot slots[24];           // (a report with every PointSSIM and point-to-distribution row holds up to 21 columns at once)
     // selections (pccm_select_*): slot s answers into sel_host[s] (host-coherent pinned memory); the histograms and pass states
     // are sized once per context
     static constexpr int kSelSlots = 32;
@@ -456,7 +461,7 @@ int grid_decide(pccm_ctx *ctx, bool *hostile);   // geometry decision for the cu
 int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; isolation verdict (cached per pair)
 int estimate_normals(pccm_ctx *ctx, int which, int k);
 int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built);   // the checks are pccm_ssim_features'
-int p2d_build(pccm_ctx *ctx, int k, int *built);                             // the checks are pccm_p2d_build's
+int p2d_build(pccm_ctx *ctx, int k, int attrs, int *built);                  // the checks are pccm_p2d_build_attrs'
 int p2d_neighbours(pccm_ctx *ctx, int dir, int k, const int32_t **nbr, const int32_t **cnt);   // device lists [n][k], [n]
 int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int normal_mode, double out[8]);
 // PCCM_TIES_MEAN producer: for the ns queries q_begin.. of direction dir (matched rows idx, squared distances d2 or null = formed
@@ -516,7 +521,12 @@ __device__ __forceinline__ double ssim_similarity(double a, double b)
     return __dsub_rn(1.0, __ddiv_rn(num, den));
 }
 
-// (PCCM_METRIC_P2D is a stored column: pccm_api.hip binds it, no point kernel sees it)
+// (PCCM_METRIC_P2D, _P2D_COLOR and _P2D_JOINT are stored columns: pccm_api.hip binds them, no point kernel sees them)
+__host__ __device__ __forceinline__ bool is_p2d_metric(int metric)
+{
+    return metric >= PCCM_METRIC_P2D && metric <= PCCM_METRIC_P2D_JOINT;
+}
+
 __host__ __device__ __forceinline__ bool is_ssim_metric(int metric)
 {
     return metric >= PCCM_METRIC_SSIM_GEOMETRY && metric <= PCCM_METRIC_SSIM_COLOR;

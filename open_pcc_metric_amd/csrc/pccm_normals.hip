@@ -518,6 +518,45 @@ __device__ __forceinline__ double p2d_value(const double *__restrict__ x64, cons
     return __dsqrt_rn(r > 0.0 ? r : 0.0);
 }
 
+// luma (ssim_value, a == 3) of row r of a cloud's colours: from the packed bytes `c8` (r | g << 8 | b << 16) when the cloud has them
+// -- 4 bytes per gathered row instead of 24; k / 255.0 is the very double rgb64 holds, so the bits agree -- or from rgb64
+__device__ __forceinline__ double p2d_luma(const uint32_t *__restrict__ c8, const double *__restrict__ rgb64, int64_t r)
+{
+    double c0, c1, c2;
+    if (c8) {
+        const uint32_t w = c8[r];
+        c0 = __ddiv_rn((double)(w & 0xffu), 255.0);
+        c1 = __ddiv_rn((double)((w >> 8) & 0xffu), 255.0);
+        c2 = __ddiv_rn((double)((w >> 16) & 0xffu), 255.0);
+    } else {
+        const double *c = rgb64 + 3 * r;
+        c0 = c[0]; c1 = c[1]; c2 = c[2];
+    }
+    return fma(0.0722, c2, fma(0.2126, c0, __dmul_rn(0.7152, c1)));
+}
+
+// Colour point-to-distribution value M_Y of query i (include/pccm.h, pccm_p2d_build_attrs): the distance of the query's luma to
+// the luma distribution of its cnt neighbours `row` (rows of the searched cloud, ascending (d2, row)), in standard deviations.
+// Moments of e_j = y(q_j) - y(p) summed left to right; the variance is clamped at 0 (it rounds below it where the neighbourhood's
+// luma is flat) and ridged by 2^-20.  Every operation is rounded separately, in the order INTEGRATION.md writes it.
+__device__ __forceinline__ double p2d_color_value(const uint32_t *__restrict__ s8, const double *__restrict__ srgb64,
+                                                  const uint32_t *__restrict__ q8, const double *__restrict__ qrgb64, int64_t i,
+                                                  const int32_t *__restrict__ row, int cnt)
+{
+    const double yp = p2d_luma(q8, qrgb64, i);
+    double s1 = 0, s2 = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const double e = __dsub_rn(p2d_luma(s8, srgb64, row[j]), yp);
+        s1 = __dadd_rn(s1, e);
+        s2 = __dadd_rn(s2, __dmul_rn(e, e));
+    }
+    const double kk = (double)cnt;
+    const double m = __ddiv_rn(s1, kk);
+    const double V = __dsub_rn(__ddiv_rn(s2, kk), __dmul_rn(m, m));
+    const double v = __dadd_rn(V < 0.0 ? 0.0 : V, 0x1.0p-20);
+    return __ddiv_rn(fabs(m), __dsqrt_rn(v));
+}
+
 // mode 0: normals from the covariances (the per-thread kernels write their own: cnt < 0)
 // mode 1 (PointSSIM): curvature of every point -> curv[n], from the neighbour lists nbr[n][k] (cnt[i] entries)
 // mode 2 (PointSSIM): the features of the attributes in `attrs` -> feat[a][n], from the neighbour lists nbr[n][k] (cnt[i] entries):
@@ -526,14 +565,25 @@ __device__ __forceinline__ double p2d_value(const double *__restrict__ x64, cons
 //   instead of being kept: up to 64 of them per thread would live in scratch memory.
 // mode 3 (point-to-distribution): p2d_value of every query i (row i of q64) -> nrm_out[n], from its neighbour list nbr[n][k] of rows
 //   of x64 (cnt[i] entries)
+// mode 4 (point-to-distribution, colour and joint): p2d_color_value M_Y of every query i -> nrm_out[n] and the joint value
+//   sqrt(M_G * M_G + M_Y * M_Y) -> curv[n], M_G = cov[i] (the column mode 3 wrote), from the same neighbour list; the searched
+//   cloud's colours are s8 (packed bytes) or else rgb64, the queries' q8 or else q64 (here the queries' COLOUR rows)
 __global__ __launch_bounds__(256) void k_normals_from_cov(const double *__restrict__ cov, const int32_t *__restrict__ cnt, int64_t n,
                                                           double *__restrict__ nrm_out, int mode, const int32_t *__restrict__ nbr, int k,
                                                           const double *__restrict__ x64, const double *__restrict__ nrm64,
                                                           const double *__restrict__ rgb64, double *__restrict__ curv,
-                                                          double *__restrict__ feat, int attrs, const double *__restrict__ q64)
+                                                          double *__restrict__ feat, int attrs, const double *__restrict__ q64,
+                                                          const uint32_t *__restrict__ s8, const uint32_t *__restrict__ q8)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (mode == 4) {
+        const double my = p2d_color_value(s8, rgb64, q8, q64, i, nbr + i * k, cnt[i]);
+        const double mg = cov[i];
+        nrm_out[i] = my;
+        curv[i] = __dsqrt_rn(__dadd_rn(__dmul_rn(mg, mg), __dmul_rn(my, my)));
+        return;
+    }
     if (mode == 3) {
         nrm_out[i] = p2d_value(x64, q64, i, nbr + i * k, cnt[i]);
         return;
@@ -715,7 +765,7 @@ int estimate_normals(pccm_ctx *ctx, int which, int k)
     PCCM_LAUNCH(ctx, k_normals_from_cov, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)cov,
                        (const int32_t *)cnt, c.n, c.nrm64, 0, (const int32_t *)nullptr, k, (const double *)nullptr,
                        (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr, 0,
-                       (const double *)nullptr);
+                       (const double *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
     PCCM_LAUNCH(ctx, k_knn_normals, dim3(2048), dim3(256), 0, ctx->stream, crecs, crecs, (const double *)nullptr, g, cs,
                        (const double *)c.xyz64, k, c.nrm64, (const uint32_t *)ctx->g_rank.p, (const uint32_t *)todo_count,
                        (int32_t *)ctx->g_cell_of.p, open_count, (int32_t *)nullptr, (int32_t *)nullptr);
@@ -763,7 +813,8 @@ int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
     if (attrs & PCCM_SSIM_CURVATURE)
         PCCM_LAUNCH(ctx, k_normals_from_cov, pgrid, dim3(256), 0, ctx->stream, (const double *)nullptr, (const int32_t *)cnt, c.n,
                            (double *)nullptr, 1, (const int32_t *)nbr, k, (const double *)c.xyz64, (const double *)nullptr,
-                           (const double *)nullptr, curv, (double *)nullptr, 0, (const double *)nullptr);
+                           (const double *)nullptr, curv, (double *)nullptr, 0, (const double *)nullptr, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr);
     // one launch per attribute: at 1M points and k = 12 the four attributes take 2.25 ms in one launch, 1.99 ms in four
     for (int a = 0; a < 4; ++a)
         if (attrs & (1 << a))
@@ -771,7 +822,7 @@ int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
                                (double *)nullptr, 2, (const int32_t *)nbr, k, (const double *)c.xyz64,
                                (const double *)((attrs & PCCM_SSIM_NORMAL) ? c.nrm64 : nullptr),
                                (const double *)((attrs & PCCM_SSIM_COLOR) ? c.rgb64 : nullptr), curv, c.ssim64, 1 << a,
-                               (const double *)nullptr);
+                               (const double *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
     PCCM_HIP(hipGetLastError());
     c.ssim_k = k;
     c.ssim_attrs = attrs;
@@ -804,33 +855,54 @@ static int p2d_search(pccm_ctx *ctx, int dir, int k, int32_t **nbr_out, int32_t 
     return PCCM_OK;
 }
 
-// pccm_p2d_build has checked k, the clouds and the context's state
-int p2d_build(pccm_ctx *ctx, int k, int *built)
+// pccm_p2d_build_attrs has checked k, attrs, the clouds (and their colours) and the context's state.  One k-NN search per
+// direction serves every column that is missing: the geometry column (mode 3) and, with PCCM_P2D_COLOR, the colour and joint columns
+// (mode 4, which reads the geometry column back) are formed from the same neighbour lists while they are in HBM.
+int p2d_build(pccm_ctx *ctx, int k, int attrs, int *built)
 {
     if (built) *built = 0;
-    if (ctx->p2d_k == k) return PCCM_OK;
+    const bool geometry = ctx->p2d_k != k;                                  // (a new k drops the colour columns too)
+    const bool color = (attrs & PCCM_P2D_COLOR) && (geometry || !ctx->p2d_color);
+    if (!geometry && !color) return PCCM_OK;
     if (ctx->capturing) {
         ctx->capture_failed = true;
         return fail(PCCM_E_STATE, "point-to-distribution columns are built before graph capture");
     }
     int rc;
-    ctx->p2d_k = 0;
+    if (geometry) {
+        ctx->p2d_k = 0;
+        ctx->p2d_color = false;
+    }
     for (int d = 0; d < 2; ++d) ctx->nn_gen[d]++;       // pending point-to-distribution reductions would read stale columns
     for (int d = 0; d < 2; ++d) {
         const Cloud &a = ctx->cloud[d], &b = ctx->cloud[1 - d];
-        const double *before = ctx->p2d64[d];
         PCCM_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = grow((void **)&ctx->p2d64[d], ctx->cap_p2d[d], (size_t)a.n * sizeof(double)))) return rc;
-        if (ctx->p2d64[d] != before) ctx->epoch++;          // (graphs that read the old column are stale)
+        double **cols[3] = {&ctx->p2d64[d], &ctx->p2d_cj64[d][0], &ctx->p2d_cj64[d][1]};
+        size_t *caps[3] = {&ctx->cap_p2d[d], &ctx->cap_p2d_cj[d][0], &ctx->cap_p2d_cj[d][1]};
+        for (int c = 0; c < 3; ++c) {
+            if (!(c == 0 ? geometry : color)) continue;
+            const double *before = *cols[c];
+            if ((rc = grow((void **)cols[c], *caps[c], (size_t)a.n * sizeof(double)))) return rc;
+            if (*cols[c] != before) ctx->epoch++;           // (graphs that read the old column are stale)
+        }
         int32_t *nbr, *cnt;
         if ((rc = p2d_search(ctx, d, k, &nbr, &cnt))) return rc;
-        PCCM_LAUNCH(ctx, k_normals_from_cov, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)nullptr,
-                           (const int32_t *)cnt, a.n, ctx->p2d64[d], 3, (const int32_t *)nbr, k, (const double *)b.xyz64,
-                           (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr, 0,
-                           (const double *)a.xyz64);
+        const dim3 pgrid((unsigned)((a.n + 255) / 256));
+        if (geometry)
+            PCCM_LAUNCH(ctx, k_normals_from_cov, pgrid, dim3(256), 0, ctx->stream, (const double *)nullptr,
+                               (const int32_t *)cnt, a.n, ctx->p2d64[d], 3, (const int32_t *)nbr, k, (const double *)b.xyz64,
+                               (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr, 0,
+                               (const double *)a.xyz64, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+        if (color)
+            PCCM_LAUNCH(ctx, k_normals_from_cov, pgrid, dim3(256), 0, ctx->stream, (const double *)ctx->p2d64[d],
+                               (const int32_t *)cnt, a.n, ctx->p2d_cj64[d][0], 4, (const int32_t *)nbr, k, (const double *)nullptr,
+                               (const double *)nullptr, (const double *)b.rgb64, ctx->p2d_cj64[d][1], (double *)nullptr, 0,
+                               (const double *)a.rgb64, (const uint32_t *)(b.rgb8_valid ? b.rgb8 : nullptr),
+                               (const uint32_t *)(a.rgb8_valid ? a.rgb8 : nullptr));
         PCCM_HIP(hipGetLastError());
     }
     ctx->p2d_k = k;
+    if (color) ctx->p2d_color = true;
     if (built) *built = 1;
     return PCCM_OK;
 }

@@ -2,7 +2,7 @@
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
-                                  [--point-to-distribution] [--p2d-neighbours K] [--csv]
+                                  [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -22,7 +22,10 @@ each direction and its PSNR, for D1 and -- with ``--point-to-plane`` -- D2, sele
 whose rows are those of R = 1 ("Ranked Hausdorff").  ``--point-to-distribution`` (no counterpart in the reference)
 adds, after all others, the point-to-distribution rows after Javaheri et al. (IEEE SPL 2020): the mean -- with ``--hausdorff``
 also the maximum -- Mahalanobis distance of each point to the distribution of its ``--p2d-neighbours`` nearest points in the other
-cloud ("Point-to-distribution").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+cloud ("Point-to-distribution").  ``--p2d-color`` (with ``--point-to-distribution``; a usage error without it)
+adds, after those, the colour and joint rows after Javaheri et al. (IEEE MMSP 2021): each point's luma against the luma
+distribution of the same neighbourhood, and sqrt(geometry^2 + colour^2) per point, pooled like the geometry rows; both clouds need
+colours ("Point-to-distribution: colour and joint").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -58,6 +61,10 @@ import click
                    "dimensionless); with --hausdorff also its worst point.  Does not depend on --ties.")
 @click.option("--p2d-neighbours", "p2d_neighbours", type=click.IntRange(4, 64), default=30, show_default=True,
               help="Points of the other cloud per point-to-distribution neighbourhood.")
+@click.option("--p2d-color", "p2d_color", required=False, is_flag=True,
+              help="With --point-to-distribution: report its colour rows (each point's luma against the luma distribution of the "
+                   "same nearest points) and joint geometry-and-colour rows as well, after all other rows.  Both clouds need "
+                   "colours.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -72,17 +79,18 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, csv, device, engine, normal_index, extent, tie_exposure, ties) -> None:
+        point_to_distribution, p2d_neighbours, p2d_color, csv, device, engine, normal_index, extent, tie_exposure, ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import (CalculateOptions, check_hausdorff_rank, check_point_ssim, check_point_to_distribution,
-                          transform_options)
+    from .options import (CalculateOptions, check_hausdorff_rank, check_p2d_color, check_point_ssim,
+                          check_point_to_distribution, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
         options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
                                    point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None,
-                                   point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours)
+                                   point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours,
+                                   p2d_color=p2d_color)
     except ValueError as exc:
         raise click.UsageError(str(exc))
     check_hausdorff_rank(options)
@@ -92,6 +100,7 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
     for path in pcloud:
         pcloud_cloud = read_point_cloud(path)
         check_point_ssim(options, ocloud_cloud, pcloud_cloud, ties=ties)       # (before the GPU context, for every processed cloud)
+        check_p2d_color(options, ocloud_cloud, pcloud_cloud)
         if cloud_pair is None:
             # (clouds read from files are freed while the GPU context works on -- with several decoded clouds, when the next one
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)

@@ -156,6 +156,23 @@ class MahalanobisDistances(PrimaryMetric, DirectionalMetric):    # no counterpar
                            lambda: cloud_pair.get_right_mahalanobis_distances(self.k))
 
 
+class ColorMahalanobisDistances(MahalanobisDistances):           # no counterpart in the reference (options.py: p2d_color)
+    """Per point of the iterating cloud, the distance of its luma to the luma distribution of the same k nearest points in the
+    OTHER cloud, in ridged standard deviations (include/pccm.h, pccm_p2d_build_attrs; INTEGRATION.md, "Point-to-distribution:
+    colour and joint")."""
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, lambda: cloud_pair.get_left_color_mahalanobis_distances(self.k),
+                           lambda: cloud_pair.get_right_color_mahalanobis_distances(self.k))
+
+
+class JointMahalanobisDistances(MahalanobisDistances):           # no counterpart in the reference (options.py: p2d_color)
+    """Per point of the iterating cloud, sqrt(M_G^2 + M_Y^2) of its geometry and colour point-to-distribution values: the
+    Mahalanobis distance in (x, y, z, Y) under a block-diagonal covariance."""
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, lambda: cloud_pair.get_left_joint_mahalanobis_distances(self.k),
+                           lambda: cloud_pair.get_right_joint_mahalanobis_distances(self.k))
+
+
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, cloud_pair: CloudPair) -> None:
@@ -353,8 +370,10 @@ class _OverMahalanobis(SecondaryMetric, DirectionalMetric):
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.is_left, self.k)
 
+    _primary = MahalanobisDistances      # (the colour and joint rows pool their own columns the same way)
+
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
-        return {"mahalanobis_distances": MahalanobisDistances(is_left=self.is_left, k=self.k)}
+        return {"mahalanobis_distances": self._primary(is_left=self.is_left, k=self.k)}
 
 
 class MahalanobisDistance(_OverMahalanobis):
@@ -374,6 +393,26 @@ class MaxMahalanobisDistance(_OverMahalanobis):
         column = mahalanobis_distances.value
         fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
         self.value = fused()[2] if fused is not None else np.max(column, axis=0)
+
+
+class ColorMahalanobisDistance(MahalanobisDistance):
+    """Colour point-to-distribution metric of one direction (after Javaheri et al., IEEE MMSP 2021): the mean of the per-point
+    luma distances.  Dimensionless and always finite."""
+    _primary = ColorMahalanobisDistances
+
+
+class MaxColorMahalanobisDistance(MaxMahalanobisDistance):
+    _primary = ColorMahalanobisDistances
+
+
+class JointMahalanobisDistance(MahalanobisDistance):
+    """Joint geometry-and-colour point-to-distribution metric of one direction: the mean of sqrt(M_G^2 + M_Y^2); inf where
+    MahalanobisDistance is."""
+    _primary = JointMahalanobisDistances
+
+
+class MaxJointMahalanobisDistance(MaxMahalanobisDistance):
+    _primary = JointMahalanobisDistances
 
 
 SSIM_CLASSES = {"geometry": GeometrySSIM, "normal": NormalSSIM, "curvature": CurvatureSSIM, "color": ColorSSIM}

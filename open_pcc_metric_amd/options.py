@@ -34,6 +34,14 @@ al., IEEE SPL 2020), after every row above, ranked Hausdorff rows included:
 
   point_to_distribution        MahalanobisDistance L/R/sym
   point_to_distribution & hd   MaxMahalanobisDistance L/R/sym
+
+and, with ``p2d_color`` (which needs ``point_to_distribution``; no counterpart in the reference: the joint geometry-and-colour
+point-to-distribution metric after Javaheri et al., IEEE MMSP 2021), after every row above:
+
+  p2d_color                    ColorMahalanobisDistance L/R/sym
+  p2d_color                    JointMahalanobisDistance L/R/sym
+  p2d_color & hd               MaxColorMahalanobisDistance L/R/sym
+  p2d_color & hd               MaxJointMahalanobisDistance L/R/sym
 """
 from __future__ import annotations
 
@@ -42,9 +50,10 @@ import typing
 import math
 import numbers
 
-from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMSE, ColorPSNR, GeoHausdorffDistance,
-                     GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR,
-                     MahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
+from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
+                     GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, GeoRankedHausdorffDistance,
+                     GeoRankedHausdorffDistancePSNR, JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
+                     MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
                      SymmetricMetric)
 
 SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
@@ -77,7 +86,8 @@ class CalculateOptions:
     def __init__(self, color: typing.Optional[str] = None, hausdorff: bool = False,
                  point_to_plane: bool = False, plane_to_plane: bool = False,
                  point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
-                 hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30):
+                 hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
+                 p2d_color: bool = False):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -100,6 +110,9 @@ class CalculateOptions:
             raise ValueError(f"p2d_neighbours must be an integer in {P2D_MIN_K}..{P2D_MAX_K}, not {p2d_neighbours!r}")
         self.point_to_distribution = bool(point_to_distribution)
         self.p2d_neighbours = int(p2d_neighbours)
+        if p2d_color and not self.point_to_distribution:
+            raise ValueError("p2d_color adds rows to the point-to-distribution metric: it needs point_to_distribution=True")
+        self.p2d_color = bool(p2d_color)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -135,6 +148,19 @@ def check_point_to_distribution(options: CalculateOptions, *, group=None) -> Non
     The columns need both whole clouds on one GPU: a sharded pair is out of scope."""
     if getattr(options, "point_to_distribution", False) and group is not None:
         raise ValueError("point-to-distribution rows are not available for sharded pairs (group=)")
+
+
+def check_p2d_color(options: CalculateOptions, origin_cloud, reconst_cloud, *, group=None) -> None:
+    """Raise ``ValueError`` when the colour and joint point-to-distribution rows ``options`` asks for cannot be computed for this
+    pair -- before any GPU work (the command line calls it for every cloud it processes; CloudPair checks the same before any GPU
+    work of a report).  Both clouds need colours, and -- like the geometry rows -- both whole clouds on one GPU."""
+    if not getattr(options, "p2d_color", False):
+        return
+    if group is not None:
+        raise ValueError("point-to-distribution rows are not available for sharded pairs (group=)")
+    from .cloud_pair import _has_colors
+    if not all(_has_colors(c) for c in (origin_cloud, reconst_cloud)):
+        raise ValueError("the colour and joint point-to-distribution rows (p2d_color) need the colours of both clouds")
 
 
 def _sides(cls, **kw):
@@ -183,4 +209,10 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
         metrics += _sides(MahalanobisDistance, **kw) + [_sym(MahalanobisDistance, False, **kw)]
         if options.hausdorff:
             metrics += _sides(MaxMahalanobisDistance, **kw) + [_sym(MaxMahalanobisDistance, False, **kw)]
+        if getattr(options, "p2d_color", False):
+            for cls in (ColorMahalanobisDistance, JointMahalanobisDistance):
+                metrics += _sides(cls, **kw) + [_sym(cls, False, **kw)]
+            if options.hausdorff:
+                for cls in (MaxColorMahalanobisDistance, MaxJointMahalanobisDistance):
+                    metrics += _sides(cls, **kw) + [_sym(cls, False, **kw)]
     return metrics
