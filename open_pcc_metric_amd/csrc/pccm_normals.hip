@@ -4,7 +4,9 @@
 // i.e. Open3D 0.18 PointCloud::EstimateNormals with its defaults (KDTreeSearchParamKNN(knn = 30),
 // fast_normal_computation): for every point, the covariance of its 30 nearest points of the same cloud
 // (the point itself included) and the eigenvector of the smallest eigenvalue.  Open3D is not in the
-// reference checkout, so this is a restatement of the published algorithm and is NOT parity-pinned:
+// reference checkout, so this is a restatement of the published algorithm and is NOT parity-pinned (tests/test_gpu_normals.py holds
+// every point to a high-precision reference within a tolerance that follows the conditioning of its own eigenproblem, per k, data
+// family, slot, grid choice and stage of the search -- still not Open3D parity):
 //   - neighbours: exact k-NN, squared distance in fp64 ((dx*dx)+(dy*dy))+(dz*dz), ties to the smaller row;
 //   - covariance: E[d d^T] - E[d] E[d]^T with d = p - q (Open3D forms the same matrix from raw moments;
 //     shifting by the query point only improves the conditioning);
@@ -241,10 +243,13 @@ __global__ __launch_bounds__(256) void k_knn_normals(const GridRec *__restrict__
 // found by a wave-wide quickselect (pivot = some staged distance inside the bracket, counted with ballots), ties at
 // the k-th distance go to the smaller rows, and the covariance of the selected points is accumulated by all lanes
 // and written out; k_normals_from_cov then solves the 3x3 eigenproblems one thread per point.  Same neighbour set
-// as the per-thread search (exact k-NN, (d2, row) order); the sums are taken in a different order.
+// as the per-thread search (exact k-NN, (d2, row) order); the sums are taken in a different order (a butterfly over the lanes
+// instead of left to right), but one the neighbour set alone decides: the selected candidates are compacted to the front of the
+// wave's LDS (ballot + prefix count), lane l < kk finds the rank of entry l among them in ascending (d2, row) order, and the
+// neighbour of rank r is summed by lane r.  The order of the records inside a cell, which the grid build leaves to its atomics,
+// does not reach the covariance: an estimate repeated on a rebuilt grid gives the same bits.
 // Points the two cubes cannot settle, or with more than kWCap candidates, are passed on to k_knn_normals.
-// With nbr_out (PointSSIM) the wave also writes the kk selected rows in ascending (d2, row) order: the selected candidates are
-// compacted to the front of the wave's LDS (ballot + prefix count), and lane l < kk writes entry l at its rank among them.
+// With nbr_out (PointSSIM) lane l also writes the row of entry l at its rank: the kk selected rows in ascending (d2, row) order.
 constexpr int kWCap = 512;
 
 __device__ __forceinline__ void wave_lds_sync()
@@ -270,6 +275,7 @@ __global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict_
 {
     __shared__ double s_d[4][kWCap];
     __shared__ uint32_t s_p[4][kWCap];
+    __shared__ uint32_t s_r[4][kKnnMax];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int dimx = g.dim[0], dimy = g.dim[1], dimz = g.dim[2];
     const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -376,19 +382,60 @@ __global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict_
                 }
                 row_cut = last;
             }
-            double m0 = 0, m1 = 0, m2 = 0, s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0;
-            for (uint32_t i = lane; i < T; i += 64) {
-                const double d = s_d[w][i];
-                if (d > tau) continue;
-                const double4 a = *reinterpret_cast<const double4 *>(&recs[s_p[w][i]]);
-                if (d == tau && (int)(__double_as_longlong(a.w) & 0xffffffffll) > row_cut) continue;
-                const double dx = a.x - qx, dy = a.y - qy, dz = a.z - qz;
-                m0 += dx; m1 += dy; m2 += dz;
-                s00 += dx * dx; s01 += dx * dy; s02 += dx * dz; s11 += dy * dy; s12 += dy * dz; s22 += dz * dz;
+            // the kk selected candidates go to the front of the wave's LDS (in place: a selected entry only moves down), then to
+            // the lane of their rank in ascending (d2, row) order: the sums below are then taken in an order that the neighbour
+            // set alone decides -- the order of the records inside a cell (the grid build's atomics) does not reach the result
+            uint32_t base = 0;
+            for (uint32_t i0 = 0; i0 < T; i0 += 64) {
+                const uint32_t i = i0 + lane;
+                double d = 0.0;
+                int row = 0;
+                uint32_t rec = 0;
+                bool sel = false;
+                if (i < T) {
+                    d = s_d[w][i];
+                    if (d <= tau) {
+                        rec = s_p[w][i];
+                        row = recs[rec].idx;
+                        sel = d < tau || row <= row_cut;
+                    }
+                }
+                const unsigned long long m = __ballot(sel);
+                wave_lds_sync();                                  // every lane has read its entry
+                if (sel) {
+                    const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                    s_d[w][pos] = d;
+                    s_p[w][pos] = (uint32_t)row;
+                    if (pos < (uint32_t)kKnnMax) s_r[w][pos] = rec;
+                }
+                base += (uint32_t)__popcll(m);
+                wave_lds_sync();
             }
-            m0 = wave_sum_f64(m0); m1 = wave_sum_f64(m1); m2 = wave_sum_f64(m2);
-            s00 = wave_sum_f64(s00); s01 = wave_sum_f64(s01); s02 = wave_sum_f64(s02);
-            s11 = wave_sum_f64(s11); s12 = wave_sum_f64(s12); s22 = wave_sum_f64(s22);
+            const uint32_t nsel = base < kk ? base : kk;           // == kk (fewer only if distances are NaN: nothing unwritten is read)
+            const bool own = (uint32_t)lane < nsel;                // lane l owns selected entry l
+            int row = 0, rank = 0;
+            uint32_t rec = 0;
+            if (own) {
+                const double d = s_d[w][lane];
+                row = (int)s_p[w][lane];
+                rec = s_r[w][lane];
+                for (uint32_t j = 0; j < nsel; ++j) {
+                    const double e = s_d[w][j];
+                    const int r = (int)s_p[w][j];
+                    rank += (e < d || (e == d && r < row)) ? 1 : 0;
+                }
+            }
+            wave_lds_sync();                                      // every owner has read its record's position
+            if (own) s_r[w][rank] = rec;
+            wave_lds_sync();
+            double dx = 0.0, dy = 0.0, dz = 0.0;                  // lane l: the neighbour of rank l (none: zeros)
+            if (own) {
+                const double4 a = *reinterpret_cast<const double4 *>(&recs[s_r[w][lane]]);
+                dx = a.x - qx; dy = a.y - qy; dz = a.z - qz;
+            }
+            double m0 = wave_sum_f64(dx), m1 = wave_sum_f64(dy), m2 = wave_sum_f64(dz);
+            const double s00 = wave_sum_f64(dx * dx), s01 = wave_sum_f64(dx * dy), s02 = wave_sum_f64(dx * dz);
+            const double s11 = wave_sum_f64(dy * dy), s12 = wave_sum_f64(dy * dz), s22 = wave_sum_f64(dz * dz);
             if (lane == 0) {
                 const double inv = 1.0 / (double)kk;
                 m0 *= inv; m1 *= inv; m2 *= inv;
@@ -397,42 +444,7 @@ __global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict_
                 o[3] = s11 * inv - m1 * m1; o[4] = s12 * inv - m1 * m2; o[5] = s22 * inv - m2 * m2;
                 cnt_out[qrow] = (int)kk;
             }
-            if (nbr_out) {
-                uint32_t base = 0;
-                for (uint32_t i0 = 0; i0 < T; i0 += 64) {              // in place: a selected entry only moves down
-                    const uint32_t i = i0 + lane;
-                    double d = 0.0;
-                    int row = 0;
-                    bool sel = false;
-                    if (i < T) {
-                        d = s_d[w][i];
-                        if (d <= tau) {
-                            row = recs[s_p[w][i]].idx;
-                            sel = d < tau || row <= row_cut;
-                        }
-                    }
-                    const unsigned long long m = __ballot(sel);
-                    wave_lds_sync();                                  // every lane has read its entry
-                    if (sel) {
-                        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                        s_d[w][pos] = d;
-                        s_p[w][pos] = (uint32_t)row;
-                    }
-                    base += (uint32_t)__popcll(m);
-                    wave_lds_sync();
-                }
-                if ((uint32_t)lane < kk) {                           // base == kk
-                    const double d = s_d[w][lane];
-                    const int row = (int)s_p[w][lane];
-                    int rank = 0;
-                    for (uint32_t j = 0; j < kk; ++j) {
-                        const double e = s_d[w][j];
-                        const int r = (int)s_p[w][j];
-                        rank += (e < d || (e == d && r < row)) ? 1 : 0;
-                    }
-                    nbr_out[(int64_t)qrow * k + rank] = row;
-                }
-            }
+            if (nbr_out && own) nbr_out[(int64_t)qrow * k + rank] = row;
             done = true;
         }
         if (!done && lane == 0) {

@@ -7,7 +7,6 @@ k-th distance, an FMA or a reordered sum changes them.  No tolerance anywhere in
 import ctypes
 import functools
 import os
-import re
 import sys
 
 import numpy as np
@@ -28,6 +27,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import p2d_reference as ref  # noqa: E402
+from knn_stages import blocked_rows, constant as _constant, settles as _settles  # noqa: E402
 
 MEAN, MAX = "MahalanobisDistance", "MaxMahalanobisDistance"
 EXTENT = [1.0, 1.0, 1.0]
@@ -117,32 +117,6 @@ def test_partly_overlapping_boxes_under_either_engine(engine):
         check_pair(pair, a, b, 30, nbr={side: r[:, :30] for side, r in rows.items()})
 
 
-def _constant(name):
-    src = open(os.path.join(ROOT, "open_pcc_metric_amd", "csrc", "pccm_normals.hip")).read()
-    return int(re.search(rf"constexpr int {name} = (\d+);", src).group(1))
-
-
-def _settles(q, b, cells_b, org, h, dim, k, rings):
-    """Does the searches' stop rule settle query q within `rings` rings of the grid (org, h, dim)?  (The rule of k_knn_normals,
-    restated: the k-th best distance inside the cube against the nearest face of the cube that is not a face of the grid.)"""
-    c = np.clip(np.floor((q - org) / h), 0, dim - 1).astype(np.int64)
-    slack = (np.abs(org) + (dim + 2) * h) * 2.0 ** -48
-    for r in range(rings + 1):
-        inside = np.all(np.abs(cells_b - c) <= r, axis=1)
-        L = np.inf
-        for x in range(3):
-            if c[x] - r > 0:
-                L = min(L, (q[x] - (org[x] + (c[x] - r) * h[x])) - slack[x])
-            if c[x] + r < dim[x] - 1:
-                L = min(L, ((org[x] + (c[x] + r + 1) * h[x]) - q[x]) - slack[x])
-        if L == np.inf:
-            return True
-        d2 = np.sort(ref.sq_dist(q[None, :], b[inside]))
-        if len(d2) >= k and L > 0 and d2[k - 1] < L * L * (1.0 - 2.0 ** -30):
-            return True
-    return False
-
-
 def test_the_staged_case_reaches_every_stage():
     """The data of FAMILIES["staged"] against the constants of pccm_normals.hip and the grid the search ran on: some queries have
     more than kWCap candidates in their first cube (the wave search hands them to the per-thread search), some are still open
@@ -182,25 +156,7 @@ def test_two_hundred_thousand_points_each():
     n, k = 200_000, 30
     a, b = rng.random((n, 3)), rng.random((n, 3))
 
-    def blocked_rows(p, q, block=1024, extra=8):
-        qt = torch.from_numpy(q).to("cuda")
-        out = np.empty((len(p), k), dtype=np.int64)
-        for s in range(0, len(p), block):
-            pt = torch.from_numpy(p[s:s + block]).to("cuda")
-            d2 = None
-            for x in range(3):
-                d = pt[:, None, x] - qt[None, :, x]
-                d = d * d
-                d2 = d if d2 is None else d2 + d
-            cand = torch.topk(d2, k + extra, dim=1, largest=False).indices.cpu().numpy()
-            cd2 = ref.sq_dist(p[s:s + block, None, :], q[cand])
-            order = np.lexsort((cand, cd2), axis=-1)
-            cd2 = np.take_along_axis(cd2, order, axis=-1)
-            assert np.all(cd2[:, k - 1] < cd2[:, -1])            # nothing outside the candidates can belong to the first k
-            out[s:s + block] = np.take_along_axis(cand, order, axis=-1)[:, :k]
-        return out
-
-    nbr = {True: blocked_rows(a, b), False: blocked_rows(b, a)}
+    nbr = {True: blocked_rows(a, b, k), False: blocked_rows(b, a, k)}
     torch.cuda.synchronize()
     with pair_of(a, b) as pair:
         check_pair(pair, a, b, k, nbr=nbr)
