@@ -456,8 +456,41 @@ __global__ __launch_bounds__(256) void k_knn_cov_wave(const GridRec *__restrict_
     }
 }
 
+// One Jacobi rotation of the symmetric 3x3 in the plane (p, q): app, aqq the two diagonal entries, apq the entry it annihilates,
+// arp, arq the two entries of the third row (Rutishauser's update: the diagonal moves by t * apq)
+__device__ __forceinline__ void jacobi_rotate(double &app, double &aqq, double &apq, double &arp, double &arq)
+{
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // (theta^2 = inf: t = 0)
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    const double h = t * apq;
+    app -= h;
+    aqq += h;
+    apq = 0.0;
+    const double g = arp;
+    arp = c * g - s * arq;
+    arq = s * g + c * arq;
+}
+
+// smallest eigenvalue of the symmetric matrix [a00 a01 a02; a01 a11 a12; a02 a12 a22], SCALED so that its largest entry is 1, by
+// cyclic Jacobi sweeps: the absolute error is a few ulps of the matrix norm whatever the spectrum -- also where the two smallest
+// eigenvalues meet (collinear neighbourhoods), where the closed form's acos keeps only half the digits.  The sweeps end when the
+// off-diagonal entries are below 2^-54 (each moves an eigenvalue by no more than itself); convergence is quadratic, 3 to 5 sweeps.
+__device__ __forceinline__ double smallest_eigenvalue_jacobi(double a00, double a01, double a02, double a11, double a12, double a22)
+{
+    for (int sweep = 0; sweep < 8; ++sweep) {
+        if ((fabs(a01) + fabs(a02)) + fabs(a12) <= 0x1.0p-54) break;
+        jacobi_rotate(a00, a11, a01, a02, a12);
+        jacobi_rotate(a00, a22, a02, a01, a12);
+        jacobi_rotate(a11, a22, a12, a01, a02);
+    }
+    return fmin(a00, fmin(a11, a22));
+}
+
 // PointSSIM curvature of point p: lambda_min / trace of the covariance normal_from_neighbours forms (E[d d^T] - E[d] E[d]^T,
-// d = q - p), summed in neighbourhood order; scale-free (taken on the matrix scaled as for the normal), 0 when the trace is 0
+// d = q - p), summed in neighbourhood order; scale-free (taken on the matrix scaled as for the normal), 0 when the trace is 0.
+// lambda_min comes from Jacobi sweeps, not from smallest_eigenvalue: c is perfectly conditioned, the closed form is not.
 __device__ __forceinline__ double curvature_of(const double *__restrict__ x64, int64_t p, const int32_t *__restrict__ row, int cnt)
 {
     const double qx = x64[3 * p], qy = x64[3 * p + 1], qz = x64[3 * p + 2];
@@ -478,7 +511,7 @@ __device__ __forceinline__ double curvature_of(const double *__restrict__ x64, i
     const double a00 = a[0] * s, a01 = a[1] * s, a02 = a[2] * s, a11 = a[3] * s, a12 = a[4] * s, a22 = a[5] * s;
     const double tr = (a00 + a11) + a22;
     if (tr == 0.0) return 0.0;
-    return smallest_eigenvalue(a00, a01, a02, a11, a12, a22) / tr;
+    return smallest_eigenvalue_jacobi(a00, a01, a02, a11, a12, a22) / tr;
 }
 
 // PointSSIM value of neighbour j of row p for attribute a (0 geometry, 1 normal, 2 curvature, 3 colour; include/pccm.h)

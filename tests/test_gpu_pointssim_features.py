@@ -1,0 +1,268 @@
+"""PointSSIM normal and curvature rows on the GPU (k_normals_from_cov modes 1 and 2: curvature_of and ssim_value in
+pccm_normals.hip) against the high-precision reference of tests/pointssim_tolerance.py, point by point.
+
+Every feature must lie within its tau_F, every similarity whose tau_s is below 1e-6 within its tau_s, and every pooled row
+within the mean tolerance of its column -- per family (wire-like, ring-like, voxel, lattice, duplicate and georeferenced data
+among them) and k in {2, 3, 5, 12, 64}, with file normals and with estimated ones (the reference is always given the normals the
+device used), by every engine, on the voxel-brick path and on 200 000 points.  Where every neighbourhood is collinear the
+curvature is 0 and CurvatureSSIM is 1: the fp64 restatement of the trigonometric closed form curvature_of used before gives
+0.98 there and misses these bounds in every case at k = 2 and on the wires at every k
+(tests/test_pointssim_tolerance_host.py)."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from open_pcc_metric_amd import _native as nat
+from open_pcc_metric_amd.calculator import MetricCalculator
+from open_pcc_metric_amd.cloud_pair import CloudPair
+from open_pcc_metric_amd.options import CalculateOptions, transform_options
+from open_pcc_metric_amd.point_cloud import PointCloud
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import pointssim_reference as ref  # noqa: E402
+import pointssim_tolerance as pt  # noqa: E402
+
+CLASS = {"normal": "NormalSSIM", "curvature": "CurvatureSSIM"}
+UNIT = [1.0, 1.0, 1.0]
+
+
+def report(pair, k, attrs=pt.ATTRIBUTES):
+    opts = CalculateOptions(point_ssim=list(attrs), ssim_neighbours=k)
+    with np.errstate(divide="ignore"):
+        return MetricCalculator(pair).calculate(transform_options(opts)).as_dict()
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def assert_features_within(got, want, tol, label):
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == want.shape
+    err = np.abs(got - want)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.where(tol > 0, err / np.where(tol > 0, tol, 1.0), np.where(err == 0, 0.0, np.inf))
+    print(f"{label}: largest |F - F_ref| {err.max():.3e}, largest |F - F_ref| / tau_F {ratio.max():.4f}")
+    bad = np.flatnonzero(err > tol)
+    assert bad.size == 0, f"{label}: {bad.size} features outside tau_F, first rows {bad[:5]}: {got[bad[:5]]} vs {want[bad[:5]]}, tau_F {tol[bad[:5]]}"
+
+
+def assert_similarities_within(got, s_ref, tau_s, label, cap=pt.LEFT_OUT_CAP):
+    """-> the bound on |mean(got) - mean(s_ref)|: the mean of tau_s over the examined points, 1 for each point left out."""
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == s_ref.shape
+    ok = pt.examined(tau_s)
+    assert 1.0 - ok.mean() <= cap, (label, float(1.0 - ok.mean()))
+    err = np.abs(got - s_ref)
+    print(f"{label}: {int(ok.sum())} of {len(ok)} examined, largest |s - s_ref| {err[ok].max():.3e}, largest |s - s_ref| / tau_s "
+          f"{(err[ok] / tau_s[ok]).max():.4f}, largest tau_s {tau_s[ok].max():.3e}")
+    bad = np.flatnonzero(err[ok] > tau_s[ok])
+    assert bad.size == 0, (f"{label}: {bad.size} similarities outside tau_s, first rows {np.flatnonzero(ok)[bad[:5]]}: "
+                           f"{got[ok][bad[:5]]} vs {s_ref[ok][bad[:5]]}, tau_s {tau_s[ok][bad[:5]]}")
+    assert np.all((got >= 0.0) & (got <= 1.0))
+    return (tau_s[ok].sum() + np.count_nonzero(~ok)) / len(ok)
+
+
+def check_pair(pair, xa, xb, nbr_a, nbr_b, idx_l, idx_r, k, label, attrs=pt.ATTRIBUTES):
+    """Everything the issue asks per (family, k): features of both clouds, similarities of both directions, pooled rows."""
+    res = report(pair, k, attrs)
+    na = nb = None
+    if "normal" in attrs:
+        na, nb = np.asarray(pair.get_normals(0)), np.asarray(pair.get_normals(1))          # the normals the device used
+    for attribute in attrs:
+        Fa, ta = pt.reference_features(xa, nbr_a, attribute, na)
+        Fb, tb = pt.reference_features(xb, nbr_b, attribute, nb)
+        ga, gb = np.asarray(pair.get_ssim_features(0, attribute, k)), np.asarray(pair.get_ssim_features(1, attribute, k))
+        assert_features_within(ga, Fa, ta, f"{label} {attribute} F_A")
+        assert_features_within(gb, Fb, tb, f"{label} {attribute} F_B")
+        cls = CLASS[attribute]
+        pooled = {}
+        for is_left, (f1, t1, f2, t2, idx) in ((True, (Fa, ta, Fb, tb, idx_l)), (False, (Fb, tb, Fa, ta, idx_r))):
+            getter = pair.get_left_ssim_similarities if is_left else pair.get_right_ssim_similarities
+            got = np.asarray(getter(attribute, k))
+            s_ref, tau_s = pt.similarity_reference(f1, t1, f2, t2, idx)
+            bound = assert_similarities_within(got, s_ref, tau_s, f"{label} {attribute} {'left' if is_left else 'right'}")
+            row = np.float64(res[(cls, is_left, k)])
+            assert row.tobytes() == np.mean(got).tobytes()                                  # the device's own column, bit for bit
+            assert abs(row - np.mean(s_ref)) <= bound + 8 * pt.EPS, (label, attribute, is_left, row, np.mean(s_ref), bound)
+            pooled[is_left] = row
+        sym = np.float64(res[("SymmetricMetric", cls, True, k, cls, False, k)])
+        assert sym.tobytes() == min(pooled[True], pooled[False]).tobytes()
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def family(name):
+    return pt.load(name)
+
+
+def cloud(x, normals=None):
+    return PointCloud(np.array(x), None if normals is None else np.array(normals), None)
+
+
+# ---- per family and k ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("normals", ["file", "estimated"])
+@pytest.mark.parametrize("name,k", pt.cases())
+def test_every_point_is_within_its_tolerance(name, k, normals):
+    """`file`: the clouds carry normals (the sheet's own; elsewhere the stand-ins of pointssim_tolerance.load); `estimated`: they
+    carry none and the device estimates them.  Either way the reference is given what pair.get_normals() returns."""
+    (xa, na, wa), (xb, nb, wb), idx_l, idx_r = family(name)
+    a, b = (cloud(xa, na), cloud(xb, nb)) if normals == "file" else (cloud(xa), cloud(xb))
+    with CloudPair(a, b, extent=UNIT) as pair:
+        res = check_pair(pair, xa, xb, wa[:, :k], wb[:, :k], idx_l, idx_r, k, f"{name} k={k} {normals}")
+        if normals == "file":
+            assert np.array_equal(np.asarray(pair.get_normals(0)), na)
+    if k == 2:                                      # every neighbourhood is collinear: curvature 0, the rows 1
+        rows = [v for key, v in res.items() if "CurvatureSSIM" in key]
+        assert len(rows) == 3 and all(abs(v - 1.0) <= 1e-12 for v in rows), rows
+
+
+# ---- exact cases ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", pt.KS)
+def test_identical_wires_give_one_in_every_curvature_row(k):
+    (xa, _, _), _, _, _ = family("wires")
+    with CloudPair(cloud(xa), cloud(xa), extent=UNIT) as pair:
+        res = report(pair, k, ["curvature"])
+        rows = [v for key, v in res.items() if "CurvatureSSIM" in key]
+        assert len(rows) == 3 and all(abs(v - 1.0) <= 1e-12 for v in rows), rows
+        got = np.asarray(pair.get_left_ssim_similarities("curvature", k))
+        assert np.all(np.abs(got - 1.0) <= 1e-12)
+
+
+@pytest.mark.parametrize("name", sorted(pt.FAMILIES))
+def test_k_2_gives_one_in_every_curvature_row(name):
+    """Two different clouds at k = 2: two points are collinear, the curvature is 0 in both clouds, so CurvatureSSIM is 1 (the
+    closed form gave 0.984 on uniform clouds)."""
+    (xa, _, _), (xb, _, _), _, _ = family(name)
+    with CloudPair(cloud(xa), cloud(xb), extent=UNIT) as pair:
+        res = report(pair, 2, ["curvature"])
+        rows = [v for key, v in res.items() if "CurvatureSSIM" in key]
+        assert len(rows) == 3 and all(abs(v - 1.0) <= 1e-12 for v in rows), rows
+        for getter in (pair.get_left_ssim_similarities, pair.get_right_ssim_similarities):
+            assert np.all(np.abs(np.asarray(getter("curvature", 2)) - 1.0) <= 1e-9)
+
+
+@pytest.mark.parametrize("na,nb,k", [(2, 2, 12), (2, 3, 2), (2, 40, 12), (40, 30, 64), (11, 12, 12)])
+def test_clouds_of_fewer_than_three_points_and_smaller_than_k(na, nb, k):
+    rng = np.random.default_rng(100 + na)
+    xa, xb = rng.random((na, 3)), rng.random((nb, 3))
+    with CloudPair(cloud(xa), cloud(xb), extent=UNIT) as pair:
+        check_pair(pair, xa, xb, pt.neighbours(xa, k), pt.neighbours(xb, k), ref.matched_rows(xa, xb), ref.matched_rows(xb, xa),
+                   k, f"n={na},{nb} k={k}")
+        if na < 3:                                  # nothing to estimate from: the default normal, curvature 0
+            assert np.array_equal(np.asarray(pair.get_normals(0)), np.tile([0.0, 0.0, 1.0], (na, 1)))
+            assert not np.any(np.asarray(pair.get_ssim_features(0, "normal", k)))
+
+
+def test_all_points_equal():
+    """Trace 0: c = 0, every feature an exact 0, every similarity and row an exact 1."""
+    same = np.tile(np.array([[1.5, -2.0, 3.25]]), (200, 1))
+    with CloudPair(cloud(same), cloud(same[:150]), extent=UNIT) as pair:
+        for k in (2, 12):
+            res = report(pair, k)
+            for attribute in pt.ATTRIBUTES:
+                for which in (0, 1):
+                    assert not np.any(np.asarray(pair.get_ssim_features(which, attribute, k)))
+                assert np.all(np.asarray(pair.get_left_ssim_similarities(attribute, k)) == 1.0)
+                assert np.all(np.asarray(pair.get_right_ssim_similarities(attribute, k)) == 1.0)
+            rows = [v for key, v in res.items() if "SSIM" in str(key)]
+            assert len(rows) == 6 and all(v == 1.0 for v in rows), rows
+
+
+# ---- other paths ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("engine", ["auto", "grid", "brute"])
+@pytest.mark.parametrize("name", ["uniform", "wires"])
+def test_every_engine(name, engine):
+    (xa, _, wa), (xb, _, wb), idx_l, idx_r = family(name)
+    with CloudPair(cloud(xa), cloud(xb), extent=UNIT, nn_engine=engine) as pair:
+        check_pair(pair, xa, xb, wa[:, :12], wb[:, :12], idx_l, idx_r, 12, f"{name} {engine}")
+
+
+def check_sample(pair, xa, xb, k, rows, label):
+    """check_pair's feature and similarity assertions on the rows `rows` of cloud A (and on their matched rows of cloud B), the
+    neighbours by scipy's cKDTree re-ranked exactly (pointssim_reference.tree_rows); the pooled rows against the device's own
+    columns."""
+    res = report(pair, k)
+    na, nb = np.asarray(pair.get_normals(0)), np.asarray(pair.get_normals(1))
+    matched = ref.tree_rows(xa[rows], xb, 1)[:, 0]
+    partner = np.unique(matched)
+    for attribute in pt.ATTRIBUTES:
+        Fa, ta = pt.sampled_features(xa, rows, k, attribute, na, lambda r: ref.tree_rows(xa[r], xa, k))
+        Fb, tb = pt.sampled_features(xb, partner, k, attribute, nb, lambda r: ref.tree_rows(xb[r], xb, k))
+        ga, gb = np.asarray(pair.get_ssim_features(0, attribute, k)), np.asarray(pair.get_ssim_features(1, attribute, k))
+        assert_features_within(ga[rows], Fa, ta, f"{label} {attribute} F_A (sample)")
+        assert_features_within(gb[partner], Fb, tb, f"{label} {attribute} F_B (sample)")
+        at = np.searchsorted(partner, matched)
+        s_ref, tau_s = pt.similarity_reference(Fa, ta, Fb[at], tb[at], np.arange(len(rows)))
+        got = np.asarray(pair.get_left_ssim_similarities(attribute, k))
+        assert_similarities_within(got[rows], s_ref, tau_s, f"{label} {attribute} left (sample)")
+        assert np.float64(res[(CLASS[attribute], True, k)]).tobytes() == np.mean(got).tobytes()
+        got_r = np.asarray(pair.get_right_ssim_similarities(attribute, k))
+        assert np.float64(res[(CLASS[attribute], False, k)]).tobytes() == np.mean(got_r).tobytes()
+
+
+def test_voxel_surrogate():
+    """Integer content: the voxel-brick search (as test_gpu_pointssim.test_voxel_surrogate), flat facets and ties at the cut."""
+    from test_gpu_vox import shell
+    xa = np.asarray(shell(30_000, 51, (0, 0, 0), 60), dtype=np.float64)
+    xb = np.asarray(shell(25_000, 52, (1, 0, 0), 60, 0.6), dtype=np.float64)
+    rows = np.sort(np.random.default_rng(54).choice(len(xa), 3000, replace=False))
+    with CloudPair(cloud(xa), cloud(xb), extent=[130.0, 130.0, 130.0]) as pair:
+        check_sample(pair, xa, xb, 12, rows, "voxel shells")
+
+
+def test_two_hundred_thousand_points_each():
+    rng = np.random.default_rng(61)
+    n = 200_000
+    xa, xb = rng.random((n, 3)), rng.random((n, 3))
+    rows = np.sort(np.random.default_rng(62).choice(n, 3000, replace=False))
+    with CloudPair(cloud(xa), cloud(xb), extent=UNIT) as pair:
+        check_sample(pair, xa, xb, 12, rows, f"n={n}")
+
+
+def features_of(eng, which, k):
+    """Cloud `which`'s normal and curvature features, built now (not found in HBM)."""
+    assert eng.ssim_features(which, k, pt.ATTRIBUTES) is True
+    return {a: eng.get_ssim_features(which, a) for a in pt.ATTRIBUTES}
+
+
+@pytest.mark.parametrize("name", ["uniform", "wires", "shell"])
+def test_features_repeat_bit_for_bit(name):
+    """A cloud's features depend on that cloud alone: built again after drop_caches (a rebuilt grid), as the other slot, and
+    beside a partner of more than twice its size (the cloud gets cells of its own), they are the same bits -- the sums of
+    curvature_of follow the neighbourhood order, not the record order of whichever grid the search ran on."""
+    (x, _, wide), (other, _, _), _, _ = family(name)
+    k = 12
+    lo, hi = x.min(axis=0), x.max(axis=0)
+    large = lo + np.random.default_rng(7).random((2 * len(x) + 500, 3)) * (hi - lo) * 1.5
+    eng = nat.Engine(0)
+    try:
+        eng.set_cloud(0, x)
+        eng.set_cloud(1, other)
+        eng.nn_pair("auto")
+        eng.estimate_normals(0, 30)
+        first = features_of(eng, 0, k)
+        nrm = eng.get_normals(0)
+        eng.drop_caches()
+        eng.nn_pair("auto")
+        eng.ssim_features(0, k - 1, pt.ATTRIBUTES)                          # (another k: the columns at k are built again)
+        again = features_of(eng, 0, k)
+        eng.set_cloud(0, large)                                             # the other slot, a large partner: solo cells
+        eng.set_cloud(1, x)
+        eng.nn_pair("auto")
+        eng.set_normals(1, nrm)
+        solo = features_of(eng, 1, k)
+    finally:
+        eng.close()
+    for attribute in pt.ATTRIBUTES:
+        assert same_bits(first[attribute], again[attribute]), (name, attribute, "after drop_caches")
+        assert same_bits(first[attribute], solo[attribute]), (name, attribute, "beside a large partner")
+        want, tol = pt.reference_features(x, wide[:, :k], attribute, nrm)
+        assert_features_within(first[attribute], want, tol, f"{name} {attribute} (engine)")

@@ -133,7 +133,8 @@ OTHER = {
     "k_knn_cov_wave": "normal estimation: test_gpu_normals",
     "k_knn_normals": "normal estimation: test_gpu_normals",
     "k_knn_normals_full": "normal estimation: test_gpu_normals",
-    "k_normals_from_cov": "normal estimation: test_gpu_normals",
+    "k_normals_from_cov": ("normal estimation: test_gpu_normals; PointSSIM curvatures and features (modes 1, 2): test_gpu_pointssim, "
+                           "test_gpu_pointssim_features"),
     "k_point_jobs": "unfused point-to-plane columns: row 'reduce_shapes'",
     "k_point_metric": "per-point projections (pccm_point_metric): the 'brick' rows, test_gpu_round2",
     "k_publish": "every reduction batch",
