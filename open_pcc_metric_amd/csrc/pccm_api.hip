@@ -1452,6 +1452,62 @@ static const double *p2d_column(const pccm_ctx *ctx, int dir, int metric)
     return metric == PCCM_METRIC_P2D ? ctx->p2d64[dir] : ctx->p2d_cj64[dir][metric - PCCM_METRIC_P2D_COLOR];
 }
 
+// normal_mode enters the column: the projection on a normal of the searched cloud and its square, nothing else
+static bool normal_mode_enters(int metric)
+{
+    return metric == PCCM_METRIC_D2 || metric == PCCM_METRIC_PROJ;
+}
+
+// What a (dir, metric, normal_mode) request of the direction's search needs before any column is bound -- one answer for
+// pccm_point_metric, the reductions and the selections: the metric exists, it is defined for this search, its operands are there.
+static int column_check(pccm_ctx *ctx, int dir, int metric, int normal_mode, const Cloud &it, const Cloud &se, const NNResult &res)
+{
+    if (metric == PCCM_METRIC_D1) return PCCM_OK;
+    if (metric == PCCM_METRIC_ANGULAR) return check_angular(ctx, dir, it, se);
+    if (is_ssim_metric(metric)) return check_ssim(ctx, dir, it, se, res, metric);
+    if (is_p2d_metric(metric)) return check_p2d(ctx, dir, metric);
+    if (!normal_mode_enters(metric)) return fail(PCCM_E_ARG, "bad metric %d", metric);
+    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
+    return check_normals(ctx, it, se, res, normal_mode);
+}
+
+// The k_point_jobs job of a checked request (column_check): the D2 / PROJ / ANGULAR / SSIM_* column of the shard's rows into out
+// ([ns]), or -- PCCM_METRIC_D1 -- their error vectors ([ns][3]).  recs: the matched rows are read from the direction's matched
+// records in place (ColumnSource::recs); otherwise from the plain idx column, which the caller has made ready.
+static int point_job_fill(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out, bool recs, const Cloud &it, const Cloud &se,
+                          const NNResult &res, PointJob &P)
+{
+    const bool matched = matched_column(metric), ssim = is_ssim_metric(metric);
+    P.q64 = it.xyz64; P.r64 = se.xyz64;
+    P.nrm = ssim ? ssim_column(se, metric) : se.nrm64;
+    P.inrm = !matched ? nullptr : ssim ? ssim_column(it, metric) : it.nrm64;
+    P.c64 = P.cn64 = nullptr;
+    if (!matched && res.ties == PCCM_TIES_MEAN) {           // the virtual neighbours, and their averaged normals where they are indexed
+        const bool nmean = normal_mode_enters(metric) && normal_mode == PCCM_NORMAL_NEIGHBOUR;
+        int rc = ensure_ties(ctx, dir, nmean, false);
+        if (rc) return rc;
+        P.c64 = (const double *)ctx->tie[dir].pos.p;
+        if (nmean) P.cn64 = (const double *)ctx->tie[dir].nrm.p;
+    }
+    P.idx = recs ? nullptr : res.idx;
+    P.recs = recs ? (const float4 *)res.rec.p : nullptr;
+    P.q_begin = res.begin; P.metric = metric; P.normal_mode = matched ? PCCM_NORMAL_NEIGHBOUR : normal_mode; P.val = out;
+    return PCCM_OK;
+}
+
+// The getters' point pass: one job, always from the plain columns -- pccm_point_metric forms D2 / PROJ here even when the records
+// hold a fused projection, and the matched columns from idx, not from matched records: an operand route apart from the reductions'
+static int point_pass(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out, const Cloud &it, const Cloud &se, NNResult &res)
+{
+    int rc = ensure_plain(ctx, res, true);
+    if (rc) return rc;
+    PointJobs pj = {};
+    pj.njobs = 1;
+    pj.off[1] = res.end - res.begin;
+    if ((rc = point_job_fill(ctx, dir, metric, normal_mode, out, false, it, se, res, pj.j[0]))) return rc;
+    return launch_point_jobs(ctx, pj);
+}
+
 int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
 {
     CHECK_CTX(ctx);
@@ -1463,71 +1519,36 @@ int pccm_error_vectors(pccm_ctx *ctx, int dir, double *out)
     if (rc) return rc;
     const int64_t ns = res->end - res->begin;
     if (ns <= 0) return PCCM_OK;
-    if ((rc = ensure_plain(ctx, *res))) return rc;
     if ((rc = ensure(ctx, ctx->val, (size_t)ns * 3 * sizeof(double)))) return rc;
-    const bool mean = res->ties == PCCM_TIES_MEAN;
-    if (mean && (rc = ensure_ties(ctx, dir, false, false))) return rc;
-    if ((rc = launch_point_metric(ctx, *it, *se, *res, PCCM_METRIC_D1, PCCM_NORMAL_ROW, nullptr, (double *)ctx->val.p,
-                                  mean ? (const double *)ctx->tie[dir].pos.p : nullptr))) return rc;
+    if ((rc = point_pass(ctx, dir, PCCM_METRIC_D1, PCCM_NORMAL_ROW, (double *)ctx->val.p, *it, *se, *res))) return rc;
     { int rcd = d2h(ctx, out, ctx->val.p, (size_t)ns * 3 * sizeof(double)); if (rcd) return rcd; }
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     return PCCM_OK;
 }
 
 // device pointer to the shard's per-point metric (computing it into ctx->val when needed)
-static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode, const double **dev, int64_t *ns_out,
-                            const Cloud **it_out, NNResult **res_out, DevBuf *valbuf = nullptr)
+static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode, const double **dev, int64_t *ns_out)
 {
-    DevBuf &vb = valbuf ? *valbuf : ctx->val;
     const Cloud *it, *se;
     NNResult *res;
     int rc = need_nn(ctx, dir, &it, &se, &res);
     if (rc) return rc;
     const int64_t ns = res->end - res->begin;
     *ns_out = ns;
-    *it_out = it;
-    *res_out = res;
-    if (metric == PCCM_METRIC_ANGULAR) {
-        if ((rc = check_angular(ctx, dir, *it, *se))) return rc;
-        if (res->ties == PCCM_TIES_MEAN) {                // the tie pass makes the column
-            if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
-            *dev = (const double *)ctx->tie[dir].ang.p;
-            return PCCM_OK;
-        }
-        if ((rc = ensure_plain(ctx, *res, true))) return rc;
-        if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
-        if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, PCCM_NORMAL_NEIGHBOUR, (double *)vb.p, nullptr))) return rc;
-        *dev = (const double *)vb.p;
-        return PCCM_OK;
-    }
-    if (is_p2d_metric(metric)) {
-        if ((rc = check_p2d(ctx, dir, metric))) return rc;
-        *dev = p2d_column(ctx, dir, metric) + res->begin;
-        return PCCM_OK;
-    }
-    if (is_ssim_metric(metric)) {
-        if ((rc = check_ssim(ctx, dir, *it, *se, *res, metric))) return rc;
-        if ((rc = ensure_plain(ctx, *res, true))) return rc;
-        if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
-        if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, PCCM_NORMAL_NEIGHBOUR, (double *)vb.p, nullptr))) return rc;
-        *dev = (const double *)vb.p;
-        return PCCM_OK;
-    }
-    if ((rc = ensure_plain(ctx, *res, metric != PCCM_METRIC_D1))) return rc;
+    if ((rc = column_check(ctx, dir, metric, normal_mode, *it, *se, *res))) return rc;
     if (metric == PCCM_METRIC_D1) {
+        if ((rc = ensure_plain(ctx, *res, false))) return rc;
         *dev = res->d2;
-        return PCCM_OK;
+    } else if (is_p2d_metric(metric)) {
+        *dev = p2d_column(ctx, dir, metric) + res->begin;
+    } else if (metric == PCCM_METRIC_ANGULAR && res->ties == PCCM_TIES_MEAN) {     // the tie pass makes the column
+        if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
+        *dev = (const double *)ctx->tie[dir].ang.p;
+    } else {
+        if ((rc = ensure(ctx, ctx->val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
+        if ((rc = point_pass(ctx, dir, metric, normal_mode, (double *)ctx->val.p, *it, *se, *res))) return rc;
+        *dev = (const double *)ctx->val.p;
     }
-    if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
-    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
-    if ((rc = check_normals(ctx, *it, *se, *res, normal_mode))) return rc;
-    if ((rc = ensure(ctx, vb, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
-    const bool mean = res->ties == PCCM_TIES_MEAN, nmean = mean && normal_mode == PCCM_NORMAL_NEIGHBOUR;
-    if (mean && (rc = ensure_ties(ctx, dir, nmean, false))) return rc;
-    if ((rc = launch_point_metric(ctx, *it, *se, *res, metric, normal_mode, (double *)vb.p, nullptr,
-                                  mean ? (const double *)ctx->tie[dir].pos.p : nullptr,
-                                  nmean ? (const double *)ctx->tie[dir].nrm.p : nullptr))) return rc;
-    *dev = (const double *)vb.p;
     return PCCM_OK;
 }
 
@@ -1554,9 +1575,7 @@ int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, doubl
     if (!out) return fail(PCCM_E_ARG, "null pointer");
     const double *dev;
     int64_t ns;
-    const Cloud *it;
-    NNResult *res;
-    int rc = metric_on_device(ctx, dir, metric, normal_mode, &dev, &ns, &it, &res);
+    int rc = metric_on_device(ctx, dir, metric, normal_mode, &dev, &ns);
     if (rc) return rc;
     if (ns > 0) { int rcd = d2h(ctx, out, dev, (size_t)ns * sizeof(double)); if (rcd) return rcd; }
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
@@ -1670,16 +1689,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     int rc = need_nn(ctx, dir, &it, &se, &res);
     if (rc) return rc;
     const int64_t ns = res->end - res->begin;
-    const bool matched = matched_column(metric), ssim = is_ssim_metric(metric);
-    if (matched) {
-        if ((rc = ssim ? check_ssim(ctx, dir, *it, *se, *res, metric) : check_angular(ctx, dir, *it, *se))) return rc;
-    } else if (is_p2d_metric(metric)) {
-        if ((rc = check_p2d(ctx, dir, metric))) return rc;
-    } else if (metric != PCCM_METRIC_D1) {
-        if (metric != PCCM_METRIC_D2 && metric != PCCM_METRIC_PROJ) return fail(PCCM_E_ARG, "bad metric %d", metric);
-        if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
-        if ((rc = check_normals(ctx, *it, *se, *res, normal_mode))) return rc;
-    }
+    if ((rc = column_check(ctx, dir, metric, normal_mode, *it, *se, *res))) return rc;
     const ColumnSource src = column_source(ctx, dir, metric, normal_mode);
     const double *dev = (const double *)res->rec.p;
     int stride = 1;
@@ -1698,22 +1708,9 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         dev = (const double *)s.val.p;
         if (ns > 0) {
             if (pj.njobs >= 4)
-                return fail(PCCM_E_ARG, matched ? "at most four unfused point-to-plane, angular or PointSSIM columns per call"
-                                                : "at most four unfused point-to-plane columns per call");
-            PointJob &P = pj.j[pj.njobs];
-            P.q64 = it->xyz64; P.r64 = se->xyz64;
-            P.nrm = ssim ? ssim_column(*se, metric) : se->nrm64;
-            P.inrm = !matched ? nullptr : ssim ? ssim_column(*it, metric) : it->nrm64;
-            P.idx = src.recs ? nullptr : res->idx;
-            P.recs = src.recs ? (const float4 *)res->rec.p : nullptr;
-            P.c64 = P.cn64 = nullptr;
-            if (!matched && res->ties == PCCM_TIES_MEAN) {
-                const bool nmean = normal_mode == PCCM_NORMAL_NEIGHBOUR;
-                if ((rc = ensure_ties(ctx, dir, nmean, false))) return rc;
-                P.c64 = (const double *)ctx->tie[dir].pos.p;
-                if (nmean) P.cn64 = (const double *)ctx->tie[dir].nrm.p;
-            }
-            P.q_begin = res->begin; P.metric = metric; P.normal_mode = matched ? PCCM_NORMAL_NEIGHBOUR : normal_mode; P.val = (double *)s.val.p;
+                return fail(PCCM_E_ARG, matched_column(metric) ? "at most four unfused point-to-plane, angular or PointSSIM columns per call"
+                                                               : "at most four unfused point-to-plane columns per call");
+            if ((rc = point_job_fill(ctx, dir, metric, normal_mode, (double *)s.val.p, src.recs, *it, *se, *res, pj.j[pj.njobs]))) return rc;
             pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;
             pj.njobs++;
         }
@@ -1789,7 +1786,7 @@ static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode
 {
     for (auto &s : ctx->slots)
         if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric &&
-            (metric == PCCM_METRIC_D1 || is_p2d_metric(metric) || matched_column(metric) || s.mode == normal_mode) &&
+            (!normal_mode_enters(metric) || s.mode == normal_mode) &&
             s.gen == ctx->nn_gen[dir])
             return &s;
     return nullptr;
@@ -1850,7 +1847,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         NNResult &res = ctx->nn[dirs[k]];
         if (!res.valid || res.ties != PCCM_TIES_MEAN) continue;
         if (metrics[k] == PCCM_METRIC_ANGULAR) tie_ang[dirs[k]] = true;
-        else if (metrics[k] != PCCM_METRIC_D1 && !is_p2d_metric(metrics[k]) && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
+        else if (normal_mode_enters(metrics[k]) && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
     }
     for (int d = 0; d < 2; ++d) {
         if (!tie_ang[d] || slot_find(ctx, d, PCCM_METRIC_ANGULAR, 0, want_units)) continue;
@@ -2110,7 +2107,7 @@ int pccm_reduce_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *met
 static SelectSlot *sel_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, int64_t k)
 {
     for (auto &q : ctx->sel_slots)
-        if (q.pending && q.dir == dir && q.metric == metric && q.k == k && (metric == PCCM_METRIC_D1 || q.mode == normal_mode) &&
+        if (q.pending && q.dir == dir && q.metric == metric && q.k == k && (!normal_mode_enters(metric) || q.mode == normal_mode) &&
             q.gen == ctx->nn_gen[dir])
             return &q;
     return nullptr;

@@ -532,7 +532,10 @@ __host__ __device__ __forceinline__ bool is_ssim_metric(int metric)
     return metric >= PCCM_METRIC_SSIM_GEOMETRY && metric <= PCCM_METRIC_SSIM_COLOR;
 }
 
-struct PointJob {               // one D2 / PROJ / ANGULAR column (k_point_jobs)
+// One per-point column formed from a search result (k_point_jobs, the only kernel that forms them): D2 / PROJ / ANGULAR / SSIM_* as
+// [ns] values, or -- PCCM_METRIC_D1 -- the error vectors as [ns][3] rows.  pccm_api.hip fills it in one place (point_job_fill), for
+// the reduction batches and the one-job launches of pccm_point_metric / pccm_error_vectors alike.
+struct PointJob {
     const double *q64, *r64, *nrm;
     const double *c64, *cn64;   // PCCM_TIES_MEAN: per shard row the virtual neighbour / its averaged normal (null: gather via idx)
     const double *inrm;         // PCCM_METRIC_ANGULAR: the iterating cloud's normals (nrm: the searched cloud's); PCCM_METRIC_SSIM_*:
@@ -541,7 +544,7 @@ struct PointJob {               // one D2 / PROJ / ANGULAR column (k_point_jobs)
     const int32_t *idx;
     int64_t q_begin;
     int metric, normal_mode;
-    double *val;
+    double *val;                // [ns], or [ns][3] (PCCM_METRIC_D1)
 };
 struct PointJobs {
     PointJob j[4];
@@ -590,11 +593,6 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 // the selection launches of jobs.sel (memset of the histograms, kSelPasses histogram passes, resolve); nothing is published
 int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs);
 int launch_publish(pccm_ctx *ctx, uint64_t *seq);     // k_publish behind whatever the stream holds; *seq as for launch_unit_jobs
-
-// (PCCM_METRIC_ANGULAR: the pick's column from both clouds' normals; under PCCM_TIES_MEAN the tie pass makes it, tie_mean)
-int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,
-                        int normal_mode, double *out_val /*[ns]*/, double *out_err /*[ns][3] or null*/,
-                        const double *c64 = nullptr, const double *cn64 = nullptr);   // PCCM_TIES_MEAN columns (PointJob)
 
 double np_pairwise_sum(const double *a, int64_t n);
 

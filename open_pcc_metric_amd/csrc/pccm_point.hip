@@ -1,4 +1,4 @@
-// Ingest, fused per-point error/projection kernel (K3) and the NumPy-ordered leaf reduction (K5).
+// Ingest, the per-point column kernel (K3) and the NumPy-ordered leaf reduction (K5).
 #include "pccm_internal.h"
 
 namespace pccm {
@@ -149,65 +149,46 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
 }
 
 // ------------------------------------------------------------------------------------------
-// K3: gather the matched point, error vector e = iter[i] - search[nn(i)] (cloud_pair.py:90-100),
+// K3 (k_point_jobs): every per-point column that is formed from a search result -- the reductions' and selections' batches
+// (up to four columns per launch) and the getters (pccm_point_metric, pccm_error_vectors: one job) alike.
+// point_row is one row of one job: gather the matched point, error vector e = iter[i] - search[nn(i)] (cloud_pair.py:90-100),
 // projection on the other cloud's normal (metric.py:146-153) and its square (metric.py:179).
 // The dot product is the FMA chain fma(e2,n2, fma(e1,n1, e0*n0)) that np.dot (OpenBLAS ddot)
 // evaluates on FMA-capable hosts; see oracle/pccm_oracle.c for how that was pinned.
 // HBM/gather bound: 24 (q) + 4 (idx) + 24 (r, gathered) + 24 (normal) + 8 (out) bytes per row.
-// PCCM_METRIC_ANGULAR (the pick's column): the own normal inrm[gi] against the matched row's nrm[j] -- 24 + 4 + 24 + 8 bytes.
-// PCCM_METRIC_SSIM_*: inrm / nrm are the two clouds' feature columns, the own feature against the matched row's -- 8 + 4 + 8 + 8.
+// PCCM_METRIC_D1: the error vector itself, val as [ns][3] rows (pccm_error_vectors; the D1 column needs no point pass).
+// PCCM_METRIC_ANGULAR (the pick's column): the own normal inrm[gi] against the matched row's nrm[j] -- 24 + 4 (or 16) + 24 + 8 bytes.
+// PCCM_METRIC_SSIM_*: inrm / nrm are the two clouds' feature columns, the own feature against the matched row's -- 8 + 4 (or 16) + 8 + 8.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_point_metric(const double *__restrict__ q64, int64_t q_begin, int64_t ns,
-                                                      const double *__restrict__ r64,
-                                                      const int32_t *__restrict__ idx,
-                                                      const double *__restrict__ nrm, int metric, int normal_mode,
-                                                      double *__restrict__ val, double *__restrict__ err,
-                                                      const double *__restrict__ c64, const double *__restrict__ cn64,
-                                                      const double *__restrict__ inrm)
+__device__ __forceinline__ void point_row(const PointJob &J, int64_t i)
 {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= ns) return;
-    const int64_t gi = q_begin + i;
-    const int64_t j = idx[i];
-    if (metric == PCCM_METRIC_ANGULAR) {
-        val[i] = angular_similarity(inrm + 3 * gi, nrm + 3 * j);
+    const int64_t gi = J.q_begin + i;
+    if (J.metric == PCCM_METRIC_ANGULAR) {
+        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
+        J.val[i] = angular_similarity(J.inrm + 3 * gi, J.nrm + 3 * j);
         return;
     }
-    if (is_ssim_metric(metric)) {
-        val[i] = ssim_similarity(inrm[gi], nrm[j]);
+    if (is_ssim_metric(J.metric)) {
+        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
+        J.val[i] = ssim_similarity(J.inrm[gi], J.nrm[j]);
         return;
     }
-    const double *r = c64 ? c64 + 3 * i : r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
-    const double ex = __dsub_rn(q64[3 * gi], r[0]);
-    const double ey = __dsub_rn(q64[3 * gi + 1], r[1]);
-    const double ez = __dsub_rn(q64[3 * gi + 2], r[2]);
-    if (err) {
-        err[3 * i] = ex;
-        err[3 * i + 1] = ey;
-        err[3 * i + 2] = ez;
+    const int64_t j = J.idx[i];
+    const double *r = J.c64 ? J.c64 + 3 * i : J.r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
+    const double ex = __dsub_rn(J.q64[3 * gi], r[0]);
+    const double ey = __dsub_rn(J.q64[3 * gi + 1], r[1]);
+    const double ez = __dsub_rn(J.q64[3 * gi + 2], r[2]);
+    if (J.metric == PCCM_METRIC_D1) {
+        J.val[3 * i] = ex;
+        J.val[3 * i + 1] = ey;
+        J.val[3 * i + 2] = ez;
+        return;
     }
-    if (val) {
-        const double *nv = (normal_mode == PCCM_NORMAL_ROW) ? nrm + 3 * gi : cn64 ? cn64 + 3 * i : nrm + 3 * j;
-        double p = __dmul_rn(ex, nv[0]);
-        p = __fma_rn(ey, nv[1], p);
-        p = __fma_rn(ez, nv[2], p);
-        val[i] = (metric == PCCM_METRIC_PROJ) ? p : __dmul_rn(p, p);
-    }
-}
-
-int launch_point_metric(pccm_ctx *ctx, const Cloud &it, const Cloud &se, const NNResult &res, int metric,
-                        int normal_mode, double *out_val, double *out_err, const double *c64, const double *cn64)
-{
-    const int64_t ns = res.end - res.begin;
-    if (ns <= 0) return PCCM_OK;
-    ProfScope ps(ctx, PCCM_K_POINT);
-    dim3 grid((unsigned)((ns + 255) / 256));
-    PCCM_LAUNCH(ctx, k_point_metric, grid, dim3(256), 0, ctx->stream, it.xyz64, res.begin, ns, se.xyz64, res.idx,
-                       is_ssim_metric(metric) ? se.ssim64 + (size_t)(metric - PCCM_METRIC_SSIM_GEOMETRY) * se.n : se.nrm64, metric,
-                       normal_mode, out_val, out_err, c64, cn64,
-                       is_ssim_metric(metric) ? it.ssim64 + (size_t)(metric - PCCM_METRIC_SSIM_GEOMETRY) * it.n : it.nrm64);
-    PCCM_HIP(hipGetLastError());
-    return PCCM_OK;
+    const double *nv = (J.normal_mode == PCCM_NORMAL_ROW) ? J.nrm + 3 * gi : J.cn64 ? J.cn64 + 3 * i : J.nrm + 3 * j;
+    double p = __dmul_rn(ex, nv[0]);
+    p = __fma_rn(ey, nv[1], p);
+    p = __fma_rn(ez, nv[2], p);
+    J.val[i] = (J.metric == PCCM_METRIC_PROJ) ? p : __dmul_rn(p, p);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -228,29 +209,7 @@ __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
 #pragma unroll
     for (int k = 1; k < 4; ++k)
         if (k < jobs.njobs && i0 >= jobs.off[k]) jb = k;
-    const PointJob &J = jobs.j[jb];
-    const int64_t i = i0 - jobs.off[jb];
-    const int64_t gi = J.q_begin + i;
-    if (J.metric == PCCM_METRIC_ANGULAR) {             // the own normal against the matched row's: 24 + 4 (or 16) + 24 + 8 bytes
-        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
-        J.val[i] = angular_similarity(J.inrm + 3 * gi, J.nrm + 3 * j);
-        return;
-    }
-    if (is_ssim_metric(J.metric)) {                    // the own feature against the matched row's: 8 + 4 (or 16) + 8 + 8 bytes
-        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
-        J.val[i] = ssim_similarity(J.inrm[gi], J.nrm[j]);
-        return;
-    }
-    const int64_t j = J.idx[i];
-    const double *r = J.c64 ? J.c64 + 3 * i : J.r64 + 3 * j;     // PCCM_TIES_MEAN: the virtual neighbour of row i
-    const double ex = __dsub_rn(J.q64[3 * gi], r[0]);
-    const double ey = __dsub_rn(J.q64[3 * gi + 1], r[1]);
-    const double ez = __dsub_rn(J.q64[3 * gi + 2], r[2]);
-    const double *nv = (J.normal_mode == PCCM_NORMAL_ROW) ? J.nrm + 3 * gi : J.cn64 ? J.cn64 + 3 * i : J.nrm + 3 * j;
-    double p = __dmul_rn(ex, nv[0]);
-    p = __fma_rn(ey, nv[1], p);
-    p = __fma_rn(ez, nv[2], p);
-    J.val[i] = (J.metric == PCCM_METRIC_PROJ) ? p : __dmul_rn(p, p);
+    point_row(jobs.j[jb], i0 - jobs.off[jb]);
 }
 
 int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs)

@@ -135,8 +135,9 @@ OTHER = {
     "k_knn_normals_full": "normal estimation: test_gpu_normals",
     "k_normals_from_cov": ("normal estimation: test_gpu_normals; PointSSIM curvatures and features (modes 1, 2): test_gpu_pointssim, "
                            "test_gpu_pointssim_features"),
-    "k_point_jobs": "unfused point-to-plane columns: row 'reduce_shapes'",
-    "k_point_metric": "per-point projections (pccm_point_metric): the 'brick' rows, test_gpu_round2",
+    "k_point_jobs": ("unfused point-to-plane columns: row 'reduce_shapes'; per-point projections (pccm_point_metric): the 'brick' "
+                     "rows, test_gpu_round2, test_gpu_point_columns; error vectors (pccm_error_vectors): test_gpu_parity, "
+                     "test_gpu_point_columns"),
     "k_publish": "every reduction batch",
     "k_unpack": "plain columns from result records: every row",
 }
