@@ -6,7 +6,8 @@
 // normal -- keeping the smallest volume).  The hull itself is Qhull on the host (as in Open3D); what is left
 // is H hull vertices x T hull triangles of projections, which is seconds of NumPy for a rounded shape
 // (H ~ 5e4, T ~ 1e5) and milliseconds here.  fp64 throughout.  Not parity-pinned (Open3D is not in the
-// reference checkout); checked against the oracle's NumPy restatement of the same search.
+// reference checkout); the three kernels of this file are held, per tile, workgroup and edge, to the exact references of
+// tests/extent_reference.py (tests/test_gpu_extent_kernels.py; DESIGN.md, "Minimal OBB").
 //
 // k_obb_frames: one thread per triangle, the hull vertices streamed through LDS in tiles (every tile is read
 // once per workgroup and broadcast to its 256 frames).  18 fp64 operations per (vertex, triangle) pair.

@@ -127,9 +127,9 @@ OTHER = {
     "k_axis_hist": "box trimming: test_gpu_edges",
     "k_cell_hist": "grid scale decision: every grid row",
     "k_count_occupied": "grid scale decision: every grid row",
-    "k_extreme_rows": "extent: test_extent",
-    "k_outside_planes": "extent: test_extent",
-    "k_obb_frames": "extent: test_extent",
+    "k_extreme_rows": "extent: test_gpu_extent_kernels (planted extremes, the fp32 bound), test_extent",
+    "k_outside_planes": "extent: test_gpu_extent_kernels (exact integer plane tests), test_extent",
+    "k_obb_frames": "extent: test_gpu_extent_kernels (one frame at a time, exact ties, whole hulls), test_extent",
     "k_knn_cov_wave": "normal estimation: test_gpu_normals",
     "k_knn_normals": "normal estimation: test_gpu_normals",
     "k_knn_normals_full": "normal estimation: test_gpu_normals",
