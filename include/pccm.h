@@ -159,6 +159,26 @@ int pccm_set_io_staged(pccm_ctx *ctx, int on);
  * magnitude is positive.  The normals stay on the device; pccm_get_normals copies [n][3] doubles out. */
 int pccm_estimate_normals(pccm_ctx *ctx, int which, int knn);
 int pccm_get_normals(pccm_ctx *ctx, int which, double *out);
+/* Carry cloud `from`'s normals over to the other cloud, to = 1 - from, the way MPEG's pc_error gives a decoded cloud the
+ * reference's normals (scaleNormals with averageNormals), from the two directional searches the context holds.  F = the search
+ * that iterates cloud `from` (PCCM_DIR_LEFT for from = 0), G = the other one; nn_F(i), nn_G(j) = their matched rows under
+ * PCCM_TIES_PICK (the smallest row on exact ties).  Per row j of cloud `to`, with S_j = { i : nn_F(i) = j } = i_1 < ... < i_m:
+ *   m >= 1: per component in fp64 s = n_from[i_1], then s = s + n_from[i_r] for r = 2..m, every add rounded separately, and
+ *           the result s / (double)m, one correctly rounded division (m = 1 gives the source normal back bit for bit, signed
+ *           zeros included);
+ *   m = 0:  n_from[nn_G(j)], copied bit for bit (a point that is nobody's nearest neighbour takes its own nearest point's).
+ * The result is NOT renormalised (as the averaged normals of PCCM_TIES_MEAN are not).  It becomes cloud `to`'s normals on the
+ * device exactly as if pccm_estimate_normals had made them: one per point, pending reductions that read normals and captured
+ * graphs go stale, pccm_get_normals(to) returns them.  The operation follows pc_error's normal carrying; parity with that program
+ * is NOT pinned: it is not available to this project's tests, it sums in single precision, and its tie order is its kd-tree's.
+ * *built (may be null) = 1 when work was done, 0 when cloud `to` already holds normals carried from the same two search results
+ * and the same source normals -- such a call does nothing and is allowed between pccm_graph_begin and pccm_graph_end.  Carried
+ * normals are dropped (cloud `to` has no normals again) when either cloud gets new points or cloud `from` gets new normals;
+ * pccm_set_normals* or pccm_estimate_normals on `to` replace them.  A search that ran without matched rows (pccm_nn_want_idx
+ * off) is repeated with them.
+ * PCCM_E_ARG: from is not 0 or 1.  PCCM_E_STATE: a cloud is missing; cloud `from` has no normal for every row (announced normals
+ * are uploaded first); either directional search has no result; a sharded context; PCCM_TIES_MEAN; a build during graph capture. */
+int pccm_carry_normals(pccm_ctx *ctx, int from, int *built);
 
 /* PointSSIM features ("PointSSIM") of cloud `which`: per point p, N_k(p) = the k points of the same cloud first
  * in ascending (d2, row) order (p itself included; all of them when the cloud has fewer than k), and per attribute the variance

@@ -40,7 +40,7 @@ KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4
 # every symbol include/pccm.h declares (tests check that the library exports all of them)
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
-    "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals",
+    "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_carry_normals",
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
@@ -108,6 +108,7 @@ def load() -> ctypes.CDLL:
     lib.pccm_set_shard_dir.argtypes = [vp, i32, i32, i32]
     lib.pccm_estimate_normals.argtypes = [vp, i32, i32]
     lib.pccm_get_normals.argtypes = [vp, i32, vp]
+    lib.pccm_carry_normals.argtypes = [vp, i32, ctypes.POINTER(i32)]
     lib.pccm_ssim_features.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_ssim_features.argtypes = [vp, i32, i32, vp]
     lib.pccm_p2d_build.argtypes = [vp, i32, ctypes.POINTER(i32)]
@@ -477,6 +478,13 @@ class Engine:
     def estimate_normals(self, which: int, knn: int = 30) -> None:
         """Open3D-style normals (k-NN covariance, smallest eigenvector) computed and kept on the device."""
         _check(self._lib.pccm_estimate_normals(self._ctx, int(which), int(knn)))
+
+    def carry_normals(self, from_which: int) -> bool:
+        """Give the other cloud the normals of cloud ``from_which``, averaged over the points whose nearest neighbour each of
+        its points is (pccm_carry_normals: MPEG pc_error's normal carrying); they stay on the device.  True when work was done."""
+        built = ctypes.c_int32(0)
+        _check(self._lib.pccm_carry_normals(self._ctx, int(from_which), ctypes.byref(built)))
+        return bool(built.value)
 
     def get_normals(self, which: int) -> np.ndarray:
         out = np.empty((self._n[which], 3), dtype=np.float64)

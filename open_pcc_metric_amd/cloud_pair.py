@@ -26,6 +26,11 @@ Differences from the reference, all deliberate:
 * ``group=`` shards the pair over the ranks of a ``torch.distributed`` group: by direction first (half of the ranks
   search cloud_pair.py:67-72, the other half :73-78, so every rank builds one cloud's search structure), then by
   query rows inside each half (``shard_mode="rows"``: every rank takes rows of both directions, as in round 1);
+* ``carry_normals=True`` gives a cloud WITHOUT normals the other cloud's normals instead of estimated ones, the way the MPEG
+  evaluation procedure treats a decoded cloud (``pc_error``'s normal carrying; include/pccm.h, pccm_carry_normals): each point
+  takes the average of the normals of the other cloud's points whose nearest neighbour it is, or -- nobody's nearest neighbour
+  -- its own nearest point's normal.  With normals on both clouds the flag does nothing; with normals on neither, cloud 0's are
+  estimated and carried to cloud 1.  Not available sharded or under ``ties="mean"`` (``ValueError``);
 * ``use_graph=True`` lets ``recompute()`` replay the whole sweep + reductions of the previous report
   as one hipGraph launch (for callers that evaluate the same resident pair repeatedly).
 """
@@ -281,13 +286,15 @@ class CloudPair:
                  nn_engine: str = "auto", normal_index: str = "row", extent=None, group=None,
                  use_graph: bool = False, estimate_normals: bool = True, normals_knn: int = 30,
                  shard_mode: str = "direction", _engine=None, _uploads_first: bool = False,
-                 staged_io: typing.Optional[bool] = None, ties: str = "pick"):
+                 staged_io: typing.Optional[bool] = None, ties: str = "pick", carry_normals: bool = False):
         if normal_index not in nat.NORMAL_MODES:
             raise ValueError("normal_index must be 'row' or 'neighbour'")
         if not isinstance(ties, str) or ties not in nat.TIES:
             raise ValueError("ties must be 'pick' or 'mean'")
         if nn_engine not in nat.ENGINES:
             raise ValueError(f"nn_engine must be one of {sorted(nat.ENGINES)}")
+        from .options import check_carry_normals
+        check_carry_normals(carry_normals, ties=ties, group=group)       # (ValueError before any GPU work)
         self.clouds = (origin_cloud, reconst_cloud)
         self.normal_index = normal_index
         self.nn_engine = nn_engine
@@ -295,6 +302,8 @@ class CloudPair:
         self._use_graph = bool(use_graph) and ties == "pick"        # (searches under "mean" are not captured: pccm_set_ties)
         self._estimate_normals, self._normals_knn = bool(estimate_normals), int(normals_knn)
         self._estimated = [False, False]
+        self._carry_normals = bool(carry_normals)
+        self._carried = [False, False]          # the cloud's normals were carried over from the other cloud (pccm_carry_normals)
         self._xchg, self._xchg_wanted = {}, []
         self._selections, self._sel_wanted = {}, []
         self._colours_on_device = [False, False]
@@ -313,6 +322,8 @@ class CloudPair:
             self._owns_engine = True
             self._coll.device = device            # the nccl exchange is staged on the same GPU
         self._engine = _engine
+        if self._carry_normals and not hasattr(_engine, "carry_normals"):
+            raise ValueError("this engine cannot carry normals from one cloud to the other")
         if hasattr(_engine, "set_ties"):
             _engine.set_ties(ties)                # (every time: a pooled context comes back with the default, pccm_ctx_reset)
         elif ties != "pick":
@@ -367,7 +378,8 @@ class CloudPair:
         if self._coll.sharded or not hasattr(eng, "nn_pair"):
             # (a sharded pair keeps nothing that pays: every rank would have to agree on what is resident)
             kw = dict(nn_engine=self.nn_engine, normal_index=self.normal_index, extent=self._extent, use_graph=self._use_graph,
-                      estimate_normals=self._estimate_normals, normals_knn=self._normals_knn, ties=self.ties)
+                      estimate_normals=self._estimate_normals, normals_knn=self._normals_knn, ties=self.ties,
+                      carry_normals=self._carry_normals)
             group, owns = self._coll.group, self._owns_engine
             self.__dict__.pop("_engine")
             if owns:
@@ -378,6 +390,8 @@ class CloudPair:
         new.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_engine"})
         new.clouds = (self.clouds[0], reconst_cloud)
         new._estimated = [self._estimated[0], False]
+        new._carried = [False, False]                    # (cloud 0's, if carried, came from the cloud that is leaving: the library
+        #                                                   drops them with it, and the next consumer carries from the new one)
         new._colours_on_device = [self._colours_on_device[0], False]
         new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
         new._selections, new._sel_wanted = {}, []
@@ -437,6 +451,7 @@ class CloudPair:
         # (and so do the angular columns, which compare each point's normal with its matched point's)
         if hasattr(eng, "nn_want_idx"):
             eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or self.__dict__.get("_ssim", False)
+                            or self.__dict__.get("_carry_normals", False)      # (the carry reads both directions' matched rows)
                             or any(_has_colors(c) for c in self.clouds))
 
     def _colours_for_ties(self) -> None:
@@ -634,11 +649,26 @@ class CloudPair:
         return self._idx_cache[direction]
 
     def _normals_ready(self, which: int) -> bool:
-        return self._estimated[which] or _has_normals(self.clouds[which])
+        return self._estimated[which] or self._carried[which] or _has_normals(self.clouds[which])
 
     def _require_normals(self, which: int) -> None:
         if self._normals_ready(which):
             return
+        if self._carry_normals:
+            # the other cloud's normals, given or estimated as below, carried over (with none on either cloud: cloud 0's)
+            other = 1 - which
+            if not self._normals_ready(other):
+                self._estimate(0)
+                if which == 0:
+                    return                          # (cloud 1 takes them over when somebody needs its normals)
+            self._engine.carry_normals(other)                            # stays in HBM; inputs are not touched
+            self._carried[which] = True
+            self._graph_id = None                                        # device buffers changed
+            self._update_fusion()
+            return
+        self._estimate(which)
+
+    def _estimate(self, which: int) -> None:
         if not (self._estimate_normals and hasattr(self._engine, "estimate_normals")):
             raise ValueError(
                 f"cloud {which} has no normals: point-to-plane metrics need them "
@@ -683,7 +713,7 @@ class CloudPair:
     def get_normals(self, which: int):
         """np.asarray(clouds[which].normals), tagged for the fused projection (metric.py:92-98)."""
         self._require_normals(which)
-        if self._estimated[which]:
+        if self._estimated[which] or self._carried[which]:
             host = self._engine.get_normals(which)
         else:
             host = np.asarray(_host_rows(self.clouds[which].normals))
@@ -924,7 +954,7 @@ class CloudPair:
                     self._require_normals(other)
                 except ValueError:
                     continue          # surfaces when the column is evaluated
-                n_other = self._engine.n_iter(nat.DIR_RIGHT if other else nat.DIR_LEFT) if self._estimated[other] \
+                n_other = self._engine.n_iter(nat.DIR_RIGHT if other else nat.DIR_LEFT) if self._estimated[other] or self._carried[other] \
                     else len(self.clouds[other].normals)
                 if self.normal_index == "row" and eng.n_iter(direction) > n_other:
                     continue      # row-indexed normals out of range (the WHOLE cloud decides, so that every rank of a

@@ -314,6 +314,21 @@ static int upload(pccm_ctx *ctx, const void *src, size_t bytes, int on_device, c
     return PCCM_OK;
 }
 
+// Carried normals (pccm_carry_normals) do not outlive what they were made from: cloud `which` is getting new points
+// (points: both clouds enter a carry) or new normals -- the other cloud's normals go if they were carried from them; a target
+// whose normals are being replaced is an ordinary cloud again.
+static void carry_drop(pccm_ctx *ctx, int which, bool points)
+{
+    const int to = ctx->carry.to;
+    if (to < 0) return;
+    ctx->carry.to = -1;
+    if (to == which && !points) return;
+    Cloud &t = ctx->cloud[to];
+    t.n_nrm = 0;
+    t.nrm_exact32 = false;
+    t.ssim_attrs &= ~PCCM_SSIM_NORMAL;
+}
+
 // upload + widening copy + validation of one cloud's normals on stream `st` (staging buffer `stage` for host sources)
 static int ingest_normals(pccm_ctx *ctx, Cloud &c, int which, const void *nrm, int64_t n, int dtype, int on_device, hipStream_t st, DevBuf &stage)
 {
@@ -494,7 +509,7 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->ssim_scratch,                      &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
+                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
     for (DevBuf *b : bufs) free_buf(*b);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
@@ -526,6 +541,7 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     if (dtype != PCCM_F32 && dtype != PCCM_F64) return fail(PCCM_E_ARG, "dtype must be PCCM_F32 or PCCM_F64");
     Cloud &c = ctx->cloud[which];
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    carry_drop(ctx, which, true);                    // (normals carried to or from this cloud belong to the old points)
     drop_cloud(c);                                   // its normals and colours go with it
     ctx->p2d_k = 0;                                  // (both point-to-distribution columns depend on either cloud)
     ctx->p2d_color = false;
@@ -590,6 +606,7 @@ int pccm_set_normals(pccm_ctx *ctx, int which, const void *nrm, int64_t n, int d
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending D2 reductions used the old normals
     ctx->epoch++;
+    carry_drop(ctx, which, false);
     c.n_nrm = 0;
     c.nrm_exact32 = false;
     c.nrm_deferred = false;
@@ -612,6 +629,7 @@ int pccm_set_normals_deferred(pccm_ctx *ctx, int which, const void *nrm, int64_t
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;
     ctx->epoch++;
+    carry_drop(ctx, which, false);
     c.nrm_exact32 = false;
     c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
     int rc = grow((void **)&c.nrm64, c.cap_nrm, (size_t)n * 3 * sizeof(double));
@@ -985,7 +1003,9 @@ int pccm_estimate_normals(pccm_ctx *ctx, int which, int knn)
     NOT_CAPTURING(ctx);
     if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
     ctx->nrm_gen++;
-    return estimate_normals(ctx, which, knn);
+    const int rc = estimate_normals(ctx, which, knn);
+    if (rc != PCCM_E_ARG && rc != PCCM_E_STATE) carry_drop(ctx, which, false);      // (those two come before the normals are touched)
+    return rc;
 }
 
 int pccm_get_normals(pccm_ctx *ctx, int which, double *out)
@@ -999,6 +1019,55 @@ int pccm_get_normals(pccm_ctx *ctx, int which, double *out)
     if (c.n_nrm <= 0) return fail(PCCM_E_STATE, "cloud %d has no normals", which);
     { int rcd = d2h(ctx, out, c.nrm64, (size_t)c.n_nrm * 3 * sizeof(double)); if (rcd) return rcd; }
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
+}
+
+int pccm_carry_normals(pccm_ctx *ctx, int from, int *built)
+{
+    CHECK_CTX(ctx);
+    if (built) *built = 0;
+    if (from != 0 && from != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    const int to = 1 - from;
+    Cloud &cf = ctx->cloud[from], &ct = ctx->cloud[to];
+    if (cf.n <= 0 || ct.n <= 0) return fail(PCCM_E_STATE, "carrying normals needs both clouds");
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "carrying normals needs whole clouds on this GPU (world = 1)");
+    if (ctx->ties != PCCM_TIES_PICK) return fail(PCCM_E_STATE, "carrying normals is not defined under PCCM_TIES_MEAN");
+    if (!ctx->capturing) { int rcn = normals_ready(ctx, cf); if (rcn) return rcn; }
+    if (cf.n_nrm != cf.n || cf.nrm_deferred) return fail(PCCM_E_STATE, "cloud %d has no normal for every point to carry over", from);
+    const int dir_f = from == 0 ? PCCM_DIR_LEFT : PCCM_DIR_RIGHT, dir_g = from == 0 ? PCCM_DIR_RIGHT : PCCM_DIR_LEFT;
+    NNResult &rf = ctx->nn[dir_f], &rg = ctx->nn[dir_g];
+    if (!rf.valid || !rg.valid) return fail(PCCM_E_STATE, "carrying normals needs the results of both directional searches (pccm_nn_pair)");
+    if (rf.ties != PCCM_TIES_PICK || rg.ties != PCCM_TIES_PICK)
+        return fail(PCCM_E_STATE, "the searches ran under PCCM_TIES_MEAN: carrying normals is not defined there");
+    if (ctx->carry.to == to && ct.n_nrm == ct.n && ctx->carry.run_f == ctx->nn_run[dir_f] && ctx->carry.run_g == ctx->nn_run[dir_g])
+        return PCCM_OK;                                // (what is there already needs no work, and may be asked for while capturing)
+    if (ctx->capturing) {
+        ctx->capture_failed = true;
+        return fail(PCCM_E_STATE, "normals are carried before graph capture");
+    }
+    int rc;
+    if ((rc = ensure_plain(ctx, rf, true)) || (rc = ensure_plain(ctx, rg, true))) return rc;     // (repeats a search that left the rows out)
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = grow((void **)&ct.nrm64, ct.cap_nrm, (size_t)ct.n * 3 * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(cf.n, ct.n)))) return rc;
+    carry_drop(ctx, to, false);                        // (normals carried the other way were made from the ones being replaced)
+    ct.n_nrm = ct.n;
+    ct.nrm_exact32 = false;
+    ct.nrm_deferred = false;
+    ct.nrm_host = nullptr;
+    ct.ssim_attrs &= ~PCCM_SSIM_NORMAL;
+    rf.form.fused = -1;                                // (a projection the search fused took cloud `to`'s earlier normals)
+    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending D2 reductions would use stale normals
+    ctx->epoch++;
+    ctx->nrm_gen++;
+    if ((rc = launch_carry(ctx, rf.idx, rg.idx, cf.nrm64, cf.n, ct.n, (uint32_t *)ctx->carry_ws.p, ct.nrm64))) {
+        ct.n_nrm = 0;
+        return rc;
+    }
+    ctx->carry.to = to;
+    ctx->carry.run_f = ctx->nn_run[dir_f];
+    ctx->carry.run_g = ctx->nn_run[dir_g];
+    if (built) *built = 1;
     return PCCM_OK;
 }
 
@@ -1121,6 +1190,7 @@ static int prepare_nn(pccm_ctx *ctx, int dir, int *trivial)
     NNResult &res = ctx->nn[dir];
     res.valid = false;
     ctx->nn_gen[dir]++;
+    ctx->nn_run[dir]++;
     shard_of(it->n, ctx->shard_rank[dir], ctx->shard_world[dir], &res.begin, &res.end);
     const int64_t ns = res.end - res.begin;
     if (ctx->capturing) {
@@ -2495,6 +2565,7 @@ int pccm_ctx_reset(pccm_ctx *ctx)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     ctx->io_staged = false;                            // (the next owner of the context says what it wants)
     ctx->ties = PCCM_TIES_PICK;
+    ctx->carry.to = -1;
     for (int k = 0; k < 2; ++k) {
         drop_cloud(ctx->cloud[k]);
         ctx->cloud[k].version++;

@@ -305,6 +305,16 @@ struct pccm_ctx {
     } tie[2], tie_rows;                   // tie_rows: the whole iterating cloud, from caller-supplied rows (sharded colours)
     pccm::DevBuf tie_list;                // queries left to the exact scan (k_tie_mean_scan): [0] count, then shard rows
     uint64_t nrm_gen = 1;                 // bumped whenever any normals change
+    // pccm_carry_normals: cloud `to` holds normals carried over from the other cloud (-1: neither does), made from the searches
+    // whose run counts (nn_run) are run_f (the direction that iterates the source cloud) and run_g; whatever changes either cloud's
+    // points or the source cloud's normals drops them (carry_drop, pccm_api.hip)
+    struct Carry {
+        int to = -1;
+        uint64_t run_f = 0, run_g = 0;
+    } carry;
+    uint64_t nn_run[3] = {0, 0, 0};       // searches of each direction so far (prepare_nn): which RESULT a direction holds -- nn_gen
+                                          // also moves when normals or features change under a result that stays
+    pccm::DevBuf carry_ws;                // pccm_carry_normals: header, counts, fills, segment starts, row lists, long-list queue
     // scratch
     pccm::DevBuf part_b1, part_g, part_b2, val, stats, staging, counters;
     pccm::DevBuf rescan_part;             // k2b_fallback's split regime: partial minima per (query, workgroup)
@@ -546,6 +556,22 @@ struct PointJob {
     int metric, normal_mode;
     double *val;                // [ns], or [ns][3] (PCCM_METRIC_D1)
 };
+// Internal job kinds of k_point_jobs (never a PCCM_METRIC_* of include/pccm.h): the passes of pccm_carry_normals, which averages the
+// source cloud's normals over the rows that matched each target row, in ascending row order (integer atomics only: where a list
+// lands is arbitrary, the order it is summed in is not).  Such a job reads the PointJob fields as
+//   idx: nn_F [n_from] (matched rows of the direction that iterates the source cloud)   inrm: nn_G [n_to], as int32
+//   nrm: the source normals [n_from][3]     val: the target normals [n_to][3]     q_begin: n_from     normal_mode: n_to
+//   c64: the workspace (uint32 words; written): [0] segment cursor, [1] queue length, [2..3] -, then cnt[n_to], fill[n_to],
+//        base[n_to], list[n_from], queue[n_from / (kCarryLong + 1) + 1]
+// kCarryCount (rows: n_from) counts; kCarryPlace (n_to) gives every list of 1..kCarryLong rows a segment of `list` and queues the
+// longer ones; kCarryScatter (n_from) fills the segments; kCarrySum (n_to) sums the short lists and copies the fallback rows;
+// kCarryWalk (64 lanes per possible queue entry) sums one queued list per wave by walking nn_F in row order.  Every pass takes
+// whole waves: the launcher pads the row counts to multiples of 64.
+constexpr int kCarryCount = 64, kCarryPlace = 65, kCarryScatter = 66, kCarrySum = 67, kCarryWalk = 68;
+// Lists of up to kCarryLong rows are summed by one lane that picks the next larger row kCarryLong times over (<= kCarryLong^2
+// loads of a segment the L2 holds); longer ones cost one wave a walk over all n_from rows each, and there are at most
+// n_from / kCarryLong of them.  128: the lane's worst case stays at 16 K loads, the walks' at n_from^2 / 8192 row reads.
+constexpr int kCarryLong = 128;
 struct PointJobs {
     PointJob j[4];
     int njobs;
@@ -585,6 +611,10 @@ struct UnitJobs {
 int rescan_jobs(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Cloud *const *ses, NNResult *const *ress, bool self, RescanJobs *out);
 constexpr unsigned kRescanCap = 512;   // most workgroups that ever share one job's list (sizes the split regime's partials)
 int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs);
+size_t carry_ws_bytes(int64_t n_from, int64_t n_to);
+// the passes of pccm_carry_normals on the stream (the caller has checked everything and sized ws: carry_ws_bytes)
+int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
+                 uint32_t *ws, double *out);
 // result records -> plain columns (q32 / row0: the iterating cloud's rows, for records of layout 1)
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2);
 // *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when

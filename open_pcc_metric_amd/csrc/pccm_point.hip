@@ -192,6 +192,188 @@ __device__ __forceinline__ void point_row(const PointJob &J, int64_t i)
 }
 
 // ------------------------------------------------------------------------------------------
+// The passes of pccm_carry_normals (kCarry*, pccm_internal.h), hosted by k_point_jobs as job kinds of their own: one call per
+// row, behind a branch at the kernel's entry, so that the columns' path above holds none of this.
+// ------------------------------------------------------------------------------------------
+struct CarryView {
+    const int32_t *nn_f, *nn_g;
+    const double *src;
+    double *out;
+    int64_t n_from, n_to;
+    uint32_t *head, *cnt, *fill, *base, *list, *queue;
+};
+
+__device__ __forceinline__ CarryView carry_view(const int32_t *nn_f, const int32_t *nn_g, const double *src, double *out, uint32_t *ws,
+                                                 int64_t n_from, int64_t n_to)
+{
+    CarryView V;
+    V.nn_f = nn_f;
+    V.nn_g = nn_g;
+    V.src = src;
+    V.out = out;
+    V.n_from = n_from;
+    V.n_to = n_to;
+    V.head = ws;
+    V.cnt = V.head + 4;
+    V.fill = V.cnt + V.n_to;
+    V.base = V.fill + V.n_to;
+    V.list = V.base + V.n_to;
+    V.queue = V.list + V.n_from;
+    return V;
+}
+
+__device__ __forceinline__ double lane_value(double v, int lane)      // v of `lane` (wave-uniform), in every lane
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// (the job's fields come by value: a reference would make the kernel keep a copy of the job on the stack)
+__device__ __noinline__ void carry_row(const int32_t *nn_f, const int32_t *nn_g, const double *src, double *out, uint32_t *ws, int64_t n_from,
+                                       int64_t n_to, int kind, int64_t i)
+{
+    const CarryView V = carry_view(nn_f, nn_g, src, out, ws, n_from, n_to);
+    const int lane = threadIdx.x & 63;
+    if (kind == kCarryCount) {
+        // one atomic per distinct target in the wave, not one per row: a target cloud of a few points would otherwise put
+        // every row's add on the same few words
+        int32_t j = -1;
+        if (i < V.n_from) {
+            j = V.nn_f[i];
+            if (j < 0 || (int64_t)j >= V.n_to) j = -1;                  // (no search writes such a row)
+        }
+        unsigned long long todo = __ballot(j >= 0);
+        while (todo) {
+            const int lead = __ffsll((long long)todo) - 1;
+            const int32_t jl = __builtin_amdgcn_readlane(j, lead);
+            const unsigned long long same = __ballot(j == jl);
+            if (lane == lead) atomicAdd(&V.cnt[jl], (uint32_t)__popcll(same));
+            todo &= ~same;
+        }
+        return;
+    }
+    if (kind == kCarryPlace) {
+        // segments for the lists of 1..kCarryLong rows: the wave's lengths are scanned, one lane moves the cursor
+        const uint32_t m = i < V.n_to ? V.cnt[i] : 0u;
+        const uint32_t len = m <= (uint32_t)kCarryLong ? m : 0u;
+        uint32_t incl = len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(incl, off);
+            if (lane >= off) incl += o;
+        }
+        const uint32_t total = __shfl(incl, 63);
+        uint32_t start = 0;
+        if (lane == 0 && total) start = atomicAdd(&V.head[0], total);
+        start = __shfl(start, 0);
+        if (i < V.n_to) V.base[i] = start + incl - len;
+        if (m > (uint32_t)kCarryLong) V.queue[atomicAdd(&V.head[1], 1u)] = (uint32_t)i;
+        return;
+    }
+    if (kind == kCarryScatter) {
+        if (i >= V.n_from) return;
+        const int32_t j = V.nn_f[i];
+        if (j < 0 || (int64_t)j >= V.n_to) return;
+        const uint32_t m = V.cnt[j];
+        if (m > (uint32_t)kCarryLong) return;                           // (the walk finds these rows itself)
+        const uint32_t p = atomicAdd(&V.fill[j], 1u);
+        if (p < m) V.list[V.base[j] + p] = (uint32_t)i;
+        return;
+    }
+    if (kind == kCarrySum) {
+        if (i >= V.n_to) return;
+        const uint32_t m = V.cnt[i];
+        if (m > (uint32_t)kCarryLong) return;
+        double *o = V.out + 3 * i;
+        if (m == 0) {                                                   // nobody's nearest neighbour: its own nearest row's normal
+            int64_t r = V.nn_g[i];
+            r = r < 0 ? 0 : (r >= V.n_from ? V.n_from - 1 : r);
+            o[0] = V.src[3 * r]; o[1] = V.src[3 * r + 1]; o[2] = V.src[3 * r + 2];
+            return;
+        }
+        const uint32_t *seg = V.list + V.base[i];
+        double s0, s1, s2;
+        if (m <= 2) {                                                   // (a two-term sum is the same either way round)
+            const double *a = V.src + 3 * (int64_t)seg[0];
+            s0 = a[0]; s1 = a[1]; s2 = a[2];
+            if (m == 2) {
+                const double *b = V.src + 3 * (int64_t)seg[1];
+                s0 = __dadd_rn(s0, b[0]); s1 = __dadd_rn(s1, b[1]); s2 = __dadd_rn(s2, b[2]);
+            }
+        } else {
+            // ascending rows without a private array: the smallest row above the last one, m times
+            int64_t last = -1;
+            s0 = s1 = s2 = 0.0;
+            for (uint32_t r = 0; r < m; ++r) {
+                int64_t next = INT64_MAX;
+                for (uint32_t t = 0; t < m; ++t) {
+                    const int64_t v = (int64_t)seg[t];
+                    next = (v > last && v < next) ? v : next;
+                }
+                if (next == INT64_MAX) break;                           // (rows of a list are distinct: never taken)
+                const double *a = V.src + 3 * next;
+                if (r == 0) { s0 = a[0]; s1 = a[1]; s2 = a[2]; }
+                else { s0 = __dadd_rn(s0, a[0]); s1 = __dadd_rn(s1, a[1]); s2 = __dadd_rn(s2, a[2]); }
+                last = next;
+            }
+        }
+        const double dm = (double)m;
+        o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
+        return;
+    }
+    // kCarryWalk: wave i / 64 takes one queued target and walks nn_F in row order, 64 rows a step (four steps' rows are loaded
+    // ahead); the lanes whose row matched hold its normal, and the sum takes them in lane order -- ascending rows -- in every
+    // lane alike
+    const int64_t w = i >> 6;
+    if (w >= (int64_t)V.head[1]) return;                                // (wave-uniform)
+    const int32_t j = (int32_t)V.queue[w];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    bool first = true;
+    for (int64_t r0 = 0; r0 < V.n_from; r0 += 256) {                   // four steps' rows in flight, then two steps' normals at a time
+        int32_t got[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int64_t r = r0 + 64 * c + lane;
+            got[c] = r < V.n_from ? V.nn_f[r] : -1;                     // (j >= 0: a row past the end never matches)
+        }
+#pragma unroll
+        for (int h = 0; h < 4; h += 2) {
+            if (!__ballot(got[h] == j || got[h + 1] == j)) continue;
+            double a[2][3];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int64_t r = r0 + 64 * (h + c) + lane;
+                a[c][0] = a[c][1] = a[c][2] = 0.0;
+                if (got[h + c] == j) { a[c][0] = V.src[3 * r]; a[c][1] = V.src[3 * r + 1]; a[c][2] = V.src[3 * r + 2]; }
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                unsigned long long mask = __ballot(got[h + c] == j);
+                if (mask == ~0ull && !first) {
+#pragma unroll
+                    for (int b = 0; b < 64; ++b) {
+                        s0 = __dadd_rn(s0, lane_value(a[c][0], b)); s1 = __dadd_rn(s1, lane_value(a[c][1], b)); s2 = __dadd_rn(s2, lane_value(a[c][2], b));
+                    }
+                    continue;
+                }
+                while (mask) {
+                    const int b = __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    const double v0 = lane_value(a[c][0], b), v1 = lane_value(a[c][1], b), v2 = lane_value(a[c][2], b);
+                    if (first) { s0 = v0; s1 = v1; s2 = v2; first = false; }
+                    else { s0 = __dadd_rn(s0, v0); s1 = __dadd_rn(s1, v1); s2 = __dadd_rn(s2, v2); }
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        const double dm = (double)V.cnt[j];
+        double *o = V.out + 3 * (int64_t)j;
+        o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // K5 (k_unit_jobs below): per 128-row leaf, eight lanes accumulate rows k, k+8, k+16, ... in order and
 // the eight accumulators are combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) -- exactly NumPy's
 // pairwise-sum leaf, so that np.sum's tree can be finished bit for bit (pccm_finish_sum / pccm_reduce_total).
@@ -209,6 +391,12 @@ __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
 #pragma unroll
     for (int k = 1; k < 4; ++k)
         if (k < jobs.njobs && i0 >= jobs.off[k]) jb = k;
+    if (jobs.j[jb].metric >= kCarryCount) {                 // pccm_carry_normals' passes: launches of their own, whole waves each
+        const PointJob &C = jobs.j[jb];                     // (the fields as a carry job reads them: pccm_internal.h)
+        carry_row(C.idx, reinterpret_cast<const int32_t *>(C.inrm), C.nrm, C.val, reinterpret_cast<uint32_t *>(const_cast<double *>(C.c64)),
+                  C.q_begin, (int64_t)C.normal_mode, C.metric, i0 - jobs.off[jb]);
+        return;
+    }
     point_row(jobs.j[jb], i0 - jobs.off[jb]);
 }
 
@@ -218,6 +406,49 @@ int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs)
     if (total <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_POINT);
     PCCM_LAUNCH(ctx, k_point_jobs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, jobs);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+size_t carry_ws_bytes(int64_t n_from, int64_t n_to)
+{
+    return (size_t)(4 + 3 * n_to + n_from + n_from / (kCarryLong + 1) + 1) * sizeof(uint32_t);
+}
+
+// pccm_carry_normals on the stream: counts and cursors zeroed, then count | place | scatter + walk | sum (kCarry*, pccm_internal.h);
+// the walk rides with the scatter (it reads neither the lists nor anything the sum writes: the sum leaves the queued rows alone)
+int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
+                 uint32_t *ws, double *out)
+{
+    ProfScope ps(ctx, PCCM_K_POINT);
+    PCCM_HIP(hipMemsetAsync(ws, 0, (size_t)(4 + 2 * n_to) * sizeof(uint32_t), ctx->stream));     // header, cnt, fill
+    PointJob P = {};
+    P.idx = nn_f;
+    P.inrm = reinterpret_cast<const double *>(nn_g);
+    P.nrm = n_from64;
+    P.val = out;
+    P.q_begin = n_from;
+    P.normal_mode = (int)n_to;
+    P.c64 = reinterpret_cast<const double *>(ws);
+    auto pad = [](int64_t rows) { return (rows + 63) / 64 * 64; };
+    const int64_t walk_lanes = (n_from / (kCarryLong + 1)) * 64;       // one wave per list that can be long
+    const int kinds[4] = {kCarryCount, kCarryPlace, kCarryScatter, kCarrySum};
+    const int64_t rows[4] = {pad(n_from), pad(n_to), pad(n_from), pad(n_to)};
+    for (int k = 0; k < 4; ++k) {
+        PointJobs pj = {};
+        pj.njobs = 1;
+        pj.j[0] = P;
+        pj.j[0].metric = kinds[k];
+        pj.off[1] = rows[k];
+        if (kinds[k] == kCarryScatter && walk_lanes > 0) {
+            pj.njobs = 2;
+            pj.j[1] = P;
+            pj.j[1].metric = kCarryWalk;
+            pj.off[2] = pj.off[1] + walk_lanes;
+        }
+        for (int r = pj.njobs; r < 4; ++r) pj.off[r + 1] = pj.off[pj.njobs];
+        PCCM_LAUNCH(ctx, k_point_jobs, dim3((unsigned)((pj.off[pj.njobs] + 255) / 256)), dim3(256), 0, ctx->stream, pj);
+    }
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

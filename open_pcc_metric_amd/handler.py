@@ -2,7 +2,7 @@
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
-                                  [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--csv]
+                                  [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -25,7 +25,12 @@ also the maximum -- Mahalanobis distance of each point to the distribution of it
 cloud ("Point-to-distribution").  ``--p2d-color`` (with ``--point-to-distribution``; a usage error without it)
 adds, after those, the colour and joint rows after Javaheri et al. (IEEE MMSP 2021): each point's luma against the luma
 distribution of the same neighbourhood, and sqrt(geometry^2 + colour^2) per point, pooled like the geometry rows; both clouds need
-colours ("Point-to-distribution: colour and joint").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+colours ("Point-to-distribution: colour and joint").  ``--carry-normals`` (no counterpart in the reference) gives
+a file WITHOUT normals the other file's normals instead of estimated ones, as the MPEG evaluation procedure does for a decoded
+cloud (``pc_error``'s normal carrying): each point takes the average of the normals of the other cloud's points whose nearest
+neighbour it is, or its own nearest point's normal when it is nobody's ("Carried normals").  The MPEG-style D2 is
+``--point-to-plane --normal-index neighbour --carry-normals``; no default changes, and ``--ties mean`` with it is a usage
+error.  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -65,6 +70,11 @@ import click
               help="With --point-to-distribution: report its colour rows (each point's luma against the luma distribution of the "
                    "same nearest points) and joint geometry-and-colour rows as well, after all other rows.  Both clouds need "
                    "colours.")
+@click.option("--carry-normals", "carry_normals", required=False, is_flag=True,
+              help="A cloud without normals takes the other cloud's instead of estimated ones, as MPEG's pc_error does for a "
+                   "decoded cloud: per point the average normal of the other cloud's points whose nearest neighbour it is, or its "
+                   "own nearest point's normal.  With normals in neither file the original's are estimated and carried over.  "
+                   "MPEG-style D2: --point-to-plane --normal-index neighbour --carry-normals.  Not with --ties mean.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -79,11 +89,12 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, csv, device, engine, normal_index, extent, tie_exposure, ties) -> None:
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, csv, device, engine, normal_index, extent, tie_exposure,
+        ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import (CalculateOptions, check_hausdorff_rank, check_p2d_color, check_point_ssim,
+    from .options import (CalculateOptions, check_carry_normals, check_hausdorff_rank, check_p2d_color, check_point_ssim,
                           check_point_to_distribution, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
@@ -91,6 +102,7 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
                                    point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None,
                                    point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours,
                                    p2d_color=p2d_color)
+        check_carry_normals(carry_normals, ties=ties)
     except ValueError as exc:
         raise click.UsageError(str(exc))
     check_hausdorff_rank(options)
@@ -105,7 +117,8 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
             # (clouds read from files are freed while the GPU context works on -- with several decoded clouds, when the next one
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)
             cloud_pair = CloudPair(ocloud_cloud, pcloud_cloud, device=device, nn_engine=engine, normal_index=normal_index,
-                                   extent=list(extent) if extent else None, staged_io=True, ties=ties)
+                                   extent=list(extent) if extent else None, staged_io=True, ties=ties,
+                                   carry_normals=carry_normals)
         else:
             cloud_pair = cloud_pair.with_reconst(pcloud_cloud)     # the original cloud stays in HBM with all that belongs to it
         calculator = MetricCalculator(cloud_pair)

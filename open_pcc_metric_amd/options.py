@@ -150,6 +150,18 @@ def check_point_to_distribution(options: CalculateOptions, *, group=None) -> Non
         raise ValueError("point-to-distribution rows are not available for sharded pairs (group=)")
 
 
+def check_carry_normals(carry_normals: bool, *, ties: str = "pick", group=None) -> None:
+    """The ValueErrors of ``CloudPair(..., carry_normals=True)`` (the command line turns them into usage errors): the carried
+    normal averages over matched rows, which ``ties="mean"`` replaces by virtual neighbours, and it needs both whole clouds and
+    both searches on one GPU (include/pccm.h, pccm_carry_normals)."""
+    if not carry_normals:
+        return
+    if ties != "pick":
+        raise ValueError("carry_normals is not defined under ties='mean' (the carried normal averages over matched rows)")
+    if group is not None:
+        raise ValueError("carry_normals needs whole clouds on one GPU: it cannot be combined with group=")
+
+
 def check_p2d_color(options: CalculateOptions, origin_cloud, reconst_cloud, *, group=None) -> None:
     """Raise ``ValueError`` when the colour and joint point-to-distribution rows ``options`` asks for cannot be computed for this
     pair -- before any GPU work (the command line calls it for every cloud it processes; CloudPair checks the same before any GPU
