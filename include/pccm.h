@@ -179,6 +179,37 @@ int pccm_get_normals(pccm_ctx *ctx, int which, double *out);
  * PCCM_E_ARG: from is not 0 or 1.  PCCM_E_STATE: a cloud is missing; cloud `from` has no normal for every row (announced normals
  * are uploaded first); either directional search has no result; a sharded context; PCCM_TIES_MEAN; a build during graph capture. */
 int pccm_carry_normals(pccm_ctx *ctx, int from, int *built);
+/* Merge the rows of cloud `which` that share their coordinates, in place on the device, the way MPEG's pc_error treats both clouds
+ * before any metric (dropDuplicates).  The key of a row is its three fp64 coordinates as stored (an fp32 upload widened exactly),
+ * compared with == per component: -0.0 equals +0.0, nothing is quantised or shifted, and two points one ulp apart in one coordinate
+ * are distinct.  Rows with equal keys form a group i_1 < ... < i_m with representative i_1.  The merged cloud has one row per group
+ * in ascending order of representative (a stable compaction, n' rows); each row holds
+ *   the representative's coordinates, bit for bit (its -0.0 survives);
+ *   its normal bit for bit, in both modes, when the cloud has one normal per point;
+ *   when the cloud has colours: PCCM_DUP_DROP the representative's colour bit for bit; PCCM_DUP_AVERAGE per component in fp64
+ *   s = c[i_1], then s = s + c[i_r] for r = 2..m, every add rounded separately, and the result s / (double)m, one correctly rounded
+ *   division (m = 1 gives the colour back bit for bit) -- the convention of pccm_carry_normals.
+ * pccm_get_merge_map returns map[i] = the merged row of original row i's group (n entries; multiplicities and representatives
+ * follow from it).  The operation follows pc_error's; parity with that program is NOT pinned: it is not available to this
+ * project's tests and it averages in its own arithmetic.
+ * A cloud without duplicates (n' == n) is left untouched: no array is rewritten, no result goes stale, the map is the identity.
+ * Otherwise the context is in the state pccm_set_cloud(which, merged, n', PCCM_F64, on_device) followed by pccm_set_normals /
+ * pccm_set_colors with the merged arrays would have left: search results of every direction that touches the cloud, carried
+ * normals in either direction, PointSSIM features, point-to-distribution columns, tie lists and pending reductions are gone and
+ * captured graphs are stale.  Announced normals (pccm_set_normals_deferred) are uploaded first.  *n_out (may be null) = n'.  The
+ * map stays on the device until the cloud gets new points or pccm_ctx_reset; for a cloud that was never merged pccm_get_merge_map
+ * returns the identity, and *n_before (may be null) = the rows the map has (`out` may be null to ask for it alone).  The call does
+ * not depend on the tie policy.
+ * pccm_get_points / pccm_get_colors copy the stored fp64 rows [n][3] out, as pccm_get_normals does.
+ * PCCM_E_ARG: which is not 0 or 1; mode is not PCCM_DUP_DROP or PCCM_DUP_AVERAGE.  PCCM_E_STATE: the cloud is missing; it has
+ * normals or colours whose count is neither 0 nor n; a sharded context; a call between pccm_graph_begin and pccm_graph_end;
+ * pccm_get_colors on a cloud without colours. */
+#define PCCM_DUP_DROP 1
+#define PCCM_DUP_AVERAGE 2
+int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out);
+int pccm_get_merge_map(pccm_ctx *ctx, int which, int32_t *out, int64_t *n_before);
+int pccm_get_points(pccm_ctx *ctx, int which, double *out);
+int pccm_get_colors(pccm_ctx *ctx, int which, double *out);
 
 /* PointSSIM features ("PointSSIM") of cloud `which`: per point p, N_k(p) = the k points of the same cloud first
  * in ascending (d2, row) order (p itself included; all of them when the cloud has fewer than k), and per attribute the variance

@@ -25,6 +25,7 @@ PATH_REDUCE = 3          # Engine.last_path: the last reduction batch
 ENGINES = {"auto": 0, "brute": 1, "grid": 2}
 NORMAL_MODES = {"row": 0, "neighbour": 1}
 TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
+DUPLICATES = {"drop": 1, "average": 2}  # PCCM_DUP_DROP / PCCM_DUP_AVERAGE
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
 METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
 # PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
@@ -41,6 +42,7 @@ KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_carry_normals",
+    "pccm_merge_duplicates", "pccm_get_merge_map", "pccm_get_points", "pccm_get_colors",
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
@@ -109,6 +111,10 @@ def load() -> ctypes.CDLL:
     lib.pccm_estimate_normals.argtypes = [vp, i32, i32]
     lib.pccm_get_normals.argtypes = [vp, i32, vp]
     lib.pccm_carry_normals.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    lib.pccm_merge_duplicates.argtypes = [vp, i32, i32, ctypes.POINTER(i64)]
+    lib.pccm_get_merge_map.argtypes = [vp, i32, vp, ctypes.POINTER(i64)]
+    lib.pccm_get_points.argtypes = [vp, i32, vp]
+    lib.pccm_get_colors.argtypes = [vp, i32, vp]
     lib.pccm_ssim_features.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_ssim_features.argtypes = [vp, i32, i32, vp]
     lib.pccm_p2d_build.argtypes = [vp, i32, ctypes.POINTER(i32)]
@@ -485,6 +491,39 @@ class Engine:
         built = ctypes.c_int32(0)
         _check(self._lib.pccm_carry_normals(self._ctx, int(from_which), ctypes.byref(built)))
         return bool(built.value)
+
+    def merge_duplicates(self, which: int, mode) -> int:
+        """Merge the rows of cloud ``which`` that share their coordinates, in place on the device (pccm_merge_duplicates: MPEG
+        pc_error's dropDuplicates).  ``mode``: "drop" (1) keeps the first row's colour, "average" (2) the group's average.  Returns
+        the number of rows left; normals and colours that were uploaded follow."""
+        if isinstance(mode, str) and mode not in DUPLICATES:
+            raise ValueError(f"duplicates mode {mode!r}: expected one of {sorted(DUPLICATES)}")
+        m = DUPLICATES[mode] if isinstance(mode, str) else mode      # (an integer goes to the library as it is)
+        n_out = ctypes.c_int64(0)
+        _check(self._lib.pccm_merge_duplicates(self._ctx, int(which), int(m), ctypes.byref(n_out)))
+        self.__dict__.get("_deferred", {}).pop(int(which), None)      # (announced normals were uploaded first)
+        if int(n_out.value) != self._n[which]:
+            self._n[which] = int(n_out.value)
+            self._p2d_k = 0               # (new points in either cloud drop both columns)
+        return int(n_out.value)
+
+    def get_merge_map(self, which: int) -> np.ndarray:
+        """For every row cloud ``which`` had before merge_duplicates, the merged row of its group (the identity if never merged)."""
+        nb = ctypes.c_int64(0)
+        _check(self._lib.pccm_get_merge_map(self._ctx, int(which), None, ctypes.byref(nb)))
+        out = np.empty(int(nb.value), dtype=np.int32)
+        _check(self._lib.pccm_get_merge_map(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p), None))
+        return out
+
+    def get_points(self, which: int) -> np.ndarray:
+        out = np.empty((self._n[which], 3), dtype=np.float64)
+        _check(self._lib.pccm_get_points(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def get_colors(self, which: int) -> np.ndarray:
+        out = np.empty((self._n[which], 3), dtype=np.float64)
+        _check(self._lib.pccm_get_colors(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def get_normals(self, which: int) -> np.ndarray:
         out = np.empty((self._n[which], 3), dtype=np.float64)

@@ -31,6 +31,13 @@ Differences from the reference, all deliberate:
   takes the average of the normals of the other cloud's points whose nearest neighbour it is, or -- nobody's nearest neighbour
   -- its own nearest point's normal.  With normals on both clouds the flag does nothing; with normals on neither, cloud 0's are
   estimated and carried to cloud 1.  Not available sharded or under ``ties="mean"`` (``ValueError``);
+* ``duplicates="drop"`` / ``"average"`` (default ``"keep"``: nothing changes) merges, on the GPU and before any search, the points
+  of each cloud that share their coordinates, as MPEG's ``pc_error`` does with both clouds (dropDuplicates; include/pccm.h,
+  pccm_merge_duplicates): one point per position in the order of first appearance, with the first point's normal and the first
+  point's colour (``"drop"``) or the group's average colour (``"average"``, pc_error's default).  Every row count, column and
+  report then belongs to the merged clouds; ``clouds`` stays the caller's objects, ``duplicates_removed`` says how many rows each
+  cloud lost and ``merge_map(which)`` where each original row went.  ``get_extent()`` still measures the given cloud 0: a convex
+  hull does not depend on multiplicities.  Not available sharded (``ValueError``);
 * ``use_graph=True`` lets ``recompute()`` replay the whole sweep + reductions of the previous report
   as one hipGraph launch (for callers that evaluate the same resident pair repeatedly).
 """
@@ -286,15 +293,17 @@ class CloudPair:
                  nn_engine: str = "auto", normal_index: str = "row", extent=None, group=None,
                  use_graph: bool = False, estimate_normals: bool = True, normals_knn: int = 30,
                  shard_mode: str = "direction", _engine=None, _uploads_first: bool = False,
-                 staged_io: typing.Optional[bool] = None, ties: str = "pick", carry_normals: bool = False):
+                 staged_io: typing.Optional[bool] = None, ties: str = "pick", carry_normals: bool = False,
+                 duplicates: str = "keep"):
         if normal_index not in nat.NORMAL_MODES:
             raise ValueError("normal_index must be 'row' or 'neighbour'")
         if not isinstance(ties, str) or ties not in nat.TIES:
             raise ValueError("ties must be 'pick' or 'mean'")
         if nn_engine not in nat.ENGINES:
             raise ValueError(f"nn_engine must be one of {sorted(nat.ENGINES)}")
-        from .options import check_carry_normals
+        from .options import check_carry_normals, check_duplicates
         check_carry_normals(carry_normals, ties=ties, group=group)       # (ValueError before any GPU work)
+        check_duplicates(duplicates, group=group)
         self.clouds = (origin_cloud, reconst_cloud)
         self.normal_index = normal_index
         self.nn_engine = nn_engine
@@ -304,6 +313,9 @@ class CloudPair:
         self._estimated = [False, False]
         self._carry_normals = bool(carry_normals)
         self._carried = [False, False]          # the cloud's normals were carried over from the other cloud (pccm_carry_normals)
+        self._duplicates = duplicates
+        self._merged = [False, False]           # the cloud lost rows to pccm_merge_duplicates: its arrays are the engine's, not the caller's
+        self.duplicates_removed = (0, 0)
         self._xchg, self._xchg_wanted = {}, []
         self._selections, self._sel_wanted = {}, []
         self._colours_on_device = [False, False]
@@ -324,6 +336,8 @@ class CloudPair:
         self._engine = _engine
         if self._carry_normals and not hasattr(_engine, "carry_normals"):
             raise ValueError("this engine cannot carry normals from one cloud to the other")
+        if duplicates != "keep" and not hasattr(_engine, "merge_duplicates"):
+            raise ValueError("this engine cannot merge duplicate points")
         if hasattr(_engine, "set_ties"):
             _engine.set_ties(ties)                # (every time: a pooled context comes back with the default, pccm_ctx_reset)
         elif ties != "pick":
@@ -345,7 +359,9 @@ class CloudPair:
         deferred = hasattr(_engine, "set_normals_deferred")
         for k, cloud in enumerate(self.clouds):
             _engine.set_cloud(k, cloud.points)
-            if _has_normals(cloud):
+            if duplicates != "keep":
+                self._merge_duplicates(k)                 # (its normals and colours go up now: the merge takes them along)
+            elif _has_normals(cloud):
                 (_engine.set_normals_deferred if deferred else _engine.set_normals)(k, cloud.normals)
         if shard_mode not in ("direction", "rows"):
             raise ValueError("shard_mode must be 'direction' or 'rows'")
@@ -379,7 +395,7 @@ class CloudPair:
             # (a sharded pair keeps nothing that pays: every rank would have to agree on what is resident)
             kw = dict(nn_engine=self.nn_engine, normal_index=self.normal_index, extent=self._extent, use_graph=self._use_graph,
                       estimate_normals=self._estimate_normals, normals_knn=self._normals_knn, ties=self.ties,
-                      carry_normals=self._carry_normals)
+                      carry_normals=self._carry_normals, duplicates=self._duplicates)
             group, owns = self._coll.group, self._owns_engine
             self.__dict__.pop("_engine")
             if owns:
@@ -393,6 +409,8 @@ class CloudPair:
         new._carried = [False, False]                    # (cloud 0's, if carried, came from the cloud that is leaving: the library
         #                                                   drops them with it, and the next consumer carries from the new one)
         new._colours_on_device = [self._colours_on_device[0], False]
+        new._merged = [self._merged[0], False]           # (cloud 0 stays merged and resident: only the new cloud 1 is merged)
+        new.duplicates_removed = (self.duplicates_removed[0], 0)
         new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
         new._selections, new._sel_wanted = {}, []
         new._graph_id, new._last_wanted = None, None
@@ -405,7 +423,9 @@ class CloudPair:
             eng.set_io_staged(True)                              # (the superseded cloud is about to be freed by its owner: see __init__)
         eng.set_cloud(1, reconst_cloud.points)               # (the library keeps cloud 0, everything it owns and its self search)
         deferred = hasattr(eng, "set_normals_deferred")
-        if _has_normals(reconst_cloud):
+        if new._duplicates != "keep":
+            new._merge_duplicates(1)
+        elif _has_normals(reconst_cloud):
             (eng.set_normals_deferred if deferred else eng.set_normals)(1, reconst_cloud.normals)
         new._update_fusion()
         new._colours_for_ties()
@@ -434,6 +454,26 @@ class CloudPair:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _merge_duplicates(self, which: int) -> None:
+        """``duplicates="drop" | "average"``: the cloud's normals and colours go up now, then its rows that share their coordinates
+        are merged on the device (pccm_merge_duplicates); every size comes from the engine afterwards."""
+        eng, cloud = self._engine, self.clouds[which]
+        before = eng.n_iter(nat.DIR_RIGHT if which else nat.DIR_LEFT)
+        if _has_normals(cloud):
+            eng.set_normals(which, cloud.normals)
+        if _has_colors(cloud):
+            self._upload_colours(which)
+        after = eng.merge_duplicates(which, self._duplicates)
+        self._merged[which] = after < before
+        removed = list(self.duplicates_removed)
+        removed[which] = before - after
+        self.duplicates_removed = tuple(removed)
+
+    def merge_map(self, which: int) -> np.ndarray:
+        """For every row of the given cloud ``which``, its row in the merged cloud the pair works on (``duplicates=``); the
+        identity when nothing was merged."""
+        return self._engine.get_merge_map(which).astype(np.int64)
 
     def _update_fusion(self) -> None:
         """Let the searches leave the D2 projection next to the distance (pccm_nn_fuse) for every direction whose
@@ -713,7 +753,7 @@ class CloudPair:
     def get_normals(self, which: int):
         """np.asarray(clouds[which].normals), tagged for the fused projection (metric.py:92-98)."""
         self._require_normals(which)
-        if self._estimated[which] or self._carried[which]:
+        if self._estimated[which] or self._carried[which] or self._merged[which]:
             host = self._engine.get_normals(which)
         else:
             host = np.asarray(_host_rows(self.clouds[which].normals))
@@ -723,7 +763,10 @@ class CloudPair:
 
     def _own_colours(self, which: int):
         """cloud_pair.py:114-118; tagged so that the colour metrics can recognise the pair's own rows."""
-        view = np.asarray(_host_rows(self.clouds[which].colors)).view(CloudColorsView)
+        if self._merged[which]:
+            view = self._engine.get_colors(which).view(CloudColorsView)      # (the merged rows: duplicates=)
+        else:
+            view = np.asarray(_host_rows(self.clouds[which].colors)).view(CloudColorsView)
         view._pccm_origin = (id(self), which)
         return view
 
@@ -733,16 +776,19 @@ class CloudPair:
     def get_right_colors(self):
         return self._own_colours(1)
 
+    def _upload_colours(self, k: int) -> None:
+        cloud = self.clouds[k]
+        u8 = getattr(cloud, "colors_u8", None)
+        if u8 is not None and hasattr(self._engine, "set_colors_u8"):
+            self._engine.set_colors_u8(k, u8)        # file colours: 3 B/point up, the k / 255.0 redone on the device
+        else:
+            self._engine.set_colors(k, _host_rows(cloud.colors))
+        self._colours_on_device[k] = True
+
     def _ensure_colours(self) -> None:
-        for k, cloud in enumerate(self.clouds):
-            if self._colours_on_device[k]:
-                continue
-            u8 = getattr(cloud, "colors_u8", None)
-            if u8 is not None and hasattr(self._engine, "set_colors_u8"):
-                self._engine.set_colors_u8(k, u8)        # file colours: 3 B/point up, the k / 255.0 redone on the device
-            else:
-                self._engine.set_colors(k, _host_rows(cloud.colors))
-            self._colours_on_device[k] = True
+        for k in range(2):
+            if not self._colours_on_device[k]:
+                self._upload_colours(k)
 
     def _colour_rows_arg(self, direction: int):
         """Neighbour rows for the colour kernels: the context's own (None) unless the search was sharded."""
@@ -955,7 +1001,7 @@ class CloudPair:
                 except ValueError:
                     continue          # surfaces when the column is evaluated
                 n_other = self._engine.n_iter(nat.DIR_RIGHT if other else nat.DIR_LEFT) if self._estimated[other] or self._carried[other] \
-                    else len(self.clouds[other].normals)
+                    or self._merged[other] else len(self.clouds[other].normals)
                 if self.normal_index == "row" and eng.n_iter(direction) > n_other:
                     continue      # row-indexed normals out of range (the WHOLE cloud decides, so that every rank of a
                     #               sharded pair agrees): surfaces, on every rank, where the reference raises

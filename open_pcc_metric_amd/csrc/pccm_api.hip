@@ -69,9 +69,9 @@ int check_device_errors(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
     for (auto &s : ctx->slots) s.pending = false;
     for (auto &q : ctx->sel_slots) q.pending = false;
-    return fail(PCCM_E_STATE, "a search kernel reported an inconsistent state (device error word 0x%x: %s%s): the results of this search were "
+    return fail(PCCM_E_STATE, "a search kernel reported an inconsistent state (device error word 0x%x: %s%s%s): the results of this search were "
                               "dropped, run it again", e, (e & 1u) ? "the tail launch's wait for its own workgroups ran out; " : "",
-                (e & 2u) ? "a voxel brick contradicts its cell start" : "");
+                (e & 2u) ? "a voxel brick contradicts its cell start; " : "", (e & kErrMergeTable) ? "the duplicate table overflowed" : "");
 }
 
 static hipEvent_t take_event(pccm_ctx *ctx)
@@ -509,7 +509,7 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
+                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
     for (DevBuf *b : bufs) free_buf(*b);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
@@ -543,6 +543,7 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     carry_drop(ctx, which, true);                    // (normals carried to or from this cloud belong to the old points)
     drop_cloud(c);                                   // its normals and colours go with it
+    ctx->merge_n[which] = 0;                         // (the merge map, pccm_merge_duplicates, spoke of the old rows)
     ctx->p2d_k = 0;                                  // (both point-to-distribution columns depend on either cloud)
     ctx->p2d_color = false;
     // (a new cloud 1 leaves the self search of cloud 0 -- cloud_pair.py:108-109 -- as valid as it was: one reference cloud
@@ -1068,6 +1069,100 @@ int pccm_carry_normals(pccm_ctx *ctx, int from, int *built)
     ctx->carry.run_f = ctx->nn_run[dir_f];
     ctx->carry.run_g = ctx->nn_run[dir_g];
     if (built) *built = 1;
+    return PCCM_OK;
+}
+
+int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out)
+{
+    CHECK_CTX(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (mode != PCCM_DUP_DROP && mode != PCCM_DUP_AVERAGE) return fail(PCCM_E_ARG, "mode must be PCCM_DUP_DROP or PCCM_DUP_AVERAGE");
+    NOT_CAPTURING(ctx);
+    Cloud &c = ctx->cloud[which];
+    if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "merging duplicates needs the whole cloud on this GPU (world = 1)");
+    { int rcn = normals_ready(ctx, c); if (rcn) return rcn; }
+    if (c.n_nrm != 0 && c.n_nrm != c.n)
+        return fail(PCCM_E_STATE, "cloud %d has %lld points but %lld normals: rows cannot be merged", which, (long long)c.n, (long long)c.n_nrm);
+    if (c.n_rgb != 0 && c.n_rgb != c.n)
+        return fail(PCCM_E_STATE, "cloud %d has %lld points but %lld colours: rows cannot be merged", which, (long long)c.n, (long long)c.n_rgb);
+    const int64_t n = c.n;
+    int rc;
+    if ((rc = ensure(ctx, ctx->merge_ws, merge_ws_bytes(n)))) return rc;
+    const MergeLayout L = merge_layout(n);
+    double *wd = (double *)ctx->merge_ws.p;
+    if ((rc = launch_merge_find(ctx, c.xyz64, n, wd))) return rc;
+    uint32_t n_new = 0;
+    PCCM_HIP(hipMemcpyAsync(&n_new, wd + L.doubles, sizeof(n_new), hipMemcpyDeviceToHost, ctx->stream));
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_errors(ctx))) return rc;
+    if (n_new == 0 || (int64_t)n_new > n) return fail(PCCM_E_HIP, "merging duplicates counted %u groups in %lld rows", n_new, (long long)n);
+    if (n_out) *n_out = (int64_t)n_new;
+    if ((int64_t)n_new == n) return PCCM_OK;               // no duplicate: nothing is rewritten, nothing goes stale
+    // rows go: what was made from the old rows goes with them, exactly as for new points (pccm_set_cloud below) -- normals that
+    // were carried to this cloud among it
+    if (ctx->carry.to == which) carry_drop(ctx, which, true);
+    const bool has_nrm = c.n_nrm == n, has_rgb = c.n_rgb == n;
+    const double *rgb = has_rgb ? c.rgb64 : nullptr;
+    if (has_rgb && mode == PCCM_DUP_AVERAGE) {
+        // the carry's passes with nn_F := rep: per representative the colours of its group, summed in ascending row order
+        if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(n, n)))) return rc;
+        const int32_t *rep = (const int32_t *)((const uint32_t *)(wd + L.doubles) + L.rep);
+        if ((rc = launch_carry(ctx, rep, nullptr, c.rgb64, n, n, (uint32_t *)ctx->carry_ws.p, wd))) return rc;
+        rgb = wd;
+    }
+    if ((rc = ensure(ctx, ctx->merge_map[which], (size_t)n * sizeof(int32_t)))) return rc;
+    if ((rc = launch_merge_gather(ctx, c.xyz64, has_nrm ? c.nrm64 : nullptr, rgb, n, wd, (int32_t *)ctx->merge_map[which].p))) return rc;
+    // the merged rows enter the way any resident fp64 rows do (one ingest path: statistics, fp32 copies, invalidation)
+    if ((rc = pccm_set_cloud(ctx, which, wd + 3 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
+    if (has_nrm && (rc = pccm_set_normals(ctx, which, wd + 6 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
+    if (has_rgb && (rc = pccm_set_colors(ctx, which, wd + 9 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
+    ctx->merge_n[which] = n;
+    return PCCM_OK;
+}
+
+int pccm_get_merge_map(pccm_ctx *ctx, int which, int32_t *out, int64_t *n_before)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    const Cloud &c = ctx->cloud[which];
+    if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    const int64_t nb = ctx->merge_n[which] ? ctx->merge_n[which] : c.n;
+    if (n_before) *n_before = nb;
+    if (!out) return PCCM_OK;
+    if (!ctx->merge_n[which]) {                            // never merged: the identity
+        for (int64_t i = 0; i < nb; ++i) out[i] = (int32_t)i;
+        return PCCM_OK;
+    }
+    { int rcd = d2h(ctx, out, ctx->merge_map[which].p, (size_t)nb * sizeof(int32_t)); if (rcd) return rcd; }
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
+}
+
+int pccm_get_points(pccm_ctx *ctx, int which, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    const Cloud &c = ctx->cloud[which];
+    if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    { int rcd = d2h(ctx, out, c.xyz64, (size_t)c.n * 3 * sizeof(double)); if (rcd) return rcd; }
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
+}
+
+int pccm_get_colors(pccm_ctx *ctx, int which, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    const Cloud &c = ctx->cloud[which];
+    if (c.n_rgb <= 0) return fail(PCCM_E_STATE, "cloud %d has no colours", which);
+    { int rcd = d2h(ctx, out, c.rgb64, (size_t)c.n_rgb * 3 * sizeof(double)); if (rcd) return rcd; }
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
     return PCCM_OK;
 }
 
@@ -2567,6 +2662,7 @@ int pccm_ctx_reset(pccm_ctx *ctx)
     ctx->ties = PCCM_TIES_PICK;
     ctx->carry.to = -1;
     for (int k = 0; k < 2; ++k) {
+        ctx->merge_n[k] = 0;
         drop_cloud(ctx->cloud[k]);
         ctx->cloud[k].version++;
     }

@@ -315,6 +315,12 @@ struct pccm_ctx {
     uint64_t nn_run[3] = {0, 0, 0};       // searches of each direction so far (prepare_nn): which RESULT a direction holds -- nn_gen
                                           // also moves when normals or features change under a result that stays
     pccm::DevBuf carry_ws;                // pccm_carry_normals: header, counts, fills, segment starts, row lists, long-list queue
+                                          // (pccm_merge_duplicates' colour averages run the same passes through it)
+    // pccm_merge_duplicates: merge_map[k] holds, for each of the merge_n[k] rows cloud k had before its rows were merged, the merged
+    // row of its group (merge_n 0: never merged, the map is the identity); new points for the cloud and pccm_ctx_reset clear it
+    pccm::DevBuf merge_map[2];
+    int64_t merge_n[2] = {0, 0};
+    pccm::DevBuf merge_ws;                // ... its workspace (merge_layout): averaged colours, merged rows, group table, scan words
     // scratch
     pccm::DevBuf part_b1, part_g, part_b2, val, stats, staging, counters;
     pccm::DevBuf rescan_part;             // k2b_fallback's split regime: partial minima per (query, workgroup)
@@ -572,6 +578,46 @@ constexpr int kCarryCount = 64, kCarryPlace = 65, kCarryScatter = 66, kCarrySum 
 // loads of a segment the L2 holds); longer ones cost one wave a walk over all n_from rows each, and there are at most
 // n_from / kCarryLong of them.  128: the lane's worst case stays at 16 K loads, the walks' at n_from^2 / 8192 row reads.
 constexpr int kCarryLong = 128;
+// pccm_merge_duplicates runs the same five passes for its colour averages -- nn_F := rep (every row's group representative),
+// n_from = n_to = n, nrm := the colours, inrm (nn_G) null: a row that no row names (m = 0: not a representative) is then skipped --
+// and these passes of its own, further job kinds of k_point_jobs.  They read the PointJob fields as
+//   q64: the points [n][3]   nrm / r64: the normals / the colours to keep per representative [n][3], or null   q_begin: n
+//   val: the merged rows (written): points [n][3], then normals [n][3], then colours [n][3]
+//   c64: the uint32 words of the workspace (MergeLayout; written)   idx: the map [n] (written)   recs: the device error word
+// kMergeInsert (rows: n) puts every row into the open-addressed table of group representatives; kMergeFind (n, whole waves) reads
+// rep[i] back and notes per wave which rows are representatives (a 64-bit mask and its count); kMergeScanWaves (one lane per wave
+// of rows) and kMergeScanTop (one wave) turn the counts into exclusive prefixes -- the ordered scan -- and leave n' in head[0];
+// kMergeGather (n) writes map[i] = the position of rep[i] and, for a representative, its merged row.
+constexpr int kMergeInsert = 69, kMergeFind = 70, kMergeScanWaves = 71, kMergeScanTop = 72, kMergeGather = 73;
+constexpr uint32_t kMergeEmpty = 0xffffffffu;      // an empty slot of the table (no cloud has that many rows)
+constexpr uint32_t kErrMergeTable = 4u;            // device error word: a probe sequence ran through the whole table
+// The workspace of pccm_merge_duplicates for a cloud of n rows.  Doubles first: the averaged colours [n][3] (by original row; only
+// representatives are written), then the merged points, normals and colours [n][3] each.  Then uint32 words: head[4] ([0] = n'),
+// the representative masks [2 * nw] (one 64-bit word per wave of 64 rows), rep[n], the waves' counts and then exclusive prefixes
+// wpre[nw], the same per 64 waves spre[nsw], and the table [cap], cap = the power of two >= 2 n.
+struct MergeLayout {
+    int64_t nw, nsw;                // waves of 64 rows; groups of 64 waves
+    uint64_t cap;
+    size_t doubles;                 // 12 n
+    size_t bits, rep, wpre, spre, table, words;      // offsets (and the total) in uint32 words behind the doubles
+    size_t bytes() const { return doubles * sizeof(double) + words * sizeof(uint32_t); }
+};
+__host__ __device__ inline MergeLayout merge_layout(int64_t n)
+{
+    MergeLayout L;
+    L.nw = (n + 63) / 64;
+    L.nsw = (L.nw + 63) / 64;
+    L.cap = 64;
+    while (L.cap < 2 * (uint64_t)n) L.cap <<= 1;
+    L.doubles = (size_t)12 * (size_t)n;
+    L.bits = 4;
+    L.rep = L.bits + 2 * (size_t)L.nw;
+    L.wpre = L.rep + (size_t)n;
+    L.spre = L.wpre + (size_t)L.nw;
+    L.table = L.spre + (size_t)L.nsw;
+    L.words = L.table + (size_t)L.cap;
+    return L;
+}
 struct PointJobs {
     PointJob j[4];
     int njobs;
@@ -612,9 +658,16 @@ int rescan_jobs(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Cloud *
 constexpr unsigned kRescanCap = 512;   // most workgroups that ever share one job's list (sizes the split regime's partials)
 int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs);
 size_t carry_ws_bytes(int64_t n_from, int64_t n_to);
-// the passes of pccm_carry_normals on the stream (the caller has checked everything and sized ws: carry_ws_bytes)
+// the passes of pccm_carry_normals on the stream (the caller has checked everything and sized ws: carry_ws_bytes); nn_g null:
+// rows of `out` that no row of nn_f names are left alone (pccm_merge_duplicates)
 int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
                  uint32_t *ws, double *out);
+inline size_t merge_ws_bytes(int64_t n) { return merge_layout(n).bytes(); }
+// pccm_merge_duplicates on the stream, in two halves with the caller's read of n' (head[0] of the workspace's words) between them:
+// table filled, insert | find | the two scans; then -- rows were merged away -- the gather (rgb: the colours to keep per
+// representative row, the cloud's own or the averages)
+int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, void *ws);
+int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, void *ws, int32_t *map);
 // result records -> plain columns (q32 / row0: the iterating cloud's rows, for records of layout 1)
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2);
 // *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when

@@ -2,7 +2,8 @@
 
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
-                                  [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--csv]
+                                  [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
+                                  [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -30,7 +31,11 @@ a file WITHOUT normals the other file's normals instead of estimated ones, as th
 cloud (``pc_error``'s normal carrying): each point takes the average of the normals of the other cloud's points whose nearest
 neighbour it is, or its own nearest point's normal when it is nobody's ("Carried normals").  The MPEG-style D2 is
 ``--point-to-plane --normal-index neighbour --carry-normals``; no default changes, and ``--ties mean`` with it is a usage
-error.  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+error.  ``--duplicates drop|average`` (default ``keep``: nothing changes; no counterpart in the reference) merges, on the GPU and
+before anything is searched, the points of each file that share their coordinates, as ``pc_error`` does with both clouds
+(dropDuplicates): one point per position, with the first one's normal and the first one's colour (``drop``) or the average colour
+(``average``, pc_error's default); a line per cloud on stderr says how many rows were merged away ("Duplicate
+points").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -75,6 +80,10 @@ import click
                    "decoded cloud: per point the average normal of the other cloud's points whose nearest neighbour it is, or its "
                    "own nearest point's normal.  With normals in neither file the original's are estimated and carried over.  "
                    "MPEG-style D2: --point-to-plane --normal-index neighbour --carry-normals.  Not with --ties mean.")
+@click.option("--duplicates", type=str, default="keep", show_default=True, metavar="[keep|drop|average]",
+              help="Merge the points of each cloud that share their coordinates before comparing, as MPEG's pc_error does "
+                   "(dropDuplicates): one point per position, with the first point's normal and the first point's colour (drop) "
+                   "or the average colour (average, pc_error's default).  keep: nothing is merged.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -89,12 +98,12 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import (CalculateOptions, check_carry_normals, check_hausdorff_rank, check_p2d_color, check_point_ssim,
+    from .options import (CalculateOptions, check_carry_normals, check_duplicates, check_hausdorff_rank, check_p2d_color, check_point_ssim,
                           check_point_to_distribution, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
@@ -103,6 +112,7 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
                                    point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours,
                                    p2d_color=p2d_color)
         check_carry_normals(carry_normals, ties=ties)
+        check_duplicates(duplicates)
     except ValueError as exc:
         raise click.UsageError(str(exc))
     check_hausdorff_rank(options)
@@ -118,9 +128,15 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)
             cloud_pair = CloudPair(ocloud_cloud, pcloud_cloud, device=device, nn_engine=engine, normal_index=normal_index,
                                    extent=list(extent) if extent else None, staged_io=True, ties=ties,
-                                   carry_normals=carry_normals)
+                                   carry_normals=carry_normals, duplicates=duplicates)
+            merged_logs = ((0, ocloud, ocloud_cloud), (1, path, pcloud_cloud))
         else:
             cloud_pair = cloud_pair.with_reconst(pcloud_cloud)     # the original cloud stays in HBM with all that belongs to it
+            merged_logs = ((1, path, pcloud_cloud),)
+        if duplicates != "keep":               # stderr: stdout stays the report
+            for which, name, given in merged_logs:
+                click.echo(f"duplicates ({duplicates}): {name}: {cloud_pair.duplicates_removed[which]} of {len(given.points)} rows "
+                           "merged away", err=True)
         calculator = MetricCalculator(cloud_pair)
         result = calculator.calculate(transform_options(options)).as_df()
         print(result.to_csv() if csv else result.to_string())

@@ -42,6 +42,9 @@ point-to-distribution metric after Javaheri et al., IEEE MMSP 2021), after every
   p2d_color                    JointMahalanobisDistance L/R/sym
   p2d_color & hd               MaxColorMahalanobisDistance L/R/sym
   p2d_color & hd               MaxJointMahalanobisDistance L/R/sym
+
+``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
+changes which rows the clouds have, never which report rows there are or their order.
 """
 from __future__ import annotations
 
@@ -160,6 +163,19 @@ def check_carry_normals(carry_normals: bool, *, ties: str = "pick", group=None) 
         raise ValueError("carry_normals is not defined under ties='mean' (the carried normal averages over matched rows)")
     if group is not None:
         raise ValueError("carry_normals needs whole clouds on one GPU: it cannot be combined with group=")
+
+
+DUPLICATES = ("keep", "drop", "average")
+
+
+def check_duplicates(mode, *, group=None) -> None:
+    """The ValueErrors of ``CloudPair(..., duplicates=mode)`` (the command line turns them into usage errors): the mode is "keep"
+    (nothing is merged), "drop" or "average" (include/pccm.h, pccm_merge_duplicates), and merging needs each whole cloud on one
+    GPU."""
+    if not isinstance(mode, str) or mode not in DUPLICATES:
+        raise ValueError(f"duplicates must be one of {', '.join(repr(m) for m in DUPLICATES)}")
+    if mode != "keep" and group is not None:
+        raise ValueError("duplicates other than 'keep' need whole clouds on one GPU: they cannot be combined with group=")
 
 
 def check_p2d_color(options: CalculateOptions, origin_cloud, reconst_cloud, *, group=None) -> None:
