@@ -1091,9 +1091,10 @@ int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out)
     if ((rc = ensure(ctx, ctx->merge_ws, merge_ws_bytes(n)))) return rc;
     const MergeLayout L = merge_layout(n);
     double *wd = (double *)ctx->merge_ws.p;
-    if ((rc = launch_merge_find(ctx, c.xyz64, n, wd))) return rc;
+    uint32_t *ww = (uint32_t *)(wd + L.doubles);
+    if ((rc = launch_merge_find(ctx, c.xyz64, n, ww))) return rc;
     uint32_t n_new = 0;
-    PCCM_HIP(hipMemcpyAsync(&n_new, wd + L.doubles, sizeof(n_new), hipMemcpyDeviceToHost, ctx->stream));
+    PCCM_HIP(hipMemcpyAsync(&n_new, ww, sizeof(n_new), hipMemcpyDeviceToHost, ctx->stream));
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     if ((rc = check_device_errors(ctx))) return rc;
     if (n_new == 0 || (int64_t)n_new > n) return fail(PCCM_E_HIP, "merging duplicates counted %u groups in %lld rows", n_new, (long long)n);
@@ -1107,12 +1108,12 @@ int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out)
     if (has_rgb && mode == PCCM_DUP_AVERAGE) {
         // the carry's passes with nn_F := rep: per representative the colours of its group, summed in ascending row order
         if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(n, n)))) return rc;
-        const int32_t *rep = (const int32_t *)((const uint32_t *)(wd + L.doubles) + L.rep);
+        const int32_t *rep = (const int32_t *)(ww + L.rep);
         if ((rc = launch_carry(ctx, rep, nullptr, c.rgb64, n, n, (uint32_t *)ctx->carry_ws.p, wd))) return rc;
         rgb = wd;
     }
     if ((rc = ensure(ctx, ctx->merge_map[which], (size_t)n * sizeof(int32_t)))) return rc;
-    if ((rc = launch_merge_gather(ctx, c.xyz64, has_nrm ? c.nrm64 : nullptr, rgb, n, wd, (int32_t *)ctx->merge_map[which].p))) return rc;
+    if ((rc = launch_merge_gather(ctx, c.xyz64, has_nrm ? c.nrm64 : nullptr, rgb, n, wd + 3 * n, ww, (int32_t *)ctx->merge_map[which].p))) return rc;
     // the merged rows enter the way any resident fp64 rows do (one ingest path: statistics, fp32 copies, invalidation)
     if ((rc = pccm_set_cloud(ctx, which, wd + 3 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
     if (has_nrm && (rc = pccm_set_normals(ctx, which, wd + 6 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;

@@ -1,0 +1,425 @@
+// The passes of pccm_carry_normals and pccm_merge_duplicates: one kernel per pass, each a launch of its own over whole waves of
+// rows (the launchers pad the row counts to multiples of 64; a kernel's first line drops the rest of the last workgroup).
+//
+// pccm_carry_normals averages the source cloud's normals over the rows that matched each target row, in ascending row order
+// (integer atomics only: where a list lands is arbitrary, the order it is summed in is not).  k_carry_count (rows: n_from)
+// counts; k_carry_place (n_to) gives every list of 1..kCarryLong rows a segment of `list` and queues the longer ones;
+// k_carry_scatter_walk fills the segments (its first n_from rows, padded) and, in the waves behind them, sums one queued list per
+// wave by walking nn_F in row order; k_carry_sum (n_to) sums the short lists and copies the fallback rows.
+//
+// pccm_merge_duplicates runs the same passes for its colour averages -- nn_F := rep (every row's group representative),
+// n_from = n_to = n, src := the colours, nn_G null: a row that no row names (m = 0: not a representative) is then skipped -- and
+// these of its own: k_merge_probe<false> (rows: n) puts every row into the open-addressed table of group representatives;
+// k_merge_probe<true> (n) reads rep[i] back and notes per wave which rows are representatives (a 64-bit mask and its count);
+// k_merge_scan_waves (one lane per wave of rows) and k_merge_scan_top (one wave) turn the counts into exclusive prefixes -- the
+// ordered scan -- and leave n' in head[0]; k_merge_gather (n) writes map[i] = the position of rep[i] and, for a representative, its
+// merged row.
+#include "pccm_internal.h"
+
+namespace pccm {
+
+// Lists of up to kCarryLong rows are summed by one lane that picks the next larger row kCarryLong times over (<= kCarryLong^2
+// loads of a segment the L2 holds); longer ones cost one wave a walk over all n_from rows each, and there are at most
+// n_from / kCarryLong of them.  128: the lane's worst case stays at 16 K loads, the walks' at n_from^2 / 8192 row reads.
+constexpr int kCarryLong = 128;
+constexpr uint32_t kMergeEmpty = 0xffffffffu;      // an empty slot of the table (no cloud has that many rows)
+
+__host__ __device__ constexpr int64_t whole_waves(int64_t rows) { return (rows + 63) / 64 * 64; }
+
+// What a carry pass works on.  The workspace (uint32 words): head[0] segment cursor, head[1] queue length, head[2..3] -, then
+// cnt[n_to], fill[n_to], base[n_to], list[n_from], queue[n_from / (kCarryLong + 1) + 1]
+struct CarryView {
+    const int32_t *nn_f, *nn_g;     // nn_F [n_from]: matched rows of the direction that iterates the source cloud; nn_G [n_to] or null
+    const double *src;              // the source normals [n_from][3]
+    double *out;                    // the target normals [n_to][3]
+    int64_t n_from, n_to;
+    uint32_t *head, *cnt, *fill, *base, *list, *queue;
+};
+
+static CarryView carry_view(const int32_t *nn_f, const int32_t *nn_g, const double *src, double *out, uint32_t *ws, int64_t n_from,
+                            int64_t n_to)
+{
+    CarryView V;
+    V.nn_f = nn_f;
+    V.nn_g = nn_g;
+    V.src = src;
+    V.out = out;
+    V.n_from = n_from;
+    V.n_to = n_to;
+    V.head = ws;
+    V.cnt = V.head + 4;
+    V.fill = V.cnt + V.n_to;
+    V.base = V.fill + V.n_to;
+    V.list = V.base + V.n_to;
+    V.queue = V.list + V.n_from;
+    return V;
+}
+
+size_t carry_ws_bytes(int64_t n_from, int64_t n_to)
+{
+    return (size_t)(4 + 3 * n_to + n_from + n_from / (kCarryLong + 1) + 1) * sizeof(uint32_t);
+}
+
+__device__ __forceinline__ double lane_value(double v, int lane)      // v of `lane` (wave-uniform), in every lane
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ void carry_count(const CarryView &V, int64_t i, int lane)
+{
+    // one atomic per distinct target in the wave, not one per row: a target cloud of a few points would otherwise put
+    // every row's add on the same few words
+    int32_t j = -1;
+    if (i < V.n_from) {
+        j = V.nn_f[i];
+        if (j < 0 || (int64_t)j >= V.n_to) j = -1;                  // (no search writes such a row)
+    }
+    unsigned long long todo = __ballot(j >= 0);
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int32_t jl = __builtin_amdgcn_readlane(j, lead);
+        const unsigned long long same = __ballot(j == jl);
+        if (lane == lead) atomicAdd(&V.cnt[jl], (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+__device__ __forceinline__ void carry_place(const CarryView &V, int64_t i, int lane)
+{
+    // segments for the lists of 1..kCarryLong rows: the wave's lengths are scanned, one lane moves the cursor
+    const uint32_t m = i < V.n_to ? V.cnt[i] : 0u;
+    const uint32_t len = m <= (uint32_t)kCarryLong ? m : 0u;
+    const uint32_t incl = wave_incl_scan_u32(len, lane);
+    const uint32_t total = __shfl(incl, 63);
+    uint32_t start = 0;
+    if (lane == 0 && total) start = atomicAdd(&V.head[0], total);
+    start = __shfl(start, 0);
+    if (i < V.n_to) V.base[i] = start + incl - len;
+    if (m > (uint32_t)kCarryLong) V.queue[atomicAdd(&V.head[1], 1u)] = (uint32_t)i;
+}
+
+__device__ __forceinline__ void carry_scatter(const CarryView &V, int64_t i)
+{
+    if (i >= V.n_from) return;
+    const int32_t j = V.nn_f[i];
+    if (j < 0 || (int64_t)j >= V.n_to) return;
+    const uint32_t m = V.cnt[j];
+    if (m > (uint32_t)kCarryLong) return;                           // (the walk finds these rows itself)
+    const uint32_t p = atomicAdd(&V.fill[j], 1u);
+    if (p < m) V.list[V.base[j] + p] = (uint32_t)i;
+}
+
+__device__ __forceinline__ void carry_sum(const CarryView &V, int64_t i)
+{
+    if (i >= V.n_to) return;
+    const uint32_t m = V.cnt[i];
+    if (m > (uint32_t)kCarryLong) return;
+    double *o = V.out + 3 * i;
+    if (m == 0) {                                                   // nobody's nearest neighbour: its own nearest row's normal
+        if (!V.nn_g) return;                                        // (pccm_merge_duplicates: not a representative, no row of its own)
+        int64_t r = V.nn_g[i];
+        r = r < 0 ? 0 : (r >= V.n_from ? V.n_from - 1 : r);
+        o[0] = V.src[3 * r]; o[1] = V.src[3 * r + 1]; o[2] = V.src[3 * r + 2];
+        return;
+    }
+    const uint32_t *seg = V.list + V.base[i];
+    double s0, s1, s2;
+    if (m <= 2) {                                                   // (a two-term sum is the same either way round)
+        const double *a = V.src + 3 * (int64_t)seg[0];
+        s0 = a[0]; s1 = a[1]; s2 = a[2];
+        if (m == 2) {
+            const double *b = V.src + 3 * (int64_t)seg[1];
+            s0 = __dadd_rn(s0, b[0]); s1 = __dadd_rn(s1, b[1]); s2 = __dadd_rn(s2, b[2]);
+        }
+    } else {
+        // ascending rows without a private array: the smallest row above the last one, m times
+        int64_t last = -1;
+        s0 = s1 = s2 = 0.0;
+        for (uint32_t r = 0; r < m; ++r) {
+            int64_t next = INT64_MAX;
+            for (uint32_t t = 0; t < m; ++t) {
+                const int64_t v = (int64_t)seg[t];
+                next = (v > last && v < next) ? v : next;
+            }
+            if (next == INT64_MAX) break;                           // (rows of a list are distinct: never taken)
+            const double *a = V.src + 3 * next;
+            if (r == 0) { s0 = a[0]; s1 = a[1]; s2 = a[2]; }
+            else { s0 = __dadd_rn(s0, a[0]); s1 = __dadd_rn(s1, a[1]); s2 = __dadd_rn(s2, a[2]); }
+            last = next;
+        }
+    }
+    const double dm = (double)m;
+    o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
+}
+
+// wave i / 64 takes one queued target and walks nn_F in row order, 64 rows a step (four steps' rows are loaded ahead); the lanes
+// whose row matched hold its normal, and the sum takes them in lane order -- ascending rows -- in every lane alike.  It reads
+// neither the lists nor anything the sum writes (the sum leaves the queued rows alone), so it rides with the scatter
+__device__ __forceinline__ void carry_walk(const CarryView &V, int64_t i, int lane)
+{
+    const int64_t w = i >> 6;
+    if (w >= (int64_t)V.head[1]) return;                                // (wave-uniform)
+    const int32_t j = (int32_t)V.queue[w];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    bool first = true;
+    for (int64_t r0 = 0; r0 < V.n_from; r0 += 256) {                   // four steps' rows in flight, then two steps' normals at a time
+        int32_t got[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int64_t r = r0 + 64 * c + lane;
+            got[c] = r < V.n_from ? V.nn_f[r] : -1;                     // (j >= 0: a row past the end never matches)
+        }
+#pragma unroll
+        for (int h = 0; h < 4; h += 2) {
+            if (!__ballot(got[h] == j || got[h + 1] == j)) continue;
+            double a[2][3];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int64_t r = r0 + 64 * (h + c) + lane;
+                a[c][0] = a[c][1] = a[c][2] = 0.0;
+                if (got[h + c] == j) { a[c][0] = V.src[3 * r]; a[c][1] = V.src[3 * r + 1]; a[c][2] = V.src[3 * r + 2]; }
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                unsigned long long mask = __ballot(got[h + c] == j);
+                if (mask == ~0ull && !first) {
+#pragma unroll
+                    for (int b = 0; b < 64; ++b) {
+                        s0 = __dadd_rn(s0, lane_value(a[c][0], b)); s1 = __dadd_rn(s1, lane_value(a[c][1], b)); s2 = __dadd_rn(s2, lane_value(a[c][2], b));
+                    }
+                    continue;
+                }
+                while (mask) {
+                    const int b = __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    const double v0 = lane_value(a[c][0], b), v1 = lane_value(a[c][1], b), v2 = lane_value(a[c][2], b);
+                    if (first) { s0 = v0; s1 = v1; s2 = v2; first = false; }
+                    else { s0 = __dadd_rn(s0, v0); s1 = __dadd_rn(s1, v1); s2 = __dadd_rn(s2, v2); }
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        const double dm = (double)V.cnt[j];
+        double *o = V.out + 3 * (int64_t)j;
+        o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_carry_count(CarryView V)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < whole_waves(V.n_from)) carry_count(V, i, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void k_carry_place(CarryView V)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < whole_waves(V.n_to)) carry_place(V, i, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void k_carry_scatter_walk(CarryView V)      // the first waves scatter, the ones behind them walk
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, rows = whole_waves(V.n_from);
+    if (i < rows) carry_scatter(V, i);
+    else carry_walk(V, i - rows, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void k_carry_sum(CarryView V)
+{
+    carry_sum(V, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// pccm_carry_normals on the stream: counts and cursors zeroed, then count | place | scatter + walk | sum
+int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
+                 uint32_t *ws, double *out)
+{
+    ProfScope ps(ctx, PCCM_K_POINT);
+    PCCM_HIP(hipMemsetAsync(ws, 0, (size_t)(4 + 2 * n_to) * sizeof(uint32_t), ctx->stream));     // header, cnt, fill
+    const CarryView V = carry_view(nn_f, nn_g, n_from64, out, ws, n_from, n_to);
+    const int64_t walk_lanes = (n_from / (kCarryLong + 1)) * 64;       // one wave per list that can be long
+    auto blocks = [](int64_t lanes) { return dim3((unsigned)((lanes + 255) / 256)); };
+    PCCM_LAUNCH(ctx, k_carry_count, blocks(whole_waves(n_from)), dim3(256), 0, ctx->stream, V);
+    PCCM_LAUNCH(ctx, k_carry_place, blocks(whole_waves(n_to)), dim3(256), 0, ctx->stream, V);
+    PCCM_LAUNCH(ctx, k_carry_scatter_walk, blocks(whole_waves(n_from) + walk_lanes), dim3(256), 0, ctx->stream, V);
+    PCCM_LAUNCH(ctx, k_carry_sum, blocks(whole_waves(n_to)), dim3(256), 0, ctx->stream, V);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// pccm_merge_duplicates.  Rows with equal coordinates (== per component) end in one slot of an open-addressed table, whose value
+// after the insert launch is the smallest of them whatever the arrival order: a slot is claimed once and never emptied, every row
+// of a key walks the same probe sequence, and the only writes are compare-and-swap on an empty slot and atomicMin.  No loop waits
+// for another lane: a probe sequence ends after at most `cap` slots (then the device error word says so).  The colour averages are
+// the carry's passes above.
+// ------------------------------------------------------------------------------------------
+struct MergeArgs {
+    const double *x;                // the points [n][3]
+    const double *nrm, *rgb;        // the normals / the colours to keep per representative [n][3], or null
+    double *out;                    // the merged rows (written): points [n][3], then normals [n][3], then colours [n][3]
+    uint32_t *ws;                   // the uint32 words of the workspace (MergeLayout)
+    int32_t *map;                   // [n] (written)
+    uint32_t *err;                  // the device error word, or null
+    int64_t n;
+};
+
+__device__ __forceinline__ uint32_t merge_hash(double x, double y, double z)
+{
+    const double k[3] = {x == 0.0 ? 0.0 : x, y == 0.0 ? 0.0 : y, z == 0.0 ? 0.0 : z};     // (-0.0 == +0.0: one key, one hash)
+    uint32_t h = 0x9e3779b9u;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        uint32_t w = (uint32_t)((a & 1) ? __double2hiint(k[a >> 1]) : __double2loint(k[a >> 1]));
+        w *= 0xcc9e2d51u;
+        w = (w << 15) | (w >> 17);
+        w *= 0x1b873593u;
+        h ^= w;
+        h = (h << 13) | (h >> 19);
+        h = h * 5u + 0xe6546b64u;
+    }
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// FIND false: the insert.  FIND true: rep[i] (a row, stored in a uint32 word) and the waves' representative masks and counts
+template <bool FIND>
+__global__ __launch_bounds__(256) void k_merge_probe(MergeArgs A)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, n = A.n;
+    if (i >= whole_waves(n)) return;
+    const MergeLayout L = merge_layout(n);
+    uint32_t *tab = A.ws + L.table;
+    int32_t r = -1;
+    if (i < n) {
+        const double *x = A.x;
+        const double kx = x[3 * i], ky = x[3 * i + 1], kz = x[3 * i + 2];
+        const uint64_t mask = L.cap - 1;
+        uint64_t slot = (uint64_t)merge_hash(kx, ky, kz) & mask;
+        bool done = false;
+        for (uint64_t probe = 0; probe < L.cap; ++probe, slot = (slot + 1) & mask) {
+            uint32_t cur = __hip_atomic_load(&tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == kMergeEmpty) {
+                if (FIND) break;                                    // (its own insert filled a slot on the way: never taken)
+                cur = atomicCAS(&tab[slot], kMergeEmpty, (uint32_t)i);
+                if (cur == kMergeEmpty) { done = true; break; }     // claimed
+            }
+            if ((int64_t)cur >= n) break;                           // (only rows are ever stored)
+            const double *o = x + 3 * (int64_t)cur;
+            if (o[0] == kx && o[1] == ky && o[2] == kz) {
+                // (the slot only ever gets smaller: a row above its value has nothing to add)
+                if (!FIND) { if (cur > (uint32_t)i) atomicMin(&tab[slot], (uint32_t)i); }
+                else r = (int32_t)cur;
+                done = true;
+                break;
+            }
+        }
+        if (!done) {
+            if (A.err) atomicOr(A.err, kErrMergeTable);
+            r = (int32_t)i;
+        }
+        if (FIND) A.ws[L.rep + i] = (uint32_t)r;
+    }
+    if (!FIND) return;
+    const unsigned long long keep = __ballot(i < n && (int64_t)r == i);
+    if ((threadIdx.x & 63) == 0) {
+        const int64_t w = i >> 6;
+        uint32_t *bits = A.ws + L.bits;
+        bits[2 * w] = (uint32_t)keep;
+        bits[2 * w + 1] = (uint32_t)(keep >> 32);
+        A.ws[L.wpre + w] = (uint32_t)__popcll(keep);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_merge_scan_waves(MergeArgs A)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const MergeLayout L = merge_layout(A.n);
+    if (i >= whole_waves(L.nw)) return;
+    uint32_t *wpre = A.ws + L.wpre, *spre = A.ws + L.spre;
+    const uint32_t c = i < L.nw ? wpre[i] : 0u;
+    const uint32_t incl = wave_incl_scan_u32(c, threadIdx.x & 63);
+    if (i < L.nw) wpre[i] = incl - c;
+    if ((threadIdx.x & 63) == 63) spre[i >> 6] = incl;
+}
+
+__global__ __launch_bounds__(256) void k_merge_scan_top(MergeArgs A)        // one wave: a run of spre per lane
+{
+    if (blockIdx.x != 0 || threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const MergeLayout L = merge_layout(A.n);
+    uint32_t *spre = A.ws + L.spre;
+    const int64_t per = (L.nsw + 63) / 64, b = lane * per, e = b + per < L.nsw ? b + per : L.nsw;
+    uint32_t sum = 0;
+    for (int64_t k = b; k < e; ++k) sum += spre[k];
+    const uint32_t incl = wave_incl_scan_u32(sum, lane);
+    uint32_t run = incl - sum;
+    for (int64_t k = b; k < e; ++k) {
+        const uint32_t c = spre[k];
+        spre[k] = run;
+        run += c;
+    }
+    if (lane == 63) A.ws[0] = incl;
+}
+
+__global__ __launch_bounds__(256) void k_merge_gather(MergeArgs A)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, n = A.n;
+    if (i >= n) return;
+    const MergeLayout L = merge_layout(n);
+    const uint32_t *bits = A.ws + L.bits;
+    const int64_t r = (int32_t)A.ws[L.rep + i], w = r >> 6;
+    const unsigned long long m64 = (unsigned long long)bits[2 * w] | ((unsigned long long)bits[2 * w + 1] << 32);
+    const int64_t p = (int64_t)A.ws[L.spre + (w >> 6)] + A.ws[L.wpre + w] + __popcll(m64 & ((1ull << (r & 63)) - 1ull));
+    A.map[i] = (int32_t)p;
+    if (r != i) return;
+    const double *x = A.x, *nrm = A.nrm, *rgb = A.rgb;
+    double *o = A.out + 3 * p;
+    o[0] = x[3 * i]; o[1] = x[3 * i + 1]; o[2] = x[3 * i + 2];
+    if (nrm) { o += 3 * n; o[0] = nrm[3 * i]; o[1] = nrm[3 * i + 1]; o[2] = nrm[3 * i + 2]; o -= 3 * n; }
+    if (rgb) { o += 6 * n; o[0] = rgb[3 * i]; o[1] = rgb[3 * i + 1]; o[2] = rgb[3 * i + 2]; }
+}
+
+static dim3 merge_blocks(int64_t rows) { return dim3((unsigned)((whole_waves(rows) + 255) / 256)); }
+
+int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, uint32_t *words)
+{
+    ProfScope ps(ctx, PCCM_K_POINT);
+    const MergeLayout L = merge_layout(n);
+    PCCM_HIP(hipMemsetAsync(words + L.table, 0xff, (size_t)L.cap * sizeof(uint32_t), ctx->stream));     // kMergeEmpty
+    MergeArgs A = {};
+    A.x = x64;
+    A.ws = words;
+    A.err = ctx->host_err;
+    A.n = n;
+    PCCM_LAUNCH(ctx, k_merge_probe<false>, merge_blocks(n), dim3(256), 0, ctx->stream, A);
+    PCCM_LAUNCH(ctx, k_merge_probe<true>, merge_blocks(n), dim3(256), 0, ctx->stream, A);
+    PCCM_LAUNCH(ctx, k_merge_scan_waves, merge_blocks(L.nw), dim3(256), 0, ctx->stream, A);
+    PCCM_LAUNCH(ctx, k_merge_scan_top, merge_blocks(64), dim3(256), 0, ctx->stream, A);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, double *out,
+                        uint32_t *words, int32_t *map)
+{
+    ProfScope ps(ctx, PCCM_K_POINT);
+    MergeArgs A = {};
+    A.x = x64;
+    A.nrm = nrm;
+    A.rgb = rgb;
+    A.out = out;
+    A.ws = words;
+    A.map = map;
+    A.n = n;
+    PCCM_LAUNCH(ctx, k_merge_gather, merge_blocks(n), dim3(256), 0, ctx->stream, A);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+}  // namespace pccm

@@ -1013,7 +1013,7 @@ static bool vox_feasible(const pccm_ctx *ctx)
 }
 
 // (re)build the combined grid when either cloud changed, the caches were dropped or the record layout asked for
-// differs from the built one (need64: a caller that reads GridRec records, pccm_normals.hip)
+// differs from the built one (need64: a caller that reads GridRec records, pccm_knn.hip)
 // A shard's rows of the iterating cloud that want the same cell sort as the grid being built: when exactly one cloud is
 // (re)built, they ride along as the second job of the same three launches instead of paying three more
 struct ShardSort {
@@ -1887,7 +1887,7 @@ int tie_mean(pccm_ctx *ctx, int dir, const int32_t *idx, const double *d2, int64
     return PCCM_OK;
 }
 
-// A grid over ONE cloud with cells sized for that cloud (GridRec records: pccm_normals.hip): the pair's geometry follows its
+// A grid over ONE cloud with cells sized for that cloud (GridRec records: pccm_knn.hip): the pair's geometry follows its
 // larger cloud, and a decoded cloud of a fifteenth of the reference's points -- a low rate of BASELINE configs[4] -- had its
 // k = 30 neighbourhoods spread over six rings of such cells (43 ms of normal estimation for 59 000 points, round 4).
 // The cell-edge factor is cached with the cloud; the pair's grid is gone afterwards (the next search builds it again).

@@ -471,7 +471,7 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx = 0);   // 
 void grid_release(pccm_ctx *ctx);
 void grid_invalidate(pccm_ctx *ctx);
 int grid_ensure(pccm_ctx *ctx, bool need64 = false, int need_mask = 3);
-int grid_ensure_solo(pccm_ctx *ctx, int which);    // GridRec grid over cloud `which` alone, cells sized for it (normal estimation)   // need64: GridRec records wanted (pccm_normals.hip reads them)
+int grid_ensure_solo(pccm_ctx *ctx, int which);    // GridRec grid over cloud `which` alone, cells sized for it (normal estimation)   // need64: GridRec records wanted (pccm_knn.hip reads them)
 int spatial_order(pccm_ctx *ctx, Cloud &c);      // fills Cloud::sp (ingest; no-op for clouds that are not fp32-exact)
 int grid_decide(pccm_ctx *ctx, bool *hostile);   // geometry decision for the current pair (cached per pair)
 int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; isolation verdict (cached per pair)
@@ -515,6 +515,17 @@ struct RescanJobs {
     RescanJob j[2];
     int njobs;
 };
+
+// inclusive scan of v over the wave's 64 lanes (lane: the caller's lane)
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(v, off);
+        if (lane >= off) v += o;
+    }
+    return v;
+}
 
 // PCCM_METRIC_ANGULAR of one pair of normals (include/pccm.h): every operation separately rounded, as NumPy's element-wise ops
 __device__ __forceinline__ double angular_similarity(const double *a, const double *b)
@@ -562,35 +573,7 @@ struct PointJob {
     int metric, normal_mode;
     double *val;                // [ns], or [ns][3] (PCCM_METRIC_D1)
 };
-// Internal job kinds of k_point_jobs (never a PCCM_METRIC_* of include/pccm.h): the passes of pccm_carry_normals, which averages the
-// source cloud's normals over the rows that matched each target row, in ascending row order (integer atomics only: where a list
-// lands is arbitrary, the order it is summed in is not).  Such a job reads the PointJob fields as
-//   idx: nn_F [n_from] (matched rows of the direction that iterates the source cloud)   inrm: nn_G [n_to], as int32
-//   nrm: the source normals [n_from][3]     val: the target normals [n_to][3]     q_begin: n_from     normal_mode: n_to
-//   c64: the workspace (uint32 words; written): [0] segment cursor, [1] queue length, [2..3] -, then cnt[n_to], fill[n_to],
-//        base[n_to], list[n_from], queue[n_from / (kCarryLong + 1) + 1]
-// kCarryCount (rows: n_from) counts; kCarryPlace (n_to) gives every list of 1..kCarryLong rows a segment of `list` and queues the
-// longer ones; kCarryScatter (n_from) fills the segments; kCarrySum (n_to) sums the short lists and copies the fallback rows;
-// kCarryWalk (64 lanes per possible queue entry) sums one queued list per wave by walking nn_F in row order.  Every pass takes
-// whole waves: the launcher pads the row counts to multiples of 64.
-constexpr int kCarryCount = 64, kCarryPlace = 65, kCarryScatter = 66, kCarrySum = 67, kCarryWalk = 68;
-// Lists of up to kCarryLong rows are summed by one lane that picks the next larger row kCarryLong times over (<= kCarryLong^2
-// loads of a segment the L2 holds); longer ones cost one wave a walk over all n_from rows each, and there are at most
-// n_from / kCarryLong of them.  128: the lane's worst case stays at 16 K loads, the walks' at n_from^2 / 8192 row reads.
-constexpr int kCarryLong = 128;
-// pccm_merge_duplicates runs the same five passes for its colour averages -- nn_F := rep (every row's group representative),
-// n_from = n_to = n, nrm := the colours, inrm (nn_G) null: a row that no row names (m = 0: not a representative) is then skipped --
-// and these passes of its own, further job kinds of k_point_jobs.  They read the PointJob fields as
-//   q64: the points [n][3]   nrm / r64: the normals / the colours to keep per representative [n][3], or null   q_begin: n
-//   val: the merged rows (written): points [n][3], then normals [n][3], then colours [n][3]
-//   c64: the uint32 words of the workspace (MergeLayout; written)   idx: the map [n] (written)   recs: the device error word
-// kMergeInsert (rows: n) puts every row into the open-addressed table of group representatives; kMergeFind (n, whole waves) reads
-// rep[i] back and notes per wave which rows are representatives (a 64-bit mask and its count); kMergeScanWaves (one lane per wave
-// of rows) and kMergeScanTop (one wave) turn the counts into exclusive prefixes -- the ordered scan -- and leave n' in head[0];
-// kMergeGather (n) writes map[i] = the position of rep[i] and, for a representative, its merged row.
-constexpr int kMergeInsert = 69, kMergeFind = 70, kMergeScanWaves = 71, kMergeScanTop = 72, kMergeGather = 73;
-constexpr uint32_t kMergeEmpty = 0xffffffffu;      // an empty slot of the table (no cloud has that many rows)
-constexpr uint32_t kErrMergeTable = 4u;            // device error word: a probe sequence ran through the whole table
+constexpr uint32_t kErrMergeTable = 4u;            // device error word: a probe sequence of pccm_merge_duplicates ran through the whole table
 // The workspace of pccm_merge_duplicates for a cloud of n rows.  Doubles first: the averaged colours [n][3] (by original row; only
 // representatives are written), then the merged points, normals and colours [n][3] each.  Then uint32 words: head[4] ([0] = n'),
 // the representative masks [2 * nw] (one 64-bit word per wave of 64 rows), rep[n], the waves' counts and then exclusive prefixes
@@ -657,17 +640,19 @@ struct UnitJobs {
 int rescan_jobs(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Cloud *const *ses, NNResult *const *ress, bool self, RescanJobs *out);
 constexpr unsigned kRescanCap = 512;   // most workgroups that ever share one job's list (sizes the split regime's partials)
 int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs);
+// pccm_carry.hip: the passes of pccm_carry_normals on the stream (the caller has checked everything and sized ws: carry_ws_bytes).
+// nn_f [n_from] / nn_g [n_to]: the matched rows of the two directions; nn_g null: rows of `out` that no row of nn_f names are left
+// alone (pccm_merge_duplicates)
 size_t carry_ws_bytes(int64_t n_from, int64_t n_to);
-// the passes of pccm_carry_normals on the stream (the caller has checked everything and sized ws: carry_ws_bytes); nn_g null:
-// rows of `out` that no row of nn_f names are left alone (pccm_merge_duplicates)
 int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
                  uint32_t *ws, double *out);
 inline size_t merge_ws_bytes(int64_t n) { return merge_layout(n).bytes(); }
 // pccm_merge_duplicates on the stream, in two halves with the caller's read of n' (head[0] of the workspace's words) between them:
-// table filled, insert | find | the two scans; then -- rows were merged away -- the gather (rgb: the colours to keep per
-// representative row, the cloud's own or the averages)
-int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, void *ws);
-int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, void *ws, int32_t *map);
+// table filled, insert | find | the two scans; then -- rows were merged away -- the gather into `out` (rgb: the colours to keep
+// per representative row, the cloud's own or the averages).  `words`: the uint32 part of the workspace (MergeLayout)
+int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, uint32_t *words);
+int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, double *out,
+                        uint32_t *words, int32_t *map);
 // result records -> plain columns (q32 / row0: the iterating cloud's rows, for records of layout 1)
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2);
 // *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when

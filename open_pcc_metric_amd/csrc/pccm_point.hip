@@ -192,310 +192,6 @@ __device__ __forceinline__ void point_row(const PointJob &J, int64_t i)
 }
 
 // ------------------------------------------------------------------------------------------
-// The passes of pccm_carry_normals (kCarry*, pccm_internal.h), hosted by k_point_jobs as job kinds of their own: one call per
-// row, behind a branch at the kernel's entry, so that the columns' path above holds none of this.
-// ------------------------------------------------------------------------------------------
-struct CarryView {
-    const int32_t *nn_f, *nn_g;
-    const double *src;
-    double *out;
-    int64_t n_from, n_to;
-    uint32_t *head, *cnt, *fill, *base, *list, *queue;
-};
-
-__device__ __forceinline__ CarryView carry_view(const int32_t *nn_f, const int32_t *nn_g, const double *src, double *out, uint32_t *ws,
-                                                 int64_t n_from, int64_t n_to)
-{
-    CarryView V;
-    V.nn_f = nn_f;
-    V.nn_g = nn_g;
-    V.src = src;
-    V.out = out;
-    V.n_from = n_from;
-    V.n_to = n_to;
-    V.head = ws;
-    V.cnt = V.head + 4;
-    V.fill = V.cnt + V.n_to;
-    V.base = V.fill + V.n_to;
-    V.list = V.base + V.n_to;
-    V.queue = V.list + V.n_from;
-    return V;
-}
-
-__device__ __forceinline__ double lane_value(double v, int lane)      // v of `lane` (wave-uniform), in every lane
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// (the job's fields come by value: a reference would make the kernel keep a copy of the job on the stack)
-__device__ __noinline__ void carry_row(const int32_t *nn_f, const int32_t *nn_g, const double *src, double *out, uint32_t *ws, int64_t n_from,
-                                       int64_t n_to, int kind, int64_t i)
-{
-    const CarryView V = carry_view(nn_f, nn_g, src, out, ws, n_from, n_to);
-    const int lane = threadIdx.x & 63;
-    if (kind == kCarryCount) {
-        // one atomic per distinct target in the wave, not one per row: a target cloud of a few points would otherwise put
-        // every row's add on the same few words
-        int32_t j = -1;
-        if (i < V.n_from) {
-            j = V.nn_f[i];
-            if (j < 0 || (int64_t)j >= V.n_to) j = -1;                  // (no search writes such a row)
-        }
-        unsigned long long todo = __ballot(j >= 0);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int32_t jl = __builtin_amdgcn_readlane(j, lead);
-            const unsigned long long same = __ballot(j == jl);
-            if (lane == lead) atomicAdd(&V.cnt[jl], (uint32_t)__popcll(same));
-            todo &= ~same;
-        }
-        return;
-    }
-    if (kind == kCarryPlace) {
-        // segments for the lists of 1..kCarryLong rows: the wave's lengths are scanned, one lane moves the cursor
-        const uint32_t m = i < V.n_to ? V.cnt[i] : 0u;
-        const uint32_t len = m <= (uint32_t)kCarryLong ? m : 0u;
-        uint32_t incl = len;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        const uint32_t total = __shfl(incl, 63);
-        uint32_t start = 0;
-        if (lane == 0 && total) start = atomicAdd(&V.head[0], total);
-        start = __shfl(start, 0);
-        if (i < V.n_to) V.base[i] = start + incl - len;
-        if (m > (uint32_t)kCarryLong) V.queue[atomicAdd(&V.head[1], 1u)] = (uint32_t)i;
-        return;
-    }
-    if (kind == kCarryScatter) {
-        if (i >= V.n_from) return;
-        const int32_t j = V.nn_f[i];
-        if (j < 0 || (int64_t)j >= V.n_to) return;
-        const uint32_t m = V.cnt[j];
-        if (m > (uint32_t)kCarryLong) return;                           // (the walk finds these rows itself)
-        const uint32_t p = atomicAdd(&V.fill[j], 1u);
-        if (p < m) V.list[V.base[j] + p] = (uint32_t)i;
-        return;
-    }
-    if (kind == kCarrySum) {
-        if (i >= V.n_to) return;
-        const uint32_t m = V.cnt[i];
-        if (m > (uint32_t)kCarryLong) return;
-        double *o = V.out + 3 * i;
-        if (m == 0) {                                                   // nobody's nearest neighbour: its own nearest row's normal
-            if (!V.nn_g) return;                                        // (pccm_merge_duplicates: not a representative, no row of its own)
-            int64_t r = V.nn_g[i];
-            r = r < 0 ? 0 : (r >= V.n_from ? V.n_from - 1 : r);
-            o[0] = V.src[3 * r]; o[1] = V.src[3 * r + 1]; o[2] = V.src[3 * r + 2];
-            return;
-        }
-        const uint32_t *seg = V.list + V.base[i];
-        double s0, s1, s2;
-        if (m <= 2) {                                                   // (a two-term sum is the same either way round)
-            const double *a = V.src + 3 * (int64_t)seg[0];
-            s0 = a[0]; s1 = a[1]; s2 = a[2];
-            if (m == 2) {
-                const double *b = V.src + 3 * (int64_t)seg[1];
-                s0 = __dadd_rn(s0, b[0]); s1 = __dadd_rn(s1, b[1]); s2 = __dadd_rn(s2, b[2]);
-            }
-        } else {
-            // ascending rows without a private array: the smallest row above the last one, m times
-            int64_t last = -1;
-            s0 = s1 = s2 = 0.0;
-            for (uint32_t r = 0; r < m; ++r) {
-                int64_t next = INT64_MAX;
-                for (uint32_t t = 0; t < m; ++t) {
-                    const int64_t v = (int64_t)seg[t];
-                    next = (v > last && v < next) ? v : next;
-                }
-                if (next == INT64_MAX) break;                           // (rows of a list are distinct: never taken)
-                const double *a = V.src + 3 * next;
-                if (r == 0) { s0 = a[0]; s1 = a[1]; s2 = a[2]; }
-                else { s0 = __dadd_rn(s0, a[0]); s1 = __dadd_rn(s1, a[1]); s2 = __dadd_rn(s2, a[2]); }
-                last = next;
-            }
-        }
-        const double dm = (double)m;
-        o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
-        return;
-    }
-    // kCarryWalk: wave i / 64 takes one queued target and walks nn_F in row order, 64 rows a step (four steps' rows are loaded
-    // ahead); the lanes whose row matched hold its normal, and the sum takes them in lane order -- ascending rows -- in every
-    // lane alike
-    const int64_t w = i >> 6;
-    if (w >= (int64_t)V.head[1]) return;                                // (wave-uniform)
-    const int32_t j = (int32_t)V.queue[w];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    bool first = true;
-    for (int64_t r0 = 0; r0 < V.n_from; r0 += 256) {                   // four steps' rows in flight, then two steps' normals at a time
-        int32_t got[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int64_t r = r0 + 64 * c + lane;
-            got[c] = r < V.n_from ? V.nn_f[r] : -1;                     // (j >= 0: a row past the end never matches)
-        }
-#pragma unroll
-        for (int h = 0; h < 4; h += 2) {
-            if (!__ballot(got[h] == j || got[h + 1] == j)) continue;
-            double a[2][3];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int64_t r = r0 + 64 * (h + c) + lane;
-                a[c][0] = a[c][1] = a[c][2] = 0.0;
-                if (got[h + c] == j) { a[c][0] = V.src[3 * r]; a[c][1] = V.src[3 * r + 1]; a[c][2] = V.src[3 * r + 2]; }
-            }
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                unsigned long long mask = __ballot(got[h + c] == j);
-                if (mask == ~0ull && !first) {
-#pragma unroll
-                    for (int b = 0; b < 64; ++b) {
-                        s0 = __dadd_rn(s0, lane_value(a[c][0], b)); s1 = __dadd_rn(s1, lane_value(a[c][1], b)); s2 = __dadd_rn(s2, lane_value(a[c][2], b));
-                    }
-                    continue;
-                }
-                while (mask) {
-                    const int b = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const double v0 = lane_value(a[c][0], b), v1 = lane_value(a[c][1], b), v2 = lane_value(a[c][2], b);
-                    if (first) { s0 = v0; s1 = v1; s2 = v2; first = false; }
-                    else { s0 = __dadd_rn(s0, v0); s1 = __dadd_rn(s1, v1); s2 = __dadd_rn(s2, v2); }
-                }
-            }
-        }
-    }
-    if (lane == 0) {
-        const double dm = (double)V.cnt[j];
-        double *o = V.out + 3 * (int64_t)j;
-        o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// The passes of pccm_merge_duplicates (kMerge*, pccm_internal.h), behind the same entry branch of k_point_jobs.  Rows with equal
-// coordinates (== per component) end in one slot of an open-addressed table, whose value after the insert launch is the smallest
-// of them whatever the arrival order: a slot is claimed once and never emptied, every row of a key walks the same probe sequence,
-// and the only writes are compare-and-swap on an empty slot and atomicMin.  No loop waits for another lane: a probe sequence
-// ends after at most `cap` slots (then the device error word says so).  The colour averages are the carry's passes above.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t merge_hash(double x, double y, double z)
-{
-    const double k[3] = {x == 0.0 ? 0.0 : x, y == 0.0 ? 0.0 : y, z == 0.0 ? 0.0 : z};     // (-0.0 == +0.0: one key, one hash)
-    uint32_t h = 0x9e3779b9u;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-        uint32_t w = (uint32_t)((a & 1) ? __double2hiint(k[a >> 1]) : __double2loint(k[a >> 1]));
-        w *= 0xcc9e2d51u;
-        w = (w << 15) | (w >> 17);
-        w *= 0x1b873593u;
-        h ^= w;
-        h = (h << 13) | (h >> 19);
-        h = h * 5u + 0xe6546b64u;
-    }
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __noinline__ void merge_row(const double *x, const double *nrm, const double *rgb, double *out, uint32_t *ws, int32_t *map,
-                                       uint32_t *err, int64_t n, int kind, int64_t i)
-{
-    const MergeLayout L = merge_layout(n);
-    const int lane = threadIdx.x & 63;
-    uint32_t *tab = ws + L.table, *wpre = ws + L.wpre, *spre = ws + L.spre, *bits = ws + L.bits;
-    int32_t *rep = reinterpret_cast<int32_t *>(ws + L.rep);
-    if (kind == kMergeInsert || kind == kMergeFind) {
-        int32_t r = -1;
-        if (i < n) {
-            const double kx = x[3 * i], ky = x[3 * i + 1], kz = x[3 * i + 2];
-            const uint64_t mask = L.cap - 1;
-            uint64_t slot = (uint64_t)merge_hash(kx, ky, kz) & mask;
-            bool done = false;
-            for (uint64_t probe = 0; probe < L.cap; ++probe, slot = (slot + 1) & mask) {
-                uint32_t cur = __hip_atomic_load(&tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == kMergeEmpty) {
-                    if (kind == kMergeFind) break;                      // (its own insert filled a slot on the way: never taken)
-                    cur = atomicCAS(&tab[slot], kMergeEmpty, (uint32_t)i);
-                    if (cur == kMergeEmpty) { done = true; break; }     // claimed
-                }
-                if ((int64_t)cur >= n) break;                           // (only rows are ever stored)
-                const double *o = x + 3 * (int64_t)cur;
-                if (o[0] == kx && o[1] == ky && o[2] == kz) {
-                    // (the slot only ever gets smaller: a row above its value has nothing to add)
-                    if (kind == kMergeInsert) { if (cur > (uint32_t)i) atomicMin(&tab[slot], (uint32_t)i); }
-                    else r = (int32_t)cur;
-                    done = true;
-                    break;
-                }
-            }
-            if (!done) {
-                if (err) atomicOr(err, kErrMergeTable);
-                r = (int32_t)i;
-            }
-            if (kind == kMergeFind) rep[i] = r;
-        }
-        if (kind == kMergeInsert) return;
-        const unsigned long long keep = __ballot(i < n && (int64_t)r == i);
-        if (lane == 0) {
-            const int64_t w = i >> 6;
-            bits[2 * w] = (uint32_t)keep;
-            bits[2 * w + 1] = (uint32_t)(keep >> 32);
-            wpre[w] = (uint32_t)__popcll(keep);
-        }
-        return;
-    }
-    if (kind == kMergeScanWaves) {
-        const uint32_t c = i < L.nw ? wpre[i] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (i < L.nw) wpre[i] = incl - c;
-        if (lane == 63) spre[i >> 6] = incl;
-        return;
-    }
-    if (kind == kMergeScanTop) {                                        // one wave: a run of spre per lane
-        if (i >= 64) return;
-        const int64_t per = (L.nsw + 63) / 64, b = lane * per, e = b + per < L.nsw ? b + per : L.nsw;
-        uint32_t sum = 0;
-        for (int64_t k = b; k < e; ++k) sum += spre[k];
-        uint32_t incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        uint32_t run = incl - sum;
-        for (int64_t k = b; k < e; ++k) {
-            const uint32_t c = spre[k];
-            spre[k] = run;
-            run += c;
-        }
-        if (lane == 63) ws[0] = incl;
-        return;
-    }
-    // kMergeGather
-    if (i >= n) return;
-    const int64_t r = rep[i], w = r >> 6;
-    const unsigned long long m64 = (unsigned long long)bits[2 * w] | ((unsigned long long)bits[2 * w + 1] << 32);
-    const int64_t p = (int64_t)spre[w >> 6] + wpre[w] + __popcll(m64 & ((1ull << (r & 63)) - 1ull));
-    map[i] = (int32_t)p;
-    if (r != i) return;
-    double *o = out + 3 * p;
-    o[0] = x[3 * i]; o[1] = x[3 * i + 1]; o[2] = x[3 * i + 2];
-    if (nrm) { o += 3 * n; o[0] = nrm[3 * i]; o[1] = nrm[3 * i + 1]; o[2] = nrm[3 * i + 2]; o -= 3 * n; }
-    if (rgb) { o += 6 * n; o[0] = rgb[3 * i]; o[1] = rgb[3 * i + 1]; o[2] = rgb[3 * i + 2]; }
-}
-
-// ------------------------------------------------------------------------------------------
 // K5 (k_unit_jobs below): per 128-row leaf, eight lanes accumulate rows k, k+8, k+16, ... in order and
 // the eight accumulators are combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) -- exactly NumPy's
 // pairwise-sum leaf, so that np.sum's tree can be finished bit for bit (pccm_finish_sum / pccm_reduce_total).
@@ -513,17 +209,6 @@ __global__ __launch_bounds__(256) void k_point_jobs(PointJobs jobs)
 #pragma unroll
     for (int k = 1; k < 4; ++k)
         if (k < jobs.njobs && i0 >= jobs.off[k]) jb = k;
-    if (jobs.j[jb].metric >= kCarryCount) {                 // pccm_carry_normals' passes: launches of their own, whole waves each
-        const PointJob &C = jobs.j[jb];                     // (the fields as a carry job reads them: pccm_internal.h)
-        if (C.metric >= kMergeInsert) {                     // pccm_merge_duplicates' own passes, likewise
-            merge_row(C.q64, C.nrm, C.r64, C.val, reinterpret_cast<uint32_t *>(const_cast<double *>(C.c64)), const_cast<int32_t *>(C.idx),
-                      reinterpret_cast<uint32_t *>(const_cast<float4 *>(C.recs)), C.q_begin, C.metric, i0 - jobs.off[jb]);
-            return;
-        }
-        carry_row(C.idx, reinterpret_cast<const int32_t *>(C.inrm), C.nrm, C.val, reinterpret_cast<uint32_t *>(const_cast<double *>(C.c64)),
-                  C.q_begin, (int64_t)C.normal_mode, C.metric, i0 - jobs.off[jb]);
-        return;
-    }
     point_row(jobs.j[jb], i0 - jobs.off[jb]);
 }
 
@@ -533,95 +218,6 @@ int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs)
     if (total <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_POINT);
     PCCM_LAUNCH(ctx, k_point_jobs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, jobs);
-    PCCM_HIP(hipGetLastError());
-    return PCCM_OK;
-}
-
-size_t carry_ws_bytes(int64_t n_from, int64_t n_to)
-{
-    return (size_t)(4 + 3 * n_to + n_from + n_from / (kCarryLong + 1) + 1) * sizeof(uint32_t);
-}
-
-// pccm_carry_normals on the stream: counts and cursors zeroed, then count | place | scatter + walk | sum (kCarry*, pccm_internal.h);
-// the walk rides with the scatter (it reads neither the lists nor anything the sum writes: the sum leaves the queued rows alone)
-int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
-                 uint32_t *ws, double *out)
-{
-    ProfScope ps(ctx, PCCM_K_POINT);
-    PCCM_HIP(hipMemsetAsync(ws, 0, (size_t)(4 + 2 * n_to) * sizeof(uint32_t), ctx->stream));     // header, cnt, fill
-    PointJob P = {};
-    P.idx = nn_f;
-    P.inrm = reinterpret_cast<const double *>(nn_g);
-    P.nrm = n_from64;
-    P.val = out;
-    P.q_begin = n_from;
-    P.normal_mode = (int)n_to;
-    P.c64 = reinterpret_cast<const double *>(ws);
-    auto pad = [](int64_t rows) { return (rows + 63) / 64 * 64; };
-    const int64_t walk_lanes = (n_from / (kCarryLong + 1)) * 64;       // one wave per list that can be long
-    const int kinds[4] = {kCarryCount, kCarryPlace, kCarryScatter, kCarrySum};
-    const int64_t rows[4] = {pad(n_from), pad(n_to), pad(n_from), pad(n_to)};
-    for (int k = 0; k < 4; ++k) {
-        PointJobs pj = {};
-        pj.njobs = 1;
-        pj.j[0] = P;
-        pj.j[0].metric = kinds[k];
-        pj.off[1] = rows[k];
-        if (kinds[k] == kCarryScatter && walk_lanes > 0) {
-            pj.njobs = 2;
-            pj.j[1] = P;
-            pj.j[1].metric = kCarryWalk;
-            pj.off[2] = pj.off[1] + walk_lanes;
-        }
-        for (int r = pj.njobs; r < 4; ++r) pj.off[r + 1] = pj.off[pj.njobs];
-        PCCM_LAUNCH(ctx, k_point_jobs, dim3((unsigned)((pj.off[pj.njobs] + 255) / 256)), dim3(256), 0, ctx->stream, pj);
-    }
-    PCCM_HIP(hipGetLastError());
-    return PCCM_OK;
-}
-
-static void merge_pass(pccm_ctx *ctx, const PointJob &P, int kind, int64_t rows)
-{
-    PointJobs pj = {};
-    pj.njobs = 1;
-    pj.j[0] = P;
-    pj.j[0].metric = kind;
-    for (int r = 1; r < 5; ++r) pj.off[r] = (rows + 63) / 64 * 64;      // whole waves
-    PCCM_LAUNCH(ctx, k_point_jobs, dim3((unsigned)((pj.off[1] + 255) / 256)), dim3(256), 0, ctx->stream, pj);
-}
-
-int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, void *ws)
-{
-    ProfScope ps(ctx, PCCM_K_POINT);
-    const MergeLayout L = merge_layout(n);
-    uint32_t *words = reinterpret_cast<uint32_t *>(static_cast<double *>(ws) + L.doubles);
-    PCCM_HIP(hipMemsetAsync(words + L.table, 0xff, (size_t)L.cap * sizeof(uint32_t), ctx->stream));     // kMergeEmpty
-    PointJob P = {};
-    P.q64 = x64;
-    P.q_begin = n;
-    P.c64 = reinterpret_cast<const double *>(words);
-    P.recs = reinterpret_cast<const float4 *>(ctx->host_err);
-    merge_pass(ctx, P, kMergeInsert, n);
-    merge_pass(ctx, P, kMergeFind, n);
-    merge_pass(ctx, P, kMergeScanWaves, L.nw);
-    merge_pass(ctx, P, kMergeScanTop, 64);
-    PCCM_HIP(hipGetLastError());
-    return PCCM_OK;
-}
-
-int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, void *ws, int32_t *map)
-{
-    ProfScope ps(ctx, PCCM_K_POINT);
-    const MergeLayout L = merge_layout(n);
-    PointJob P = {};
-    P.q64 = x64;
-    P.nrm = nrm;
-    P.r64 = rgb;
-    P.q_begin = n;
-    P.val = static_cast<double *>(ws) + 3 * n;                           // (behind the averaged colours)
-    P.c64 = reinterpret_cast<const double *>(static_cast<double *>(ws) + L.doubles);
-    P.idx = map;
-    merge_pass(ctx, P, kMergeGather, n);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

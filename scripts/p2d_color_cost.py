@@ -1,5 +1,5 @@
 """Cost of the colour and joint point-to-distribution columns (CalculateOptions(p2d_color=True)) on a resident 1M + 1M coloured
-pair, and the regression guard for the kernel they share with normal estimation and PointSSIM ("Point-to-distribution:
+pair, and the regression guard for the k-NN searches they share with normal estimation and PointSSIM ("Point-to-distribution:
 colour and joint").
 
     python scripts/p2d_color_cost.py [--rounds 15] [--n 1000000] [--k 30] [--baseline-lib PATH/libpccm.so] [--only builds|report]
@@ -16,7 +16,7 @@ colour and joint").
 
 One JSON line per part.  For the kernels' own times run the builds alone under
 ``rocprofv3 --kernel-trace --stats -- python scripts/p2d_color_cost.py --only builds --rounds 5 --arms color_u8``: with one
-colour arm the launches of k_normals_from_cov alternate between the geometry mode and the colour mode."""
+colour arm the launches of k_p2d_geometry and k_p2d_color alternate."""
 import argparse
 import ctypes
 import json

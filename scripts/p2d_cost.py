@@ -14,7 +14,7 @@ Hausdorff rows).  Two figures per pair:
 
 One JSON line per pair.  For the kernels' own times run the build alone under
 ``rocprofv3 --kernel-trace --stats -- python scripts/p2d_cost.py --only build --pair uniform`` (k_knn_cov_wave, k_knn_normals,
-k_knn_normals_full, k_normals_from_cov and the grid build)."""
+k_knn_normals_full, k_p2d_geometry and the grid build)."""
 import argparse
 import json
 import os

@@ -11,7 +11,7 @@ bench.py's 1M vs 1M uniform pair (unit normals, byte colours; D1 + D2 + Hausdorf
   report.  The figure is the median per report and the difference to "without".
 
 One JSON line.  For the kernels' own times run it under
-``rocprofv3 --kernel-trace --stats -- python scripts/pointssim_cost.py --only all`` (k_knn_cov_wave, k_normals_from_cov and
+``rocprofv3 --kernel-trace --stats -- python scripts/pointssim_cost.py --only all`` (k_knn_cov_wave, k_ssim_curvature, k_ssim_features and
 k_point_jobs)."""
 import argparse
 import json

@@ -1,6 +1,6 @@
-"""The stop rule of the k-NN searches of pccm_normals.hip, restated on the host, and the stage each query is settled in.
+"""The stop rule of the k-NN searches of pccm_knn.hip (knn_stop_bound, pccm_knn.h), restated on the host, and the stage each query is settled in.
 
-TEST INFRASTRUCTURE.  It does not import the product's kernels: the constants are parsed from the .hip file, the grid (org, h,
+TEST INFRASTRUCTURE.  It does not import the product's kernels: the constants are parsed from pccm_knn.h, the grid (org, h,
 dim) is the one the engine reports (Engine.grid_geometry), everything else is NumPy.  Shared by the point-to-distribution tests
 (a search across the clouds) and the normal-estimation tests (a cloud against itself)."""
 import os
@@ -18,7 +18,7 @@ STAGES = {WAVE2: "wave search, r = 2", WAVE3: "wave search, r = 3", THREAD_CAP: 
 
 
 def constant(name):
-    src = open(os.path.join(ROOT, "open_pcc_metric_amd", "csrc", "pccm_normals.hip")).read()
+    src = open(os.path.join(ROOT, "open_pcc_metric_amd", "csrc", "pccm_knn.h")).read()
     return int(re.search(rf"constexpr int {name} = (\d+);", src).group(1))
 
 

@@ -1,4 +1,4 @@
-"""High-precision reference of normal estimation (pccm_estimate_normals; pccm_normals.hip) and the per-point tolerance the
+"""High-precision reference of normal estimation (pccm_estimate_normals; pccm_normals.hip, pccm_normals.h) and the per-point tolerance the
 normal-estimation tests hold the GPU to.
 
 TEST INFRASTRUCTURE.  It does not import the product's kernels.
@@ -166,7 +166,7 @@ def examined(tau):
 
 # ---- fp64 restatement of the kernel's arithmetic (normal_from_neighbours + smallest_eigenvector) --------------------------------
 def closed_form_normals(p, nbr):
-    """The normals as pccm_normals.hip forms them, in NumPy fp64: raw moments of d = neighbour - query summed in neighbourhood
+    """The normals as pccm_normals.h forms them, in NumPy fp64: raw moments of d = neighbour - query summed in neighbourhood
     order, E[d d^T] - E[d] E[d]^T, the matrix scaled by its largest entry, the trigonometric smallest eigenvalue, the largest
     cross product of two rows of (A - lambda I), the component of largest magnitude made positive."""
     p = np.asarray(p, dtype=np.float64)

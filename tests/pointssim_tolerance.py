@@ -1,5 +1,5 @@
-"""High-precision reference of the PointSSIM normal and curvature rows ("PointSSIM"; k_normals_from_cov modes 1
-and 2, curvature_of and ssim_value in pccm_normals.hip) and the per-point tolerance the tests hold the GPU to.
+"""High-precision reference of the PointSSIM normal and curvature rows ("PointSSIM"; k_ssim_curvature and
+k_ssim_features, curvature_of and ssim_value in pccm_ssim.hip) and the per-point tolerance the tests hold the GPU to.
 
 TEST INFRASTRUCTURE.  It does not import the product's kernels.
   neighbours  exact, in (d2, row) order (pointssim_reference.knn_rows);
@@ -264,7 +264,7 @@ def _scaled_covariance(x, nbr):
 
 
 def _rotate(app, aqq, apq, arp, arq, on):
-    """jacobi_rotate of pccm_normals.hip on the rows `on` whose apq is not 0."""
+    """jacobi_rotate of pccm_ssim.hip on the rows `on` whose apq is not 0."""
     on = on & (apq != 0.0)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         theta = (aqq - app) / (2.0 * np.where(on, apq, 1.0))

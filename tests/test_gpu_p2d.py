@@ -118,7 +118,7 @@ def test_partly_overlapping_boxes_under_either_engine(engine):
 
 
 def test_the_staged_case_reaches_every_stage():
-    """The data of FAMILIES["staged"] against the constants of pccm_normals.hip and the grid the search ran on: some queries have
+    """The data of FAMILIES["staged"] against the constants of pccm_knn.h and the grid the search ran on: some queries have
     more than kWCap candidates in their first cube (the wave search hands them to the per-thread search), some are still open
     after kKnnMaxRing rings (the full scan), and most settle in the wave search."""
     wcap, max_ring = _constant("kWCap"), _constant("kKnnMaxRing")

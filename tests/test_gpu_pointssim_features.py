@@ -1,5 +1,5 @@
-"""PointSSIM normal and curvature rows on the GPU (k_normals_from_cov modes 1 and 2: curvature_of and ssim_value in
-pccm_normals.hip) against the high-precision reference of tests/pointssim_tolerance.py, point by point.
+"""PointSSIM normal and curvature rows on the GPU (k_ssim_curvature and k_ssim_features: curvature_of and ssim_value in
+pccm_ssim.hip) against the high-precision reference of tests/pointssim_tolerance.py, point by point.
 
 Every feature must lie within its tau_F, every similarity whose tau_s is below 1e-6 within its tau_s, and every pooled row
 within the mean tolerance of its column -- per family (wire-like, ring-like, voxel, lattice, duplicate and georeferenced data

@@ -130,14 +130,27 @@ OTHER = {
     "k_extreme_rows": "extent: test_gpu_extent_kernels (planted extremes, the fp32 bound), test_extent",
     "k_outside_planes": "extent: test_gpu_extent_kernels (exact integer plane tests), test_extent",
     "k_obb_frames": "extent: test_gpu_extent_kernels (one frame at a time, exact ties, whole hulls), test_extent",
-    "k_knn_cov_wave": "normal estimation: test_gpu_normals",
-    "k_knn_normals": "normal estimation: test_gpu_normals",
-    "k_knn_normals_full": "normal estimation: test_gpu_normals",
-    "k_normals_from_cov": ("normal estimation: test_gpu_normals; PointSSIM curvatures and features (modes 1, 2): test_gpu_pointssim, "
-                           "test_gpu_pointssim_features"),
-    "k_point_jobs": ("unfused point-to-plane columns: row 'reduce_shapes'; per-point projections (pccm_point_metric): the 'brick' "
-                     "rows, test_gpu_round2, test_gpu_point_columns; error vectors (pccm_error_vectors): test_gpu_parity, "
-                     "test_gpu_point_columns"),
+    "k_knn_cov_wave": "k-NN search, a wave per point: test_gpu_normals (normals), test_gpu_pointssim_features, test_gpu_p2d (lists)",
+    "k_knn_normals": "k-NN search, a thread per point: test_gpu_normals (normals), test_gpu_pointssim_features, test_gpu_p2d (lists)",
+    "k_knn_normals_full": "k-NN search, full scan: test_gpu_normals (normals), test_gpu_pointssim_features, test_gpu_p2d (lists)",
+    "k_normals_from_cov": "normal estimation, the eigenvectors of the wave search's covariances: test_gpu_normals",
+    "k_ssim_curvature": "PointSSIM curvatures from the neighbour lists: test_gpu_pointssim, test_gpu_pointssim_features",
+    "k_ssim_features": "PointSSIM features, one launch per attribute: test_gpu_pointssim, test_gpu_pointssim_features",
+    "k_p2d_geometry": "point-to-distribution, the Mahalanobis column: test_gpu_p2d",
+    "k_p2d_color": "point-to-distribution, the colour and joint columns: test_gpu_p2d_color",
+    "k_carry_count": "carried normals, rows per target: test_gpu_carry; colour averages of merged duplicates: test_gpu_merge",
+    "k_carry_place": "carried normals, list segments and the queue of long lists: test_gpu_carry, test_gpu_merge",
+    "k_carry_scatter_walk": "carried normals, short lists filled and long lists walked in one launch: test_gpu_carry, test_gpu_merge",
+    "k_carry_sum": "carried normals, short lists summed in row order and fallback rows: test_gpu_carry, test_gpu_merge",
+    "k_merge_probe<false>": "merged duplicates, the insert into the table of representatives: test_gpu_merge",
+    "k_merge_probe<true>": "merged duplicates, every row's representative and the waves' masks: test_gpu_merge",
+    "k_merge_scan_waves": "merged duplicates, the ordered scan over waves of rows: test_gpu_merge",
+    "k_merge_scan_top": "merged duplicates, the ordered scan over groups of 64 waves: test_gpu_merge",
+    "k_merge_gather": "merged duplicates, the map and the merged rows: test_gpu_merge",
+    "k_point_jobs": ("per-point columns formed from a search result, and nothing else -- unfused point-to-plane columns: row "
+                     "'reduce_shapes'; per-point projections (pccm_point_metric): the 'brick' rows, test_gpu_round2, "
+                     "test_gpu_point_columns; error vectors (pccm_error_vectors): test_gpu_parity, test_gpu_point_columns; angular "
+                     "and PointSSIM similarity columns: test_gpu_angular, test_gpu_pointssim"),
     "k_publish": "every reduction batch",
     "k_unpack": "plain columns from result records: every row",
 }
