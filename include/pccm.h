@@ -96,6 +96,12 @@ extern "C" {
  * PCCM_METRIC_P2D, with the same rules; PCCM_E_STATE while they are not built (a geometry-only build, or new colours since). */
 #define PCCM_METRIC_P2D_COLOR 9
 #define PCCM_METRIC_P2D_JOINT 10
+/* The point spacings r (pccm_resolution_build) of the cloud the direction ITERATES: direction 0 reads cloud 0's column, direction
+ * 1 cloud 1's (the self search: PCCM_E_ARG).  A stored column exactly like PCCM_METRIC_P2D: neither the matched rows, the tie
+ * policy nor normal_mode enter it, and the direction needs a search result (the slot takes its row range and generation from
+ * it).  PCCM_E_STATE while that cloud's column is not built.  Accepted by pccm_point_metric and every pccm_reduce* call; a plain
+ * column, reduced like D1. */
+#define PCCM_METRIC_RESOLUTION 11
 
 /* kernel classes for pccm_profile_get() */
 #define PCCM_K_INGEST 0
@@ -269,6 +275,29 @@ int pccm_p2d_build_attrs(pccm_ctx *ctx, int k, int attrs, int *built);
  * from count[i] on are -1), count[n].  Searches again (the build keeps no lists); PCCM_E_STATE while the columns are not built. */
 int pccm_get_p2d_neighbours(pccm_ctx *ctx, int dir, int32_t *out, int32_t *count);
 
+/* Point spacings of cloud `which` ("Resolution-adaptive PSNR"; after Javaheri et al., ICIP 2020): r[n] doubles in
+ * HBM, the mean distance of every point to its K nearest neighbours in its own cloud.  Per point p, fp64, every operation
+ * separately rounded:
+ *   N(p) = the first m = min(K + 1, n) points of the cloud in ascending (d2, row) order, d2 = ((dx*dx) + (dy*dy)) + dz*dz on the
+ *          stored coordinates: q_0 (distance 0), q_1, ... -- exactly PointSSIM's N_k at k = K + 1
+ *   r(p) = (sum_{j = 1 .. m - 1} sqrt(d2(p, q_j))) / (double)(m - 1), the sum from 0.0 left to right in list order (one correctly
+ *          rounded square root and one add per entry, then one division);  r(p) = 0 when m < 2.
+ * r(p) depends only on the sorted multiset of the m smallest squared distances: equal d2 give equal square roots, so neither
+ * the order of exact ties nor which of several tied rows survives the cut at entry K can change a bit of it.  The column
+ * therefore does not depend on the row order of the cloud (a permutation of the rows permutes r) nor on the tie policy.
+ * The intrinsic resolution of the cloud is np.sum(r) / n (the plain-column reduction of PCCM_METRIC_RESOLUTION).  K = 10 is
+ * this project's default; the paper's own choice is not available here and parity with its authors' code is NOT pinned.
+ * K in 1..63 (the list has K + 1 entries).  The column stays with the cloud until the cloud gets new points (pccm_set_cloud, a
+ * pccm_merge_duplicates that removes rows, pccm_ctx_reset); new normals or colours, and anything that happens to the other
+ * cloud, leave it alone.  A call that finds the column at the same K does no work (*built = 0, else 1; built may be null) and is
+ * allowed during graph capture.  A build makes pending reductions stale and, when the column moves, captured graphs too; the
+ * pair's grid is rebuilt (as by pccm_ssim_features).
+ * PCCM_E_ARG: which is not 0 or 1; K outside 1..63.  PCCM_E_STATE: the cloud is missing; a sharded context; a build during graph
+ * capture. */
+int pccm_resolution_build(pccm_ctx *ctx, int which, int K, int *built);
+/* the spacing column of cloud `which`: n doubles (PCCM_E_STATE while it is not built) */
+int pccm_get_resolution(pccm_ctx *ctx, int which, double *out);
+
 /* Query-axis shard of this context: rank r of `world` owns, in every direction, the rows
  * [begin, end) of the iterating cloud returned by pccm_shard_range (boundaries are multiples
  * of 8192 rows -- whole chunks of NumPy's sum: pccm_reduce_chunks_many -- when the cloud has a chunk for every rank,
@@ -349,7 +378,7 @@ int pccm_set_ties(pccm_ctx *ctx, int policy);
 int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
 
 /* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR and
- * PCCM_METRIC_SSIM_* and PCCM_METRIC_P2D* ignore normal_mode. */
+ * PCCM_METRIC_SSIM_*, PCCM_METRIC_P2D* and PCCM_METRIC_RESOLUTION ignore normal_mode. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
 /* Fused reduction of a per-point metric over the shard: the np.sum / np.max of

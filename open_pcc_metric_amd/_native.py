@@ -34,6 +34,7 @@ METRIC_SSIM = {"geometry": 4, "normal": 5, "curvature": 6, "color": 7}
 METRIC_P2D = 8           # point-to-distribution (Mahalanobis) column of a direction (pccm_p2d_build; normal_mode does not apply)
 METRIC_P2D_COLOR = 9     # ... its colour (luma) column and
 METRIC_P2D_JOINT = 10    # ... its joint geometry-and-colour column (pccm_p2d_build_attrs with P2D_COLOR)
+METRIC_RESOLUTION = 11   # point spacings of the cloud a direction iterates (pccm_resolution_build; normal_mode does not apply)
 P2D_GEOMETRY, P2D_COLOR = 1, 2      # PCCM_P2D_*: what pccm_p2d_build_attrs builds (P2D_COLOR: the colour and the joint column)
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
@@ -43,7 +44,8 @@ SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_carry_normals",
     "pccm_merge_duplicates", "pccm_get_merge_map", "pccm_get_points", "pccm_get_colors",
-    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
+    "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours",
+    "pccm_resolution_build", "pccm_get_resolution", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
@@ -120,6 +122,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_p2d_build.argtypes = [vp, i32, ctypes.POINTER(i32)]
     lib.pccm_p2d_build_attrs.argtypes = [vp, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_p2d_neighbours.argtypes = [vp, i32, vp, vp]
+    lib.pccm_resolution_build.argtypes = [vp, i32, i32, ctypes.POINTER(i32)]
+    lib.pccm_get_resolution.argtypes = [vp, i32, vp]
     lib.pccm_shard_range.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.pccm_nn.argtypes = [vp, i32, i32]
     lib.pccm_nn_pair.argtypes = [vp, i32]
@@ -565,6 +569,19 @@ class Engine:
         _check(self._lib.pccm_get_p2d_neighbours(self._ctx, int(direction), rows.ctypes.data_as(ctypes.c_void_p),
                                                  counts.ctypes.data_as(ctypes.c_void_p)))
         return rows, counts
+
+    def resolution_build(self, which: int, k: int) -> bool:
+        """Build (or find) cloud ``which``'s point spacings over ``k`` neighbours in HBM; True when work was done
+        (pccm_resolution_build)."""
+        built = ctypes.c_int32()
+        _check(self._lib.pccm_resolution_build(self._ctx, int(which), int(k), ctypes.byref(built)))
+        return bool(built.value)
+
+    def get_resolution(self, which: int) -> np.ndarray:
+        """Cloud ``which``'s point spacings, n doubles (pccm_get_resolution)."""
+        out = np.empty(self._n[which], dtype=np.float64)
+        _check(self._lib.pccm_get_resolution(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def set_shard(self, rank: int, world: int) -> None:
         _check(self._lib.pccm_set_shard(self._ctx, int(rank), int(world)))

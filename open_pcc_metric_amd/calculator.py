@@ -15,8 +15,8 @@ import pandas as pd
 
 from .cloud_pair import CloudPair
 from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, ColorMahalanobisDistances, EuclideanDistance,
-                     GeoRankedHausdorffDistance, JointMahalanobisDistances, MahalanobisDistances, PrimaryMetric, SecondaryMetric,
-                     SSIMSimilarities, SymmetricMetric)
+                     GeoRankedHausdorffDistance, JointMahalanobisDistances, MahalanobisDistances, PointSpacings, PrimaryMetric,
+                     SecondaryMetric, SSIMSimilarities, SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -100,6 +100,8 @@ class MetricCalculator:
                 wanted.append(("p2d_joint", metric.is_left, metric.k))
             elif isinstance(metric, MahalanobisDistances):
                 wanted.append(("p2d", metric.is_left, metric.k))
+            elif isinstance(metric, PointSpacings):
+                wanted.append(("spacing", metric.is_left, metric.k))
             (late if waits else early).append((metric, None, key))
         elif role == 2:
             if isinstance(metric, EuclideanDistance):

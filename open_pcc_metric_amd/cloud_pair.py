@@ -131,7 +131,9 @@ class DeviceColumn(_DeviceArray):
     ``"p2d"``       point-to-distribution (Mahalanobis) distances (get_left/right_mahalanobis_distances; PCCM_METRIC_P2D: the
                     direction's stored column, at the neighbourhood size the pair's columns were built with),
     ``"p2d_color"`` / ``"p2d_joint"``  its colour and joint columns (get_left/right_color_mahalanobis_distances,
-                    get_left/right_joint_mahalanobis_distances; PCCM_METRIC_P2D_COLOR / PCCM_METRIC_P2D_JOINT).
+                    get_left/right_joint_mahalanobis_distances; PCCM_METRIC_P2D_COLOR / PCCM_METRIC_P2D_JOINT),
+    ``"spacing"``   the point spacings of the cloud the direction iterates (get_left/right_point_spacings;
+                    PCCM_METRIC_RESOLUTION: that cloud's stored column, over the neighbours it was built with).
     """
 
     def __init__(self, pair: "CloudPair", direction: int, kind: str):
@@ -142,7 +144,7 @@ class DeviceColumn(_DeviceArray):
 
     _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2,
                "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}, "p2d": nat.METRIC_P2D,
-               "p2d_color": nat.METRIC_P2D_COLOR, "p2d_joint": nat.METRIC_P2D_JOINT}
+               "p2d_color": nat.METRIC_P2D_COLOR, "p2d_joint": nat.METRIC_P2D_JOINT, "spacing": nat.METRIC_RESOLUTION}
 
     def _materialise(self) -> np.ndarray:
         p = self._pair
@@ -918,6 +920,41 @@ class CloudPair:
     def get_right_joint_mahalanobis_distances(self, k: int = 30):
         return self._p2d_column(nat.DIR_RIGHT, k, "p2d_joint")
 
+    # -- resolution-adaptive PSNR ("Resolution-adaptive PSNR") -------------------------------------------------
+    def _check_resolution(self, k: int) -> None:
+        """The ValueErrors of CalculateOptions and options.check_resolution_psnr, for this pair -- raised before any GPU work of
+        a report.  (``ties="mean"`` is fine: the column does not depend on the policy.)"""
+        from .options import CalculateOptions, check_resolution_psnr
+        check_resolution_psnr(CalculateOptions(resolution_psnr=True, resolution_neighbours=k),
+                              group=self._coll.group if self._coll.sharded else None)
+
+    def _ensure_resolution(self, k: int) -> None:
+        """Both clouds' spacing columns over ``k`` neighbours, built in HBM where missing (pccm_resolution_build: the origin
+        cloud's survives with_reconst, so only the new cloud's is built then)."""
+        self._check_resolution(k)
+        if not hasattr(self._engine, "resolution_build"):
+            raise ValueError("this engine has no point spacings")
+        built = False
+        for which in (0, 1):
+            built = self._engine.resolution_build(which, int(k)) or built
+        if built or self.__dict__.get("_resolution_k") != int(k):     # totals of earlier columns are stale
+            self._totals = {key: v for key, v in self._totals.items() if key[1] != nat.METRIC_RESOLUTION}
+        self._resolution_k = int(k)
+
+    def _spacing_column(self, direction: int, k: int) -> DeviceColumn:
+        self._ensure_resolution(k)
+        return DeviceColumn(self, direction, "spacing")
+
+    def get_left_point_spacings(self, k: int = 10):
+        """Per point of the origin cloud: the mean distance to its k nearest neighbours in the origin cloud (fp64; a device
+        column: ``np.asarray`` fetches it, ``np.sum`` / ``np.max`` reduce it on the GPU).  ``np.sum(...) / n`` is the cloud's
+        intrinsic resolution.  Neither the other cloud nor the tie policy enters it."""
+        return self._spacing_column(nat.DIR_LEFT, k)
+
+    def get_right_point_spacings(self, k: int = 10):
+        """The same for the reconstructed cloud."""
+        return self._spacing_column(nat.DIR_RIGHT, k)
+
     def get_left_neighbour_colors(self):
         """cloud_pair.py:120-121: the matched points' colours -- gathered on the device when asked for."""
         return DeviceColorRows(self, nat.DIR_LEFT, "neighbour")
@@ -930,7 +967,7 @@ class CloudPair:
 
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
         ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
-        ``("p2d_joint", is_left, k)`` and/or the string ``"boundary"``.
+        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -963,10 +1000,17 @@ class CloudPair:
             self._check_p2d(k, color)
         for k, color in p2d_color.items():
             self._ensure_p2d(k, color)
+        # point spacings: likewise, one build per cloud and neighbour count; their requests ride with the other stored columns
+        spacing_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "spacing"]
+        for k in sorted({item[2] for item in spacing_items}):
+            self._check_resolution(k)
+        for k in sorted({item[2] for item in spacing_items}):
+            self._ensure_resolution(k)
         requests, ssim_requests, selections = [], [], []
-        p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, DeviceColumn._METRIC[item[0]]) for item in p2d_items]
+        stored_items = p2d_items + spacing_items
+        p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, DeviceColumn._METRIC[item[0]]) for item in stored_items]
         for item in wanted:
-            if item in ranked_items or item in p2d_items:
+            if item in ranked_items or item in stored_items:
                 continue              # (ranked: their columns are requests of their own, EuclideanDistance's)
             if item in ssim_items:
                 ssim_requests.append((nat.DIR_LEFT if item[2] else nat.DIR_RIGHT, nat.METRIC_SSIM[item[1]]))

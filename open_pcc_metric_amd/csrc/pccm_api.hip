@@ -143,6 +143,10 @@ static void free_cloud(Cloud &c)
     c.ssim64 = nullptr;
     c.cap_ssim = 0;
     c.ssim_attrs = c.ssim_k = 0;
+    if (c.res64) (void)hipFree(c.res64);
+    c.res64 = nullptr;
+    c.cap_res = 0;
+    c.res_k = 0;
     c.sp = nullptr;
     c.cap_sp = 0;
     c.sp_valid = false;
@@ -167,6 +171,7 @@ static void drop_cloud(Cloud &c)
     c.sp_valid = c.sp_tried = false;
     c.rgb8_valid = false;
     c.ssim_attrs = c.ssim_k = 0;
+    c.res_k = 0;
 }
 
 static void free_nn(NNResult &r)
@@ -1200,6 +1205,30 @@ int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out)
     return PCCM_OK;
 }
 
+int pccm_resolution_build(pccm_ctx *ctx, int which, int K, int *built)
+{
+    CHECK_CTX(ctx);
+    if (built) *built = 0;
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (K < 1 || K > 63) return fail(PCCM_E_ARG, "point spacings average 1..63 neighbours, not %d", K);
+    if (ctx->cloud[which].n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "point spacings need the whole cloud on this GPU (world = 1)");
+    return resolution_build(ctx, which, K, built);     // (what is there already needs no work, and may be asked for while capturing)
+}
+
+int pccm_get_resolution(pccm_ctx *ctx, int which, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    const Cloud &c = ctx->cloud[which];
+    if (c.n <= 0 || c.res_k <= 0) return fail(PCCM_E_STATE, "the point spacings of cloud %d are not built (pccm_resolution_build)", which);
+    { int rcd = d2h(ctx, out, c.res64, (size_t)c.n * sizeof(double)); if (rcd) return rcd; }
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
+}
+
 int pccm_p2d_build_attrs(pccm_ctx *ctx, int k, int attrs, int *built)
 {
     CHECK_CTX(ctx);
@@ -1613,8 +1642,18 @@ static int check_p2d(pccm_ctx *ctx, int dir, int metric)
     return PCCM_OK;
 }
 
-static const double *p2d_column(const pccm_ctx *ctx, int dir, int metric)
+// PCCM_METRIC_RESOLUTION: the stored spacing column of the cloud the direction iterates (pccm_resolution_build)
+static int check_resolution(const pccm_ctx *ctx, int dir)
 {
+    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "the spacing column belongs to directions 0 and 1, not to the self search");
+    if (ctx->cloud[dir].res_k <= 0) return fail(PCCM_E_STATE, "the point spacings of cloud %d are not built (pccm_resolution_build)", dir);
+    return PCCM_OK;
+}
+
+// the column of a stored metric (is_stored_metric) that column_check has passed
+static const double *stored_column(const pccm_ctx *ctx, int dir, int metric)
+{
+    if (metric == PCCM_METRIC_RESOLUTION) return ctx->cloud[dir].res64;
     return metric == PCCM_METRIC_P2D ? ctx->p2d64[dir] : ctx->p2d_cj64[dir][metric - PCCM_METRIC_P2D_COLOR];
 }
 
@@ -1632,6 +1671,7 @@ static int column_check(pccm_ctx *ctx, int dir, int metric, int normal_mode, con
     if (metric == PCCM_METRIC_ANGULAR) return check_angular(ctx, dir, it, se);
     if (is_ssim_metric(metric)) return check_ssim(ctx, dir, it, se, res, metric);
     if (is_p2d_metric(metric)) return check_p2d(ctx, dir, metric);
+    if (metric == PCCM_METRIC_RESOLUTION) return check_resolution(ctx, dir);
     if (!normal_mode_enters(metric)) return fail(PCCM_E_ARG, "bad metric %d", metric);
     if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "point-to-plane is not defined for the self search");
     return check_normals(ctx, it, se, res, normal_mode);
@@ -1705,8 +1745,8 @@ static int metric_on_device(pccm_ctx *ctx, int dir, int metric, int normal_mode,
     if (metric == PCCM_METRIC_D1) {
         if ((rc = ensure_plain(ctx, *res, false))) return rc;
         *dev = res->d2;
-    } else if (is_p2d_metric(metric)) {
-        *dev = p2d_column(ctx, dir, metric) + res->begin;
+    } else if (is_stored_metric(metric)) {
+        *dev = stored_column(ctx, dir, metric) + res->begin;
     } else if (metric == PCCM_METRIC_ANGULAR && res->ties == PCCM_TIES_MEAN) {     // the tie pass makes the column
         if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
         *dev = (const double *)ctx->tie[dir].ang.p;
@@ -1798,7 +1838,7 @@ struct ColumnSource {
         kPlainD2,         // the plain d2 column (no records: the engine wrote the plain columns)
         kPointJob,        // a k_point_jobs job that reads the matched rows from the plain idx column, or from matched records (recs)
         kTieColumn,       // the tie pass's column (PCCM_TIES_MEAN)
-        kStored,          // a stride-1 column kept with the context (PCCM_METRIC_P2D*: pccm_p2d_build_attrs)
+        kStored,          // a stride-1 column kept with the context or a cloud (PCCM_METRIC_P2D*, PCCM_METRIC_RESOLUTION)
     } from = kPointJob;
     // the plain columns: none needed or they are there; the binder unpacks them; or they come before any column of the batch is
     // bound.  Which columns the binder unpacks (an unfused projection over stride-4 records) is today's split: it decides which
@@ -1821,7 +1861,7 @@ static ColumnSource column_source(const pccm_ctx *ctx, int dir, int metric, int 
         return c;
     }
     if (dir == PCCM_DIR_SELF) return c;
-    if (is_p2d_metric(metric)) {
+    if (is_stored_metric(metric)) {
         c.from = ColumnSource::kStored;
         return c;
     }
@@ -1866,7 +1906,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         if ((rc = ensure_ties(ctx, dir, false, false, true))) return rc;
         dev = (const double *)ctx->tie[dir].ang.p;
         break;
-    case ColumnSource::kStored: dev = p2d_column(ctx, dir, metric) + res->begin; break;
+    case ColumnSource::kStored: dev = stored_column(ctx, dir, metric) + res->begin; break;
     case ColumnSource::kPointJob:
         // (PCCM_METRIC_SSIM_*: the angular column's job on the two clouds' feature columns instead of their normals)
         if (src.prep != ColumnSource::kReady && (rc = ensure_plain(ctx, *res, true))) return rc;

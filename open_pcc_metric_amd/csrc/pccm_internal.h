@@ -79,6 +79,10 @@ struct Cloud {
     double *ssim64 = nullptr;
     size_t cap_ssim = 0;
     int ssim_attrs = 0, ssim_k = 0;
+    // point spacings (pccm_resolution_build): [n] fp64, valid for res_k neighbours (0: not built); dropped with the points only
+    double *res64 = nullptr;
+    size_t cap_res = 0;
+    int res_k = 0;
     double solo_scale = 1.0;    // cell-edge factor of a grid over this cloud alone (grid_ensure_solo), decided for ...
     uint64_t solo_scale_version = ~0ull;   // ... this version of the cloud
 };
@@ -478,6 +482,7 @@ int grid_prefers_brute(pccm_ctx *ctx, bool *yes); // builds the grid if needed; 
 int estimate_normals(pccm_ctx *ctx, int which, int k);
 int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built);   // the checks are pccm_ssim_features'
 int p2d_build(pccm_ctx *ctx, int k, int attrs, int *built);                  // the checks are pccm_p2d_build_attrs'
+int resolution_build(pccm_ctx *ctx, int which, int K, int *built);           // the checks are pccm_resolution_build's
 int p2d_neighbours(pccm_ctx *ctx, int dir, int k, const int32_t **nbr, const int32_t **cnt);   // device lists [n][k], [n]
 int tie_exposure(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, const NNResult &res, int normal_mode, double out[8]);
 // PCCM_TIES_MEAN producer: for the ns queries q_begin.. of direction dir (matched rows idx, squared distances d2 or null = formed
@@ -552,6 +557,13 @@ __device__ __forceinline__ double ssim_similarity(double a, double b)
 __host__ __device__ __forceinline__ bool is_p2d_metric(int metric)
 {
     return metric >= PCCM_METRIC_P2D && metric <= PCCM_METRIC_P2D_JOINT;
+}
+
+// every column kept in HBM and bound as it is (ColumnSource::kStored): the point-to-distribution columns of a direction, and the
+// spacing column (PCCM_METRIC_RESOLUTION, pccm_resolution_build) of the cloud the direction iterates
+__host__ __device__ __forceinline__ bool is_stored_metric(int metric)
+{
+    return is_p2d_metric(metric) || metric == PCCM_METRIC_RESOLUTION;
 }
 
 __host__ __device__ __forceinline__ bool is_ssim_metric(int metric)

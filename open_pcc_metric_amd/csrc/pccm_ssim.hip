@@ -81,6 +81,10 @@ __global__ __launch_bounds__(256) void k_ssim_curvature(const double *__restrict
 //   m values v_j over N_k(p), mu = (sum v_j) / m, F = (sum (v_j - mu)^2) / (m - 1), F = 0 for m < 2; left-to-right sums, every
 //   operation separately rounded.  Geometry and normal skip q_0 (the point itself).  The values are formed twice (two passes)
 //   instead of being kept: up to 64 of them per thread would live in scratch memory.
+// kSsimSpacing in `attrs` (resolution_build; no PointSSIM attribute beside it): the point's spacing instead -- the MEAN of the
+//   geometry values, r = (sum_{j >= 1} sqrt(d2(p, q_j))) / (c - 1) in one pass, 0 for c < 2 -- into feat[n] (include/pccm.h,
+//   pccm_resolution_build).
+constexpr int kSsimSpacing = 16;
 __global__ __launch_bounds__(256) void k_ssim_features(const double *__restrict__ x64, const double *__restrict__ nrm64,
                                                        const double *__restrict__ rgb64, const double *__restrict__ curv,
                                                        const int32_t *__restrict__ nbr, const int32_t *__restrict__ cnt, int k, int64_t n,
@@ -90,6 +94,16 @@ __global__ __launch_bounds__(256) void k_ssim_features(const double *__restrict_
     if (i >= n) return;
     const int32_t *row = nbr + i * k;
     const int c = cnt[i];
+    if (attrs & kSsimSpacing) {
+        double r = 0.0;
+        if (c >= 2) {
+            double sum = 0.0;
+            for (int j = 1; j < c; ++j) sum = __dadd_rn(sum, ssim_value(0, i, row[j], x64, nrm64, curv, rgb64));
+            r = __ddiv_rn(sum, (double)(c - 1));
+        }
+        feat[i] = r;
+        return;
+    }
     for (int a = 0; a < 4; ++a) {
         if (!(attrs & (1 << a))) continue;
         const int j0 = (a <= 1) ? 1 : 0;
@@ -158,6 +172,47 @@ int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
     PCCM_HIP(hipGetLastError());
     c.ssim_k = k;
     c.ssim_attrs = attrs;
+    if (built) *built = 1;
+    return PCCM_OK;
+}
+
+// Point spacings of cloud `which` (pccm_resolution_build has checked K, the cloud and the shard).  The searches of ssim_features
+// at k = K + 1 in neighbour-list mode, then k_ssim_features' spacing branch on the lists.  The lists are scratch: 4 (K + 1) bytes
+// per point.
+int resolution_build(pccm_ctx *ctx, int which, int K, int *built)
+{
+    Cloud &c = ctx->cloud[which];
+    if (built) *built = 0;
+    if (c.res_k == K) return PCCM_OK;
+    if (ctx->capturing) {
+        ctx->capture_failed = true;
+        return fail(PCCM_E_STATE, "point spacings are built before graph capture");
+    }
+    const int k = K + 1;
+    int rc;
+    KnnGeom g;
+    const uint32_t *cs;
+    const GridRec *crecs;
+    if ((rc = knn_setup(ctx, which, g, cs, crecs))) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    const double *before = c.res64;
+    if ((rc = grow((void **)&c.res64, c.cap_res, (size_t)c.n * sizeof(double)))) return rc;
+    c.res_k = 0;
+    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending reductions of the column would read stale spacings
+    if (c.res64 != before) ctx->epoch++;                // (graphs that read the old column are stale)
+    double *cov;
+    int32_t *cnt;
+    uint32_t *open_count, *todo_count;
+    if ((rc = knn_scratch(ctx, c.n, &cov, &cnt, &open_count, &todo_count))) return rc;
+    if ((rc = ensure(ctx, ctx->ssim_scratch, (size_t)c.n * k * sizeof(int32_t)))) return rc;
+    int32_t *nbr = (int32_t *)ctx->ssim_scratch.p;
+    launch_knn(ctx, crecs, cs, g, c.xyz64, c.n, crecs, nullptr, c.xyz64, c.n, k, cov, cnt, open_count, todo_count,
+               KnnSink{nullptr, nbr});
+    PCCM_LAUNCH(ctx, k_ssim_features, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)c.xyz64,
+                       (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const int32_t *)nbr,
+                       (const int32_t *)cnt, k, c.n, kSsimSpacing, c.res64);
+    PCCM_HIP(hipGetLastError());
+    c.res_k = K;
     if (built) *built = 1;
     return PCCM_OK;
 }

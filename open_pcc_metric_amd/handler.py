@@ -3,7 +3,7 @@
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
                                   [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
-                                  [--csv]
+                                  [--resolution-psnr] [--resolution-neighbours K] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -35,7 +35,11 @@ error.  ``--duplicates drop|average`` (default ``keep``: nothing changes; no cou
 before anything is searched, the points of each file that share their coordinates, as ``pc_error`` does with both clouds
 (dropDuplicates): one point per position, with the first one's normal and the first one's colour (``drop``) or the average colour
 (``average``, pc_error's default); a line per cloud on stderr says how many rows were merged away ("Duplicate
-points").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+points").  ``--resolution-psnr`` (no counterpart in the reference) adds, after all others, the resolution-adaptive PSNR rows after
+Javaheri et al. (ICIP 2020): each cloud's intrinsic resolution -- the average distance of a point to its
+``--resolution-neighbours`` nearest neighbours in its own cloud -- and the PSNR of the D1 and, with ``--point-to-plane``, D2 errors
+(with ``--hausdorff`` also of the Hausdorff distances) against the ORIGINAL cloud's resolution as the peak, instead of its
+bounding box ("Resolution-adaptive PSNR").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -84,6 +88,12 @@ import click
               help="Merge the points of each cloud that share their coordinates before comparing, as MPEG's pc_error does "
                    "(dropDuplicates): one point per position, with the first point's normal and the first point's colour (drop) "
                    "or the average colour (average, pc_error's default).  keep: nothing is merged.")
+@click.option("--resolution-psnr", "resolution_psnr", required=False, is_flag=True,
+              help="Report each cloud's intrinsic resolution (the average distance of a point to its nearest neighbours in its own "
+                   "cloud) and PSNR rows whose peak is the original cloud's resolution as well, after all other rows; with "
+                   "--point-to-plane for D2 and with --hausdorff for the Hausdorff distances too.  Does not depend on --ties.")
+@click.option("--resolution-neighbours", "resolution_neighbours", type=click.IntRange(1, 63), default=10, show_default=True,
+              help="Nearest neighbours a point's spacing is averaged over (the point itself not counted).")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -98,25 +108,27 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
     from .options import (CalculateOptions, check_carry_normals, check_duplicates, check_hausdorff_rank, check_p2d_color, check_point_ssim,
-                          check_point_to_distribution, transform_options)
+                          check_point_to_distribution, check_resolution_psnr, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
         options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
                                    point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None,
                                    point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours,
-                                   p2d_color=p2d_color)
+                                   p2d_color=p2d_color, resolution_psnr=resolution_psnr,
+                                   resolution_neighbours=resolution_neighbours)
         check_carry_normals(carry_normals, ties=ties)
         check_duplicates(duplicates)
     except ValueError as exc:
         raise click.UsageError(str(exc))
     check_hausdorff_rank(options)
     check_point_to_distribution(options)
+    check_resolution_psnr(options)
     ocloud_cloud = read_point_cloud(ocloud)
     cloud_pair = None
     for path in pcloud:

@@ -173,6 +173,21 @@ class JointMahalanobisDistances(MahalanobisDistances):           # no counterpar
                            lambda: cloud_pair.get_right_joint_mahalanobis_distances(self.k))
 
 
+class PointSpacings(PrimaryMetric, DirectionalMetric):           # no counterpart in the reference (options.py: resolution_psnr)
+    """Per point of ONE cloud -- left: the origin cloud, right: the reconstructed one -- the mean distance to its k nearest
+    neighbours in that same cloud (include/pccm.h, pccm_resolution_build; INTEGRATION.md, "Resolution-adaptive PSNR")."""
+    def __init__(self, is_left: bool, k: int = 10):
+        super().__init__(is_left)
+        self.k = int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.k)
+
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, lambda: cloud_pair.get_left_point_spacings(self.k),
+                           lambda: cloud_pair.get_right_point_spacings(self.k))
+
+
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, cloud_pair: CloudPair) -> None:
@@ -466,6 +481,59 @@ class GeoRankedHausdorffDistancePSNR(SecondaryMetric, PointToPlaneable):
 
     def calculate(self, max_sqrt: MaxSqrtDistance, ranked_distance: GeoRankedHausdorffDistance) -> None:
         self.value = _psnr(max_sqrt.value, ranked_distance.value)
+
+
+class IntrinsicResolution(SecondaryMetric, DirectionalMetric):   # no counterpart in the reference (options.py: resolution_psnr)
+    """Intrinsic resolution of one cloud (after Javaheri et al., ICIP 2020): the mean of its point spacings (sum / n, NumPy's
+    pairwise sum).  A property of the cloud, not a comparison: left is the origin cloud, right the reconstructed one."""
+    _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+
+    def __init__(self, is_left: bool, k: int = 10):
+        super().__init__(is_left)
+        self.k = int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.k)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"point_spacings": PointSpacings(is_left=self.is_left, k=self.k)}
+
+    def calculate(self, point_spacings: PointSpacings) -> None:
+        column = point_spacings.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
+        total = fused()[0] if fused is not None else None
+        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+
+
+class _ResolutionPSNR(SecondaryMetric, PointToPlaneable):
+    """A PSNR whose peak is the ORIGIN cloud's intrinsic resolution over k neighbours, for both sides (as GeoPSNR always takes
+    the origin's extent): no dependency reaches CloudExtent or MaxSqrtDistance."""
+    def __init__(self, is_left: bool, point_to_plane: bool, k: int = 10):
+        super().__init__(is_left, point_to_plane)
+        self.k = int(k)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.point_to_plane, self.k)
+
+
+class GeoResolutionPSNR(_ResolutionPSNR):
+    """GeoPSNR's expression (metric.py:231-247) with the origin cloud's intrinsic resolution as the peak."""
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"resolution": IntrinsicResolution(is_left=True, k=self.k),
+                "geo_mse": GeoMSE(is_left=self.is_left, point_to_plane=self.point_to_plane)}
+
+    def calculate(self, resolution: IntrinsicResolution, geo_mse: GeoMSE) -> None:
+        self.value = _psnr(resolution.value, geo_mse.value)
+
+
+class GeoHausdorffResolutionPSNR(_ResolutionPSNR):
+    """GeoHausdorffDistancePSNR's expression (metric.py:369-386) with the origin cloud's intrinsic resolution as the peak."""
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"resolution": IntrinsicResolution(is_left=True, k=self.k),
+                "hausdorff_distance": GeoHausdorffDistance(is_left=self.is_left, point_to_plane=self.point_to_plane)}
+
+    def calculate(self, resolution: IntrinsicResolution, hausdorff_distance: GeoHausdorffDistance) -> None:
+        self.value = _psnr(resolution.value, hausdorff_distance.value)
 
 
 # --------------------------------------------------------------------------- colour secondaries

@@ -43,6 +43,15 @@ point-to-distribution metric after Javaheri et al., IEEE MMSP 2021), after every
   p2d_color & hd               MaxColorMahalanobisDistance L/R/sym
   p2d_color & hd               MaxJointMahalanobisDistance L/R/sym
 
+and, with ``resolution_psnr`` (no counterpart in the reference: the resolution-adaptive PSNR after Javaheri et al., ICIP 2020,
+whose peak is the origin cloud's intrinsic resolution over ``resolution_neighbours`` neighbours), after every row above:
+
+  resolution_psnr              IntrinsicResolution L, R (the clouds' own resolutions: no symmetric row)
+  resolution_psnr              GeoResolutionPSNR L/R/sym (D1)
+  resolution_psnr & p2plane    GeoResolutionPSNR L/R/sym with point_to_plane=True
+  resolution_psnr & hd         GeoHausdorffResolutionPSNR L/R/sym (D1)
+  ... & hd & p2plane           GeoHausdorffResolutionPSNR L/R/sym with point_to_plane=True
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -54,8 +63,9 @@ import math
 import numbers
 
 from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
-                     GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoMSE, GeoPSNR, GeoRankedHausdorffDistance,
-                     GeoRankedHausdorffDistancePSNR, JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
+                     GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
+                     GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
+                     JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
                      MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
                      SymmetricMetric)
 
@@ -63,6 +73,7 @@ SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row ord
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
 MAX_HAUSDORFF_RANKS = 4
 P2D_MIN_K, P2D_MAX_K = 4, 64
+RESOLUTION_MIN_K, RESOLUTION_MAX_K = 1, 63
 
 
 def _hausdorff_ranks(value) -> typing.Tuple[float, ...]:
@@ -90,7 +101,7 @@ class CalculateOptions:
                  point_to_plane: bool = False, plane_to_plane: bool = False,
                  point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
-                 p2d_color: bool = False):
+                 p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -116,6 +127,12 @@ class CalculateOptions:
         if p2d_color and not self.point_to_distribution:
             raise ValueError("p2d_color adds rows to the point-to-distribution metric: it needs point_to_distribution=True")
         self.p2d_color = bool(p2d_color)
+        k = resolution_neighbours
+        if isinstance(k, bool) or type(k).__name__ == "bool_" or not isinstance(k, numbers.Real) \
+                or not math.isfinite(k) or int(k) != k or not RESOLUTION_MIN_K <= int(k) <= RESOLUTION_MAX_K:
+            raise ValueError(f"resolution_neighbours must be an integer in {RESOLUTION_MIN_K}..{RESOLUTION_MAX_K}, not {k!r}")
+        self.resolution_psnr = bool(resolution_psnr)
+        self.resolution_neighbours = int(k)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -191,6 +208,14 @@ def check_p2d_color(options: CalculateOptions, origin_cloud, reconst_cloud, *, g
         raise ValueError("the colour and joint point-to-distribution rows (p2d_color) need the colours of both clouds")
 
 
+def check_resolution_psnr(options: CalculateOptions, *, group=None) -> None:
+    """Raise ``ValueError`` when the resolution-adaptive PSNR rows ``options`` asks for cannot be computed for this pair -- before
+    any GPU work (the command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).
+    A cloud's spacings come from a k-NN search of the whole cloud on one GPU: a sharded pair is out of scope."""
+    if getattr(options, "resolution_psnr", False) and group is not None:
+        raise ValueError("resolution-adaptive PSNR rows are not available for sharded pairs (group=)")
+
+
 def _sides(cls, **kw):
     return [cls(is_left=True, **kw), cls(is_left=False, **kw)]
 
@@ -243,4 +268,12 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
             if options.hausdorff:
                 for cls in (MaxColorMahalanobisDistance, MaxJointMahalanobisDistance):
                     metrics += _sides(cls, **kw) + [_sym(cls, False, **kw)]
+    if getattr(options, "resolution_psnr", False):
+        k = getattr(options, "resolution_neighbours", 10)
+        metrics += _sides(IntrinsicResolution, k=k)
+        # higher is better: the symmetric rows report the smaller side
+        for cls in (GeoResolutionPSNR, GeoHausdorffResolutionPSNR) if options.hausdorff else (GeoResolutionPSNR,):
+            for point_to_plane in (False, True) if options.point_to_plane else (False,):
+                kw = dict(point_to_plane=point_to_plane, k=k)
+                metrics += _sides(cls, **kw) + [_sym(cls, True, **kw)]
     return metrics
