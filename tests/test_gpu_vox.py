@@ -9,7 +9,11 @@
   the same bricks: the voxels at exactly the nearest distance are enumerated and the smallest row among their points wins,
   the tie rule of every other kernel (include/pccm.h); a pair that was first read for distances only is searched again with
   the rows' table built;
-* PCCM_VOX=0 (the per-thread lattice search) gives the same numbers: tests/test_gpu_ab_paths.py."""
+* PCCM_VOX=0 (the per-thread lattice search) gives the same numbers: tests/test_gpu_ab_paths.py.
+
+The shells here put nearly every neighbour at d2 <= 3 in the query's cell or a face neighbour.  The planted integer cases of
+tests/test_gpu_vox_planted.py reach the rest: every table entry, exact ties at the tie list's boundary, the d2 = 64 / 65 hand-off,
+grid borders, crowded cells -- and pin how many queries each search leaves to the tail kernels."""
 import numpy as np
 import pytest
 

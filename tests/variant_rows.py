@@ -111,8 +111,8 @@ OTHER = {
     "k_tie_mean_scan": "ties='mean': test_gpu_ties_mean",
     "k_count_isolated<pccm::Rec32>": "grid scale decision: every fp32 row above",
     "k_count_isolated<pccm::GridRec>": "grid scale decision: every fp64 row above",
-    "k_vox_bricks": "voxel bricks: row 'vox'",
-    "k_vox_list": "voxel bricks: row 'vox'",
+    "k_vox_bricks": "voxel bricks: row 'vox'; planted per-voxel rows, tiles of more than 4096 records: test_gpu_vox_planted.py",
+    "k_vox_list": "voxel bricks: row 'vox'; grids of 1 .. 2.2M cells (several words per thread): test_gpu_vox_planted.py",
     "k_ingest_points<float>": "every fp32 row",
     "k_ingest_points<double>": "every fp64 row",
     "k_ingest_normals<float>": "every row with fp32-exact normals",
