@@ -117,13 +117,13 @@ OTHER = {
     "k_ingest_points<double>": "every fp64 row",
     "k_ingest_normals<float>": "every row with fp32-exact normals",
     "k_ingest_normals<double>": "every row with fp64 normals",
-    "k_color_rows<true>": "colours: test_gpu_color",
-    "k_color_rows<false>": "colours: test_gpu_color",
-    "k_colors_from_u8": "colours: test_gpu_color",
-    "k_colsum_approx": "colours: test_gpu_color",
-    "k_colsum_chain": "colours: test_gpu_color",
-    "k_colsum_units": "colours: test_gpu_color",
-    "k_rgb8_pack": "colours: test_gpu_color",
+    "k_color_rows<true>": "colours, the packed byte tables: test_gpu_color, test_gpu_color_planted (the byte decision, mixed pairs)",
+    "k_color_rows<false>": "colours as doubles: test_gpu_color, test_gpu_color_planted (off-byte values, NaN and inf)",
+    "k_colors_from_u8": "colours: test_gpu_color, test_gpu_color_planted (uchar beside double clouds)",
+    "k_colsum_approx": "colours: test_gpu_color, test_gpu_color_planted (planted columns, two jobs of unequal chunk counts, maxima)",
+    "k_colsum_chain": "colours: test_gpu_color, test_gpu_color_planted (planted columns, two jobs of unequal chunk counts, maxima)",
+    "k_colsum_units": "colours: test_gpu_color, test_gpu_color_planted (planted columns, two jobs of unequal chunk counts)",
+    "k_rgb8_pack": "colours: test_gpu_color, test_gpu_color_planted (values one ulp off, -0.0, out of range, NaN; kind changes)",
     "k_axis_hist": "box trimming: test_gpu_edges",
     "k_cell_hist": "grid scale decision: every grid row",
     "k_count_occupied": "grid scale decision: every grid row",
