@@ -11,7 +11,7 @@
 #include <new>
 #include <thread>
 
-#include "pccm_internal.h"
+#include "pccm_stale.h"
 
 namespace pccm {
 
@@ -66,9 +66,7 @@ int check_device_errors(pccm_ctx *ctx)
     if (!ctx->host_err) return PCCM_OK;
     const uint32_t e = __atomic_exchange_n(ctx->host_err, 0u, __ATOMIC_RELAXED);
     if (!e) return PCCM_OK;
-    for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
-    for (auto &s : ctx->slots) s.pending = false;
-    for (auto &q : ctx->sel_slots) q.pending = false;
+    results_dropped(ctx);
     return fail(PCCM_E_STATE, "a search kernel reported an inconsistent state (device error word 0x%x: %s%s%s): the results of this search were "
                               "dropped, run it again", e, (e & 1u) ? "the tail launch's wait for its own workgroups ran out; " : "",
                 (e & 2u) ? "a voxel brick contradicts its cell start; " : "", (e & kErrMergeTable) ? "the duplicate table overflowed" : "");
@@ -129,49 +127,13 @@ static void free_buf(DevBuf &b)
 
 static void free_cloud(Cloud &c)
 {
-    if (c.xyz32) (void)hipFree(c.xyz32);
-    if (c.xyz64) (void)hipFree(c.xyz64);
-    if (c.xyz32r) (void)hipFree(c.xyz32r);
-    c.xyz32r = nullptr;
-    c.cap32r = 0;
-    if (c.nrm64) (void)hipFree(c.nrm64);
-    if (c.nrm32) (void)hipFree(c.nrm32);
-    if (c.rgb64) (void)hipFree(c.rgb64);
-    if (c.rgb8) (void)hipFree(c.rgb8);
-    if (c.sp) (void)hipFree(c.sp);
-    if (c.ssim64) (void)hipFree(c.ssim64);
-    c.ssim64 = nullptr;
-    c.cap_ssim = 0;
-    c.ssim_attrs = c.ssim_k = 0;
-    if (c.res64) (void)hipFree(c.res64);
-    c.res64 = nullptr;
-    c.cap_res = 0;
-    c.res_k = 0;
-    c.sp = nullptr;
-    c.cap_sp = 0;
-    c.sp_valid = false;
-    c.xyz32 = nullptr;
-    c.xyz64 = nullptr;
-    c.nrm64 = nullptr;
-    c.nrm32 = nullptr;
-    c.rgb64 = nullptr;
-    c.rgb8 = nullptr;
-    c.cap_rgb8 = 0;
-    c.rgb8_valid = false;
-    c.cap32 = c.cap64 = c.cap_nrm = c.cap_nrm32 = c.cap_rgb = 0;
-    c.n = c.n_pad = c.n_nrm = c.n_rgb = 0;
-}
-
-// forget the content, keep the allocations
-static void drop_cloud(Cloud &c)
-{
-    c.n = c.n_pad = c.n_nrm = c.n_rgb = 0;
-    c.nrm_deferred = false;
-    c.nrm_host = nullptr;
-    c.sp_valid = c.sp_tried = false;
-    c.rgb8_valid = false;
-    c.ssim_attrs = c.ssim_k = 0;
-    c.res_k = 0;
+    for (void **p : {(void **)&c.xyz32, (void **)&c.xyz64, (void **)&c.xyz32r, (void **)&c.nrm64, (void **)&c.nrm32, (void **)&c.rgb64,
+                     (void **)&c.rgb8, (void **)&c.sp, (void **)&c.ssim64, (void **)&c.res64}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c.cap32 = c.cap64 = c.cap32r = c.cap_nrm = c.cap_nrm32 = c.cap_rgb = c.cap_rgb8 = c.cap_sp = c.cap_ssim = c.cap_res = 0;
+    drop_cloud(c);
 }
 
 static void free_nn(NNResult &r)
@@ -186,7 +148,6 @@ static void free_nn(NNResult &r)
     r.idx = nullptr;
     r.d2 = nullptr;
     r.cap = 0;
-    r.valid = false;
 }
 
 static void shard_of(int64_t n, int rank, int world, int64_t *b, int64_t *e)
@@ -319,26 +280,9 @@ static int upload(pccm_ctx *ctx, const void *src, size_t bytes, int on_device, c
     return PCCM_OK;
 }
 
-// Carried normals (pccm_carry_normals) do not outlive what they were made from: cloud `which` is getting new points
-// (points: both clouds enter a carry) or new normals -- the other cloud's normals go if they were carried from them; a target
-// whose normals are being replaced is an ordinary cloud again.
-static void carry_drop(pccm_ctx *ctx, int which, bool points)
-{
-    const int to = ctx->carry.to;
-    if (to < 0) return;
-    ctx->carry.to = -1;
-    if (to == which && !points) return;
-    Cloud &t = ctx->cloud[to];
-    t.n_nrm = 0;
-    t.nrm_exact32 = false;
-    t.ssim_attrs &= ~PCCM_SSIM_NORMAL;
-}
-
 // upload + widening copy + validation of one cloud's normals on stream `st` (staging buffer `stage` for host sources)
 static int ingest_normals(pccm_ctx *ctx, Cloud &c, int which, const void *nrm, int64_t n, int dtype, int on_device, hipStream_t st, DevBuf &stage)
 {
-    ctx->nrm_gen++;                                      // (averaged normals of PCCM_TIES_MEAN are stale)
-    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
     const size_t esz = dtype == PCCM_F32 ? 4 : 8;
     const void *dsrc = nrm;
     if (!on_device) {
@@ -509,8 +453,6 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
             ctx->cap_p2d_cj[d][c] = 0;
         }
     }
-    ctx->p2d_k = 0;
-    ctx->p2d_color = false;
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
@@ -546,20 +488,7 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     if (dtype != PCCM_F32 && dtype != PCCM_F64) return fail(PCCM_E_ARG, "dtype must be PCCM_F32 or PCCM_F64");
     Cloud &c = ctx->cloud[which];
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    carry_drop(ctx, which, true);                    // (normals carried to or from this cloud belong to the old points)
-    drop_cloud(c);                                   // its normals and colours go with it
-    ctx->merge_n[which] = 0;                         // (the merge map, pccm_merge_duplicates, spoke of the old rows)
-    ctx->p2d_k = 0;                                  // (both point-to-distribution columns depend on either cloud)
-    ctx->p2d_color = false;
-    // (a new cloud 1 leaves the self search of cloud 0 -- cloud_pair.py:108-109 -- as valid as it was: one reference cloud
-    // against several decoded ones, BASELINE configs[4], keeps it, see CloudPair.with_reconst)
-    for (int d = 0; d < 3; ++d) {
-        if (which == 1 && d == PCCM_DIR_SELF) continue;
-        ctx->nn[d].valid = false;
-        ctx->nn_gen[d]++;
-    }
-    ctx->epoch++;
-    c.version++;
+    points_changed(ctx, which);
     const int64_t n_pad = (n + kScanTile - 1) / kScanTile * kScanTile;
     int rc = grow((void **)&c.xyz32, c.cap32, (size_t)n_pad * 3 * sizeof(float));
     if (!rc) rc = grow((void **)&c.xyz64, c.cap64, (size_t)n * 3 * sizeof(double));
@@ -601,46 +530,37 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     return PCCM_OK;
 }
 
-int pccm_set_normals(pccm_ctx *ctx, int which, const void *nrm, int64_t n, int dtype, int on_device)
+// the front of the two normals setters: arguments, the stream drained, everything made from the old normals forgotten
+// (normals_changed), room for the new ones
+static int normals_front(pccm_ctx *ctx, int which, const void *nrm, int64_t n, int dtype)
 {
-    CHECK_CTX(ctx);
-    NOT_CAPTURING(ctx);
     if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
     if (!nrm || n <= 0) return fail(PCCM_E_ARG, "empty normals");
     if (dtype != PCCM_F32 && dtype != PCCM_F64) return fail(PCCM_E_ARG, "dtype must be PCCM_F32 or PCCM_F64");
     Cloud &c = ctx->cloud[which];
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending D2 reductions used the old normals
-    ctx->epoch++;
-    carry_drop(ctx, which, false);
-    c.n_nrm = 0;
-    c.nrm_exact32 = false;
-    c.nrm_deferred = false;
-    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
-    c.nrm_host = nullptr;
+    normals_changed(ctx, which);
     int rc = grow((void **)&c.nrm64, c.cap_nrm, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
-    if ((rc = grow((void **)&c.nrm32, c.cap_nrm32, (size_t)n * sizeof(float4)))) return rc;
-    return ingest_normals(ctx, c, which, nrm, n, dtype, on_device, ctx->stream, ctx->staging);
+    return grow((void **)&c.nrm32, c.cap_nrm32, (size_t)n * sizeof(float4));
+}
+
+int pccm_set_normals(pccm_ctx *ctx, int which, const void *nrm, int64_t n, int dtype, int on_device)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    int rc = normals_front(ctx, which, nrm, n, dtype);
+    if (rc) return rc;
+    return ingest_normals(ctx, ctx->cloud[which], which, nrm, n, dtype, on_device, ctx->stream, ctx->staging);
 }
 
 int pccm_set_normals_deferred(pccm_ctx *ctx, int which, const void *nrm, int64_t n, int dtype)
 {
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
-    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
-    if (!nrm || n <= 0) return fail(PCCM_E_ARG, "empty normals");
-    if (dtype != PCCM_F32 && dtype != PCCM_F64) return fail(PCCM_E_ARG, "dtype must be PCCM_F32 or PCCM_F64");
-    Cloud &c = ctx->cloud[which];
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;
-    ctx->epoch++;
-    carry_drop(ctx, which, false);
-    c.nrm_exact32 = false;
-    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
-    int rc = grow((void **)&c.nrm64, c.cap_nrm, (size_t)n * 3 * sizeof(double));
+    int rc = normals_front(ctx, which, nrm, n, dtype);
     if (rc) return rc;
-    if ((rc = grow((void **)&c.nrm32, c.cap_nrm32, (size_t)n * sizeof(float4)))) return rc;
+    Cloud &c = ctx->cloud[which];
     c.n_nrm = n;                                       // announced: the searches know that (and how many) normals exist
     c.nrm_host = nrm;
     c.nrm_host_dtype = dtype;
@@ -687,18 +607,10 @@ int pccm_flush_uploads(pccm_ctx *ctx)
     return PCCM_OK;
 }
 
-// new colours in either cloud: the colour and joint point-to-distribution columns of both directions go, the geometry columns stay
-static void drop_p2d_color(pccm_ctx *ctx)
+// the front of the two colour setters: arguments, the point count, the stream drained, everything made from the old colours
+// forgotten (colors_changed), room for the new ones in both forms
+static int colors_front(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dtype)
 {
-    if (!ctx->p2d_color) return;
-    ctx->p2d_color = false;
-    for (int d = 0; d < 2; ++d) ctx->nn_gen[d]++;      // pending reductions of those columns used the old colours
-}
-
-int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dtype, int on_device)
-{
-    CHECK_CTX(ctx);
-    NOT_CAPTURING(ctx);
     if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
     if (!rgb || n <= 0) return fail(PCCM_E_ARG, "empty colours");
     if (dtype != PCCM_F32 && dtype != PCCM_F64) return fail(PCCM_E_ARG, "dtype must be PCCM_F32 or PCCM_F64");
@@ -706,12 +618,19 @@ int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dt
     if (c.n == 0) return fail(PCCM_E_STATE, "set cloud %d before its colours", which);
     if (n != c.n) return fail(PCCM_E_ARG, "cloud %d has %lld points but %lld colours", which, (long long)c.n, (long long)n);
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    c.n_rgb = 0;
-    c.ssim_attrs &= ~PCCM_SSIM_COLOR;
-    drop_p2d_color(ctx);
-    ctx->rgb_gen++;
+    colors_changed(ctx, which);
     int rc = grow((void **)&c.rgb64, c.cap_rgb, (size_t)n * 3 * sizeof(double));
     if (rc) return rc;
+    return grow((void **)&c.rgb8, c.cap_rgb8, (size_t)n * sizeof(uint32_t));
+}
+
+int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dtype, int on_device)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    int rc = colors_front(ctx, which, rgb, n, dtype);
+    if (rc) return rc;
+    Cloud &c = ctx->cloud[which];
     const void *dsrc = nullptr;
     rc = upload(ctx, rgb, (size_t)n * 3 * (dtype == PCCM_F32 ? 4 : 8), on_device, &dsrc);
     if (rc) return rc;
@@ -720,8 +639,6 @@ int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dt
     rc = launch_ingest_normals(ctx, dsrc, dtype, n, c.rgb64, nullptr, stats);      // same widening copy; non-finite values are
     if (rc) return rc;                                                    // allowed here (NumPy propagates them)
     // colours that are bytes / 255 (nearly all are) also as packed words: Cloud::rgb8
-    c.rgb8_valid = false;
-    if ((rc = grow((void **)&c.rgb8, c.cap_rgb8, (size_t)n * sizeof(uint32_t)))) return rc;
     PCCM_HIP(hipMemsetAsync(stats + 4, 0, sizeof(unsigned long long), ctx->stream));
     if ((rc = launch_rgb8(ctx, c, nullptr, (unsigned int *)(stats + 4)))) return rc;
     unsigned long long not_bytes = 1;
@@ -736,25 +653,14 @@ int pccm_set_colors_u8(pccm_ctx *ctx, int which, const unsigned char *rgb, int64
 {
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
-    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
-    if (!rgb || n <= 0) return fail(PCCM_E_ARG, "empty colours");
-    Cloud &c = ctx->cloud[which];
-    if (c.n == 0) return fail(PCCM_E_STATE, "set cloud %d before its colours", which);
-    if (n != c.n) return fail(PCCM_E_ARG, "cloud %d has %lld points but %lld colours", which, (long long)c.n, (long long)n);
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    c.n_rgb = 0;
-    c.ssim_attrs &= ~PCCM_SSIM_COLOR;
-    drop_p2d_color(ctx);
-    ctx->rgb_gen++;
-    int rc = grow((void **)&c.rgb64, c.cap_rgb, (size_t)n * 3 * sizeof(double));
+    int rc = colors_front(ctx, which, rgb, n, PCCM_F64);      // (bytes: no dtype to check, they widen to fp64)
     if (rc) return rc;
+    Cloud &c = ctx->cloud[which];
     const void *dsrc = nullptr;
     rc = upload(ctx, rgb, (size_t)n * 3, 0, &dsrc);
     if (rc) return rc;
     rc = launch_colors_from_u8(ctx, (const unsigned char *)dsrc, n * 3, c.rgb64);
     if (rc) return rc;
-    c.rgb8_valid = false;
-    if ((rc = grow((void **)&c.rgb8, c.cap_rgb8, (size_t)n * sizeof(uint32_t)))) return rc;
     if ((rc = launch_rgb8(ctx, c, (const unsigned char *)dsrc, nullptr))) return rc;
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     c.rgb8_valid = true;
@@ -1008,10 +914,16 @@ int pccm_estimate_normals(pccm_ctx *ctx, int which, int knn)
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
     if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
-    ctx->nrm_gen++;
-    const int rc = estimate_normals(ctx, which, knn);
-    if (rc != PCCM_E_ARG && rc != PCCM_E_STATE) carry_drop(ctx, which, false);      // (those two come before the normals are touched)
-    return rc;
+    return estimate_normals(ctx, which, knn);
+}
+
+// the back of the getters (each has decided that what it hands out is there): the copy and the wait for it
+static int fetch(pccm_ctx *ctx, void *out, const void *dev, size_t bytes)
+{
+    int rc = d2h(ctx, out, dev, bytes);
+    if (rc) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return PCCM_OK;
 }
 
 int pccm_get_normals(pccm_ctx *ctx, int which, double *out)
@@ -1023,9 +935,7 @@ int pccm_get_normals(pccm_ctx *ctx, int which, double *out)
     Cloud &c = ctx->cloud[which];
     { int rcn = normals_ready(ctx, c); if (rcn) return rcn; }
     if (c.n_nrm <= 0) return fail(PCCM_E_STATE, "cloud %d has no normals", which);
-    { int rcd = d2h(ctx, out, c.nrm64, (size_t)c.n_nrm * 3 * sizeof(double)); if (rcd) return rcd; }
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    return PCCM_OK;
+    return fetch(ctx, out, c.nrm64, (size_t)c.n_nrm * 3 * sizeof(double));
 }
 
 int pccm_carry_normals(pccm_ctx *ctx, int from, int *built)
@@ -1056,16 +966,8 @@ int pccm_carry_normals(pccm_ctx *ctx, int from, int *built)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     if ((rc = grow((void **)&ct.nrm64, ct.cap_nrm, (size_t)ct.n * 3 * sizeof(double)))) return rc;
     if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(cf.n, ct.n)))) return rc;
-    carry_drop(ctx, to, false);                        // (normals carried the other way were made from the ones being replaced)
+    normals_changed(ctx, to);                          // (normals carried the other way were made from the ones being replaced)
     ct.n_nrm = ct.n;
-    ct.nrm_exact32 = false;
-    ct.nrm_deferred = false;
-    ct.nrm_host = nullptr;
-    ct.ssim_attrs &= ~PCCM_SSIM_NORMAL;
-    rf.form.fused = -1;                                // (a projection the search fused took cloud `to`'s earlier normals)
-    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending D2 reductions would use stale normals
-    ctx->epoch++;
-    ctx->nrm_gen++;
     if ((rc = launch_carry(ctx, rf.idx, rg.idx, cf.nrm64, cf.n, ct.n, (uint32_t *)ctx->carry_ws.p, ct.nrm64))) {
         ct.n_nrm = 0;
         return rc;
@@ -1106,9 +1008,8 @@ int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out)
     if (n_out) *n_out = (int64_t)n_new;
     if ((int64_t)n_new == n) return PCCM_OK;               // no duplicate: nothing is rewritten, nothing goes stale
     // rows go: what was made from the old rows goes with them, exactly as for new points (pccm_set_cloud below) -- normals that
-    // were carried to this cloud among it
-    if (ctx->carry.to == which) carry_drop(ctx, which, true);
-    const bool has_nrm = c.n_nrm == n, has_rgb = c.n_rgb == n;
+    // were carried to this cloud among it: they are not merged
+    const bool has_nrm = c.n_nrm == n && ctx->carry.to != which, has_rgb = c.n_rgb == n;
     const double *rgb = has_rgb ? c.rgb64 : nullptr;
     if (has_rgb && mode == PCCM_DUP_AVERAGE) {
         // the carry's passes with nn_F := rep: per representative the colours of its group, summed in ascending row order
@@ -1141,9 +1042,7 @@ int pccm_get_merge_map(pccm_ctx *ctx, int which, int32_t *out, int64_t *n_before
         for (int64_t i = 0; i < nb; ++i) out[i] = (int32_t)i;
         return PCCM_OK;
     }
-    { int rcd = d2h(ctx, out, ctx->merge_map[which].p, (size_t)nb * sizeof(int32_t)); if (rcd) return rcd; }
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    return PCCM_OK;
+    return fetch(ctx, out, ctx->merge_map[which].p, (size_t)nb * sizeof(int32_t));
 }
 
 int pccm_get_points(pccm_ctx *ctx, int which, double *out)
@@ -1154,9 +1053,7 @@ int pccm_get_points(pccm_ctx *ctx, int which, double *out)
     if (!out) return fail(PCCM_E_ARG, "null pointer");
     const Cloud &c = ctx->cloud[which];
     if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
-    { int rcd = d2h(ctx, out, c.xyz64, (size_t)c.n * 3 * sizeof(double)); if (rcd) return rcd; }
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    return PCCM_OK;
+    return fetch(ctx, out, c.xyz64, (size_t)c.n * 3 * sizeof(double));
 }
 
 int pccm_get_colors(pccm_ctx *ctx, int which, double *out)
@@ -1167,9 +1064,7 @@ int pccm_get_colors(pccm_ctx *ctx, int which, double *out)
     if (!out) return fail(PCCM_E_ARG, "null pointer");
     const Cloud &c = ctx->cloud[which];
     if (c.n_rgb <= 0) return fail(PCCM_E_STATE, "cloud %d has no colours", which);
-    { int rcd = d2h(ctx, out, c.rgb64, (size_t)c.n_rgb * 3 * sizeof(double)); if (rcd) return rcd; }
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    return PCCM_OK;
+    return fetch(ctx, out, c.rgb64, (size_t)c.n_rgb * 3 * sizeof(double));
 }
 
 int pccm_ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
@@ -1200,9 +1095,7 @@ int pccm_get_ssim_features(pccm_ctx *ctx, int which, int attr, double *out)
     const Cloud &c = ctx->cloud[which];
     if (!(c.ssim_attrs & attr)) return fail(PCCM_E_STATE, "cloud %d has no PointSSIM features of attribute %d", which, attr);
     const int a = attr == PCCM_SSIM_GEOMETRY ? 0 : attr == PCCM_SSIM_NORMAL ? 1 : attr == PCCM_SSIM_CURVATURE ? 2 : 3;
-    { int rcd = d2h(ctx, out, c.ssim64 + (size_t)a * c.n, (size_t)c.n * sizeof(double)); if (rcd) return rcd; }
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    return PCCM_OK;
+    return fetch(ctx, out, c.ssim64 + (size_t)a * c.n, (size_t)c.n * sizeof(double));
 }
 
 int pccm_resolution_build(pccm_ctx *ctx, int which, int K, int *built)
@@ -1224,9 +1117,7 @@ int pccm_get_resolution(pccm_ctx *ctx, int which, double *out)
     if (!out) return fail(PCCM_E_ARG, "null pointer");
     const Cloud &c = ctx->cloud[which];
     if (c.n <= 0 || c.res_k <= 0) return fail(PCCM_E_STATE, "the point spacings of cloud %d are not built (pccm_resolution_build)", which);
-    { int rcd = d2h(ctx, out, c.res64, (size_t)c.n * sizeof(double)); if (rcd) return rcd; }
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    return PCCM_OK;
+    return fetch(ctx, out, c.res64, (size_t)c.n * sizeof(double));
 }
 
 int pccm_p2d_build_attrs(pccm_ctx *ctx, int k, int attrs, int *built)
@@ -1276,8 +1167,7 @@ int pccm_set_shard(pccm_ctx *ctx, int rank, int world)
         ctx->shard_rank[d] = rank;
         ctx->shard_world[d] = world;
     }
-    ctx->epoch++;
-    for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
+    shard_changed(ctx, kDirsAll);
     return PCCM_OK;
 }
 
@@ -1289,9 +1179,7 @@ int pccm_set_shard_dir(pccm_ctx *ctx, int dir, int rank, int world)
     if (world < 0 || (world > 0 && (rank < 0 || rank >= world))) return fail(PCCM_E_ARG, "bad shard %d of %d", rank, world);
     ctx->shard_rank[dir] = world > 0 ? rank : 0;
     ctx->shard_world[dir] = world;
-    ctx->epoch++;
-    ctx->nn[dir].valid = false;
-    ctx->nn_gen[dir]++;
+    shard_changed(ctx, 1 << dir);
     return PCCM_OK;
 }
 
@@ -1313,8 +1201,7 @@ static int prepare_nn(pccm_ctx *ctx, int dir, int *trivial)
     int rc = dir_clouds(ctx, dir, &it, &se);
     if (rc) return rc;
     NNResult &res = ctx->nn[dir];
-    res.valid = false;
-    ctx->nn_gen[dir]++;
+    results_void(ctx, 1 << dir);
     ctx->nn_run[dir]++;
     shard_of(it->n, ctx->shard_rank[dir], ctx->shard_world[dir], &res.begin, &res.end);
     const int64_t ns = res.end - res.begin;
@@ -2621,9 +2508,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
         (void)hipGetLastError();
         if (g.graph) (void)hipGraphDestroy(g.graph);
         // whatever the captured calls recorded on the host never ran on the GPU
-        for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
-        for (auto &s : ctx->slots) s.pending = false;
-    for (auto &q : ctx->sel_slots) q.pending = false;
+        results_dropped(ctx);
         grid_invalidate(ctx);
         return fail(PCCM_E_STATE, "graph capture failed (%s); the context is usable, results were invalidated",
                     e != hipSuccess ? hipGetErrorString(e) : "a captured call reported an error");
@@ -2631,9 +2516,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
     if (e != hipSuccess) {
         (void)hipGraphDestroy(g.graph);
-        for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
-        for (auto &s : ctx->slots) s.pending = false;
-    for (auto &q : ctx->sel_slots) q.pending = false;
+        results_dropped(ctx);
         grid_invalidate(ctx);
         return fail(PCCM_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     }
@@ -2701,24 +2584,9 @@ int pccm_ctx_reset(pccm_ctx *ctx)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     ctx->io_staged = false;                            // (the next owner of the context says what it wants)
     ctx->ties = PCCM_TIES_PICK;
-    ctx->carry.to = -1;
-    for (int k = 0; k < 2; ++k) {
-        ctx->merge_n[k] = 0;
-        drop_cloud(ctx->cloud[k]);
-        ctx->cloud[k].version++;
-    }
-    ctx->p2d_k = 0;
-    ctx->p2d_color = false;
-    for (int d = 0; d < 3; ++d) {
-        ctx->shard_rank[d] = 0;
-        ctx->shard_world[d] = 1;
-    }
-    for (int d = 0; d < 3; ++d) { ctx->nn[d].valid = false; ctx->nn_gen[d]++; }
-    for (auto &s : ctx->slots) s.pending = false;
-    for (auto &q : ctx->sel_slots) q.pending = false;
+    context_cleared(ctx);
     for (auto &g : ctx->graphs) graph_free(g);
     ctx->graphs.clear();
-    ctx->epoch++;
     grid_invalidate(ctx);                              // the geometry decisions stay: the next pair may inherit them
     int rc = collect_spans(ctx);
     ctx->prof_on = false;

@@ -311,7 +311,7 @@ struct pccm_ctx {
     uint64_t nrm_gen = 1;                 // bumped whenever any normals change
     // pccm_carry_normals: cloud `to` holds normals carried over from the other cloud (-1: neither does), made from the searches
     // whose run counts (nn_run) are run_f (the direction that iterates the source cloud) and run_g; whatever changes either cloud's
-    // points or the source cloud's normals drops them (carry_drop, pccm_api.hip)
+    // points or the source cloud's normals drops them (points_changed / normals_changed, pccm_stale.h)
     struct Carry {
         int to = -1;
         uint64_t run_f = 0, run_g = 0;

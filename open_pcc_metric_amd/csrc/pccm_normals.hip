@@ -18,6 +18,7 @@
 // The neighbours come from the shared k-NN searches (pccm_knn.hip); the eigen code is pccm_normals.h's.
 #include "pccm_knn.h"
 #include "pccm_normals.h"
+#include "pccm_stale.h"
 
 namespace pccm {
 
@@ -54,13 +55,8 @@ int estimate_normals(pccm_ctx *ctx, int which, int k)
     if ((rc = knn_setup(ctx, which, g, cs, crecs))) return rc;
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     if ((rc = grow((void **)&c.nrm64, c.cap_nrm, (size_t)c.n * 3 * sizeof(double)))) return rc;
+    normals_changed(ctx, which);
     c.n_nrm = c.n;
-    c.nrm_exact32 = false;
-    c.nrm_deferred = false;
-    c.nrm_host = nullptr;
-    c.ssim_attrs &= ~PCCM_SSIM_NORMAL;
-    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending D2 reductions would use stale normals
-    ctx->epoch++;
     double *cov;
     int32_t *cnt;
     uint32_t *open_count, *todo_count;

@@ -2,6 +2,7 @@
 // clouds, in neighbour-list mode, then the Mahalanobis distance of every query to its neighbours' distribution (k_p2d_geometry)
 // and, with PCCM_P2D_COLOR, the colour and joint columns (k_p2d_color), all from the neighbour lists.
 #include "pccm_knn.h"
+#include "pccm_stale.h"
 
 namespace pccm {
 
@@ -148,11 +149,7 @@ int p2d_build(pccm_ctx *ctx, int k, int attrs, int *built)
         return fail(PCCM_E_STATE, "point-to-distribution columns are built before graph capture");
     }
     int rc;
-    if (geometry) {
-        ctx->p2d_k = 0;
-        ctx->p2d_color = false;
-    }
-    for (int d = 0; d < 2; ++d) ctx->nn_gen[d]++;       // pending point-to-distribution reductions would read stale columns
+    column_rebuild(ctx, geometry ? Stored::kP2d : Stored::kP2dColor);
     for (int d = 0; d < 2; ++d) {
         const Cloud &a = ctx->cloud[d], &b = ctx->cloud[1 - d];
         PCCM_HIP(hipStreamSynchronize(ctx->stream));
@@ -162,7 +159,7 @@ int p2d_build(pccm_ctx *ctx, int k, int attrs, int *built)
             if (!(c == 0 ? geometry : color)) continue;
             const double *before = *cols[c];
             if ((rc = grow((void **)cols[c], *caps[c], (size_t)a.n * sizeof(double)))) return rc;
-            if (*cols[c] != before) ctx->epoch++;           // (graphs that read the old column are stale)
+            if (*cols[c] != before) column_moved(ctx);
         }
         int32_t *nbr, *cnt;
         if ((rc = p2d_search(ctx, d, k, &nbr, &cnt))) return rc;

@@ -5,6 +5,7 @@
 // depend on the pair it is in.
 #include "pccm_knn.h"
 #include "pccm_normals.h"
+#include "pccm_stale.h"
 
 namespace pccm {
 
@@ -145,9 +146,8 @@ int ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     const double *ssim_before = c.ssim64;
     if ((rc = grow((void **)&c.ssim64, c.cap_ssim, (size_t)c.n * 4 * sizeof(double)))) return rc;
-    c.ssim_attrs = 0;
-    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending PointSSIM reductions would use stale features
-    if (c.ssim64 != ssim_before) ctx->epoch++;          // (graphs that read the old columns are stale)
+    column_rebuild(ctx, Stored::kSsim, which);
+    if (c.ssim64 != ssim_before) column_moved(ctx);
     double *cov;
     int32_t *cnt;
     uint32_t *open_count, *todo_count;
@@ -197,9 +197,8 @@ int resolution_build(pccm_ctx *ctx, int which, int K, int *built)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     const double *before = c.res64;
     if ((rc = grow((void **)&c.res64, c.cap_res, (size_t)c.n * sizeof(double)))) return rc;
-    c.res_k = 0;
-    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;      // pending reductions of the column would read stale spacings
-    if (c.res64 != before) ctx->epoch++;                // (graphs that read the old column are stale)
+    column_rebuild(ctx, Stored::kSpacing, which);
+    if (c.res64 != before) column_moved(ctx);
     double *cov;
     int32_t *cnt;
     uint32_t *open_count, *todo_count;
