@@ -65,7 +65,8 @@ ROWS = {
                        expect=["k_vox_query<false, false>"]),
     "lattice": dict(kind="search", env="", gen=dict(n=40_000, m=40_000, voxel=True, spread=True),
                     expect=["k_lattice_query<false>", "k_lattice_query<true>"]),
-    # the brute-force engine: fp32 scan, fp64 refine, exact rescan of what it could not certify
+    # the brute-force engine: fp32 scan, fp64 refine, exact rescan of what it could not certify (what the certificate must flag and
+    # must not flag, row by row: tests/test_gpu_brute_planted.py)
     "brute": dict(kind="search", env="", engine="brute", gen=dict(n=20_011, m=19_997, ties=True),
                   expect=["k1_scan<8, false>", "k1_scan<8, true>", "k2_refine<false>", "k2_refine<true>", "k2b_fallback<false>",
                           "k2b_fallback<true>"]),
