@@ -436,6 +436,12 @@ inline void note_kernel(pccm_ctx *ctx, const void *k)
         ::pccm::note_kernel((ctx), reinterpret_cast<const void *>(&(kernel)));          \
         hipLaunchKernelGGL(kernel, __VA_ARGS__);                                        \
     } while (0)
+// ... through a pointer to the kernel's host stub (a table entry): the pointer's value is the handle, not its address
+#define PCCM_LAUNCH_STUB(ctx, stub, ...)                                                \
+    do {                                                                                \
+        ::pccm::note_kernel((ctx), reinterpret_cast<const void *>(stub));               \
+        hipLaunchKernelGGL(stub, __VA_ARGS__);                                          \
+    } while (0)
 
 // while alive, launches are noted in the logs of `mask` (bit d: search of direction d, bit 3: reduction batch), which start
 // empty unless `keep` (work a search leaves for later -- tie means, tie exposure -- joins that search's log)

@@ -1,5 +1,6 @@
 // Ingest, the per-point column kernel (K3) and the NumPy-ordered leaf reduction (K5).
 #include "pccm_internal.h"
+#include "pccm_reduce_shape.h"
 
 namespace pccm {
 
@@ -452,146 +453,11 @@ __device__ __forceinline__ void unit_select(const UnitJobs &jobs, unsigned char 
     }
 }
 
-__global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
-{
-    __shared__ double ls[2][32], lmn[2][32], lmx[2][32];
-    __shared__ __attribute__((aligned(16))) unsigned char sel_smem[kSelLds];      // selection launches only
-    if (jobs.sel.pass) {                                   // block-uniform (a kernel argument)
-        unit_select(jobs, sel_smem);
-        return;
-    }
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t unit_threads = jobs.uoff[jobs.njobs];
-    if (t < unit_threads) {                                // block-uniform: jobs start at multiples of 256 lanes
-        int jb = 0;
-#pragma unroll
-        for (int k = 1; k < 8; ++k)
-            if (k < jobs.njobs && t >= jobs.uoff[k]) jb = k;
-        jb = __builtin_amdgcn_readfirstlane(jb);              // block-uniform by construction: scalar loads of the job
-        const UnitJob &J = jobs.j[jb];
-        const UnitView V = unit_view(J);
-        const int ncols = J.ncols;
-        const int64_t u = (t - jobs.uoff[jb]) >> 3;
-        const int k = threadIdx.x & 7, grp = threadIdx.x >> 3;
-        const int64_t base = u * kLeaf;
-        const bool live = u < J.nunits;
-        const int64_t cnt = !live ? 0 : ((J.ns - base < kLeaf) ? J.ns - base : kLeaf);
-        double r[2] = {0.0, 0.0}, mn[2] = {INFINITY, INFINITY}, mx[2] = {-INFINITY, -INFINITY};
-        if (cnt == kLeaf) {
-            double v[kLeaf / 8][2];
-            // sixteen independent loads first; the layout test sits outside the loop so that they are issued together
-            if (V.stride >= 2 && V.defer) {
-#pragma unroll
-                for (int j = 0; j < kLeaf / 8; ++j) unit_load(V, base + 8 * j + k, v[j]);
-            } else if (V.stride >= 2) {
-#pragma unroll
-                for (int j = 0; j < kLeaf / 8; ++j) {
-                    const double2 t = *reinterpret_cast<const double2 *>(&V.val[(base + 8 * j + k) * V.stride]);
-                    v[j][0] = t.x;
-                    v[j][1] = t.y;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < kLeaf / 8; ++j) v[j][0] = v[j][1] = V.val[base + 8 * j + k];
-            }
-#pragma unroll
-            for (int j = 0; j < kLeaf / 8; ++j) unit_pick(V, v[j]);
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                r[c] = v[0][c];
-                mn[c] = mx[c] = r[c];
-#pragma unroll
-                for (int j = 1; j < kLeaf / 8; ++j) {
-                    r[c] = __dadd_rn(r[c], v[j][c]);
-                    mn[c] = fmin(mn[c], v[j][c]);
-                    mx[c] = fmax(mx[c], v[j][c]);
-                }
-            }
-        } else {
-            for (int64_t e = k; e < cnt; e += 8) {
-                double v[2];
-                unit_load(V, base + e, v);
-                unit_pick(V, v);
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    r[c] = __dadd_rn(r[c], v[c]);
-                    mn[c] = fmin(mn[c], v[c]);
-                    mx[c] = fmax(mx[c], v[c]);
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-#pragma unroll
-            for (int off = 1; off < 8; off <<= 1) {
-                r[c] = __dadd_rn(r[c], __shfl_xor(r[c], off));
-                mn[c] = fmin(mn[c], __shfl_xor(mn[c], off));
-                mx[c] = fmax(mx[c], __shfl_xor(mx[c], off));
-            }
-        }
-        if (k == 0) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {                  // (constant bounds: r / mn / mx stay in registers)
-                double *ou = c < ncols ? J.c[c].out_units : nullptr;
-                if (live && ou) {                          // per-leaf results: the sharded exchange needs them
-                    ou[u] = r[c];
-                    ou[J.nunits + u] = mn[c];
-                    ou[2 * J.nunits + u] = mx[c];
-                }
-            }
-            for (int c = 0; c < 2; ++c) {
-                ls[c][grp] = r[c];
-                lmn[c][grp] = mn[c];
-                lmx[c][grp] = mx[c];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            // this block's 32 leaves = one half of an 8192-row NumPy chunk when the shard starts on a chunk
-            // boundary: finish NumPy's pairwise tree for the half here (adjacent pairs, five levels), so the
-            // host only adds 2 numbers per chunk instead of walking 64 leaves.  Lanes 0..31: column 0, 32..63: column 1.
-            const int c = threadIdx.x >> 5, l = threadIdx.x & 31;
-            double s = ls[c][l], a = lmn[c][l], b = lmx[c][l];
-#pragma unroll
-            for (int off = 1; off < 32; off <<= 1) {
-                s = __dadd_rn(s, __shfl_xor(s, off));
-                a = fmin(a, __shfl_xor(a, off));
-                b = fmax(b, __shfl_xor(b, off));
-            }
-            if (l == 0 && c < ncols) {
-                const int64_t blk = (t - jobs.uoff[jb]) >> 8;
-                double *ob = J.c[c].out_blocks;
-                ob[blk] = s;
-                ob[J.nblocks + blk] = a;
-                ob[2 * J.nblocks + blk] = b;
-            }
-        }
-        return;
-    }
-    // raw values of the last, partial 8192-row chunk (NumPy sums them with its own tree on the host)
-    const int64_t c0 = t - unit_threads;
-    if (c0 >= jobs.toff[jobs.njobs]) return;
-    int jb = 0;
-#pragma unroll
-    for (int k = 1; k < 8; ++k)
-        if (k < jobs.njobs && c0 >= jobs.toff[k]) jb = k;
-    const UnitJob &J = jobs.j[jb];
-    const UnitView V = unit_view(J);
-    const int64_t e = c0 - jobs.toff[jb];
-    double v[2];
-    unit_load(V, J.tail_first + e, v);
-    unit_pick(V, v);
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-        if (c < J.ncols) J.c[c].out_tail[e] = v[c];
-}
-
-// The same reduction with the jobs' shape fixed at compile time (every report's jobs share one shape): record stride and
-// which field feeds which column are template arguments, so the sixteen loads of a lane are one base address + immediate
-// offsets and no value passes through a select.  CFG 0: two columns {field 0, field 1 squared} (D1 + D2 of a direction in
-// one pass over its result records), 1: field 0, 2: field 1 squared, 3: field 1.  (The general kernel above spends most of
-// its 20 us at 1M + 1M points on per-value selects, 64-bit index products and dependent scalar loads; a kernel of this
-// shape streams the same 32 MB in 7 us: scripts/micro/reduce_gap.hip.)
+// ---- the leaf reduction, written once (UnitCols / LeanCols: what a record is; k_unit_jobs / k_unit_lean: who runs it) ----------
+// A policy type says how a job's records become column values and nothing else: NC, the columns the kernel carries (compile
+// time: loops over columns with constant bounds keep r / mn / mx in registers -- DESIGN.md, "k_unit_jobs compiled for gfx950");
+// live(c): column c is reduced and stored; leaf(base, k, v): the values of rows base + k + 8 j of a full leaf, the sixteen
+// loads of lane k issued together; one(i, v): the values of row i; min / max: what orders the extrema.
 __device__ __forceinline__ double dmin_raw(double a, double b)       // operands are finite: no canonicalisation needed
 {
     double r;
@@ -605,153 +471,227 @@ __device__ __forceinline__ double dmax_raw(double a, double b)
     return r;
 }
 
-template <int STRIDE, int CFG, int DEFER = 0>      // DEFER: UnitJob::defer of every job (records of layout 1; STRIDE 2)
-__global__ __launch_bounds__(256) void k_unit_lean(UnitJobs jobs)
-{
-    constexpr int NC = CFG == 0 ? 2 : 1;
-    __shared__ double ls[NC][32], lmn[NC][32], lmx[NC][32];
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t unit_threads = jobs.uoff[jobs.njobs];
-    if ((int64_t)blockIdx.x * 256 < unit_threads) {            // block-uniform: jobs start at multiples of 256 lanes
-        int jb = 0;
+// The layout read from the job at run time: every shape, two columns carried whether the job has one or two.  fmin / fmax: a
+// signed projection column holds -0.0 beside 0.0, which the raw instructions do not order.
+struct UnitCols {
+    static constexpr int NC = 2;
+    const UnitView V;
+    const int ncols;
+    __device__ __forceinline__ explicit UnitCols(const UnitJob &J) : V(unit_view(J)), ncols(J.ncols) {}
+    __device__ __forceinline__ bool live(int c) const { return c < ncols; }
+    static __device__ __forceinline__ double min(double a, double b) { return fmin(a, b); }
+    static __device__ __forceinline__ double max(double a, double b) { return fmax(a, b); }
+    __device__ __forceinline__ void one(int64_t i, double v[2]) const { unit_load(V, i, v); unit_pick(V, v); }
+    __device__ __forceinline__ void leaf(int64_t base, int k, double v[kLeaf / 8][2]) const
+    {
+        __builtin_assume((base & (kLeaf - 1)) == 0 && k >= 0 && k < 8);       // (see LeanCols::leaf)
+        // sixteen independent loads first; the layout test sits outside the loop so that they are issued together
+        if (V.stride >= 2 && V.defer) {
 #pragma unroll
-        for (int k = 1; k < 8; ++k)
-            if (k < jobs.njobs && (int64_t)blockIdx.x * 256 >= jobs.uoff[k]) jb = k;
-        const UnitJob &J = jobs.j[jb];
-        const double *__restrict__ val = J.val;
-        const int64_t ns = J.ns, nunits = J.nunits;
-        const int64_t u = (t - jobs.uoff[jb]) >> 3;
-        const int k = threadIdx.x & 7, grp = threadIdx.x >> 3;
-        const int64_t base = u * kLeaf;
-        const bool live = u < nunits;
-        const int64_t cnt = !live ? 0 : ((ns - base < kLeaf) ? ns - base : kLeaf);
-        double r[NC], mn[NC], mx[NC];
-        // column values of one record (e: its index in the shard)
-        const double *__restrict__ nrm64 = J.nrm64;
-        const float4 *__restrict__ nrm32 = J.nrm32;
-        const float4 *__restrict__ q32 = J.q32;
-        const int64_t row0 = J.row0, nrm_rows = J.nrm_rows;
-        auto cols = [&](const double *p, int64_t e, double out[NC]) {
-            if (DEFER) {
-                double x, y;
-                matched_fields(*reinterpret_cast<const float4 *>(p), q32, DEFER, nrm64, nrm32, row0 + e, CFG != 1, x, y, nrm_rows);
-                if (CFG == 0) { out[0] = x; out[1] = __dmul_rn(y, y); }
-                else if (CFG == 1) out[0] = x;
-                else if (CFG == 2) out[0] = __dmul_rn(y, y);
-                else out[0] = y;
-            } else if (STRIDE >= 2) {
-                const double2 q = *reinterpret_cast<const double2 *>(p);
-                if (CFG == 0) { out[0] = q.x; out[1] = __dmul_rn(q.y, q.y); }
-                else if (CFG == 1) out[0] = q.x;
-                else if (CFG == 2) out[0] = __dmul_rn(q.y, q.y);
-                else out[0] = q.y;
-            } else {
-                out[0] = *p;
-            }
-        };
-        if (cnt == kLeaf) {
-            const double *p = val + (base + k) * STRIDE;
-            double v[kLeaf / 8][NC];
+            for (int j = 0; j < kLeaf / 8; ++j) unit_load(V, base + 8 * j + k, v[j]);
+        } else if (V.stride >= 2) {
 #pragma unroll
-            for (int j = 0; j < kLeaf / 8; ++j) cols(p + (int64_t)j * 8 * STRIDE, base + k + 8 * j, v[j]);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                r[c] = v[0][c];
-                mn[c] = mx[c] = v[0][c];
-#pragma unroll
-                for (int j = 1; j < kLeaf / 8; ++j) {
-                    r[c] = __dadd_rn(r[c], v[j][c]);
-                    mn[c] = dmin_raw(mn[c], v[j][c]);
-                    mx[c] = dmax_raw(mx[c], v[j][c]);
-                }
+            for (int j = 0; j < kLeaf / 8; ++j) {
+                const double2 t = *reinterpret_cast<const double2 *>(&V.val[(base + 8 * j + k) * V.stride]);
+                v[j][0] = t.x;
+                v[j][1] = t.y;
             }
         } else {
 #pragma unroll
-            for (int c = 0; c < NC; ++c) { r[c] = 0.0; mn[c] = INFINITY; mx[c] = -INFINITY; }
-            for (int64_t e = k; e < cnt; e += 8) {
-                double w[NC];
-                cols(val + (base + e) * STRIDE, base + e, w);
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    r[c] = __dadd_rn(r[c], w[c]);
-                    mn[c] = dmin_raw(mn[c], w[c]);
-                    mx[c] = dmax_raw(mx[c], w[c]);
-                }
-            }
+            for (int j = 0; j < kLeaf / 8; ++j) v[j][0] = v[j][1] = V.val[base + 8 * j + k];
         }
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-#pragma unroll
-            for (int off = 1; off < 8; off <<= 1) {
-                r[c] = __dadd_rn(r[c], __shfl_xor(r[c], off));
-                mn[c] = dmin_raw(mn[c], __shfl_xor(mn[c], off));
-                mx[c] = dmax_raw(mx[c], __shfl_xor(mx[c], off));
-            }
-        }
-        if (k == 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                double *ou = J.c[c].out_units;
-                if (live && ou) {                          // per-leaf results: the sharded exchange needs them
-                    ou[u] = r[c];
-                    ou[nunits + u] = mn[c];
-                    ou[2 * nunits + u] = mx[c];
-                }
-                ls[c][grp] = r[c];
-                lmn[c][grp] = mn[c];
-                lmx[c][grp] = mx[c];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 32 * NC) {
-            // this block's 32 leaves = one half of an 8192-row NumPy chunk: finish NumPy's pairwise tree for the half here
-            const int c = threadIdx.x >> 5, l = threadIdx.x & 31;
-            double s = ls[c][l], a = lmn[c][l], b = lmx[c][l];
-#pragma unroll
-            for (int off = 1; off < 32; off <<= 1) {
-                s = __dadd_rn(s, __shfl_xor(s, off));
-                a = dmin_raw(a, __shfl_xor(a, off));
-                b = dmax_raw(b, __shfl_xor(b, off));
-            }
-            if (l == 0) {
-                const int64_t blk = (t - jobs.uoff[jb]) >> 8;
-                double *ob = J.c[c].out_blocks;
-                ob[blk] = s;
-                ob[J.nblocks + blk] = a;
-                ob[2 * J.nblocks + blk] = b;
-            }
-        }
-        return;
+        for (int j = 0; j < kLeaf / 8; ++j) unit_pick(V, v[j]);
     }
-    // raw values of the last, partial 8192-row chunk (NumPy sums them with its own tree on the host)
-    const int64_t c0 = t - unit_threads;
-    if (c0 >= jobs.toff[jobs.njobs]) return;
+};
+
+// The jobs' shape fixed at compile time (every report's jobs share one shape; ReduceShape, pccm_reduce_shape.h): record stride
+// and which field feeds which column are template arguments, so the sixteen loads of a lane are one base address + immediate
+// offsets and no value passes through a select.  CFG 0: two columns {field 0, field 1 squared} (D1 + D2 of a direction in
+// one pass over its result records), 1: field 0, 2: field 1 squared.  A signed projection column (field 1 as it is) has no
+// such kernel: its minimum and maximum need fmin / fmax (-0.0 beside 0.0), so it goes to the general kernel.  (That kernel
+// spends most of its 20 us at 1M + 1M points on per-value selects, 64-bit index products and dependent scalar loads; a kernel
+// of this shape streams the same 32 MB in 7 us: scripts/micro/reduce_gap.hip.)
+template <int STRIDE, int CFG, int DEFER>          // DEFER: UnitJob::defer of every job (records of layout 1; STRIDE 2)
+struct LeanCols {
+    static constexpr int NC = CFG == 0 ? 2 : 1;
+    const double *__restrict__ val, *__restrict__ nrm64;
+    const float4 *__restrict__ nrm32, *__restrict__ q32;
+    const int64_t row0, nrm_rows;
+    __device__ __forceinline__ explicit LeanCols(const UnitJob &J)
+        : val(J.val), nrm64(J.nrm64), nrm32(J.nrm32), q32(J.q32), row0(J.row0), nrm_rows(J.nrm_rows) {}
+    __device__ __forceinline__ bool live(int) const { return true; }
+    static __device__ __forceinline__ double min(double a, double b) { return dmin_raw(a, b); }
+    static __device__ __forceinline__ double max(double a, double b) { return dmax_raw(a, b); }
+    __device__ __forceinline__ void one(int64_t i, double out[NC]) const { at(val + i * STRIDE, i, out); }
+    __device__ __forceinline__ void at(const double *p, int64_t i, double out[NC]) const       // p: record i
+    {
+        double x, y = 0.0;
+        if (DEFER) {
+            matched_fields(*reinterpret_cast<const float4 *>(p), q32, DEFER, nrm64, nrm32, row0 + i, CFG != 1, x, y, nrm_rows);
+        } else if (STRIDE >= 2) {
+            const double2 q = *reinterpret_cast<const double2 *>(p);
+            x = q.x; y = q.y;
+        } else {
+            x = *p;
+        }
+        if (CFG == 0) { out[0] = x; out[1] = __dmul_rn(y, y); }
+        else out[0] = CFG == 1 ? x : __dmul_rn(y, y);
+    }
+    __device__ __forceinline__ void leaf(int64_t base, int k, double v[kLeaf / 8][NC]) const
+    {
+        // What the kernel knows of a leaf's first row and the lane's place in it, said here because this function is optimised
+        // before it is inlined: the row indices then stay base | k | 8 j, as they were when the loop stood in the kernel.  Folded
+        // into row0 + first they cost the kernels with fp64 normals 10 to 18 VGPRs (<2, 2, 2>: three waves per SIMD for four)
+        __builtin_assume((base & (kLeaf - 1)) == 0 && k >= 0 && k < 8);
+        const int64_t first = base + k;
+        const double *p = val + first * STRIDE;            // one base address + immediate offsets
+#pragma unroll
+        for (int j = 0; j < kLeaf / 8; ++j) at(p + (int64_t)j * 8 * STRIDE, first + 8 * j, v[j]);
+    }
+};
+
+// the job position `pos` falls into, for prefix sums `off` of the jobs' extents
+__device__ __forceinline__ int unit_job_at(const int64_t (&off)[9], int njobs, int64_t pos)
+{
     int jb = 0;
 #pragma unroll
     for (int k = 1; k < 8; ++k)
-        if (k < jobs.njobs && c0 >= jobs.toff[k]) jb = k;
+        if (k < njobs && pos >= off[k]) jb = k;
+    return jb;
+}
+
+// The leaves of job jb this workgroup owns (lane t of the launch; 8 lanes per leaf, 32 leaves per workgroup): per-leaf and
+// per-workgroup sums, minima and maxima.  The order of the additions is NumPy's (K5 above).
+template <class P>
+__device__ __forceinline__ void unit_leaves(const UnitJobs &jobs, int jb, int64_t t)
+{
+    constexpr int NC = P::NC;
+    __shared__ double ls[NC][32], lmn[NC][32], lmx[NC][32];
     const UnitJob &J = jobs.j[jb];
-    const int64_t e = c0 - jobs.toff[jb];
-    const double *p = J.val + (J.tail_first + e) * STRIDE;
-    double w[NC];
-    if (DEFER) {
-        double x, y;
-        matched_fields(*reinterpret_cast<const float4 *>(p), J.q32, DEFER, J.nrm64, J.nrm32, J.row0 + J.tail_first + e, CFG != 1, x, y, J.nrm_rows);
-        if (CFG == 0) { w[0] = x; w[1] = __dmul_rn(y, y); }
-        else if (CFG == 1) w[0] = x;
-        else if (CFG == 2) w[0] = __dmul_rn(y, y);
-        else w[0] = y;
-    } else if (STRIDE >= 2) {
-        const double2 q = *reinterpret_cast<const double2 *>(p);
-        if (CFG == 0) { w[0] = q.x; w[1] = __dmul_rn(q.y, q.y); }
-        else if (CFG == 1) w[0] = q.x;
-        else if (CFG == 2) w[0] = __dmul_rn(q.y, q.y);
-        else w[0] = q.y;
+    const P cols(J);
+    const int64_t ns = J.ns, nunits = J.nunits;
+    const int64_t lane = t - jobs.uoff[jb], u = lane >> 3;
+    const int k = threadIdx.x & 7, grp = threadIdx.x >> 3;
+    const int64_t base = u * kLeaf;
+    const bool live = u < nunits;
+    const int64_t cnt = !live ? 0 : ((ns - base < kLeaf) ? ns - base : kLeaf);
+    double r[NC], mn[NC], mx[NC];
+    if (cnt == kLeaf) {
+        double v[kLeaf / 8][NC];
+        cols.leaf(base, k, v);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            r[c] = v[0][c];
+            mn[c] = mx[c] = v[0][c];
+#pragma unroll
+            for (int j = 1; j < kLeaf / 8; ++j) {
+                r[c] = __dadd_rn(r[c], v[j][c]);
+                mn[c] = P::min(mn[c], v[j][c]);
+                mx[c] = P::max(mx[c], v[j][c]);
+            }
+        }
     } else {
-        w[0] = *p;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { r[c] = 0.0; mn[c] = INFINITY; mx[c] = -INFINITY; }
+        for (int64_t e = k; e < cnt; e += 8) {
+            double w[NC];
+            cols.one(base + e, w);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                r[c] = __dadd_rn(r[c], w[c]);
+                mn[c] = P::min(mn[c], w[c]);
+                mx[c] = P::max(mx[c], w[c]);
+            }
+        }
     }
 #pragma unroll
-    for (int c = 0; c < NC; ++c) J.c[c].out_tail[e] = w[c];
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) {
+            r[c] = __dadd_rn(r[c], __shfl_xor(r[c], off));
+            mn[c] = P::min(mn[c], __shfl_xor(mn[c], off));
+            mx[c] = P::max(mx[c], __shfl_xor(mx[c], off));
+        }
+    }
+    if (k == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {                     // (constant bounds: r / mn / mx stay in registers)
+            double *ou = cols.live(c) ? J.c[c].out_units : nullptr;
+            if (live && ou) {                              // per-leaf results: the sharded exchange needs them
+                ou[u] = r[c];
+                ou[nunits + u] = mn[c];
+                ou[2 * nunits + u] = mx[c];
+            }
+            ls[c][grp] = r[c];
+            lmn[c][grp] = mn[c];
+            lmx[c][grp] = mx[c];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 * NC) {
+        // this block's 32 leaves = one half of an 8192-row NumPy chunk when the shard starts on a chunk
+        // boundary: finish NumPy's pairwise tree for the half here (adjacent pairs, five levels), so the
+        // host only adds 2 numbers per chunk instead of walking 64 leaves.  Lanes 0..31: column 0, 32..63: column 1.
+        const int c = threadIdx.x >> 5, l = threadIdx.x & 31;
+        double s = ls[c][l], a = lmn[c][l], b = lmx[c][l];
+#pragma unroll
+        for (int off = 1; off < 32; off <<= 1) {
+            s = __dadd_rn(s, __shfl_xor(s, off));
+            a = P::min(a, __shfl_xor(a, off));
+            b = P::max(b, __shfl_xor(b, off));
+        }
+        if (l == 0 && cols.live(c)) {
+            const int64_t blk = lane >> 8;
+            double *ob = J.c[c].out_blocks;
+            ob[blk] = s;
+            ob[J.nblocks + blk] = a;
+            ob[2 * J.nblocks + blk] = b;
+        }
+    }
+}
+
+// raw values of the last, partial 8192-row chunk (NumPy sums them with its own tree on the host); c0: lane behind the leaves' lanes
+template <class P>
+__device__ __forceinline__ void unit_tail(const UnitJobs &jobs, int64_t c0)
+{
+    if (c0 >= jobs.toff[jobs.njobs]) return;
+    const int jb = unit_job_at(jobs.toff, jobs.njobs, c0);
+    const UnitJob &J = jobs.j[jb];
+    const P cols(J);
+    const int64_t e = c0 - jobs.toff[jb];
+    double v[P::NC];
+    cols.one(J.tail_first + e, v);
+#pragma unroll
+    for (int c = 0; c < P::NC; ++c)
+        if (cols.live(c)) J.c[c].out_tail[e] = v[c];
+}
+
+__global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char sel_smem[kSelLds];      // selection launches only
+    if (jobs.sel.pass) {                                   // block-uniform (a kernel argument)
+        unit_select(jobs, sel_smem);
+        return;
+    }
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t unit_threads = jobs.uoff[jobs.njobs];
+    if (t < unit_threads)                                  // block-uniform: jobs start at multiples of 256 lanes
+        // (the job index is block-uniform by construction: readfirstlane makes the job's fields scalar loads)
+        unit_leaves<UnitCols>(jobs, __builtin_amdgcn_readfirstlane(unit_job_at(jobs.uoff, jobs.njobs, t)), t);
+    else
+        unit_tail<UnitCols>(jobs, t - unit_threads);
+}
+
+template <int STRIDE, int CFG, int DEFER = 0>
+__global__ __launch_bounds__(256) void k_unit_lean(UnitJobs jobs)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t unit_threads = jobs.uoff[jobs.njobs];
+    if ((int64_t)blockIdx.x * 256 < unit_threads)          // block-uniform: jobs start at multiples of 256 lanes
+        unit_leaves<LeanCols<STRIDE, CFG, DEFER>>(jobs, unit_job_at(jobs.uoff, jobs.njobs, (int64_t)blockIdx.x * 256), t);
+    else
+        unit_tail<LeanCols<STRIDE, CFG, DEFER>>(jobs, t - unit_threads);
 }
 
 // A batch's completion, published to the host: one wave launched behind the batch's last reduction kernel on the same stream
@@ -771,54 +711,49 @@ __global__ __launch_bounds__(64) void k_publish(unsigned long long *done)
     }
 }
 
-// a job's shape, or -1: (stride, CFG, defer) as stride * 4 + cfg + 64 * defer
-static int job_shape(const UnitJob &J)
+// the kernel of every shape pccm_reduce_shape.h lists, row for row: adding a shape is a row there and a row here
+struct LeanKernel {
+    ReduceShape shape;
+    void (*stub)(UnitJobs);
+};
+template <int STRIDE, int CFG, int DEFER>
+constexpr LeanKernel lean() { return {{STRIDE, CFG, DEFER}, k_unit_lean<STRIDE, CFG, DEFER>}; }
+static constexpr LeanKernel kLeanKernels[] = {
+    lean<1, 1, 0>(),
+    lean<2, 0, 0>(),
+    lean<2, 1, 0>(),
+    lean<2, 2, 0>(),
+    lean<4, 0, 0>(),
+    lean<4, 1, 0>(),
+    lean<4, 2, 0>(),
+    lean<2, 0, 1>(),      // matched records, fp32-exact normals
+    lean<2, 1, 1>(),
+    lean<2, 2, 1>(),
+    lean<2, 0, 2>(),      // ... fp64 normals
+    lean<2, 1, 2>(),
+    lean<2, 2, 2>(),
+    lean<2, 1, 3>(),      // ... no normals: distances only
+    lean<2, 0, 4>(),      // ... the matched row's normal, fp32-exact
+    lean<2, 2, 4>(),
+    lean<2, 0, 5>(),      // ... fp64
+    lean<2, 2, 5>(),
+};
+constexpr bool lean_rows_match()
 {
-    int cfg = -1;
-    if (J.stride == 1) cfg = (J.ncols == 1 && J.c[0].off == 0 && !J.c[0].square) ? 1 : -1;
-    else if (J.ncols == 2) cfg = (J.c[0].off == 0 && !J.c[0].square && J.c[1].off == 1 && J.c[1].square) ? 0 : -1;
-    else if (J.c[0].off == 0) cfg = J.c[0].square ? -1 : 1;
-    else cfg = J.c[0].square ? 2 : 3;
-    if (cfg < 0 || (J.stride != 1 && J.stride != 2 && J.stride != 4)) return -1;
-    if (J.defer && J.stride != 2) return -1;
-    return J.stride * 4 + cfg + 64 * J.defer;
+    if (sizeof(kLeanKernels) / sizeof(kLeanKernels[0]) != (size_t)kLeanCount) return false;
+    for (int i = 0; i < kLeanCount; ++i)
+        if (!(kLeanKernels[i].shape == kLeanShapes[i])) return false;
+    return true;
 }
+static_assert(lean_rows_match(), "kLeanKernels and kLeanShapes (pccm_reduce_shape.h) must list the same shapes in the same order");
 
-// one launch for jobs of one shape (-1: the general kernel)
-static void launch_unit_shape(pccm_ctx *ctx, const UnitJobs &jobs, int shape)
+// one launch for jobs of one shape (lean: row of kLeanShapes, or -1: the general kernel)
+static void launch_unit_shape(pccm_ctx *ctx, const UnitJobs &jobs, int lean)
 {
     const int64_t total = jobs.uoff[jobs.njobs] + jobs.toff[jobs.njobs];
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    switch (shape) {
-    case 1 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<1, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0>), grid, block, 0, ctx->stream, jobs); break;
-    case 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 4 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<4, 0>), grid, block, 0, ctx->stream, jobs); break;
-    case 4 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<4, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 4 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<4, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 64 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 1>), grid, block, 0, ctx->stream, jobs); break;      // matched records, fp32-exact normals
-    case 64 + 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 64 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 1>), grid, block, 0, ctx->stream, jobs); break;
-    case 128 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 2>), grid, block, 0, ctx->stream, jobs); break;     // ... fp64 normals
-    case 128 + 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 128 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 2>), grid, block, 0, ctx->stream, jobs); break;
-    case 192 + 2 * 4 + 1: PCCM_LAUNCH(ctx, (k_unit_lean<2, 1, 3>), grid, block, 0, ctx->stream, jobs); break;     // ... no normals: distances only
-    case 256 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 4>), grid, block, 0, ctx->stream, jobs); break;     // ... the matched row's normal, fp32-exact
-    case 256 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 4>), grid, block, 0, ctx->stream, jobs); break;
-    case 320 + 2 * 4 + 0: PCCM_LAUNCH(ctx, (k_unit_lean<2, 0, 5>), grid, block, 0, ctx->stream, jobs); break;     // ... fp64
-    case 320 + 2 * 4 + 2: PCCM_LAUNCH(ctx, (k_unit_lean<2, 2, 5>), grid, block, 0, ctx->stream, jobs); break;
-    default: PCCM_LAUNCH(ctx, k_unit_jobs, grid, block, 0, ctx->stream, jobs); break;      // signed projections (min / max of -0.0 and 0.0: fmin / fmax there), other shapes
-    }
-}
-
-static bool lean_has(int shape)
-{
-    switch (shape) {
-    case 5: case 8: case 9: case 10: case 16: case 17: case 18: case 72: case 73: case 74: case 136: case 137: case 138: case 201: case 264: case 266:
-    case 328: case 330: return true;
-    default: return false;
-    }
+    if (lean >= 0) PCCM_LAUNCH_STUB(ctx, kLeanKernels[lean].stub, grid, block, 0, ctx->stream, jobs);
+    else PCCM_LAUNCH(ctx, k_unit_jobs, grid, block, 0, ctx->stream, jobs);      // signed projections (min / max of -0.0 and 0.0: fmin / fmax there), other shapes
 }
 
 int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
@@ -831,8 +766,8 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
     int shape[8], nshapes = 0, first_of[8];
     bool all_lean = !general;
     for (int k = 0; k < jobs.njobs; ++k) {
-        shape[k] = job_shape(jobs.j[k]);
-        all_lean = all_lean && lean_has(shape[k]);
+        shape[k] = lean_index(reduce_shape(jobs.j[k]));       // row of kLeanShapes, or -1
+        all_lean = all_lean && shape[k] >= 0;
         bool seen = false;
         for (int j = 0; j < nshapes; ++j) seen = seen || shape[first_of[j]] == shape[k];
         if (!seen) first_of[nshapes++] = k;

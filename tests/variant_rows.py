@@ -78,7 +78,7 @@ ROWS = {
                        expect=["k_tie_mean<pccm::Rec32>", "k_tie_exposure<pccm::Rec32>"]),
     "ties_gridrec": dict(kind="ties", env="", gen=dict(n=20_011, m=19_997, ties=True, f64=True),
                          expect=["k_tie_mean<pccm::GridRec>", "k_tie_exposure<pccm::GridRec>"]),
-    # ---- reductions: every k_unit_lean shape lean_has() lists, and the general kernel ----------------------------------
+    # ---- reductions: every k_unit_lean shape kLeanShapes (pccm_reduce_shape.h) lists, and the general kernel -----------
     "reduce_shapes": dict(kind="reduce", env="", gen=dict(n=8192 * 8 + 127, m=8192 * 7 + 129,
                                                         lengths=[(8192 * 8 + 127, 8192 * 7 + 129), (8192 * 8, 8192 * 7 + 1),
                                                                  (8192 * 8 - 1, 128 * 40), (8192 + 128, 8191), (128 * 41 + 1, 127 * 41)]),
