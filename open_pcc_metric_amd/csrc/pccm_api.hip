@@ -150,23 +150,6 @@ static void free_nn(NNResult &r)
     r.cap = 0;
 }
 
-static void shard_of(int64_t n, int rank, int world, int64_t *b, int64_t *e)
-{
-    if (world <= 0) {                     // this context owns no rows of the direction
-        *b = 0;
-        *e = 0;
-        return;
-    }
-    // shards start on whole 8192-row chunks of NumPy's sum whenever every rank can have one (the ranks then exchange
-    // one number per chunk: pccm_reduce_chunks_many), else on 128-row leaves (pccm_reduce's per-leaf exchange vector)
-    const int64_t unit = n >= (int64_t)world * kChunk ? kChunk : kLeaf;
-    const int64_t units = (n + unit - 1) / unit;
-    int64_t u0 = units * rank / world, u1 = units * (rank + 1) / world;
-    int64_t lo = u0 * unit, hi = u1 * unit;
-    *b = lo < n ? lo : n;
-    *e = hi < n ? hi : n;
-}
-
 static int dir_clouds(pccm_ctx *ctx, int dir, const Cloud **it, const Cloud **se)
 {
     if (dir == PCCM_DIR_LEFT) { *it = &ctx->cloud[0]; *se = &ctx->cloud[1]; }
@@ -231,10 +214,10 @@ static int h2d(pccm_ctx *ctx, void *dev, const void *host, size_t bytes, hipStre
     if (ctx->pin_ev_set[which]) PCCM_HIP(hipEventSynchronize(ctx->pin_ev[which]));      // the previous upload has left the buffer
     int rc = pin_ensure(ctx, which, bytes < kPinWindow ? bytes : kPinWindow);
     if (rc) return rc;
-    constexpr size_t kChunk = 4u << 20;                          // the copy of piece k + 1 runs beside the DMA of piece k
-    static_assert(kPinWindow % kChunk == 0, "whole pieces per window");
-    for (size_t off = 0; off < bytes; off += kChunk) {
-        const size_t len = bytes - off < kChunk ? bytes - off : kChunk, at = off % kPinWindow;
+    constexpr size_t kPiece = 4u << 20;                          // the copy of piece k + 1 runs beside the DMA of piece k
+    static_assert(kPinWindow % kPiece == 0, "whole pieces per window");
+    for (size_t off = 0; off < bytes; off += kPiece) {
+        const size_t len = bytes - off < kPiece ? bytes - off : kPiece, at = off % kPinWindow;
         if (off && at == 0) {                                    // the window is full: its pieces must have left before it is refilled
             PCCM_HIP(hipEventRecord(ctx->pin_ev[which], st));
             PCCM_HIP(hipEventSynchronize(ctx->pin_ev[which]));
@@ -1544,12 +1527,6 @@ static const double *stored_column(const pccm_ctx *ctx, int dir, int metric)
     return metric == PCCM_METRIC_P2D ? ctx->p2d64[dir] : ctx->p2d_cj64[dir][metric - PCCM_METRIC_P2D_COLOR];
 }
 
-// normal_mode enters the column: the projection on a normal of the searched cloud and its square, nothing else
-static bool normal_mode_enters(int metric)
-{
-    return metric == PCCM_METRIC_D2 || metric == PCCM_METRIC_PROJ;
-}
-
 // What a (dir, metric, normal_mode) request of the direction's search needs before any column is bound -- one answer for
 // pccm_point_metric, the reductions and the selections: the metric exists, it is defined for this search, its operands are there.
 static int column_check(pccm_ctx *ctx, int dir, int metric, int normal_mode, const Cloud &it, const Cloud &se, const NNResult &res)
@@ -1675,11 +1652,7 @@ int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, doubl
     return PCCM_OK;
 }
 
-int64_t pccm_xvec_len(int64_t n_iter)
-{
-    if (n_iter <= 0) return 0;
-    return (n_iter / kChunk) * (kChunk / kLeaf) + (n_iter % kChunk);
-}
+int64_t pccm_xvec_len(int64_t n_iter) { return slot_shape(n_iter, 0, n_iter).xvec_len(); }
 
 // ---- reductions: enqueue (prefetch) and consume ---------------------------------------------------------
 // A reduction is enqueued into a slot: point kernel (D2/PROJ) -> per-unit sums/min/max -> async copy of
@@ -1811,15 +1784,10 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     }
     s.dir = dir; s.metric = metric; s.mode = normal_mode;
     s.gen = ctx->nn_gen[dir];
-    s.n_iter = it->n; s.begin = res->begin; s.end = res->end;
-    s.nunits = ns > 0 ? (ns + kLeaf - 1) / kLeaf : 0;
-    s.nblocks = (s.nunits + 31) / 32;
+    static_cast<SlotShape &>(s) = slot_shape(it->n, res->begin, res->end);
     s.has_units = want_units;
     s.has_job = false;
-    const int64_t nfull = it->n / kChunk, full_rows = nfull * kChunk;
-    s.t0 = res->begin > full_rows ? res->begin : full_rows;
-    s.tail_n = s.t0 < res->end ? res->end - s.t0 : 0;
-    const size_t need = (size_t)(3 * s.nunits + 3 * s.nblocks + s.tail_n + 1) * sizeof(double);
+    const size_t need = (size_t)s.host_doubles() * sizeof(double);
     if (ctx->capturing && (need > s.host_cap || !s.ev)) {
         ctx->capture_failed = true;
         return fail(PCCM_E_STATE, "a reduction slot must be allocated during graph capture: run the sequence once first");
@@ -1836,17 +1804,13 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         UnitCol col;
         col.off = src.off;
         col.square = src.square;
-        col.out_units = want_units ? s.host : nullptr;
-        col.out_blocks = s.host + 3 * s.nunits;
-        col.out_tail = s.host + 3 * s.nunits + 3 * s.nblocks;
+        bind_outputs(col, SlotView(s, s.host), want_units);
         // the column as a job of its own (what a selection of this column ranks: pccm_select_prefetch_many)
         UnitJob &U = s.job;
         U.val = dev; U.stride = stride; U.ncols = 1;
         U.defer = src.defer; U.nrm64 = se->nrm64; U.nrm32 = se->nrm32; U.nrm_rows = se->n_nrm; U.q32 = it->xyz32r; U.row0 = res->begin;
         U.c[0] = col; U.c[1] = col;
-        U.ns = ns; U.nunits = s.nunits;
-        U.tail_first = s.t0 - res->begin; U.tail_n = s.tail_n;
-        U.nblocks = s.nblocks;
+        bind_shape(U, s);
         s.has_job = true;
         // a second column over the same result records rides along with the job that already reads them
         UnitJob *host_job = nullptr;
@@ -1878,25 +1842,7 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
 static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, bool need_units = false)
 {
     for (auto &s : ctx->slots)
-        if (s.pending && (s.has_units || !need_units) && s.dir == dir && s.metric == metric &&
-            (!normal_mode_enters(metric) || s.mode == normal_mode) &&
-            s.gen == ctx->nn_gen[dir])
-            return &s;
-    return nullptr;
-}
-
-// A slot for a new reduction: an idle or stale one; failing that, a pending one that does NOT belong to the batch being
-// assembled (`fresh`): its unconsumed result is given up (a later pccm_reduce recomputes it) -- never a slot of the current
-// batch, whose host buffers an earlier job of the same launch is about to write.
-static ReduceSlot *slot_free(pccm_ctx *ctx, ReduceSlot *const *fresh, int nfresh)
-{
-    for (auto &s : ctx->slots)
-        if (!s.pending || s.gen != ctx->nn_gen[s.dir]) return &s;
-    for (auto &s : ctx->slots) {
-        bool mine = false;
-        for (int k = 0; k < nfresh; ++k) mine = mine || fresh[k] == &s;
-        if (!mine) return &s;
-    }
+        if (s.matches(dir, metric, normal_mode, ctx->nn_gen[dir], need_units)) return &s;
     return nullptr;
 }
 
@@ -1913,7 +1859,7 @@ int pccm_reduce_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *
             if (dirs[k] < 0 || dirs[k] > 2) continue;                 // reported by prefetch_many
             const NNResult &res = ctx->nn[dirs[k]];
             const Cloud &it = ctx->cloud[dirs[k] == PCCM_DIR_RIGHT ? 1 : 0];
-            units = res.end > res.begin && (res.begin % kChunk != 0 || (res.end % kChunk != 0 && res.end != it.n));
+            units = !slot_shape(it.n, res.begin, res.end).chunk_aligned();
         }
     return prefetch_many(ctx, n, dirs, metrics, normal_modes, units);
 }
@@ -1963,13 +1909,13 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     PathScope path(ctx, 1u << 3);          // the batch's kernels: per-point columns (slot_prepare), point and unit jobs
     for (int k = 0; k < n; ++k) {
         if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
-        ReduceSlot *s = slot_free(ctx, fresh, nfresh);
+        ReduceSlot *s = pick_free(ctx->slots, fresh, nfresh, ctx->nn_gen);
         if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 24 live columns in one batch");
         if (s->pending && !ctx->capturing && s->wait_ev) { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
         s->pending = false;
         int rc = slot_prepare(ctx, *s, dirs[k], metrics[k], normal_modes[k], want_units, pj, uj);
         if (rc) return rc;
-        s->pending = true;                 // so that slot_free/slot_find see it while the batch is assembled
+        s->pending = true;                 // so that pick_free/slot_find see it while the batch is assembled
         fresh[nfresh++] = s;
     }
     if (nfresh == 0) {
@@ -1988,7 +1934,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
             op.kind = 2;
             op.dir = s.dir;
             op.slot = (int)(&s - ctx->slots);
-            op.snap = s;
+            op.snap = snapshot(s);
             ctx->cap_ops.push_back(op);
         } else {
             s.wait_ev = ctx->batch_ev;
@@ -2029,114 +1975,39 @@ int pccm_reduce(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *xve
     if (!xvec || !minmax) return fail(PCCM_E_ARG, "null pointer");
     ReduceSlot *s;
     { int rc = take_slot(ctx, dir, metric, normal_mode, true, &s); if (rc) return rc; }
-    const int64_t n = s->n_iter;
-    const int64_t xlen = pccm_xvec_len(n);
-    memset(xvec, 0, (size_t)xlen * sizeof(double));
-    minmax[0] = INFINITY;
-    minmax[1] = -INFINITY;
-    const int64_t nunits = s->nunits;
-    const int64_t nfull = n / kChunk, full_rows = nfull * kChunk;
-    const double *usum = s->host, *umin = usum + nunits, *umax = usum + 2 * nunits;
-    for (int64_t u = 0; u < nunits; ++u) {
-        const int64_t row = s->begin + u * kLeaf;    // shard boundaries are multiples of kLeaf
-        if (row < full_rows) xvec[row / kLeaf] = usum[u];
-        if (umin[u] < minmax[0]) minmax[0] = umin[u];
-        if (umax[u] > minmax[1]) minmax[1] = umax[u];
-    }
-    if (s->tail_n > 0)   // raw values of the last, partial 8192-row chunk that fall into this shard
-        memcpy(xvec + nfull * (kChunk / kLeaf) + (s->t0 - full_rows), s->host + 3 * nunits + 3 * s->nblocks,
-               (size_t)s->tail_n * sizeof(double));
+    slot_fill_xvec(*s, SlotView(*s, s->host), xvec, minmax);
     return PCCM_OK;
-}
-
-static double leaf_tree(const double *l, int cnt)
-{
-    if (cnt == 1) return l[0];
-    return leaf_tree(l, cnt / 2) + leaf_tree(l + cnt / 2, cnt / 2);
 }
 
 int pccm_finish_sum(const double *xvec, int64_t n_iter, double *sum)
 {
     if (!xvec || !sum || n_iter < 0) return fail(PCCM_E_ARG, "bad argument");
-    const int64_t nfull = n_iter / kChunk, tail = n_iter % kChunk;
-    const int lpc = kChunk / kLeaf;
-    double s = 0.0;
-    bool first = true;
-    for (int64_t c = 0; c < nfull; ++c) {
-        double cs = leaf_tree(xvec + c * lpc, lpc);
-        s = first ? cs : s + cs;
-        first = false;
-    }
-    if (tail) {
-        double ts = np_pairwise_sum(xvec + nfull * lpc, tail);
-        s = first ? ts : s + ts;
-    }
-    *sum = s;
+    const SlotShape w = slot_shape(n_iter, 0, n_iter);       // the whole column
+    *sum = np_chunked_sum(w.nfull(), [=](int64_t c) { return leaf_tree(xvec + c * kLeavesPerChunk, kLeavesPerChunk); },
+                          xvec + w.nfull() * kLeavesPerChunk, w.tail_n);
     return PCCM_OK;
 }
 
-// one column's total from its slot (unsharded): np.sum = chunks of 8192 rows in sequence, each chunk = NumPy's pairwise tree
-// = (tree of its first 32 leaves) + (tree of its last 32 leaves), and the GPU already finished both halves (begin = 0 here)
+// one column's total from its slot (unsharded, begin = 0)
 static int total_from_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, double out[3])
 {
     ReduceSlot *s;
     { int rc = take_slot(ctx, dir, metric, normal_mode, false, &s); if (rc) return rc; }
-    const int64_t n = s->n_iter, nunits = s->nunits, nblocks = s->nblocks;
-    const int64_t nfull = n / kChunk;
-    const double *bsum = s->host + 3 * nunits, *bmin = bsum + nblocks, *bmax = bsum + 2 * nblocks;
-    double total = 0.0;
-    bool first = true;
-    for (int64_t c = 0; c < nfull; ++c) {
-        const double cs = bsum[2 * c] + bsum[2 * c + 1];
-        total = first ? cs : total + cs;
-        first = false;
-    }
-    if (s->tail_n > 0) {
-        const double ts = np_pairwise_sum(s->host + 3 * nunits + 3 * nblocks, s->tail_n);
-        total = first ? ts : total + ts;
-    }
-    double mn = INFINITY, mx = -INFINITY;
-    for (int64_t b = 0; b < nblocks; ++b) {
-        mn = bmin[b] < mn ? bmin[b] : mn;
-        mx = bmax[b] > mx ? bmax[b] : mx;
-    }
-    out[0] = total;
-    out[1] = mn;
-    out[2] = mx;
+    slot_total(*s, SlotView(*s, s->host), out);
     return PCCM_OK;
 }
 
-int64_t pccm_cvec_len(int64_t n_iter)
-{
-    if (n_iter <= 0) return 0;
-    return n_iter / kChunk + n_iter % kChunk;
-}
+int64_t pccm_cvec_len(int64_t n_iter) { return slot_shape(n_iter, 0, n_iter).cvec_len(); }
 
-// one column's chunk vector from its slot: a number per full 8192-row chunk this shard owns (the GPU finished both
-// halves of the chunk's pairwise tree) + the raw values of the last, partial chunk; zero elsewhere
+// one column's chunk vector from its slot
 static int chunks_from_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *cvec, double minmax[2])
 {
     ReduceSlot *s;
     { int rc = take_slot(ctx, dir, metric, normal_mode, false, &s); if (rc) return rc; }
-    const int64_t n = s->n_iter, nunits = s->nunits, nblocks = s->nblocks;
-    const int64_t nfull = n / kChunk, full_rows = nfull * kChunk;
-    memset(cvec, 0, (size_t)pccm_cvec_len(n) * sizeof(double));
-    minmax[0] = INFINITY;
-    minmax[1] = -INFINITY;
-    if (s->end <= s->begin) return PCCM_OK;                  // this rank owns no rows of the direction
-    if (s->begin % kChunk != 0 || (s->end % kChunk != 0 && s->end != n))
+    if (!s->chunk_aligned())
         return fail(PCCM_E_STATE, "rows [%lld, %lld) do not start and end on 8192-row chunks: use pccm_reduce", (long long)s->begin,
                     (long long)s->end);
-    const double *bsum = s->host + 3 * nunits, *bmin = bsum + nblocks, *bmax = bsum + 2 * nblocks;
-    const int64_t c0 = s->begin / kChunk;
-    const int64_t owned = ((s->end < full_rows ? s->end : full_rows) - s->begin) / kChunk;
-    for (int64_t c = 0; c < owned; ++c) cvec[c0 + c] = bsum[2 * c] + bsum[2 * c + 1];
-    if (s->tail_n > 0)
-        memcpy(cvec + nfull + (s->t0 - full_rows), s->host + 3 * nunits + 3 * nblocks, (size_t)s->tail_n * sizeof(double));
-    for (int64_t b = 0; b < nblocks; ++b) {
-        minmax[0] = bmin[b] < minmax[0] ? bmin[b] : minmax[0];
-        minmax[1] = bmax[b] > minmax[1] ? bmax[b] : minmax[1];
-    }
+    slot_fill_cvec(*s, SlotView(*s, s->host), cvec, minmax);
     return PCCM_OK;
 }
 
@@ -2159,18 +2030,8 @@ int pccm_reduce_chunks_many(pccm_ctx *ctx, int n, const int *dirs, const int *me
 int pccm_finish_chunks(const double *cvec, int64_t n_iter, double *sum)
 {
     if (!cvec || !sum || n_iter < 0) return fail(PCCM_E_ARG, "bad argument");
-    const int64_t nfull = n_iter / kChunk, tail = n_iter % kChunk;
-    double s = 0.0;
-    bool first = true;
-    for (int64_t c = 0; c < nfull; ++c) {                    // np.sum: the chunks one after the other
-        s = first ? cvec[c] : s + cvec[c];
-        first = false;
-    }
-    if (tail) {
-        const double ts = np_pairwise_sum(cvec + nfull, tail);
-        s = first ? ts : s + ts;
-    }
-    *sum = s;
+    const SlotShape w = slot_shape(n_iter, 0, n_iter);       // the whole column
+    *sum = np_chunked_sum(w.nfull(), [=](int64_t c) { return cvec[c]; }, cvec + w.nfull(), w.tail_n);
     return PCCM_OK;
 }
 
@@ -2200,9 +2061,7 @@ int pccm_reduce_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *met
 static SelectSlot *sel_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, int64_t k)
 {
     for (auto &q : ctx->sel_slots)
-        if (q.pending && q.dir == dir && q.metric == metric && q.k == k && (!normal_mode_enters(metric) || q.mode == normal_mode) &&
-            q.gen == ctx->nn_gen[dir])
-            return &q;
+        if (q.matches(dir, metric, normal_mode, ctx->nn_gen[dir], k)) return &q;
     return nullptr;
 }
 
@@ -2267,14 +2126,7 @@ static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *met
             int taken = 0;
             for (int j = 0; j < ntodo && taken < kSelPerCol; ++j) {
                 if (placed[j] || col_of[j] != c) continue;
-                SelectSlot *q = nullptr;
-                for (auto &cand : ctx->sel_slots)
-                    if (!q && (!cand.pending || cand.gen != ctx->nn_gen[cand.dir])) q = &cand;
-                for (auto &cand : ctx->sel_slots) {               // failing that, one that is not of this call: its result is given up
-                    bool mine = false;
-                    for (int f = 0; f < nfresh; ++f) mine = mine || fresh[f] == &cand;
-                    if (!q && !mine) q = &cand;
-                }
+                SelectSlot *q = pick_free(ctx->sel_slots, fresh, nfresh, ctx->nn_gen);      // (a live one of another call: its result is given up)
                 if (!q) return fail(PCCM_E_STATE, "no free selection slot");
                 if (q->pending && !ctx->capturing && q->wait_ev && (rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
                 const int i = todo[j];
@@ -2452,15 +2304,10 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
                 int rcw = wait_slot(ctx, &s);
                 if (rcw) return rcw;
             }
-            s.dir = op.snap.dir; s.metric = op.snap.metric; s.mode = op.snap.mode;
-            s.n_iter = op.snap.n_iter; s.begin = op.snap.begin; s.end = op.snap.end;
-            s.nunits = op.snap.nunits; s.nblocks = op.snap.nblocks; s.has_units = op.snap.has_units;
-            s.t0 = op.snap.t0; s.tail_n = op.snap.tail_n;
-            s.has_job = op.snap.has_job; s.job = op.snap.job;
+            restore(s, op.snap);
             s.gen = ctx->nn_gen[s.dir];
             s.pending = true;
-            s.wait_ev = ctx->batch_ev;
-            s.wait_seq = op.snap.wait_seq ? ctx->batches_issued + op.snap.wait_seq : 0;
+            rearm(s, ctx, op.snap.key.wait_seq);
         } else if (op.kind == 3) {
             SelectSlot &q = ctx->sel_slots[op.slot];
             if (q.pending && q.gen == ctx->nn_gen[q.dir] && q.wait_ev) {       // still in use by someone else
@@ -2470,8 +2317,7 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
             q = op.ssnap;
             q.gen = ctx->nn_gen[q.dir];
             q.pending = true;
-            q.wait_ev = ctx->batch_ev;
-            q.wait_seq = op.ssnap.wait_seq ? ctx->batches_issued + op.ssnap.wait_seq : 0;
+            rearm(q, ctx, op.ssnap.wait_seq);
         }
     }
     ctx->batches_issued += g.batches;                            // before the launch: a failed one only delays a waiter
@@ -2528,13 +2374,8 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     g.valid = true;
     // the captured calls changed the host bookkeeping but nothing ran yet: run the graph once now
     for (auto &op : g.ops)
-        if (op.kind == 2) {
-            ctx->slots[op.slot].wait_ev = ctx->batch_ev;
-            ctx->slots[op.slot].wait_seq = op.snap.wait_seq ? ctx->batches_issued + op.snap.wait_seq : 0;
-        } else if (op.kind == 3) {
-            ctx->sel_slots[op.slot].wait_ev = ctx->batch_ev;
-            ctx->sel_slots[op.slot].wait_seq = op.ssnap.wait_seq ? ctx->batches_issued + op.ssnap.wait_seq : 0;
-        }
+        if (op.kind == 2) rearm(ctx->slots[op.slot], ctx, op.snap.key.wait_seq);
+        else if (op.kind == 3) rearm(ctx->sel_slots[op.slot], ctx, op.ssnap.wait_seq);
     ctx->batches_issued += g.batches;
     PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pccm.h"
+#include "pccm_slot.h"
 
 // A/B switches that no test of the shipped library uses (brick length, register cap, build bins, cells per point, ...) exist in
 // diagnostic builds only (make DIAG=1): the product reads the environment for the switches tests/test_gpu_ab_paths.py exercises
@@ -28,9 +29,7 @@ constexpr float kBig32 = 3.0e38f;   // "no candidate" distance (finite: no inf a
 constexpr float kPadCoord = 1.0e18f;  // coordinates of padding points: d2 ~ 3e36, never wins
 constexpr double kMaxAbsCoord = 1.0e15;
 
-// ---- reduction geometry: NumPy's pairwise sum (numpy/_core/src/umath/loops_utils.h.src) --
-constexpr int kLeaf = 128;          // PW_BLOCKSIZE
-constexpr int kChunk = 8192;        // NumPy's default ufunc buffer size in elements
+// (the reduction geometry -- kLeaf, kChunk -- is pccm_slot.h's)
 
 struct Cloud {
     int64_t n = 0;
@@ -224,32 +223,57 @@ struct UnitJob {                // one per-point array to reduce (k_unit_jobs): 
     int64_t nblocks;            // ceil(nunits / 32)
 };
 
-struct ReduceSlot {            // one enqueued reduction (pccm_reduce_prefetch / pccm_reduce)
-    bool pending = false;
-    int dir = 0, metric = 0, mode = 0;
-    uint64_t gen = 0;          // nn generation of `dir` it was computed from
-    int64_t n_iter = 0, begin = 0, end = 0, nunits = 0, nblocks = 0, t0 = 0, tail_n = 0;
+// the shape SlotShape describes, as the kernels are told it: a job's rows, units and tail ...
+inline void bind_shape(UnitJob &U, const SlotShape &s)
+{
+    U.ns = s.ns; U.nunits = s.nunits; U.nblocks = s.nblocks;
+    U.tail_first = s.t0 - s.begin; U.tail_n = s.tail_n;
+}
+// ... and where in the slot's host buffer a column's results go (the per-leaf results only when somebody will read them)
+inline void bind_outputs(UnitCol &c, const SlotView &v, bool want_units)
+{
+    c.out_units = want_units ? v.usum : nullptr;
+    c.out_blocks = v.bsum;
+    c.out_tail = v.tail;
+}
+
+struct ReduceWhat : SlotShape { // what a reduction slot holds: everything a captured graph's replay has to put back
     bool has_units = false;    // per-leaf results were written (needed by pccm_reduce's exchange vector)
     bool has_job = false;      // job below describes the column (pccm_select_*: a selection ranks what the reduction reduced)
     UnitJob job;               // the column as a one-column k_unit_jobs job, as bound when the reduction was enqueued
-    DevBuf val;
-    double *host = nullptr;    // pinned: [3][nunits] leaf sums/min/max | [3][nblocks] half-chunk trees | tail_n raw values
-    size_t host_cap = 0;
-    hipEvent_t ev = nullptr;
-    hipEvent_t wait_ev = nullptr;   // what says "this slot's numbers are on the host": the context's batch event (one record serves
-                                    // every slot of a call / of a graph replay; waiting on a later record of it only waits longer)
-    uint64_t wait_seq = 0;          // ... or, sooner, the context's completion counter reaching this value (0: the event only;
-                                    // in a GraphOp's snapshot: the batch's ordinal within the captured sequence)
 };
 
-struct SelectSlot {            // one enqueued selection (pccm_select_prefetch_many / pccm_select_many)
-    bool pending = false;
-    int dir = 0, metric = 0, mode = 0;
-    int64_t k = 0;
-    uint64_t gen = 0;          // nn generation of `dir` it was computed from
-    hipEvent_t wait_ev = nullptr;
-    uint64_t wait_seq = 0;     // as ReduceSlot's
+struct ReduceSlot : SlotKey, ReduceWhat {   // one enqueued reduction (pccm_reduce_prefetch / pccm_reduce) and what the slot owns
+    DevBuf val;
+    double *host = nullptr;    // pinned, SlotShape::host_doubles() doubles at least: SlotView names its regions
+    size_t host_cap = 0;
+    hipEvent_t ev = nullptr;
+
+    bool matches(int d, int m, int normal_mode, uint64_t gen_now, bool need_units) const
+    {
+        return SlotKey::matches(d, m, normal_mode, gen_now) && (has_units || !need_units);
+    }
 };
+
+struct SelectSlot : SlotKey {  // one enqueued selection (pccm_select_prefetch_many / pccm_select_many)
+    int64_t k = 0;
+
+    bool matches(int d, int m, int normal_mode, uint64_t gen_now, int64_t rank) const
+    {
+        return SlotKey::matches(d, m, normal_mode, gen_now) && k == rank;
+    }
+};
+
+struct ReduceSnap {            // a reduction slot's bookkeeping at capture time, without what the slot owns
+    SlotKey key;
+    ReduceWhat what;
+};
+inline ReduceSnap snapshot(const ReduceSlot &s) { return {s, s}; }
+inline void restore(ReduceSlot &s, const ReduceSnap &snap)
+{
+    static_cast<SlotKey &>(s) = snap.key;
+    static_cast<ReduceWhat &>(s) = snap.what;
+}
 
 struct ProfSpan {
     hipEvent_t a, b;
@@ -260,7 +284,7 @@ struct GraphOp {               // host-side effect of one captured call, replaye
     int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch(slot)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
-    ReduceSlot snap;           // kind 2: the slot's bookkeeping at capture time (pointers are not owned)
+    ReduceSnap snap;           // kind 2: the slot's bookkeeping at capture time
     SelectSlot ssnap;          // kind 3: likewise for a selection slot
 };
 
@@ -357,10 +381,10 @@ struct pccm_ctx {
     pccm::Grid grid;
     pccm::DevBuf g_cell_of, g_rank, g_hist, g_blocksum, g_qrecs;   // grid-engine scratch (g_qrecs: cell-sorted shard rows)
     pccm::DevBuf g_bins, g_tmp;            // grid build: per-tile bin histogram + scan state; bin-partitioned records
-    hipEvent_t batch_ev = nullptr;   // recorded once behind every batch of reductions (ReduceSlot::wait_ev)
+    hipEvent_t batch_ev = nullptr;   // recorded once behind every batch of reductions (SlotKey::wait_ev)
     // completion counter: k_publish, behind the last kernel of a reduction batch, adds 1 to *done (host-coherent pinned memory, a
     // cache line of its own) when the batch's results are on the host; batches_issued counts the publishing batches enqueued
-    // so far, so a slot waits for *done to reach the count its batch was given (ReduceSlot::wait_seq) -- a spin on host
+    // so far, so a slot waits for *done to reach the count its batch was given (SlotKey::wait_seq) -- a spin on host
     // memory instead of the runtime's event completion path (pccm_set_wait)
     uint64_t *done = nullptr;
     uint64_t batches_issued = 0;
@@ -403,6 +427,14 @@ struct pccm_ctx {
 };
 
 namespace pccm {
+
+// a captured batch is about to run (again): its slot waits for the context's batch event, or for the completion counter to reach
+// the batch's ordinal in the captured sequence (snap_seq, 0: the event only) counted from the batches issued so far
+inline void rearm(SlotKey &k, const pccm_ctx *ctx, uint64_t snap_seq)
+{
+    k.wait_ev = ctx->batch_ev;
+    k.wait_seq = snap_seq ? ctx->batches_issued + snap_seq : 0;
+}
 
 // error plumbing ---------------------------------------------------------------------
 int fail(int code, const char *fmt, ...);
@@ -679,8 +711,6 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 // the selection launches of jobs.sel (memset of the histograms, kSelPasses histogram passes, resolve); nothing is published
 int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs);
 int launch_publish(pccm_ctx *ctx, uint64_t *seq);     // k_publish behind whatever the stream holds; *seq as for launch_unit_jobs
-
-double np_pairwise_sum(const double *a, int64_t n);
 
 // minimal-OBB frame search (pccm_obb.hip)
 int launch_obb_frames(pccm_ctx *ctx, const double *verts, int64_t nv, const double *tri, int64_t nt, double *ext_out, double *vol_out);

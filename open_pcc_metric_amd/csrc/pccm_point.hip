@@ -864,27 +864,4 @@ int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, cons
     return PCCM_OK;
 }
 
-// NumPy's DOUBLE pairwise sum over one contiguous run of at most kChunk values.
-double np_pairwise_sum(const double *a, int64_t n)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int64_t i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    if (n <= kLeaf) {
-        double r[8];
-        for (int k = 0; k < 8; ++k) r[k] = a[k];
-        int64_t i;
-        for (i = 8; i < n - (n % 8); i += 8)
-            for (int k = 0; k < 8; ++k) r[k] += a[i + k];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
-}
-
 }  // namespace pccm

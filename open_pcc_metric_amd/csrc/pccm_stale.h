@@ -9,7 +9,7 @@
 //
 // The counters.  Each is only ever compared for equality with a copy taken earlier; each counts one thing:
 //   nn_gen[d]  whatever a reduction or selection of direction d reads has changed: the result itself, or normals, features and
-//              stored columns under a result that stays.  Copies: ReduceSlot::gen, SelectSlot::gen, TieCols::gen, ColorMemo::gen.
+//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, selections), TieCols::gen, ColorMemo::gen.
 //   nn_run[d]  searches of direction d (prepare_nn alone bumps it): WHICH result the direction holds.  Copies: Carry::run_f / run_g.
 //   nrm_gen    any cloud's normals changed.  Copies: TieCols::nrm_gen / ang_gen.
 //   rgb_gen    any cloud's colours changed.  Copies: TieCols::rgb_gen, ColorMemo::rgb_gen.
