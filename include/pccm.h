@@ -102,6 +102,13 @@ extern "C" {
  * it).  PCCM_E_STATE while that cloud's column is not built.  Accepted by pccm_point_metric and every pccm_reduce* call; a plain
  * column, reduced like D1. */
 #define PCCM_METRIC_RESOLUTION 11
+/* Squared reflectance error of directions 0 and 1 (the self search: PCCM_E_ARG).  a = the iterating cloud's reflectance of row i,
+ * b = the searched cloud's reflectance of the MATCHED row nn(i) -- normal_mode does not apply and is ignored -- both fp64 with the
+ * values as given (pccm_set_reflectance*), each operation separately rounded:
+ *   d = a - b,  val = d * d
+ * PCCM_E_STATE unless both clouds hold one reflectance per point, and under PCCM_TIES_MEAN.  Accepted by pccm_point_metric and
+ * every pccm_reduce* call; a plain column, reduced like D1. */
+#define PCCM_METRIC_REFLECTANCE 12
 
 /* kernel classes for pccm_profile_get() */
 #define PCCM_K_INGEST 0
@@ -192,6 +199,7 @@ int pccm_carry_normals(pccm_ctx *ctx, int from, int *built);
  * in ascending order of representative (a stable compaction, n' rows); each row holds
  *   the representative's coordinates, bit for bit (its -0.0 survives);
  *   its normal bit for bit, in both modes, when the cloud has one normal per point;
+ *   its reflectance, when the cloud has one, by the rule at pccm_set_reflectance;
  *   when the cloud has colours: PCCM_DUP_DROP the representative's colour bit for bit; PCCM_DUP_AVERAGE per component in fp64
  *   s = c[i_1], then s = s + c[i_r] for r = 2..m, every add rounded separately, and the result s / (double)m, one correctly rounded
  *   division (m = 1 gives the colour back bit for bit) -- the convention of pccm_carry_normals.
@@ -208,7 +216,7 @@ int pccm_carry_normals(pccm_ctx *ctx, int from, int *built);
  * not depend on the tie policy.
  * pccm_get_points / pccm_get_colors copy the stored fp64 rows [n][3] out, as pccm_get_normals does.
  * PCCM_E_ARG: which is not 0 or 1; mode is not PCCM_DUP_DROP or PCCM_DUP_AVERAGE.  PCCM_E_STATE: the cloud is missing; it has
- * normals or colours whose count is neither 0 nor n; a sharded context; a call between pccm_graph_begin and pccm_graph_end;
+ * normals, colours or reflectance whose count is neither 0 nor n; a sharded context; a call between pccm_graph_begin and pccm_graph_end;
  * pccm_get_colors on a cloud without colours. */
 #define PCCM_DUP_DROP 1
 #define PCCM_DUP_AVERAGE 2
@@ -378,7 +386,7 @@ int pccm_set_ties(pccm_ctx *ctx, int policy);
 int pccm_tie_counts(pccm_ctx *ctx, int dir, int32_t *k);
 
 /* Per-point metric vector of the shard (PCCM_METRIC_*), metric.py:124-179; PCCM_METRIC_ANGULAR and
- * PCCM_METRIC_SSIM_*, PCCM_METRIC_P2D* and PCCM_METRIC_RESOLUTION ignore normal_mode. */
+ * PCCM_METRIC_SSIM_*, PCCM_METRIC_P2D*, PCCM_METRIC_RESOLUTION and PCCM_METRIC_REFLECTANCE ignore normal_mode. */
 int pccm_point_metric(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out);
 
 /* Fused reduction of a per-point metric over the shard: the np.sum / np.max of
@@ -460,6 +468,23 @@ int pccm_set_colors(pccm_ctx *ctx, int which, const void *rgb, int64_t n, int dt
 /* The same from the uchar colours point-cloud files hold: rgb[n][3] bytes, widened on the device as k / 255.0 -- the
  * division o3d.io.read_point_cloud (and io.py) perform on the host, bit for bit. */
 int pccm_set_colors_u8(pccm_ctx *ctx, int which, const unsigned char *rgb, int64_t n);
+
+/* Reflectance of cloud `which`: one scalar per point (the laser return intensity of LiDAR content), n = the cloud's point count,
+ * dtype PCCM_F32 or PCCM_F64.  Held as fp64 on the device with the values as given: nothing is normalised or divided.  Values
+ * must be finite.  A new reflectance leaves searches, normals, colours, PointSSIM features, spacings and point-to-distribution
+ * columns as they are; pending reductions and captured graphs go stale (they may read the column).  New points on the cloud
+ * (pccm_set_cloud, pccm_ctx_reset) take its reflectance away; pccm_merge_duplicates carries it: PCCM_DUP_DROP keeps the
+ * representative's value bit for bit, PCCM_DUP_AVERAGE gives s / (double)m with s = r[i_1], then s = s + r[i_k] in ascending row
+ * order, every add rounded (the colour rule; m = 1 gives the value back bit for bit).
+ * PCCM_E_STATE: the cloud is not set.  PCCM_E_ARG: n is not the cloud's point count; a non-finite value (the cloud then has no
+ * reflectance). */
+int pccm_set_reflectance(pccm_ctx *ctx, int which, const void *r, int64_t n, int dtype, int on_device);
+/* The same from the 16-bit values LiDAR files hold (host memory; 40000 becomes 40000.0).  The library widens them to float on
+ * the host -- exact: every 16-bit value is a float -- and they cross PCIe as four bytes per point through the float ingest; a
+ * device-side widening of the two-byte values would need a kernel of its own, which this library does not have yet. */
+int pccm_set_reflectance_u16(pccm_ctx *ctx, int which, const uint16_t *r, int64_t n);
+/* the stored column: n doubles (PCCM_E_STATE when the cloud has no reflectance) */
+int pccm_get_reflectance(pccm_ctx *ctx, int which, double *out);
 
 /* Colour metrics of one direction on the device, metric.py:302-333 and :389-427.  Per row i of the
  * iterating cloud: own = T(rgb_own[i]), other = T(rgb_other[nn(i)]) (the gather of

@@ -35,6 +35,7 @@ METRIC_P2D = 8           # point-to-distribution (Mahalanobis) column of a direc
 METRIC_P2D_COLOR = 9     # ... its colour (luma) column and
 METRIC_P2D_JOINT = 10    # ... its joint geometry-and-colour column (pccm_p2d_build_attrs with P2D_COLOR)
 METRIC_RESOLUTION = 11   # point spacings of the cloud a direction iterates (pccm_resolution_build; normal_mode does not apply)
+METRIC_REFLECTANCE = 12  # squared reflectance error against the matched point (pccm_set_reflectance; normal_mode does not apply)
 P2D_GEOMETRY, P2D_COLOR = 1, 2      # PCCM_P2D_*: what pccm_p2d_build_attrs builds (P2D_COLOR: the colour and the joint column)
 KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4, "reduce": 5,
                   "grid_build": 6, "grid_query": 7, "grid_finish": 8}
@@ -49,6 +50,7 @@ SYMBOLS = (
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
     "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
+    "pccm_set_reflectance", "pccm_set_reflectance_u16", "pccm_get_reflectance",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
     "pccm_color_transform", "pccm_lzf_decompress", "pccm_drop_caches", "pccm_graph_begin", "pccm_graph_end", "pccm_graph_launch", "pccm_graph_destroy",
     "pccm_sync",
@@ -157,6 +159,9 @@ def load() -> ctypes.CDLL:
     lib.pccm_lzf_decompress.argtypes = [vp, i64, vp, i64, ctypes.POINTER(i64)]
     lib.pccm_set_colors.argtypes = [vp, i32, vp, i64, i32, i32]
     lib.pccm_set_colors_u8.argtypes = [vp, i32, vp, i64]
+    lib.pccm_set_reflectance.argtypes = [vp, i32, vp, i64, i32, i32]
+    lib.pccm_set_reflectance_u16.argtypes = [vp, i32, vp, i64]
+    lib.pccm_get_reflectance.argtypes = [vp, i32, vp]
     lib.pccm_color_reduce.argtypes = [vp, i32, i32, ctypes.c_double, vp, i64, dp, dp]
     lib.pccm_seq_colsum.argtypes = [vp, vp, i64, dp]
     lib.pccm_obb_frames.argtypes = [vp, vp, i64, vp, i64, dp, dp]
@@ -527,6 +532,29 @@ class Engine:
     def get_colors(self, which: int) -> np.ndarray:
         out = np.empty((self._n[which], 3), dtype=np.float64)
         _check(self._lib.pccm_get_colors(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def set_reflectance(self, which: int, reflectance) -> None:
+        """One scalar per point of cloud ``which`` (pccm_set_reflectance*): ``uint8`` / ``uint16`` arrays go to the library
+        as 16-bit words (pccm_set_reflectance_u16 widens them exactly), ``float32`` as it is, anything else as ``float64``; the
+        values are kept as given.  ValueError for a wrong length or a non-finite value."""
+        r = np.asarray(reflectance)
+        if r.ndim == 2 and r.shape[1] == 1:
+            r = r[:, 0]
+        if r.ndim != 1:
+            raise ValueError("reflectance must have shape (N,)")
+        if r.dtype in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            r = np.ascontiguousarray(r, dtype=np.uint16)
+            _check(self._lib.pccm_set_reflectance_u16(self._ctx, int(which), r.ctypes.data_as(ctypes.c_void_p), r.shape[0]))
+            return
+        r = np.ascontiguousarray(r, dtype=np.float32 if r.dtype == np.float32 else np.float64)
+        _check(self._lib.pccm_set_reflectance(self._ctx, int(which), r.ctypes.data_as(ctypes.c_void_p), r.shape[0],
+                                              F32 if r.dtype == np.float32 else F64, 0))
+
+    def get_reflectance(self, which: int) -> np.ndarray:
+        """The stored fp64 reflectance column of cloud ``which`` (the merged one after merge_duplicates)."""
+        out = np.empty(self._n[which], dtype=np.float64)
+        _check(self._lib.pccm_get_reflectance(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def get_normals(self, which: int) -> np.ndarray:

@@ -16,7 +16,7 @@ import pandas as pd
 from .cloud_pair import CloudPair
 from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, ColorMahalanobisDistances, EuclideanDistance,
                      GeoRankedHausdorffDistance, JointMahalanobisDistances, MahalanobisDistances, PointSpacings, PrimaryMetric,
-                     SecondaryMetric, SSIMSimilarities, SymmetricMetric)
+                     ReflectanceErrors, SecondaryMetric, SSIMSimilarities, SymmetricMetric)
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -38,6 +38,8 @@ class CalculateResult:
             label = type(inner).__name__
             if getattr(inner, "rank", None) is not None:        # ranked Hausdorff rows: one block per rank
                 label += f"[{inner.rank!r}]"
+            if getattr(inner, "peak", None) is not None:        # reflectance PSNR rows: the peak they were taken against
+                label += f"[{inner.peak!r}]"
             if inner is not m:
                 label += "(symmetric)"
             rows["label"].append(label)
@@ -102,6 +104,8 @@ class MetricCalculator:
                 wanted.append(("p2d", metric.is_left, metric.k))
             elif isinstance(metric, PointSpacings):
                 wanted.append(("spacing", metric.is_left, metric.k))
+            elif isinstance(metric, ReflectanceErrors):
+                wanted.append(("reflectance", metric.is_left))
             (late if waits else early).append((metric, None, key))
         elif role == 2:
             if isinstance(metric, EuclideanDistance):

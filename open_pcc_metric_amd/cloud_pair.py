@@ -38,6 +38,10 @@ Differences from the reference, all deliberate:
   report then belongs to the merged clouds; ``clouds`` stays the caller's objects, ``duplicates_removed`` says how many rows each
   cloud lost and ``merge_map(which)`` where each original row went.  ``get_extent()`` still measures the given cloud 0: a convex
   hull does not depend on multiplicities.  Not available sharded (``ValueError``);
+* a cloud may carry a ``reflectance`` (one scalar per point; ``getattr(cloud, "reflectance", None)``, so Open3D clouds, which have
+  none, keep working): it goes up the first time a reflectance row needs it, stays with the origin cloud across
+  ``with_reconst`` and is merged by ``duplicates=`` like the colours ("Reflectance").  The rows are not
+  available sharded or under ``ties="mean"`` (``ValueError``);
 * ``use_graph=True`` lets ``recompute()`` replay the whole sweep + reductions of the previous report
   as one hipGraph launch (for callers that evaluate the same resident pair repeatedly).
 """
@@ -133,7 +137,9 @@ class DeviceColumn(_DeviceArray):
     ``"p2d_color"`` / ``"p2d_joint"``  its colour and joint columns (get_left/right_color_mahalanobis_distances,
                     get_left/right_joint_mahalanobis_distances; PCCM_METRIC_P2D_COLOR / PCCM_METRIC_P2D_JOINT),
     ``"spacing"``   the point spacings of the cloud the direction iterates (get_left/right_point_spacings;
-                    PCCM_METRIC_RESOLUTION: that cloud's stored column, over the neighbours it was built with).
+                    PCCM_METRIC_RESOLUTION: that cloud's stored column, over the neighbours it was built with),
+    ``"reflectance"``  squared reflectance differences (get_left/right_reflectance_errors; PCCM_METRIC_REFLECTANCE: the own
+                    reflectance against the matched point's, values as given).
     """
 
     def __init__(self, pair: "CloudPair", direction: int, kind: str):
@@ -144,7 +150,8 @@ class DeviceColumn(_DeviceArray):
 
     _METRIC = {"d1": nat.METRIC_D1, "boundary": nat.METRIC_D1, "proj": nat.METRIC_PROJ, "d2": nat.METRIC_D2,
                "angular": nat.METRIC_ANGULAR, **{f"ssim:{a}": m for a, m in nat.METRIC_SSIM.items()}, "p2d": nat.METRIC_P2D,
-               "p2d_color": nat.METRIC_P2D_COLOR, "p2d_joint": nat.METRIC_P2D_JOINT, "spacing": nat.METRIC_RESOLUTION}
+               "p2d_color": nat.METRIC_P2D_COLOR, "p2d_joint": nat.METRIC_P2D_JOINT, "spacing": nat.METRIC_RESOLUTION,
+               "reflectance": nat.METRIC_REFLECTANCE}
 
     def _materialise(self) -> np.ndarray:
         p = self._pair
@@ -321,6 +328,8 @@ class CloudPair:
         self._xchg, self._xchg_wanted = {}, []
         self._selections, self._sel_wanted = {}, []
         self._colours_on_device = [False, False]
+        self._reflectance_on_device = [False, False]
+        self._reflectance = False           # a report asked for the reflectance columns: the searches keep the matched rows
         self._colour_red = {}
         self._graph_id = None
         self._last_wanted = None
@@ -411,6 +420,7 @@ class CloudPair:
         new._carried = [False, False]                    # (cloud 0's, if carried, came from the cloud that is leaving: the library
         #                                                   drops them with it, and the next consumer carries from the new one)
         new._colours_on_device = [self._colours_on_device[0], False]
+        new._reflectance_on_device = [self._reflectance_on_device[0], False]     # (the origin cloud's column stays in HBM)
         new._merged = [self._merged[0], False]           # (cloud 0 stays merged and resident: only the new cloud 1 is merged)
         new.duplicates_removed = (self.duplicates_removed[0], 0)
         new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
@@ -466,6 +476,8 @@ class CloudPair:
             eng.set_normals(which, cloud.normals)
         if _has_colors(cloud):
             self._upload_colours(which)
+        if _has_reflectance(cloud) and hasattr(eng, "set_reflectance"):
+            self._upload_reflectance(which)
         after = eng.merge_duplicates(which, self._duplicates)
         self._merged[which] = after < before
         removed = list(self.duplicates_removed)
@@ -493,6 +505,7 @@ class CloudPair:
         # (and so do the angular columns, which compare each point's normal with its matched point's)
         if hasattr(eng, "nn_want_idx"):
             eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or self.__dict__.get("_ssim", False)
+                            or self.__dict__.get("_reflectance", False)        # (each point's reflectance against its matched point's)
                             or self.__dict__.get("_carry_normals", False)      # (the carry reads both directions' matched rows)
                             or any(_has_colors(c) for c in self.clouds))
 
@@ -955,6 +968,79 @@ class CloudPair:
         """The same for the reconstructed cloud."""
         return self._spacing_column(nat.DIR_RIGHT, k)
 
+    # -- reflectance (INTEGRATION.md, "Reflectance") ---------------------------------------------------------------------------
+    def _pair_has_reflectance(self, which: int) -> bool:
+        return self._reflectance_on_device[which] or _has_reflectance(self.clouds[which])
+
+    def _check_reflectance(self) -> None:
+        """The ValueErrors of options.check_reflectance, for this pair -- raised before any GPU work of a report."""
+        if self.ties != "pick":
+            raise ValueError("reflectance rows are not defined for ties='mean'")
+        if self._coll.sharded:
+            raise ValueError("reflectance rows are not available for sharded pairs (group=)")
+        if not all(self._pair_has_reflectance(k) for k in range(2)):
+            raise ValueError("the reflectance rows need the reflectance of both clouds")
+        if not hasattr(self._engine, "set_reflectance"):
+            raise ValueError("this engine has no reflectance column")
+
+    def _upload_reflectance(self, k: int) -> None:
+        self._engine.set_reflectance(k, _host_rows(self.clouds[k].reflectance))   # (uint8 / uint16 go as 16-bit words, widened exactly)
+        self._reflectance_on_device[k] = True
+
+    def _ensure_reflectance(self) -> None:
+        """Both clouds' reflectance in HBM (uploaded on first need, like the colours), and the matched rows kept by later
+        searches."""
+        self._check_reflectance()
+        for k in range(2):
+            if not self._reflectance_on_device[k]:
+                self._upload_reflectance(k)
+        if not self._reflectance:
+            self._reflectance = True
+            self._update_fusion()     # later searches keep the matched rows (this one's are recovered once)
+
+    def set_reflectance(self, which: int, reflectance) -> None:
+        """Replace the reflectance the pair holds for cloud ``which`` (the caller's cloud object is not touched): the searches,
+        normals, colours and every other column stay as they are; the next report reduces the reflectance columns again.  One value
+        per row of the cloud the pair WORKS ON: under ``duplicates=`` that is the merged cloud (``merge_map(which)`` says which
+        merged row each given row became), not the cloud that was given; a wrong length raises ``ValueError``."""
+        if which not in (0, 1):
+            raise ValueError("which must be 0 or 1")
+        if not hasattr(self._engine, "set_reflectance"):
+            raise ValueError("this engine has no reflectance column")
+        values = _host_rows(reflectance)
+        rows = self._engine.n_iter(nat.DIR_RIGHT if which else nat.DIR_LEFT)
+        if values.shape[0] != rows:
+            hint = (f" (duplicates={self._duplicates!r} merged {self.duplicates_removed[which]} of its rows away: pass one value per merged"
+                    " row, see merge_map)") if self._merged[which] else ""
+            raise ValueError(f"cloud {which} has {rows} rows but {values.shape[0]} reflectance values were given{hint}")
+        self._reflectance_on_device[which] = False
+        self._totals = {key: v for key, v in self._totals.items() if key[1] != nat.METRIC_REFLECTANCE}
+        self._graph_id = None                                        # (a captured point job read the old column)
+        self._engine.set_reflectance(which, values)
+        self._reflectance_on_device[which] = True
+
+    def get_reflectance(self, which: int) -> np.ndarray:
+        """The fp64 reflectance column the pair works on for cloud ``which`` (the merged one under ``duplicates=``)."""
+        if which not in (0, 1):
+            raise ValueError("which must be 0 or 1")
+        if not self._pair_has_reflectance(which):
+            raise ValueError(f"cloud {which} has no reflectance")
+        if not self._reflectance_on_device[which]:
+            self._upload_reflectance(which)
+        return self._engine.get_reflectance(which)
+
+    def _reflectance_column(self, direction: int) -> DeviceColumn:
+        self._ensure_reflectance()
+        return DeviceColumn(self, direction, "reflectance")
+
+    def get_left_reflectance_errors(self):
+        """Per point of the origin cloud: the squared difference of its reflectance and its nearest reconstructed point's (fp64;
+        a device column: ``np.asarray`` fetches it, ``np.sum`` / ``np.max`` reduce it on the GPU)."""
+        return self._reflectance_column(nat.DIR_LEFT)
+
+    def get_right_reflectance_errors(self):
+        return self._reflectance_column(nat.DIR_RIGHT)
+
     def get_left_neighbour_colors(self):
         """cloud_pair.py:120-121: the matched points' colours -- gathered on the device when asked for."""
         return DeviceColorRows(self, nat.DIR_LEFT, "neighbour")
@@ -967,7 +1053,7 @@ class CloudPair:
 
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
         ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
-        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)`` and/or the string ``"boundary"``.
+        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -1006,11 +1092,16 @@ class CloudPair:
             self._check_resolution(k)
         for k in sorted({item[2] for item in spacing_items}):
             self._ensure_resolution(k)
+        # reflectance: the check, then both clouds' columns in HBM (uploaded here the first time, outside any capture)
+        reflectance_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "reflectance"]
+        if reflectance_items:
+            self._ensure_reflectance()
+        reflectance_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_REFLECTANCE) for item in reflectance_items]
         requests, ssim_requests, selections = [], [], []
         stored_items = p2d_items + spacing_items
         p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, DeviceColumn._METRIC[item[0]]) for item in stored_items]
         for item in wanted:
-            if item in ranked_items or item in stored_items:
+            if item in ranked_items or item in stored_items or item in reflectance_items:
                 continue              # (ranked: their columns are requests of their own, EuclideanDistance's)
             if item in ssim_items:
                 ssim_requests.append((nat.DIR_LEFT if item[2] else nat.DIR_RIGHT, nat.METRIC_SSIM[item[1]]))
@@ -1058,13 +1149,21 @@ class CloudPair:
             column = (direction, nat.METRIC_D2 if p2p else nat.METRIC_D1)
             if column in requests:
                 selections.append(column + (rank_index(rank, eng.n_iter(direction)),))
-        self._xchg_wanted = list(requests) + ssim_requests + p2d_requests
+        # the reflectance columns join the first batch -- its k_point_jobs launch and its reduction launch -- when it has room
+        # for them: eight columns, of which at most four are formed by point jobs (unfused D2, angular, reflectance)
+        if reflectance_requests:
+            point_jobs = sum(1 for _, m in requests if m in (nat.METRIC_D2, nat.METRIC_ANGULAR))
+            if len(requests) + len(reflectance_requests) <= 8 and point_jobs + len(reflectance_requests) <= 4:
+                requests, reflectance_requests = requests + reflectance_requests, []
+        self._xchg_wanted = list(requests) + reflectance_requests + ssim_requests + p2d_requests
         self._sel_wanted = sorted(set(selections))
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
             ride = len(requests) + len(p2d_requests) <= 8     # (stored columns: they join the first batch when it has room)
             eng.reduce_prefetch_many((requests + p2d_requests if ride else requests)[:8], self.normal_index)
+            if reflectance_requests:
+                eng.reduce_prefetch_many(reflectance_requests, self.normal_index)
             for b in range(0, len(ssim_requests), 4):     # (at most four matched-row columns per batch: k_point_jobs)
                 eng.reduce_prefetch_many(ssim_requests[b:b + 4], self.normal_index)
             if not ride:
@@ -1073,7 +1172,7 @@ class CloudPair:
                 for batch in _selection_batches(self._sel_wanted):
                     eng.select_prefetch_many(batch, self.normal_index)
         else:
-            requests = requests + ssim_requests + p2d_requests
+            requests = requests + reflectance_requests + ssim_requests + p2d_requests
             for direction, metric in requests:
                 eng.reduce_prefetch(direction, metric, self.normal_index)
 
@@ -1114,6 +1213,14 @@ def _has_colors(cloud) -> bool:
         return bool(has())
     col = getattr(cloud, "colors", None)
     return col is not None and len(col) > 0
+
+
+def _has_reflectance(cloud) -> bool:
+    has = getattr(cloud, "has_reflectance", None)
+    if callable(has):
+        return bool(has())
+    refl = getattr(cloud, "reflectance", None)
+    return refl is not None and len(refl) > 0
 
 
 def _host_rows(a) -> np.ndarray:

@@ -128,11 +128,11 @@ static void free_buf(DevBuf &b)
 static void free_cloud(Cloud &c)
 {
     for (void **p : {(void **)&c.xyz32, (void **)&c.xyz64, (void **)&c.xyz32r, (void **)&c.nrm64, (void **)&c.nrm32, (void **)&c.rgb64,
-                     (void **)&c.rgb8, (void **)&c.sp, (void **)&c.ssim64, (void **)&c.res64}) {
+                     (void **)&c.rgb8, (void **)&c.sp, (void **)&c.ssim64, (void **)&c.res64, (void **)&c.refl64}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
-    c.cap32 = c.cap64 = c.cap32r = c.cap_nrm = c.cap_nrm32 = c.cap_rgb = c.cap_rgb8 = c.cap_sp = c.cap_ssim = c.cap_res = 0;
+    c.cap32 = c.cap64 = c.cap32r = c.cap_nrm = c.cap_nrm32 = c.cap_rgb = c.cap_rgb8 = c.cap_sp = c.cap_ssim = c.cap_res = c.cap_refl = 0;
     drop_cloud(c);
 }
 
@@ -439,7 +439,7 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
+                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_refl, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
     for (DevBuf *b : bufs) free_buf(*b);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
@@ -649,6 +649,55 @@ int pccm_set_colors_u8(pccm_ctx *ctx, int which, const unsigned char *rgb, int64
     c.rgb8_valid = true;
     c.n_rgb = n;
     return PCCM_OK;
+}
+
+// The two reflectance setters: arguments, the point count, the stream drained, what read the old column forgotten
+// (reflectance_changed), the upload (bytes per value: esz), the widening ingest and its count of non-finite values.
+static int set_reflectance(pccm_ctx *ctx, int which, const void *r, int64_t n, int dtype, size_t esz, int on_device)
+{
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!r || n <= 0) return fail(PCCM_E_ARG, "empty reflectance");
+    Cloud &c = ctx->cloud[which];
+    if (c.n == 0) return fail(PCCM_E_STATE, "set cloud %d before its reflectance", which);
+    if (n != c.n) return fail(PCCM_E_ARG, "cloud %d has %lld points but %lld reflectance values", which, (long long)c.n, (long long)n);
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    reflectance_changed(ctx, which);
+    int rc = grow((void **)&c.refl64, c.cap_refl, (size_t)n * sizeof(double));
+    if (rc) return rc;
+    const void *dsrc = nullptr;
+    if ((rc = upload(ctx, r, (size_t)n * esz, on_device, &dsrc))) return rc;
+    unsigned long long *stats = (unsigned long long *)ctx->stats.p;
+    PCCM_HIP(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    if ((rc = launch_ingest_reflectance(ctx, dsrc, dtype, n, c.refl64, stats))) return rc;
+    unsigned long long bad = 1;
+    PCCM_HIP(hipMemcpyAsync(&bad, stats + 2, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    if (bad != 0) return fail(PCCM_E_ARG, "reflectance of cloud %d is not finite", which);      // n_refl stays 0: no reflectance
+    c.n_refl = n;
+    return PCCM_OK;
+}
+
+int pccm_set_reflectance(pccm_ctx *ctx, int which, const void *r, int64_t n, int dtype, int on_device)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (dtype != PCCM_F32 && dtype != PCCM_F64) return fail(PCCM_E_ARG, "dtype must be PCCM_F32 or PCCM_F64");
+    return set_reflectance(ctx, which, r, n, dtype, dtype == PCCM_F32 ? 4 : 8, on_device);
+}
+
+int pccm_set_reflectance_u16(pccm_ctx *ctx, int which, const uint16_t *r, int64_t n)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!r || n <= 0) return fail(PCCM_E_ARG, "empty reflectance");
+    if (ctx->cloud[which].n == 0) return fail(PCCM_E_STATE, "set cloud %d before its reflectance", which);
+    if (n != ctx->cloud[which].n)
+        return fail(PCCM_E_ARG, "cloud %d has %lld points but %lld reflectance values", which, (long long)ctx->cloud[which].n, (long long)n);
+    // every 16-bit value is a float: widened exactly here, the float ingest takes it from there (four bytes per point up)
+    std::vector<float> wide;
+    try { wide.assign(r, r + n); } catch (const std::bad_alloc &) { return fail(PCCM_E_OOM, "no host memory for %lld reflectance values", (long long)n); }
+    return set_reflectance(ctx, which, wide.data(), n, PCCM_F32, sizeof(float), 0);
 }
 
 // common front end of the two colour calls: operands of direction `dir` and the neighbour rows to use
@@ -951,7 +1000,7 @@ int pccm_carry_normals(pccm_ctx *ctx, int from, int *built)
     if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(cf.n, ct.n)))) return rc;
     normals_changed(ctx, to);                          // (normals carried the other way were made from the ones being replaced)
     ct.n_nrm = ct.n;
-    if ((rc = launch_carry(ctx, rf.idx, rg.idx, cf.nrm64, cf.n, ct.n, (uint32_t *)ctx->carry_ws.p, ct.nrm64))) {
+    if ((rc = launch_carry(ctx, rf.idx, rg.idx, cf.nrm64, cf.n, ct.n, (uint32_t *)ctx->carry_ws.p, ct.nrm64, 3))) {
         ct.n_nrm = 0;
         return rc;
     }
@@ -976,6 +1025,8 @@ int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out)
         return fail(PCCM_E_STATE, "cloud %d has %lld points but %lld normals: rows cannot be merged", which, (long long)c.n, (long long)c.n_nrm);
     if (c.n_rgb != 0 && c.n_rgb != c.n)
         return fail(PCCM_E_STATE, "cloud %d has %lld points but %lld colours: rows cannot be merged", which, (long long)c.n, (long long)c.n_rgb);
+    if (c.n_refl != 0 && c.n_refl != c.n)
+        return fail(PCCM_E_STATE, "cloud %d has %lld points but %lld reflectance values: rows cannot be merged", which, (long long)c.n, (long long)c.n_refl);
     const int64_t n = c.n;
     int rc;
     if ((rc = ensure(ctx, ctx->merge_ws, merge_ws_bytes(n)))) return rc;
@@ -998,15 +1049,31 @@ int pccm_merge_duplicates(pccm_ctx *ctx, int which, int mode, int64_t *n_out)
         // the carry's passes with nn_F := rep: per representative the colours of its group, summed in ascending row order
         if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(n, n)))) return rc;
         const int32_t *rep = (const int32_t *)(ww + L.rep);
-        if ((rc = launch_carry(ctx, rep, nullptr, c.rgb64, n, n, (uint32_t *)ctx->carry_ws.p, wd))) return rc;
+        if ((rc = launch_carry(ctx, rep, nullptr, c.rgb64, n, n, (uint32_t *)ctx->carry_ws.p, wd, 3))) return rc;
         rgb = wd;
     }
+    // the reflectance likewise, by the same passes over rows of one double: merge_refl holds the merged column [n] and, behind it,
+    // the averages by original row [n]
+    const bool has_refl = c.n_refl == n, refl_avg = has_refl && mode == PCCM_DUP_AVERAGE;
+    const double *refl = has_refl ? c.refl64 : nullptr;
+    double *rd = nullptr;
+    if (has_refl) {
+        if ((rc = ensure(ctx, ctx->merge_refl, (size_t)(refl_avg ? 2 : 1) * n * sizeof(double)))) return rc;
+        rd = (double *)ctx->merge_refl.p;
+    }
+    if (refl_avg) {
+        if ((rc = ensure(ctx, ctx->carry_ws, carry_ws_bytes(n, n)))) return rc;
+        if ((rc = launch_carry(ctx, (const int32_t *)(ww + L.rep), nullptr, c.refl64, n, n, (uint32_t *)ctx->carry_ws.p, rd + n, 1))) return rc;
+        refl = rd + n;
+    }
     if ((rc = ensure(ctx, ctx->merge_map[which], (size_t)n * sizeof(int32_t)))) return rc;
-    if ((rc = launch_merge_gather(ctx, c.xyz64, has_nrm ? c.nrm64 : nullptr, rgb, n, wd + 3 * n, ww, (int32_t *)ctx->merge_map[which].p))) return rc;
+    if ((rc = launch_merge_gather(ctx, c.xyz64, has_nrm ? c.nrm64 : nullptr, rgb, refl, n, wd + 3 * n, rd, ww, (int32_t *)ctx->merge_map[which].p)))
+        return rc;
     // the merged rows enter the way any resident fp64 rows do (one ingest path: statistics, fp32 copies, invalidation)
     if ((rc = pccm_set_cloud(ctx, which, wd + 3 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
     if (has_nrm && (rc = pccm_set_normals(ctx, which, wd + 6 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
     if (has_rgb && (rc = pccm_set_colors(ctx, which, wd + 9 * n, (int64_t)n_new, PCCM_F64, 1))) return rc;
+    if (has_refl && (rc = pccm_set_reflectance(ctx, which, rd, (int64_t)n_new, PCCM_F64, 1))) return rc;
     ctx->merge_n[which] = n;
     return PCCM_OK;
 }
@@ -1048,6 +1115,17 @@ int pccm_get_colors(pccm_ctx *ctx, int which, double *out)
     const Cloud &c = ctx->cloud[which];
     if (c.n_rgb <= 0) return fail(PCCM_E_STATE, "cloud %d has no colours", which);
     return fetch(ctx, out, c.rgb64, (size_t)c.n_rgb * 3 * sizeof(double));
+}
+
+int pccm_get_reflectance(pccm_ctx *ctx, int which, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    const Cloud &c = ctx->cloud[which];
+    if (c.n_refl <= 0) return fail(PCCM_E_STATE, "cloud %d has no reflectance", which);
+    return fetch(ctx, out, c.refl64, (size_t)c.n_refl * sizeof(double));
 }
 
 int pccm_ssim_features(pccm_ctx *ctx, int which, int k, int attrs, int *built)
@@ -1490,16 +1568,27 @@ static int check_ssim(pccm_ctx *ctx, int dir, const Cloud &it, const Cloud &se, 
     return PCCM_OK;
 }
 
+// PCCM_METRIC_REFLECTANCE: one reflectance per point on both clouds (pccm_set_reflectance*)
+static int check_reflectance(int dir, const Cloud &it, const Cloud &se, const NNResult &res)
+{
+    if (dir == PCCM_DIR_SELF) return fail(PCCM_E_ARG, "the reflectance error is not defined for the self search");
+    if (res.ties == PCCM_TIES_MEAN) return fail(PCCM_E_STATE, "the reflectance error is not defined under PCCM_TIES_MEAN");
+    if (it.n_refl != it.n || se.n_refl != se.n)
+        return fail(PCCM_E_STATE, "the reflectance error needs the reflectance of both clouds (pccm_set_reflectance)");
+    return PCCM_OK;
+}
+
 // the feature column of a PCCM_METRIC_SSIM_* metric
 static const double *ssim_column(const Cloud &c, int metric)
 {
     return c.ssim64 + (size_t)(metric - PCCM_METRIC_SSIM_GEOMETRY) * c.n;
 }
 
-// columns that compare a row with its matched row (PCCM_METRIC_ANGULAR, PCCM_METRIC_SSIM_*): normal_mode does not apply
+// columns that compare a row with its matched row (PCCM_METRIC_ANGULAR, PCCM_METRIC_SSIM_*, PCCM_METRIC_REFLECTANCE): normal_mode
+// does not apply
 static bool matched_column(int metric)
 {
-    return metric == PCCM_METRIC_ANGULAR || is_ssim_metric(metric);
+    return metric == PCCM_METRIC_ANGULAR || is_ssim_metric(metric) || metric == PCCM_METRIC_REFLECTANCE;
 }
 
 // PCCM_METRIC_P2D*: a stored column of the direction (pccm_p2d_build_attrs); neither the matched rows nor normal_mode enter it
@@ -1534,6 +1623,7 @@ static int column_check(pccm_ctx *ctx, int dir, int metric, int normal_mode, con
     if (metric == PCCM_METRIC_D1) return PCCM_OK;
     if (metric == PCCM_METRIC_ANGULAR) return check_angular(ctx, dir, it, se);
     if (is_ssim_metric(metric)) return check_ssim(ctx, dir, it, se, res, metric);
+    if (metric == PCCM_METRIC_REFLECTANCE) return check_reflectance(dir, it, se, res);
     if (is_p2d_metric(metric)) return check_p2d(ctx, dir, metric);
     if (metric == PCCM_METRIC_RESOLUTION) return check_resolution(ctx, dir);
     if (!normal_mode_enters(metric)) return fail(PCCM_E_ARG, "bad metric %d", metric);
@@ -1541,7 +1631,7 @@ static int column_check(pccm_ctx *ctx, int dir, int metric, int normal_mode, con
     return check_normals(ctx, it, se, res, normal_mode);
 }
 
-// The k_point_jobs job of a checked request (column_check): the D2 / PROJ / ANGULAR / SSIM_* column of the shard's rows into out
+// The k_point_jobs job of a checked request (column_check): the D2 / PROJ / ANGULAR / SSIM_* / REFLECTANCE column of the shard's rows into out
 // ([ns]), or -- PCCM_METRIC_D1 -- their error vectors ([ns][3]).  recs: the matched rows are read from the direction's matched
 // records in place (ColumnSource::recs); otherwise from the plain idx column, which the caller has made ready.
 static int point_job_fill(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *out, bool recs, const Cloud &it, const Cloud &se,
@@ -1549,8 +1639,9 @@ static int point_job_fill(pccm_ctx *ctx, int dir, int metric, int normal_mode, d
 {
     const bool matched = matched_column(metric), ssim = is_ssim_metric(metric);
     P.q64 = it.xyz64; P.r64 = se.xyz64;
-    P.nrm = ssim ? ssim_column(se, metric) : se.nrm64;
-    P.inrm = !matched ? nullptr : ssim ? ssim_column(it, metric) : it.nrm64;
+    const bool refl = metric == PCCM_METRIC_REFLECTANCE;
+    P.nrm = ssim ? ssim_column(se, metric) : refl ? se.refl64 : se.nrm64;
+    P.inrm = !matched ? nullptr : ssim ? ssim_column(it, metric) : refl ? it.refl64 : it.nrm64;
     P.c64 = P.cn64 = nullptr;
     if (!matched && res.ties == PCCM_TIES_MEAN) {           // the virtual neighbours, and their averaged normals where they are indexed
         const bool nmean = normal_mode_enters(metric) && normal_mode == PCCM_NORMAL_NEIGHBOUR;
@@ -1768,13 +1859,13 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
         break;
     case ColumnSource::kStored: dev = stored_column(ctx, dir, metric) + res->begin; break;
     case ColumnSource::kPointJob:
-        // (PCCM_METRIC_SSIM_*: the angular column's job on the two clouds' feature columns instead of their normals)
+        // (PCCM_METRIC_SSIM_* / REFLECTANCE: the angular column's job on the two clouds' feature / reflectance columns instead of their normals)
         if (src.prep != ColumnSource::kReady && (rc = ensure_plain(ctx, *res, true))) return rc;
         if ((rc = ensure(ctx, s.val, (size_t)(ns > 0 ? ns : 1) * sizeof(double)))) return rc;
         dev = (const double *)s.val.p;
         if (ns > 0) {
             if (pj.njobs >= 4)
-                return fail(PCCM_E_ARG, matched_column(metric) ? "at most four unfused point-to-plane, angular or PointSSIM columns per call"
+                return fail(PCCM_E_ARG, matched_column(metric) ? "at most four unfused point-to-plane, angular, PointSSIM or reflectance columns per call"
                                                                : "at most four unfused point-to-plane columns per call");
             if ((rc = point_job_fill(ctx, dir, metric, normal_mode, (double *)s.val.p, src.recs, *it, *se, *res, pj.j[pj.njobs]))) return rc;
             pj.off[pj.njobs + 1] = pj.off[pj.njobs] + ns;

@@ -13,7 +13,7 @@
 // k_merge_probe<true> (n) reads rep[i] back and notes per wave which rows are representatives (a 64-bit mask and its count);
 // k_merge_scan_waves (one lane per wave of rows) and k_merge_scan_top (one wave) turn the counts into exclusive prefixes -- the
 // ordered scan -- and leave n' in head[0]; k_merge_gather (n) writes map[i] = the position of rep[i] and, for a representative, its
-// merged row.
+// merged row.  A reflectance column is averaged by the same passes over rows of one double (CarryView::nc).
 #include "pccm_internal.h"
 
 namespace pccm {
@@ -30,16 +30,18 @@ __host__ __device__ constexpr int64_t whole_waves(int64_t rows) { return (rows +
 // cnt[n_to], fill[n_to], base[n_to], list[n_from], queue[n_from / (kCarryLong + 1) + 1]
 struct CarryView {
     const int32_t *nn_f, *nn_g;     // nn_F [n_from]: matched rows of the direction that iterates the source cloud; nn_G [n_to] or null
-    const double *src;              // the source normals [n_from][3]
-    double *out;                    // the target normals [n_to][3]
+    const double *src;              // the source rows [n_from][nc]: normals or colours (nc 3), or a scalar column (nc 1)
+    double *out;                    // the target rows [n_to][nc]
+    int nc;
     int64_t n_from, n_to;
     uint32_t *head, *cnt, *fill, *base, *list, *queue;
 };
 
 static CarryView carry_view(const int32_t *nn_f, const int32_t *nn_g, const double *src, double *out, uint32_t *ws, int64_t n_from,
-                            int64_t n_to)
+                            int64_t n_to, int nc)
 {
     CarryView V;
+    V.nc = nc;
     V.nn_f = nn_f;
     V.nn_g = nn_g;
     V.src = src;
@@ -64,6 +66,22 @@ __device__ __forceinline__ double lane_value(double v, int lane)      // v of `l
 {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
     return __hiloint2double(hi, lo);
+}
+
+// one row of the source / of the target: three doubles, of which a scalar column (nc 1) holds the first -- the other two are
+// zeros that every sum carries along and nobody stores
+__device__ __forceinline__ void carry_load(const CarryView &V, int64_t row, double &a0, double &a1, double &a2)
+{
+    const double *p = V.src + V.nc * row;
+    a0 = p[0];
+    a1 = a2 = 0.0;
+    if (V.nc == 3) { a1 = p[1]; a2 = p[2]; }
+}
+__device__ __forceinline__ void carry_store(const CarryView &V, int64_t row, double s0, double s1, double s2)
+{
+    double *o = V.out + V.nc * row;
+    o[0] = s0;
+    if (V.nc == 3) { o[1] = s1; o[2] = s2; }
 }
 
 __device__ __forceinline__ void carry_count(const CarryView &V, int64_t i, int lane)
@@ -115,22 +133,22 @@ __device__ __forceinline__ void carry_sum(const CarryView &V, int64_t i)
     if (i >= V.n_to) return;
     const uint32_t m = V.cnt[i];
     if (m > (uint32_t)kCarryLong) return;
-    double *o = V.out + 3 * i;
+    double s0, s1, s2;
     if (m == 0) {                                                   // nobody's nearest neighbour: its own nearest row's normal
         if (!V.nn_g) return;                                        // (pccm_merge_duplicates: not a representative, no row of its own)
         int64_t r = V.nn_g[i];
         r = r < 0 ? 0 : (r >= V.n_from ? V.n_from - 1 : r);
-        o[0] = V.src[3 * r]; o[1] = V.src[3 * r + 1]; o[2] = V.src[3 * r + 2];
+        carry_load(V, r, s0, s1, s2);
+        carry_store(V, i, s0, s1, s2);
         return;
     }
     const uint32_t *seg = V.list + V.base[i];
-    double s0, s1, s2;
     if (m <= 2) {                                                   // (a two-term sum is the same either way round)
-        const double *a = V.src + 3 * (int64_t)seg[0];
-        s0 = a[0]; s1 = a[1]; s2 = a[2];
+        carry_load(V, (int64_t)seg[0], s0, s1, s2);
         if (m == 2) {
-            const double *b = V.src + 3 * (int64_t)seg[1];
-            s0 = __dadd_rn(s0, b[0]); s1 = __dadd_rn(s1, b[1]); s2 = __dadd_rn(s2, b[2]);
+            double b0, b1, b2;
+            carry_load(V, (int64_t)seg[1], b0, b1, b2);
+            s0 = __dadd_rn(s0, b0); s1 = __dadd_rn(s1, b1); s2 = __dadd_rn(s2, b2);
         }
     } else {
         // ascending rows without a private array: the smallest row above the last one, m times
@@ -143,14 +161,15 @@ __device__ __forceinline__ void carry_sum(const CarryView &V, int64_t i)
                 next = (v > last && v < next) ? v : next;
             }
             if (next == INT64_MAX) break;                           // (rows of a list are distinct: never taken)
-            const double *a = V.src + 3 * next;
-            if (r == 0) { s0 = a[0]; s1 = a[1]; s2 = a[2]; }
-            else { s0 = __dadd_rn(s0, a[0]); s1 = __dadd_rn(s1, a[1]); s2 = __dadd_rn(s2, a[2]); }
+            double a0, a1, a2;
+            carry_load(V, next, a0, a1, a2);
+            if (r == 0) { s0 = a0; s1 = a1; s2 = a2; }
+            else { s0 = __dadd_rn(s0, a0); s1 = __dadd_rn(s1, a1); s2 = __dadd_rn(s2, a2); }
             last = next;
         }
     }
     const double dm = (double)m;
-    o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
+    carry_store(V, i, __ddiv_rn(s0, dm), __ddiv_rn(s1, dm), __ddiv_rn(s2, dm));
 }
 
 // wave i / 64 takes one queued target and walks nn_F in row order, 64 rows a step (four steps' rows are loaded ahead); the lanes
@@ -178,7 +197,7 @@ __device__ __forceinline__ void carry_walk(const CarryView &V, int64_t i, int la
             for (int c = 0; c < 2; ++c) {
                 const int64_t r = r0 + 64 * (h + c) + lane;
                 a[c][0] = a[c][1] = a[c][2] = 0.0;
-                if (got[h + c] == j) { a[c][0] = V.src[3 * r]; a[c][1] = V.src[3 * r + 1]; a[c][2] = V.src[3 * r + 2]; }
+                if (got[h + c] == j) carry_load(V, r, a[c][0], a[c][1], a[c][2]);
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -202,8 +221,7 @@ __device__ __forceinline__ void carry_walk(const CarryView &V, int64_t i, int la
     }
     if (lane == 0) {
         const double dm = (double)V.cnt[j];
-        double *o = V.out + 3 * (int64_t)j;
-        o[0] = __ddiv_rn(s0, dm); o[1] = __ddiv_rn(s1, dm); o[2] = __ddiv_rn(s2, dm);
+        carry_store(V, (int64_t)j, __ddiv_rn(s0, dm), __ddiv_rn(s1, dm), __ddiv_rn(s2, dm));
     }
 }
 
@@ -233,11 +251,11 @@ __global__ __launch_bounds__(256) void k_carry_sum(CarryView V)
 
 // pccm_carry_normals on the stream: counts and cursors zeroed, then count | place | scatter + walk | sum
 int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
-                 uint32_t *ws, double *out)
+                 uint32_t *ws, double *out, int nc)
 {
     ProfScope ps(ctx, PCCM_K_POINT);
     PCCM_HIP(hipMemsetAsync(ws, 0, (size_t)(4 + 2 * n_to) * sizeof(uint32_t), ctx->stream));     // header, cnt, fill
-    const CarryView V = carry_view(nn_f, nn_g, n_from64, out, ws, n_from, n_to);
+    const CarryView V = carry_view(nn_f, nn_g, n_from64, out, ws, n_from, n_to, nc);
     const int64_t walk_lanes = (n_from / (kCarryLong + 1)) * 64;       // one wave per list that can be long
     auto blocks = [](int64_t lanes) { return dim3((unsigned)((lanes + 255) / 256)); };
     PCCM_LAUNCH(ctx, k_carry_count, blocks(whole_waves(n_from)), dim3(256), 0, ctx->stream, V);
@@ -259,6 +277,8 @@ struct MergeArgs {
     const double *x;                // the points [n][3]
     const double *nrm, *rgb;        // the normals / the colours to keep per representative [n][3], or null
     double *out;                    // the merged rows (written): points [n][3], then normals [n][3], then colours [n][3]
+    const double *refl;             // the reflectance to keep per representative [n], or null
+    double *refl_out;               // the merged reflectance [n] (written)
     uint32_t *ws;                   // the uint32 words of the workspace (MergeLayout)
     int32_t *map;                   // [n] (written)
     uint32_t *err;                  // the device error word, or null
@@ -383,6 +403,7 @@ __global__ __launch_bounds__(256) void k_merge_gather(MergeArgs A)
     o[0] = x[3 * i]; o[1] = x[3 * i + 1]; o[2] = x[3 * i + 2];
     if (nrm) { o += 3 * n; o[0] = nrm[3 * i]; o[1] = nrm[3 * i + 1]; o[2] = nrm[3 * i + 2]; o -= 3 * n; }
     if (rgb) { o += 6 * n; o[0] = rgb[3 * i]; o[1] = rgb[3 * i + 1]; o[2] = rgb[3 * i + 2]; }
+    if (A.refl) A.refl_out[p] = A.refl[i];
 }
 
 static dim3 merge_blocks(int64_t rows) { return dim3((unsigned)((whole_waves(rows) + 255) / 256)); }
@@ -405,8 +426,8 @@ int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, uint32_t *wor
     return PCCM_OK;
 }
 
-int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, double *out,
-                        uint32_t *words, int32_t *map)
+int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, const double *refl, int64_t n, double *out,
+                        double *refl_out, uint32_t *words, int32_t *map)
 {
     ProfScope ps(ctx, PCCM_K_POINT);
     MergeArgs A = {};
@@ -414,6 +435,8 @@ int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, con
     A.nrm = nrm;
     A.rgb = rgb;
     A.out = out;
+    A.refl = refl_out ? refl : nullptr;
+    A.refl_out = refl_out;
     A.ws = words;
     A.map = map;
     A.n = n;

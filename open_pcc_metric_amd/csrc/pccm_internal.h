@@ -82,6 +82,10 @@ struct Cloud {
     double *res64 = nullptr;
     size_t cap_res = 0;
     int res_k = 0;
+    // reflectance (pccm_set_reflectance*): [n_refl] fp64, one scalar per point with the values as given; n_refl is 0 or n
+    double *refl64 = nullptr;
+    size_t cap_refl = 0;
+    int64_t n_refl = 0;
     double solo_scale = 1.0;    // cell-edge factor of a grid over this cloud alone (grid_ensure_solo), decided for ...
     uint64_t solo_scale_version = ~0ull;   // ... this version of the cloud
 };
@@ -348,6 +352,7 @@ struct pccm_ctx {
     // row of its group (merge_n 0: never merged, the map is the identity); new points for the cloud and pccm_ctx_reset clear it
     pccm::DevBuf merge_map[2];
     int64_t merge_n[2] = {0, 0};
+    pccm::DevBuf merge_refl;              // ... and for a cloud with reflectance: the merged column [n], then (PCCM_DUP_AVERAGE) the averages by original row [n]
     pccm::DevBuf merge_ws;                // ... its workspace (merge_layout): averaged colours, merged rows, group table, scan words
     // scratch
     pccm::DevBuf part_b1, part_g, part_b2, val, stats, staging, counters;
@@ -609,15 +614,23 @@ __host__ __device__ __forceinline__ bool is_ssim_metric(int metric)
     return metric >= PCCM_METRIC_SSIM_GEOMETRY && metric <= PCCM_METRIC_SSIM_COLOR;
 }
 
-// One per-point column formed from a search result (k_point_jobs, the only kernel that forms them): D2 / PROJ / ANGULAR / SSIM_* as
+// PCCM_METRIC_REFLECTANCE: a point's reflectance a against its matched point's b (include/pccm.h), each operation separately rounded
+__device__ __forceinline__ double reflectance_error(double a, double b)
+{
+    const double d = __dsub_rn(a, b);
+    return __dmul_rn(d, d);
+}
+
+// One per-point column formed from a search result (k_point_jobs, the only kernel that forms them): D2 / PROJ / ANGULAR / SSIM_* / REFLECTANCE as
 // [ns] values, or -- PCCM_METRIC_D1 -- the error vectors as [ns][3] rows.  pccm_api.hip fills it in one place (point_job_fill), for
 // the reduction batches and the one-job launches of pccm_point_metric / pccm_error_vectors alike.
 struct PointJob {
     const double *q64, *r64, *nrm;
     const double *c64, *cn64;   // PCCM_TIES_MEAN: per shard row the virtual neighbour / its averaged normal (null: gather via idx)
     const double *inrm;         // PCCM_METRIC_ANGULAR: the iterating cloud's normals (nrm: the searched cloud's); PCCM_METRIC_SSIM_*:
-                                // the iterating cloud's feature column (nrm: the searched cloud's)
-    const float4 *recs;         // PCCM_METRIC_ANGULAR / SSIM_*: matched records {x, y, z, row} (NNForm::layout 1) instead of idx, or null
+                                // the iterating cloud's feature column (nrm: the searched cloud's); PCCM_METRIC_REFLECTANCE: the
+                                // iterating cloud's reflectance column (nrm: the searched cloud's)
+    const float4 *recs;         // PCCM_METRIC_ANGULAR / SSIM_* / REFLECTANCE: matched records {x, y, z, row} (NNForm::layout 1) instead of idx, or null
     const int32_t *idx;
     int64_t q_begin;
     int metric, normal_mode;
@@ -694,15 +707,21 @@ int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs);
 // nn_f [n_from] / nn_g [n_to]: the matched rows of the two directions; nn_g null: rows of `out` that no row of nn_f names are left
 // alone (pccm_merge_duplicates)
 size_t carry_ws_bytes(int64_t n_from, int64_t n_to);
+// nc: the doubles per row of n_from64 and out -- 3 (normals, colours) or 1 (a scalar column: the reflectance)
 int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
-                 uint32_t *ws, double *out);
+                 uint32_t *ws, double *out, int nc);
 inline size_t merge_ws_bytes(int64_t n) { return merge_layout(n).bytes(); }
 // pccm_merge_duplicates on the stream, in two halves with the caller's read of n' (head[0] of the workspace's words) between them:
 // table filled, insert | find | the two scans; then -- rows were merged away -- the gather into `out` (rgb: the colours to keep
 // per representative row, the cloud's own or the averages).  `words`: the uint32 part of the workspace (MergeLayout)
 int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, uint32_t *words);
-int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, int64_t n, double *out,
-                        uint32_t *words, int32_t *map);
+// refl / refl_out: the reflectance to keep per representative row [n] (the cloud's own column or the averages) and the merged
+// column [n] (written), or both null
+int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, const double *refl, int64_t n, double *out,
+                        double *refl_out, uint32_t *words, int32_t *map);
+// pccm_point.hip: the reflectance ingest -- src [n] of PCCM_F32 or PCCM_F64 widened exactly into out [n] (the normals' widening
+// copy over n values); stats[2] counts the waves that met a non-finite value
+int launch_ingest_reflectance(pccm_ctx *ctx, const void *src, int dtype, int64_t n, double *out, unsigned long long *stats);
 // result records -> plain columns (q32 / row0: the iterating cloud's rows, for records of layout 1)
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2);
 // *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when

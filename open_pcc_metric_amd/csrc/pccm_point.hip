@@ -149,6 +149,20 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
     return PCCM_OK;
 }
 
+// Reflectance: [n] scalars of f32 or f64 -> the fp64 column, values as given.  The widening copy of the normals' ingest over n
+// values instead of 3 n (no fp32 copy): stats[2] counts the waves that met a non-finite value.
+int launch_ingest_reflectance(pccm_ctx *ctx, const void *src, int dtype, int64_t n, double *out, unsigned long long *stats)
+{
+    ProfScope ps(ctx, PCCM_K_INGEST);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (dtype == PCCM_F32)
+        PCCM_LAUNCH(ctx, (k_ingest_normals<float>), grid, block, 0, ctx->stream, (const float *)src, n, out, (float *)nullptr, stats);
+    else
+        PCCM_LAUNCH(ctx, (k_ingest_normals<double>), grid, block, 0, ctx->stream, (const double *)src, n, out, (float *)nullptr, stats);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // K3 (k_point_jobs): every per-point column that is formed from a search result -- the reductions' and selections' batches
 // (up to four columns per launch) and the getters (pccm_point_metric, pccm_error_vectors: one job) alike.
@@ -160,6 +174,7 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
 // PCCM_METRIC_D1: the error vector itself, val as [ns][3] rows (pccm_error_vectors; the D1 column needs no point pass).
 // PCCM_METRIC_ANGULAR (the pick's column): the own normal inrm[gi] against the matched row's nrm[j] -- 24 + 4 (or 16) + 24 + 8 bytes.
 // PCCM_METRIC_SSIM_*: inrm / nrm are the two clouds' feature columns, the own feature against the matched row's -- 8 + 4 (or 16) + 8 + 8.
+// PCCM_METRIC_REFLECTANCE: inrm / nrm are the two clouds' reflectance columns, the same traffic.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void point_row(const PointJob &J, int64_t i)
 {
@@ -172,6 +187,11 @@ __device__ __forceinline__ void point_row(const PointJob &J, int64_t i)
     if (is_ssim_metric(J.metric)) {
         const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
         J.val[i] = ssim_similarity(J.inrm[gi], J.nrm[j]);
+        return;
+    }
+    if (J.metric == PCCM_METRIC_REFLECTANCE) {
+        const int64_t j = J.recs ? (int64_t)__float_as_int(J.recs[i].w) : (int64_t)J.idx[i];
+        J.val[i] = reflectance_error(J.inrm[gi], J.nrm[j]);
         return;
     }
     const int64_t j = J.idx[i];

@@ -3,7 +3,7 @@
 //
 // The products: the searches' results (NNResult::valid, NNForm::fused), normals carried to a cloud (pccm_ctx::carry), the
 // merge maps (merge_n), PointSSIM features (Cloud::ssim_attrs / ssim_k), point spacings (Cloud::res_k), the point-to-distribution
-// columns (p2d_k, p2d_color), and everything keyed on a counter: pending reductions and selections, tie columns, the colour memo,
+// columns (p2d_k, p2d_color), a cloud's reflectance (Cloud::n_refl), and everything keyed on a counter: pending reductions and selections, tie columns, the colour memo,
 // captured graphs, grid caches.  What ESTABLISHES a product stays with its builder (ssim_attrs = attrs, res_k = K, p2d_k = k,
 // carry.to = to, merge_n = n, valid = true, form = ...).
 //
@@ -72,7 +72,7 @@ inline void column_moved(pccm_ctx *ctx) { ctx->epoch++; }
 // forget the content, keep the allocations
 inline void drop_cloud(Cloud &c)
 {
-    c.n = c.n_pad = c.n_nrm = c.n_rgb = 0;
+    c.n = c.n_pad = c.n_nrm = c.n_rgb = c.n_refl = 0;
     c.nrm_deferred = false;
     c.nrm_host = nullptr;
     c.sp_valid = c.sp_tried = false;
@@ -140,6 +140,17 @@ inline void colors_changed(pccm_ctx *ctx, int which)
     c.ssim_attrs &= ~PCCM_SSIM_COLOR;
     if (ctx->p2d_color) column_rebuild(ctx, Stored::kP2dColor);
     ctx->rgb_gen++;                                    // (the colour memo and the tie columns' averaged colours are stale)
+}
+
+// Cloud `which` is getting a new reflectance.  The column is read only by PCCM_METRIC_REFLECTANCE point jobs, so the searches'
+// results, normals, colours, features, spacings and point-to-distribution columns stay; pending reductions of every direction may
+// have bound the old column, and a captured graph's point job reads it (the buffer may move as well).  The cloud is left without
+// reflectance; the setter says what it has once the values are there.
+inline void reflectance_changed(pccm_ctx *ctx, int which)
+{
+    ctx->cloud[which].n_refl = 0;
+    for (int d = 0; d < 3; ++d) ctx->nn_gen[d]++;
+    ctx->epoch++;
 }
 
 // pccm_ctx_reset's bookkeeping: nothing of the last owner's inputs or results is left, the allocations stay

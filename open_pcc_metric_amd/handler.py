@@ -3,7 +3,7 @@
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
                                   [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
-                                  [--resolution-psnr] [--resolution-neighbours K] [--csv]
+                                  [--resolution-psnr] [--resolution-neighbours K] [--reflectance] [--reflectance-peak P] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -39,7 +39,11 @@ points").  ``--resolution-psnr`` (no counterpart in the reference) adds, after a
 Javaheri et al. (ICIP 2020): each cloud's intrinsic resolution -- the average distance of a point to its
 ``--resolution-neighbours`` nearest neighbours in its own cloud -- and the PSNR of the D1 and, with ``--point-to-plane``, D2 errors
 (with ``--hausdorff`` also of the Hausdorff distances) against the ORIGINAL cloud's resolution as the peak, instead of its
-bounding box ("Resolution-adaptive PSNR").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+bounding box ("Resolution-adaptive PSNR").  ``--reflectance`` (no counterpart in the reference) adds, after all
+others, the reflectance rows MPEG's ``pc_error`` reports for LiDAR content: the mean -- with ``--hausdorff`` also the maximum --
+squared difference between each point's reflectance and its matched point's, on the files' values as given, and their PSNR against
+``--reflectance-peak`` (default 65535, the 16-bit range; 255 for 8-bit intensity).  Both files need a reflectance property;
+``--ties mean`` with it is a usage error ("Reflectance").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -94,6 +98,12 @@ import click
                    "--point-to-plane for D2 and with --hausdorff for the Hausdorff distances too.  Does not depend on --ties.")
 @click.option("--resolution-neighbours", "resolution_neighbours", type=click.IntRange(1, 63), default=10, show_default=True,
               help="Nearest neighbours a point's spacing is averaged over (the point itself not counted).")
+@click.option("--reflectance", "reflectance", required=False, is_flag=True,
+              help="Report the reflectance MSE and PSNR (LiDAR return intensity, as MPEG's pc_error reports it) as well, after all "
+                   "other rows: the squared difference between each point's reflectance and its matched point's, values as given; "
+                   "with --hausdorff also its worst point.  Both clouds need a reflectance.  Not with --ties mean.")
+@click.option("--reflectance-peak", "reflectance_peak", type=float, default=65535.0, show_default=True,
+              help="Peak of the reflectance PSNR rows (65535: 16-bit reflectance; 255: 8-bit intensity).")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -108,20 +118,21 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
     from .options import (CalculateOptions, check_carry_normals, check_duplicates, check_hausdorff_rank, check_p2d_color, check_point_ssim,
-                          check_point_to_distribution, check_resolution_psnr, transform_options)
+                          check_point_to_distribution, check_reflectance, check_resolution_psnr, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
         options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
                                    point_ssim=point_ssim, ssim_neighbours=ssim_neighbours, hausdorff_rank=hausdorff_rank or None,
                                    point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours,
                                    p2d_color=p2d_color, resolution_psnr=resolution_psnr,
-                                   resolution_neighbours=resolution_neighbours)
+                                   resolution_neighbours=resolution_neighbours, reflectance=reflectance,
+                                   reflectance_peak=reflectance_peak)
         check_carry_normals(carry_normals, ties=ties)
         check_duplicates(duplicates)
     except ValueError as exc:
@@ -135,6 +146,10 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
         pcloud_cloud = read_point_cloud(path)
         check_point_ssim(options, ocloud_cloud, pcloud_cloud, ties=ties)       # (before the GPU context, for every processed cloud)
         check_p2d_color(options, ocloud_cloud, pcloud_cloud)
+        try:
+            check_reflectance(options, ocloud_cloud, pcloud_cloud, ties=ties)
+        except ValueError as exc:
+            raise click.UsageError(str(exc))
         if cloud_pair is None:
             # (clouds read from files are freed while the GPU context works on -- with several decoded clouds, when the next one
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)

@@ -5,12 +5,31 @@ type), optional ``nx ny nz`` and ``red green blue`` (uchar -> [0, 1] like Open3D
 taken as they are); PCL's PCD (ascii, binary, binary_compressed; x y z, normal_*, packed rgb/rgba);
 whitespace-separated ``.xyz`` / ``.xyzn`` / ``.txt`` (x y z [nx ny nz]), ``.xyzrgb`` and ``.pts``.  Coordinates are
 returned as float64 -- Open3D holds ``Vector3d`` -- so a float PLY yields fp32-representable doubles.
+
+Reflectance (one scalar per point, the laser return intensity of LiDAR content; Open3D's reader drops it) is read with the values
+as given: from a PLY vertex property named ``reflectance``, ``refc``, ``intensity``, ``scalar_intensity`` or
+``scalar_Intensity`` (the first of these that is present, any scalar type: ``uchar`` / ``ushort`` stay integers, ``float`` stays
+``float32``, everything else becomes ``float64``), from a PCD field ``intensity`` or ``reflectance``, and from the intensity
+column of a ``.pts`` file (x y z i, or x y z i r g b).  ``write_point_cloud`` writes it as ``property ushort reflectance`` for
+``uint8`` / ``uint16`` arrays and ``property double reflectance`` otherwise, and nothing for a cloud without one.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .point_cloud import PointCloud
+
+_PLY_REFLECTANCE = ("reflectance", "refc", "intensity", "scalar_intensity", "scalar_Intensity")     # first present wins
+_PCD_REFLECTANCE = ("intensity", "reflectance")
+
+
+def _reflectance_column(col, raw_dtype):
+    """A file's reflectance column with the type the file gave it (an ascii table comes as float64)."""
+    raw_dtype = np.dtype(raw_dtype).newbyteorder("=")
+    if raw_dtype in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32)):
+        return np.ascontiguousarray(col, dtype=raw_dtype)
+    return np.ascontiguousarray(col, dtype=np.float64)
+
 
 _PLY_TYPES = {
     "char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
@@ -100,6 +119,10 @@ def _read_ply(path: str) -> PointCloud:
         cloud.colors = colors
         if bytes_:
             cloud.attach_colors_u8(raw)
+    for name in _PLY_REFLECTANCE:
+        if name in cols:
+            cloud.reflectance = _reflectance_column(cols[name], raw_dtypes[name])
+            break
     return cloud
 
 
@@ -142,6 +165,8 @@ def _read_pts(path: str) -> PointCloud:
         cloud.colors = np.ascontiguousarray(table[:, 4:7]) / 255.0
     elif table.shape[1] == 6:
         cloud.colors = np.ascontiguousarray(table[:, 3:6]) / 255.0
+    if table.shape[1] == 4 or table.shape[1] >= 7:          # (six columns: x y z r g b, no intensity)
+        cloud.reflectance = np.ascontiguousarray(table[:, 3])
     return cloud
 
 
@@ -228,6 +253,10 @@ def _read_pcd(path: str) -> PointCloud:
         u8 = np.stack([(bits >> 16) & 255, (bits >> 8) & 255, bits & 255], axis=1).astype(np.uint8)
         cloud.colors = u8.astype(np.float64) / 255.0
         cloud.attach_colors_u8(u8)
+    for name in _PCD_REFLECTANCE:
+        if name in cols:
+            cloud.reflectance = _reflectance_column(cols[name], cols[name].dtype)
+            break
     return cloud
 
 
@@ -258,6 +287,10 @@ def write_point_cloud(path: str, cloud, *, binary: bool = True, coord_dtype: str
         fields += [("nx", t), ("ny", t), ("nz", t)]
     if has_c:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    has_r = getattr(cloud, "has_reflectance", lambda: False)()
+    if has_r:
+        refl = np.asarray(cloud.reflectance)
+        fields += [("reflectance", "u2" if refl.dtype in (np.dtype(np.uint8), np.dtype(np.uint16)) else "f8")]
     data = np.empty(pts.shape[0], dtype=np.dtype([(k, "<" + v) for k, v in fields]))
     for k, col in zip("xyz", pts.T):
         data[k] = col
@@ -268,7 +301,9 @@ def write_point_cloud(path: str, cloud, *, binary: bool = True, coord_dtype: str
         rgb = np.clip(np.rint(np.asarray(cloud.colors, dtype=np.float64) * 255.0), 0, 255)
         for k, col in zip(("red", "green", "blue"), rgb.T):
             data[k] = col
-    ply_name = {"f4": "float", "f8": "double", "u1": "uchar"}
+    if has_r:
+        data["reflectance"] = refl
+    ply_name = {"f4": "float", "f8": "double", "u1": "uchar", "u2": "ushort"}
     header = ["ply", "format " + ("binary_little_endian 1.0" if binary else "ascii 1.0"),
               f"element vertex {pts.shape[0]}"]
     header += [f"property {ply_name[v]} {k}" for k, v in fields] + ["end_header"]

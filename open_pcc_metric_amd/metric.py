@@ -188,6 +188,13 @@ class PointSpacings(PrimaryMetric, DirectionalMetric):           # no counterpar
                            lambda: cloud_pair.get_right_point_spacings(self.k))
 
 
+class ReflectanceErrors(PrimaryMetric, DirectionalMetric):       # no counterpart in the reference (options.py: reflectance)
+    """Per point of the iterating cloud, the squared difference of its reflectance and its matched point's (include/pccm.h,
+    PCCM_METRIC_REFLECTANCE; INTEGRATION.md, "Reflectance"): (a - b)^2 on the values as given."""
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        self.value = _side(self, cloud_pair.get_left_reflectance_errors, cloud_pair.get_right_reflectance_errors)
+
+
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, cloud_pair: CloudPair) -> None:
@@ -534,6 +541,65 @@ class GeoHausdorffResolutionPSNR(_ResolutionPSNR):
 
     def calculate(self, resolution: IntrinsicResolution, hausdorff_distance: GeoHausdorffDistance) -> None:
         self.value = _psnr(resolution.value, hausdorff_distance.value)
+
+
+# --------------------------------------------------------------------------- reflectance secondaries
+class _OverReflectance(SecondaryMetric, DirectionalMetric):
+    _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"reflectance_errors": ReflectanceErrors(is_left=self.is_left)}
+
+
+class ReflectanceMSE(_OverReflectance):                          # no counterpart in the reference (options.py: reflectance)
+    """Reflectance MSE of one direction, as MPEG's pc_error reports beside D1 / D2: the mean of the per-point squared
+    differences (sum / n, NumPy's pairwise sum), in the units of the values as given."""
+    def calculate(self, reflectance_errors: ReflectanceErrors) -> None:
+        column = reflectance_errors.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
+        total = fused()[0] if fused is not None else None
+        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+
+
+class ReflectanceHausdorffDistance(_OverReflectance):
+    """The worst point of one direction (reported with hausdorff): a SQUARED difference, like GeoHausdorffDistance."""
+    def calculate(self, reflectance_errors: ReflectanceErrors) -> None:
+        column = reflectance_errors.value
+        fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
+        self.value = fused()[2] if fused is not None else np.max(column, axis=0)
+
+
+def _reflectance_psnr(peak: float, distortion):
+    """_psnr on float64 operands: identical columns give 0 / inf the way NumPy does, without its divide warning."""
+    with np.errstate(divide="ignore"):
+        return _psnr(np.float64(peak), np.float64(distortion))
+
+
+class _ReflectancePSNR(SecondaryMetric, DirectionalMetric):
+    """A PSNR whose peak is given (options.py: reflectance_peak; 65535.0 is the full 16-bit range pc_error uses)."""
+    _distortion = ReflectanceMSE
+
+    def __init__(self, is_left: bool, peak: float = 65535.0):
+        super().__init__(is_left)
+        self.peak = float(peak)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.peak)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"distortion": self._distortion(is_left=self.is_left)}
+
+    def calculate(self, distortion: AbstractMetric) -> None:
+        self.value = _reflectance_psnr(self.peak, distortion.value)
+
+
+class ReflectancePSNR(_ReflectancePSNR):
+    """GeoPSNR's expression (metric.py:231-247) with the reflectance peak and ReflectanceMSE."""
+
+
+class ReflectanceHausdorffDistancePSNR(_ReflectancePSNR):
+    """GeoHausdorffDistancePSNR's expression (metric.py:369-386) with the reflectance peak and ReflectanceHausdorffDistance."""
+    _distortion = ReflectanceHausdorffDistance
 
 
 # --------------------------------------------------------------------------- colour secondaries

@@ -52,6 +52,12 @@ whose peak is the origin cloud's intrinsic resolution over ``resolution_neighbou
   resolution_psnr & hd         GeoHausdorffResolutionPSNR L/R/sym (D1)
   ... & hd & p2plane           GeoHausdorffResolutionPSNR L/R/sym with point_to_plane=True
 
+and, with ``reflectance`` (no counterpart in the reference: the reflectance rows MPEG's ``pc_error`` reports for LiDAR content,
+on the clouds' per-point scalars as given, PSNR against ``reflectance_peak``), after every row above:
+
+  reflectance                  ReflectanceMSE L/R/sym, ReflectancePSNR L/R/sym
+  reflectance & hd             ReflectanceHausdorffDistance L/R/sym, ReflectanceHausdorffDistancePSNR L/R/sym
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -67,7 +73,7 @@ from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahal
                      GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
                      JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
                      MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
-                     SymmetricMetric)
+                     ReflectanceHausdorffDistance, ReflectanceHausdorffDistancePSNR, ReflectanceMSE, ReflectancePSNR, SymmetricMetric)
 
 SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
@@ -101,7 +107,8 @@ class CalculateOptions:
                  point_to_plane: bool = False, plane_to_plane: bool = False,
                  point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
-                 p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10):
+                 p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10,
+                 reflectance: bool = False, reflectance_peak: float = 65535.0):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -133,6 +140,12 @@ class CalculateOptions:
             raise ValueError(f"resolution_neighbours must be an integer in {RESOLUTION_MIN_K}..{RESOLUTION_MAX_K}, not {k!r}")
         self.resolution_psnr = bool(resolution_psnr)
         self.resolution_neighbours = int(k)
+        peak = reflectance_peak
+        if isinstance(peak, bool) or type(peak).__name__ == "bool_" or not isinstance(peak, numbers.Real) \
+                or not math.isfinite(peak) or not peak > 0:
+            raise ValueError(f"reflectance_peak must be a positive finite number, not {peak!r}")
+        self.reflectance = bool(reflectance)
+        self.reflectance_peak = float(peak)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -216,6 +229,22 @@ def check_resolution_psnr(options: CalculateOptions, *, group=None) -> None:
         raise ValueError("resolution-adaptive PSNR rows are not available for sharded pairs (group=)")
 
 
+def check_reflectance(options: CalculateOptions, origin_cloud, reconst_cloud, *, ties: str = "pick", group=None) -> None:
+    """Raise ``ValueError`` when the reflectance rows ``options`` asks for cannot be computed for this pair -- before any GPU
+    work (the command line calls it for every cloud it processes; CloudPair checks the same before any GPU work of a report).
+    Both clouds need a reflectance; the rows compare a point with its matched point, which ``ties="mean"`` replaces by a virtual
+    neighbour; and the matched rows of a sharded search would have to be gathered: out of scope."""
+    if not getattr(options, "reflectance", False):
+        return
+    if ties != "pick":
+        raise ValueError("reflectance rows are not defined for ties='mean'")
+    if group is not None:
+        raise ValueError("reflectance rows are not available for sharded pairs (group=)")
+    from .cloud_pair import _has_reflectance
+    if not all(_has_reflectance(c) for c in (origin_cloud, reconst_cloud)):
+        raise ValueError("the reflectance rows need the reflectance of both clouds")
+
+
 def _sides(cls, **kw):
     return [cls(is_left=True, **kw), cls(is_left=False, **kw)]
 
@@ -276,4 +305,11 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
             for point_to_plane in (False, True) if options.point_to_plane else (False,):
                 kw = dict(point_to_plane=point_to_plane, k=k)
                 metrics += _sides(cls, **kw) + [_sym(cls, True, **kw)]
+    if getattr(options, "reflectance", False):
+        kw = dict(peak=getattr(options, "reflectance_peak", 65535.0))
+        metrics += (_sides(ReflectanceMSE) + [_sym(ReflectanceMSE, False)]
+                    + _sides(ReflectancePSNR, **kw) + [_sym(ReflectancePSNR, True, **kw)])
+        if options.hausdorff:
+            metrics += (_sides(ReflectanceHausdorffDistance) + [_sym(ReflectanceHausdorffDistance, False)]
+                        + _sides(ReflectanceHausdorffDistancePSNR, **kw) + [_sym(ReflectanceHausdorffDistancePSNR, True, **kw)])
     return metrics
