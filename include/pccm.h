@@ -435,6 +435,23 @@ int pccm_select_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *
 int pccm_select_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks,
                      double *out /*[n]*/);
 
+/* The inverse query: out[i] is the number of rows of the column whose value is <= xs[i] -- np.count_nonzero(column <= xs[i]) --
+ * for PCCM_METRIC_D1 or PCCM_METRIC_D2 of direction 0 or 1, under the context's tie policy.  With xs[i] = tau * tau on a D1
+ * column this is the number of points within tau of the other cloud: the numerator of the precision / recall behind an
+ * F-score, and at tau = 0 the number of points reproduced exactly.  The comparison is the IEEE one on the values the column's
+ * reduction sums and pccm_select_many ranks (0.0 <= -0.0 holds; +inf counts every row, -inf none); the column is read once, in
+ * HBM, in whatever form the search left it, by a further mode of the kernel that reduces it: no column is allocated or copied.
+ * n <= 8 counts per call; more than four thresholds on one column take two passes over it.
+ *   pccm_count_prefetch_many  enqueues the launches (and the columns' reductions where nobody has); capturable into a
+ *                             hipGraph between pccm_graph_begin / pccm_graph_end like pccm_select_prefetch_many.
+ *   pccm_count_many           consumes them (enqueuing first what nobody prefetched) and waits once.
+ * PCCM_E_ARG: PCCM_DIR_SELF, any other metric, a NaN threshold, a cloud of 2^32 rows or more (counts are 32 bits wide on the
+ * device); PCCM_E_STATE: no search result yet, a sharded context; PCCM_METRIC_D2 without the normals it needs: PCCM_E_STATE /
+ * PCCM_E_RANGE exactly where pccm_reduce_total gives them. */
+int pccm_count_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const double *xs);
+int pccm_count_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const double *xs,
+                    int64_t *out /*[n]*/);
+
 /* Sharded contexts whose rows start and end on whole 8192-row chunks (pccm_set_shard / pccm_set_shard_dir do that
  * whenever every rank can have a chunk): the exchange vector shrinks to ONE number per chunk -- NumPy adds the
  * chunks of a column one after the other, and the GPU has finished each chunk's pairwise tree -- plus the raw values
@@ -538,11 +555,11 @@ int pccm_color_transform(const double *rgb, int64_t n, int scheme, double *out);
 int pccm_drop_caches(pccm_ctx *ctx);
 
 /* hipGraph capture.  Between pccm_graph_begin() and pccm_graph_end() only pccm_drop_caches(),
- * pccm_nn(), pccm_reduce_prefetch[_many]() and pccm_select_prefetch_many() may be called; they are recorded on the
+ * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many() and pccm_count_prefetch_many() may be called; they are recorded on the
  * context's stream instead of executed.  The same sequence must have run once before (capture cannot allocate).
  * pccm_graph_end() instantiates the graph, runs it once and returns its id; pccm_graph_launch()
  * replays the whole sequence -- kernels and host-side bookkeeping -- with a single launch, after which
- * pccm_reduce()/pccm_select_many()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
+ * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
  * clouds, normals, shard or any buffer it references change.  One report over resident clouds is
  * ~45 small launches, which an eager host cannot issue as fast as the GPU retires them. */
 int pccm_graph_begin(pccm_ctx *ctx);

@@ -48,7 +48,7 @@ SYMBOLS = (
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours",
     "pccm_resolution_build", "pccm_get_resolution", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
-    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
+    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_reflectance", "pccm_set_reflectance_u16", "pccm_get_reflectance",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
@@ -149,6 +149,8 @@ def load() -> ctypes.CDLL:
     lp = ctypes.POINTER(i64)
     lib.pccm_select_prefetch_many.argtypes = [vp, i32, ip, ip, ip, lp]
     lib.pccm_select_many.argtypes = [vp, i32, ip, ip, ip, lp, dp]
+    lib.pccm_count_prefetch_many.argtypes = [vp, i32, ip, ip, ip, dp]
+    lib.pccm_count_many.argtypes = [vp, i32, ip, ip, ip, dp, lp]
     lib.pccm_cvec_len.argtypes = [i64]
     lib.pccm_cvec_len.restype = i64
     lib.pccm_reduce_chunks_many.argtypes = [vp, i32, ip, ip, ip, dp, dp]
@@ -747,6 +749,28 @@ class Engine:
         out = (ctypes.c_double * args[0])()
         _check(self._lib.pccm_select_many(self._ctx, *args, out))
         return [np.float64(v) for v in out]
+
+    def _count_args(self, requests, normal_mode):
+        k = len(requests)
+        arr = ctypes.c_int * k
+        return (k, arr(*[int(r[0]) for r in requests]), arr(*[int(r[1]) for r in requests]), arr(*_modes(normal_mode, k)),
+                (ctypes.c_double * k)(*[float(r[2]) for r in requests]))
+
+    def count_prefetch_many(self, requests, normal_mode: str = "row") -> None:
+        """``requests``: up to 8 ``(direction, metric, x)``: enqueue the count of the rows ``<= x`` of each D1 / D2 column without
+        waiting (pccm_count_prefetch_many); a later count_many() consumes them."""
+        if requests:
+            _check(self._lib.pccm_count_prefetch_many(self._ctx, *self._count_args(requests, normal_mode)))
+
+    def count_many(self, requests, normal_mode: str = "row"):
+        """-> the number of rows ``<= x`` of each of up to 8 columns ``(direction, metric, x)``, counted in HBM (pccm_count_many):
+        ``np.count_nonzero(column <= x)``."""
+        if not requests:
+            return []
+        args = self._count_args(requests, normal_mode)
+        out = (ctypes.c_int64 * args[0])()
+        _check(self._lib.pccm_count_many(self._ctx, *args, out))
+        return [int(v) for v in out]
 
     def reduce_chunks_many(self, requests, normal_mode: str = "row"):
         """-> (one float64 array holding the chunk vectors of up to 8 columns ``(direction, metric)`` one after the other,

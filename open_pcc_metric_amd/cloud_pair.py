@@ -190,6 +190,18 @@ class DeviceColumn(_DeviceArray):
                 return value
         return np.partition(np.asarray(self), k - 1)[k - 1]
 
+    def count_le(self, x) -> int:
+        """The number of elements ``<= x``: ``np.count_nonzero(column <= x)``, counted in HBM when the engine can
+        (pccm_count_many: D1 and D2 columns) -- no column leaves the GPU then."""
+        x = float(x)
+        if x != x:
+            raise ValueError("count_le: the threshold is NaN")
+        if self._kind in ("d1", "d2"):
+            value = self._pair._counted(self._dir, self._METRIC[self._kind], x)
+            if value is not None:
+                return value
+        return int(np.count_nonzero(np.asarray(self) <= x))
+
     def _fused_function(self, func, args, kwargs):
         which = _REDUCERS.get(func)
         if which is None or len(args) != 1 or args[0] is not self:
@@ -327,6 +339,7 @@ class CloudPair:
         self.duplicates_removed = (0, 0)
         self._xchg, self._xchg_wanted = {}, []
         self._selections, self._sel_wanted = {}, []
+        self._counts, self._cnt_wanted = {}, []
         self._colours_on_device = [False, False]
         self._reflectance_on_device = [False, False]
         self._reflectance = False           # a report asked for the reflectance columns: the searches keep the matched rows
@@ -425,6 +438,7 @@ class CloudPair:
         new.duplicates_removed = (self.duplicates_removed[0], 0)
         new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
         new._selections, new._sel_wanted = {}, []
+        new._counts, new._cnt_wanted = {}, []
         new._graph_id, new._last_wanted = None, None
         keep_self = bool(self.__dict__.get("_self_done")) and bool(getattr(eng, "keeps_self_search", False))
         self_total = self.__dict__.get("_totals", {}).get((nat.DIR_SELF, nat.METRIC_D1)) if keep_self else None
@@ -523,6 +537,7 @@ class CloudPair:
         self._xchg = {}
         self._totals = {}
         self._selections = {}
+        self._counts = {}
         self._colour_red = {}
         if self._use_graph and self._last_wanted is not None and hasattr(eng, "graph_begin"):
             wants_self = "boundary" in self._last_wanted
@@ -661,6 +676,26 @@ class CloudPair:
             for q, v in zip(batch, eng.select_many(batch, self.normal_index)):
                 self._selections[q] = v
         return self._selections[key]
+
+    def _check_fscore(self) -> None:
+        """options.check_fscore for this pair: ValueError before any GPU work of a report."""
+        if self._coll.sharded:
+            raise ValueError("F-score rows are not available for sharded pairs (group=)")
+
+    def _counted(self, direction: int, metric: int, x: float):
+        """The number of rows ``<= x`` of a whole D1 / D2 column, counted on the GPU.  The first count a report asks for brings
+        every count the report enqueued (prefetch_reductions) back in one call per eight.  None: this engine has no count (a
+        test double): the caller counts the materialised column."""
+        self._check_fscore()
+        eng = self._engine
+        if not hasattr(eng, "count_many"):
+            return None
+        key = (direction, metric, x)
+        if key not in self._counts:
+            batch = next((b for b in _selection_batches(self._cnt_wanted) if key in b), [key])
+            for q, v in zip(batch, eng.count_many(batch, self.normal_index)):
+                self._counts[q] = v
+        return self._counts[key]
 
     def tie_exposure(self, is_left: bool = True, point_to_plane: bool = True) -> dict:
         """Opt-in diagnostic (not part of any report): how far the order of EXACT ties can move the point-to-plane MSE.
@@ -1053,7 +1088,8 @@ class CloudPair:
 
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
         ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
-        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)`` and/or the string ``"boundary"``.
+        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)``, ``("within", is_left, tau)`` and/or
+        the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -1078,6 +1114,10 @@ class CloudPair:
         ranked_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "ranked"]
         if ranked_items:
             self._check_ranked()
+        within_items = [item for item in wanted if item[0] == "within"]
+        if within_items:
+            self._check_fscore()
+            wanted = [item for item in wanted if item not in within_items]     # (their columns are requests of their own, EuclideanDistance's)
         # point-to-distribution: the check, then the columns -- built here like the features, eagerly and outside any capture
         # (one build per neighbourhood size, with the union of what the report needs at that size)
         p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] in ("p2d", "p2d_color", "p2d_joint")]
@@ -1097,7 +1137,7 @@ class CloudPair:
         if reflectance_items:
             self._ensure_reflectance()
         reflectance_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_REFLECTANCE) for item in reflectance_items]
-        requests, ssim_requests, selections = [], [], []
+        requests, ssim_requests, selections, counts = [], [], [], []
         stored_items = p2d_items + spacing_items
         p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, DeviceColumn._METRIC[item[0]]) for item in stored_items]
         for item in wanted:
@@ -1149,6 +1189,12 @@ class CloudPair:
             column = (direction, nat.METRIC_D2 if p2p else nat.METRIC_D1)
             if column in requests:
                 selections.append(column + (rank_index(rank, eng.n_iter(direction)),))
+        # F-score rows: the points within tau of the other cloud, counted on the D1 column of each direction at tau * tau (the
+        # product GeoInlierRatio forms) -- both directions and every threshold, eight counts at the most, in one batch
+        for _, is_left, tau in within_items:
+            column = (nat.DIR_LEFT if is_left else nat.DIR_RIGHT, nat.METRIC_D1)
+            if column in requests:
+                counts.append(column + (float(np.float64(tau) * np.float64(tau)),))
         # the reflectance columns join the first batch -- its k_point_jobs launch and its reduction launch -- when it has room
         # for them: eight columns, of which at most four are formed by point jobs (unfused D2, angular, reflectance)
         if reflectance_requests:
@@ -1157,6 +1203,7 @@ class CloudPair:
                 requests, reflectance_requests = requests + reflectance_requests, []
         self._xchg_wanted = list(requests) + reflectance_requests + ssim_requests + p2d_requests
         self._sel_wanted = sorted(set(selections))
+        self._cnt_wanted = sorted(set(counts)) if counts else []
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
@@ -1171,6 +1218,9 @@ class CloudPair:
             if hasattr(eng, "select_prefetch_many"):
                 for batch in _selection_batches(self._sel_wanted):
                     eng.select_prefetch_many(batch, self.normal_index)
+            if self._cnt_wanted and hasattr(eng, "count_prefetch_many"):
+                for batch in _selection_batches(self._cnt_wanted):
+                    eng.count_prefetch_many(batch, self.normal_index)
         else:
             requests = requests + reflectance_requests + ssim_requests + p2d_requests
             for direction, metric in requests:
@@ -1184,7 +1234,8 @@ class CloudPair:
 
 def _selection_batches(selections, cap: int = 8):
     """Sorted ``(direction, metric, k)`` selections in batches of at most ``cap`` (pccm_select_many's limit) that keep the ranks
-    of a column together: every pass of a batch streams each of its columns once, whatever the number of ranks."""
+    of a column together: every pass of a batch streams each of its columns once, whatever the number of ranks.  Counts
+    ``(direction, metric, x)`` are batched the same way (pccm_count_many)."""
     batches, current = [], []
     for column in sorted({q[:2] for q in selections}):
         ranks = [q for q in selections if q[:2] == column]

@@ -1393,6 +1393,7 @@ static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx)
         PathScope path(ctx, 1u << dir);
         int rc = nn_grid(ctx, 1, &dir, /*force_idx=*/1);
         if (rc) return rc;
+        records_rewritten(ctx, dir);           // (jobs bound to the old records must not be read again: pccm_stale.h)
     }
     const bool rows = res.form.has_rows();
     const Cloud &uit = ctx->cloud[dir == PCCM_DIR_RIGHT ? 1 : 0];
@@ -2148,39 +2149,49 @@ int pccm_reduce_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *met
     return PCCM_OK;
 }
 
-// ---- selections: the k-th smallest element of a column (include/pccm.h) ------------------------------------------------------
-static SelectSlot *sel_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, int64_t k)
+// ---- selections and counts: the k-th smallest element of a column, the rows of a column <= x (include/pccm.h) ---------------
+// One slot table, one enqueue path: a request is (kind, column, key) -- the key a selection's rank or the bit pattern of a count's
+// threshold -- and the two differ in the check of the key, the launches and the type of the host word.
+static SelectSlot *sel_find(pccm_ctx *ctx, int kind, int dir, int metric, int normal_mode, int64_t k)
 {
     for (auto &q : ctx->sel_slots)
-        if (q.matches(dir, metric, normal_mode, ctx->nn_gen[dir], k)) return &q;
+        if (q.matches(dir, metric, normal_mode, ctx->nn_gen[dir], k, kind)) return &q;
     return nullptr;
 }
 
-static int select_check(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
+static int select_check(pccm_ctx *ctx, int kind, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes,
+                        const int64_t *ks)
 {
+    const char *what = kind == kSlotCount ? "counts" : "selections";
     if (n < 0 || n > kSelMax || (n > 0 && (!dirs || !metrics || !normal_modes || !ks))) return fail(PCCM_E_ARG, "1..8 requests expected");
     if (ctx->sharded()) return fail(PCCM_E_STATE, "%s needs the whole columns on this GPU (world = 1)", who);
     for (int i = 0; i < n; ++i) {
-        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "selections rank directions 0 and 1, not %d", dirs[i]);
+        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "%s read directions 0 and 1, not %d", what, dirs[i]);
         if (metrics[i] != PCCM_METRIC_D1 && metrics[i] != PCCM_METRIC_D2)
-            return fail(PCCM_E_ARG, "selections rank PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", metrics[i]);
+            return fail(PCCM_E_ARG, "%s read PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", what, metrics[i]);
         const Cloud *it, *se;
         NNResult *res;
         int rc = need_nn(ctx, dirs[i], &it, &se, &res);
         if (rc) return rc;
-        if (it->n >= ((int64_t)1 << 32)) return fail(PCCM_E_ARG, "selections count rows in 32 bits: columns of 2^32 rows or more are not supported");
-        if (ks[i] < 1 || ks[i] > it->n) return fail(PCCM_E_ARG, "rank %lld outside 1..%lld", (long long)ks[i], (long long)it->n);
+        if (it->n >= ((int64_t)1 << 32)) return fail(PCCM_E_ARG, "%s count rows in 32 bits: columns of 2^32 rows or more are not supported", what);
+        if (kind == kSlotCount) {
+            double x;
+            memcpy(&x, &ks[i], sizeof x);
+            if (x != x) return fail(PCCM_E_ARG, "a count's threshold is a number or an infinity, not NaN");
+        } else if (ks[i] < 1 || ks[i] > it->n) {
+            return fail(PCCM_E_ARG, "rank %lld outside 1..%lld", (long long)ks[i], (long long)it->n);
+        }
     }
     return PCCM_OK;
 }
 
-static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
+static int select_prefetch(pccm_ctx *ctx, int kind, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
 {
-    // what is not enqueued yet, by column; a column's reduction is enqueued first when nobody has: the selection ranks the
-    // column as that reduction's job describes it
+    // what is not enqueued yet, by column; a column's reduction is enqueued first when nobody has: the selection ranks (the
+    // count reads) the column as that reduction's job describes it
     int todo[kSelMax], ntodo = 0, cd[kSelMax], cm[kSelMax], cmode[kSelMax], col_of[kSelMax], ncols = 0;
     for (int i = 0; i < n; ++i) {
-        if (sel_find(ctx, dirs[i], metrics[i], normal_modes[i], ks[i])) continue;
+        if (sel_find(ctx, kind, dirs[i], metrics[i], normal_modes[i], ks[i])) continue;
         bool dup = false;
         for (int j = 0; j < ntodo; ++j)
             dup = dup || (dirs[todo[j]] == dirs[i] && metrics[todo[j]] == metrics[i] && ks[todo[j]] == ks[i] &&
@@ -2206,7 +2217,7 @@ static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *met
     int nfresh = 0;
     bool placed[kSelMax] = {};
     PathScope path(ctx, 1u << 3, true);            // the selection's launches join the log of the column's reduction batch
-    for (int left = ntodo; left > 0;) {            // rounds of at most kSelPerCol selections per column (two at the most)
+    for (int left = ntodo; left > 0;) {            // rounds of at most kSelPerCol requests per column (two at the most)
         UnitJobs uj;
         uj.njobs = 0;
         for (int k = 0; k < 9; ++k) uj.uoff[k] = uj.toff[k] = 0;
@@ -2221,6 +2232,7 @@ static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *met
                 if (!q) return fail(PCCM_E_STATE, "no free selection slot");
                 if (q->pending && !ctx->capturing && q->wait_ev && (rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
                 const int i = todo[j];
+                q->kind = kind;
                 q->dir = dirs[i]; q->metric = metrics[i]; q->mode = normal_modes[i]; q->k = ks[i];
                 q->gen = ctx->nn_gen[dirs[i]];
                 q->pending = true;
@@ -2240,7 +2252,7 @@ static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *met
         }
         for (int k = uj.njobs; k < 9; ++k) S.sfirst[k] = S.nsel;
         for (int k = uj.njobs; k < 8; ++k) uj.j[k] = uj.j[0];
-        if ((rc = launch_unit_select(ctx, uj))) return rc;
+        if ((rc = kind == kSlotCount ? launch_unit_count(ctx, uj) : launch_unit_select(ctx, uj))) return rc;
     }
     uint64_t seq = 0;
     if ((rc = launch_publish(ctx, &seq))) return rc;
@@ -2261,12 +2273,32 @@ static int select_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *met
     return PCCM_OK;
 }
 
+// consume: enqueue first what nobody prefetched, in one batch; wait once; word[i]: the host word of request i
+static int select_consume(pccm_ctx *ctx, int kind, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes,
+                          const int64_t *ks, double *word)
+{
+    int rc = select_check(ctx, kind, who, n, dirs, metrics, normal_modes, ks);
+    if (!rc) rc = select_prefetch(ctx, kind, n, dirs, metrics, normal_modes, ks);
+    if (rc) return rc;
+    SelectSlot *got[kSelMax];
+    for (int i = 0; i < n; ++i) {
+        SelectSlot *q = sel_find(ctx, kind, dirs[i], metrics[i], normal_modes[i], ks[i]);
+        if (!q) return fail(PCCM_E_STATE, "selection slot lost");
+        if ((rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
+        if ((rc = check_device_errors(ctx))) return rc;
+        word[i] = ctx->sel_host[q - ctx->sel_slots];
+        got[i] = q;
+    }
+    for (int i = 0; i < n; ++i) got[i]->pending = false;
+    return PCCM_OK;
+}
+
 int pccm_select_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
 {
     CHECK_CTX(ctx);
-    int rc = select_check(ctx, "pccm_select_prefetch_many", n, dirs, metrics, normal_modes, ks);
+    int rc = select_check(ctx, kSlotSelect, "pccm_select_prefetch_many", n, dirs, metrics, normal_modes, ks);
     if (rc) return rc;
-    return select_prefetch(ctx, n, dirs, metrics, normal_modes, ks);
+    return select_prefetch(ctx, kSlotSelect, n, dirs, metrics, normal_modes, ks);
 }
 
 int pccm_select_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks, double *out)
@@ -2274,19 +2306,38 @@ int pccm_select_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, 
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
     if (n > 0 && !out) return fail(PCCM_E_ARG, "null pointer");
-    int rc = select_check(ctx, "pccm_select_many", n, dirs, metrics, normal_modes, ks);
-    if (!rc) rc = select_prefetch(ctx, n, dirs, metrics, normal_modes, ks);      // whatever is not enqueued yet, in one batch
+    return select_consume(ctx, kSlotSelect, "pccm_select_many", n, dirs, metrics, normal_modes, ks, out);
+}
+
+// the thresholds as slot keys: their bit patterns (0.0 and -0.0 are two keys with one answer)
+static int count_keys(int n, const double *xs, int64_t *keys)
+{
+    if (n < 0 || n > kSelMax || (n > 0 && !xs)) return fail(PCCM_E_ARG, "1..8 requests expected");
+    memcpy(keys, xs, (size_t)n * sizeof(double));
+    return PCCM_OK;
+}
+
+int pccm_count_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const double *xs)
+{
+    CHECK_CTX(ctx);
+    int64_t keys[kSelMax];
+    int rc = count_keys(n, xs, keys);
+    if (!rc) rc = select_check(ctx, kSlotCount, "pccm_count_prefetch_many", n, dirs, metrics, normal_modes, keys);
     if (rc) return rc;
-    SelectSlot *got[kSelMax];
-    for (int i = 0; i < n; ++i) {
-        SelectSlot *q = sel_find(ctx, dirs[i], metrics[i], normal_modes[i], ks[i]);
-        if (!q) return fail(PCCM_E_STATE, "selection slot lost");
-        if ((rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
-        if ((rc = check_device_errors(ctx))) return rc;
-        out[i] = ctx->sel_host[q - ctx->sel_slots];
-        got[i] = q;
-    }
-    for (int i = 0; i < n; ++i) got[i]->pending = false;
+    return select_prefetch(ctx, kSlotCount, n, dirs, metrics, normal_modes, keys);
+}
+
+int pccm_count_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const double *xs, int64_t *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (n > 0 && !out) return fail(PCCM_E_ARG, "null pointer");
+    int64_t keys[kSelMax];
+    double words[kSelMax];
+    int rc = count_keys(n, xs, keys);
+    if (!rc) rc = select_consume(ctx, kSlotCount, "pccm_count_many", n, dirs, metrics, normal_modes, keys, words);
+    if (rc) return rc;
+    memcpy(out, words, (size_t)n * sizeof(double));       // (the store launch wrote 64-bit counts into the slots' words)
     return PCCM_OK;
 }
 

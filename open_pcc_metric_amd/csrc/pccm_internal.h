@@ -259,12 +259,14 @@ struct ReduceSlot : SlotKey, ReduceWhat {   // one enqueued reduction (pccm_redu
     }
 };
 
-struct SelectSlot : SlotKey {  // one enqueued selection (pccm_select_prefetch_many / pccm_select_many)
-    int64_t k = 0;
+constexpr int kSlotSelect = 0, kSlotCount = 1;     // SelectSlot::kind
+struct SelectSlot : SlotKey {  // one enqueued selection (pccm_select_prefetch_many / pccm_select_many) or count (pccm_count_*)
+    int kind = kSlotSelect;
+    int64_t k = 0;             // the rank; of a count: the bit pattern of its threshold
 
-    bool matches(int d, int m, int normal_mode, uint64_t gen_now, int64_t rank) const
+    bool matches(int d, int m, int normal_mode, uint64_t gen_now, int64_t rank, int what = kSlotSelect) const
     {
-        return SlotKey::matches(d, m, normal_mode, gen_now) && k == rank;
+        return SlotKey::matches(d, m, normal_mode, gen_now) && kind == what && k == rank;
     }
 };
 
@@ -285,11 +287,11 @@ struct ProfSpan {
 };
 
 struct GraphOp {               // host-side effect of one captured call, replayed by pccm_graph_launch
-    int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch(slot)
+    int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch / count_prefetch(slot)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
     ReduceSnap snap;           // kind 2: the slot's bookkeeping at capture time
-    SelectSlot ssnap;          // kind 3: likewise for a selection slot
+    SelectSlot ssnap;          // kind 3: likewise for a selection or count slot
 };
 
 struct GraphRec {
@@ -678,18 +680,23 @@ constexpr int kSelPasses = 6;       // 6 x 11 >= 64 (the last pass holds the 9 l
 constexpr int kSelMax = 8;          // selections per launch sequence ...
 constexpr int kSelPerCol = 4;       // ... of which at most this many rank one column (one 8 KB LDS histogram each)
 constexpr size_t kSelLds = (size_t)kSelPerCol * kSelBins * sizeof(uint32_t) + 256;   // LDS of the selection mode
+// Count mode of k_unit_jobs (pccm_count_*), the inverse query: how many rows of a job's column 0 are <= x, for up to kSelMax
+// thresholds per launch sequence, kSelPerCol per column -- one streaming pass over the same values and one workgroup that stores.
+constexpr int kSelCountPass = kSelPasses + 2, kSelStorePass = kSelPasses + 3;       // UnitSelect::pass of its two launches
 struct SelState {
     unsigned long long prefix;  // the settled high bits of the key (zero below them)
     unsigned long long k;       // rank among the rows that share them (1-based)
 };
 struct UnitSelect {
-    int pass = 0;               // 0: a reduction launch.  1..kSelPasses: histogram pass `pass - 1`; kSelPasses + 1: resolve and store
+    int pass = 0;               // 0: a reduction launch.  1..kSelPasses: histogram pass `pass - 1`; kSelPasses + 1: resolve and store;
+                                // kSelCountPass: count rows <= x; kSelStorePass: store the counts
     int nsel = 0;
     int sfirst[9] = {};         // selections sfirst[j] .. sfirst[j + 1] - 1 rank column 0 of job j
     int boff[9] = {};           // prefix sums of the jobs' workgroups in a histogram pass
-    unsigned long long k[kSelMax] = {};   // 1-based ranks
-    double *out[kSelMax] = {};  // pinned host memory: one double per selection
-    uint32_t *hist = nullptr;   // [kSelPasses][kSelMax][kSelBins], zeroed on the stream before pass 0
+    unsigned long long k[kSelMax] = {};   // 1-based ranks (count mode: the bit patterns of the thresholds)
+    double *out[kSelMax] = {};  // pinned host memory: one double per selection (count mode: one 64-bit count in its place)
+    uint32_t *hist = nullptr;   // [kSelPasses][kSelMax][kSelBins], zeroed on the stream before pass 0 (count mode: the first
+                                // kSelMax words are the counters, zeroed before the count launch)
     SelState *state = nullptr;  // [kSelPasses][kSelMax]: what pass p matched and ranked by (written by pass p, read by pass p + 1)
 };
 struct UnitJobs {
@@ -729,6 +736,8 @@ int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, cons
 int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 // the selection launches of jobs.sel (memset of the histograms, kSelPasses histogram passes, resolve); nothing is published
 int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs);
+// the count launches of jobs.sel (memset of the counters, the count pass, the store); nothing is published
+int launch_unit_count(pccm_ctx *ctx, UnitJobs &jobs);
 int launch_publish(pccm_ctx *ctx, uint64_t *seq);     // k_publish behind whatever the stream holds; *seq as for launch_unit_jobs
 
 // minimal-OBB frame search (pccm_obb.hip)

@@ -473,6 +473,70 @@ __device__ __forceinline__ void unit_select(const UnitJobs &jobs, unsigned char 
     }
 }
 
+// ---- count mode (UnitSelect::pass kSelCountPass / kSelStorePass, pccm_internal.h) -------------------------------------------
+// The inverse query of the selection: how many rows of a job's column 0 are <= x, for the m <= kSelPerCol thresholds s0.. of the
+// job (UnitSelect::k holds their bit patterns).  The comparison is the IEEE one on the values unit_load / unit_pick form, not one
+// of order keys: 0.0 <= -0.0 holds, a NaN row is counted by no threshold.  One streaming pass laid out as a histogram pass is
+// (UnitSelect::boff); a counter per threshold in registers, combined across the wave by shuffles, across the workgroup through
+// 64 bytes of the selection's LDS, and added to the zeroed device counters (the first kSelMax words of UnitSelect::hist) with one
+// atomic per threshold and workgroup.  The store launch, one workgroup behind it, widens the counters into the slots' host words.
+__device__ __forceinline__ void unit_count(const UnitJobs &jobs, unsigned char *smem)
+{
+    const UnitSelect &S = jobs.sel;
+    const int t = threadIdx.x;
+    if (S.pass == kSelStorePass) {
+        for (int s = 0; s < S.nsel; ++s)
+            if (t == s) *reinterpret_cast<unsigned long long *>(S.out[s]) = (unsigned long long)S.hist[s];
+        return;
+    }
+    uint32_t *wc = reinterpret_cast<uint32_t *>(smem);         // [4 waves][kSelPerCol]
+    int jb = 0;
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        if (k < jobs.njobs && (int)blockIdx.x >= S.boff[k]) jb = k;
+    jb = __builtin_amdgcn_readfirstlane(jb);
+    const int s0 = S.sfirst[jb], m = S.sfirst[jb + 1] - s0;
+    const int blk = (int)blockIdx.x - S.boff[jb], nblk = S.boff[jb + 1] - S.boff[jb];
+    double x[kSelPerCol];
+    uint32_t c[kSelPerCol];
+#pragma unroll
+    for (int r = 0; r < kSelPerCol; ++r) {
+        x[r] = __longlong_as_double((long long)S.k[s0 + (r < m ? r : 0)]);
+        c[r] = 0u;
+    }
+    const UnitView V = unit_view(jobs.j[jb]);
+    const int64_t ns = jobs.j[jb].ns;
+    const int64_t step = (int64_t)nblk * 256;
+    int64_t i = (int64_t)blk * 256 + t;
+    for (; i + 3 * step < ns; i += 4 * step) {                  // four independent loads in flight
+        double v[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) unit_load(V, i + j * step, v[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unit_pick(V, v[j]);
+#pragma unroll
+            for (int r = 0; r < kSelPerCol; ++r) c[r] += v[j][0] <= x[r] ? 1u : 0u;
+        }
+    }
+    for (; i < ns; i += step) {
+        double v[2];
+        unit_load(V, i, v);
+        unit_pick(V, v);
+#pragma unroll
+        for (int r = 0; r < kSelPerCol; ++r) c[r] += v[0] <= x[r] ? 1u : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < kSelPerCol; ++r) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c[r] += __shfl_xor(c[r], off);
+        if ((t & 63) == 0) wc[(t >> 6) * kSelPerCol + r] = c[r];
+    }
+    __syncthreads();
+    // integer adds commute: the global counts do not depend on the order the workgroups arrive in
+    if (t < m) atomicAdd(&S.hist[s0 + t], wc[t] + wc[kSelPerCol + t] + wc[2 * kSelPerCol + t] + wc[3 * kSelPerCol + t]);
+}
+
 // ---- the leaf reduction, written once (UnitCols / LeanCols: what a record is; k_unit_jobs / k_unit_lean: who runs it) ----------
 // A policy type says how a job's records become column values and nothing else: NC, the columns the kernel carries (compile
 // time: loops over columns with constant bounds keep r / mn / mx in registers -- DESIGN.md, "k_unit_jobs compiled for gfx950");
@@ -689,9 +753,10 @@ __device__ __forceinline__ void unit_tail(const UnitJobs &jobs, int64_t c0)
 
 __global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char sel_smem[kSelLds];      // selection launches only
+    __shared__ __attribute__((aligned(16))) unsigned char sel_smem[kSelLds];      // selection and count launches only
     if (jobs.sel.pass) {                                   // block-uniform (a kernel argument)
-        unit_select(jobs, sel_smem);
+        if (jobs.sel.pass >= kSelCountPass) unit_count(jobs, sel_smem);
+        else unit_select(jobs, sel_smem);
         return;
     }
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -831,6 +896,21 @@ int launch_publish(pccm_ctx *ctx, uint64_t *seq)
     return PCCM_OK;
 }
 
+// the workgroups of a histogram or count pass, job after job (UnitSelect::boff); -> their number
+static int select_grid(UnitJobs &jobs)
+{
+    int nb = 0;
+    for (int k = 0; k < 8; ++k) {
+        jobs.sel.boff[k] = nb;
+        if (k < jobs.njobs) {                 // 4096 rows per workgroup, at most one workgroup per CU and job
+            const int64_t want = (jobs.j[k].ns + 4095) / 4096;
+            nb += (int)(want < 1 ? 1 : want > 256 ? 256 : want);
+        }
+    }
+    jobs.sel.boff[8] = nb;
+    return nb;
+}
+
 // The selections of jobs.sel: the histograms zeroed on the stream, one launch per radix pass (each reads the counts of the one
 // before: the launch boundary is the only synchronisation), one workgroup that resolves the values into pinned host memory.
 int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs)
@@ -838,20 +918,30 @@ int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs)
     UnitSelect &S = jobs.sel;
     if (S.nsel <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_REDUCE);
-    int nb = 0;
-    for (int k = 0; k < 8; ++k) {
-        S.boff[k] = nb;
-        if (k < jobs.njobs) {                 // 4096 rows per workgroup, at most one workgroup per CU and job
-            const int64_t want = (jobs.j[k].ns + 4095) / 4096;
-            nb += (int)(want < 1 ? 1 : want > 256 ? 256 : want);
-        }
-    }
-    S.boff[8] = nb;
+    const int nb = select_grid(jobs);
     PCCM_HIP(hipMemsetAsync(S.hist, 0, (size_t)kSelPasses * kSelMax * kSelBins * sizeof(uint32_t), ctx->stream));
     for (int p = 0; p <= kSelPasses; ++p) {
         S.pass = p + 1;
         PCCM_LAUNCH(ctx, k_unit_jobs, dim3(p < kSelPasses ? (unsigned)nb : 1u), dim3(256), 0, ctx->stream, jobs);
     }
+    S.pass = 0;
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+// The counts of jobs.sel: the counters (the first kSelMax words of the histograms) zeroed on the stream, one count launch, one
+// workgroup that stores the counts into pinned host memory -- the launch boundary is the only synchronisation.
+int launch_unit_count(pccm_ctx *ctx, UnitJobs &jobs)
+{
+    UnitSelect &S = jobs.sel;
+    if (S.nsel <= 0) return PCCM_OK;
+    ProfScope ps(ctx, PCCM_K_REDUCE);
+    const int nb = select_grid(jobs);
+    PCCM_HIP(hipMemsetAsync(S.hist, 0, (size_t)kSelMax * sizeof(uint32_t), ctx->stream));
+    S.pass = kSelCountPass;
+    PCCM_LAUNCH(ctx, k_unit_jobs, dim3((unsigned)nb), dim3(256), 0, ctx->stream, jobs);
+    S.pass = kSelStorePass;
+    PCCM_LAUNCH(ctx, k_unit_jobs, dim3(1), dim3(256), 0, ctx->stream, jobs);
     S.pass = 0;
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;

@@ -3,13 +3,13 @@
 //
 // The products: the searches' results (NNResult::valid, NNForm::fused), normals carried to a cloud (pccm_ctx::carry), the
 // merge maps (merge_n), PointSSIM features (Cloud::ssim_attrs / ssim_k), point spacings (Cloud::res_k), the point-to-distribution
-// columns (p2d_k, p2d_color), a cloud's reflectance (Cloud::n_refl), and everything keyed on a counter: pending reductions and selections, tie columns, the colour memo,
+// columns (p2d_k, p2d_color), a cloud's reflectance (Cloud::n_refl), and everything keyed on a counter: pending reductions, selections and counts, tie columns, the colour memo,
 // captured graphs, grid caches.  What ESTABLISHES a product stays with its builder (ssim_attrs = attrs, res_k = K, p2d_k = k,
 // carry.to = to, merge_n = n, valid = true, form = ...).
 //
 // The counters.  Each is only ever compared for equality with a copy taken earlier; each counts one thing:
-//   nn_gen[d]  whatever a reduction or selection of direction d reads has changed: the result itself, or normals, features and
-//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, selections), TieCols::gen, ColorMemo::gen.
+//   nn_gen[d]  whatever a reduction, selection or count of direction d reads has changed: the result itself, or normals, features and
+//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, selections, counts), TieCols::gen, ColorMemo::gen.
 //   nn_run[d]  searches of direction d (prepare_nn alone bumps it): WHICH result the direction holds.  Copies: Carry::run_f / run_g.
 //   nrm_gen    any cloud's normals changed.  Copies: TieCols::nrm_gen / ang_gen.
 //   rgb_gen    any cloud's colours changed.  Copies: TieCols::rgb_gen, ColorMemo::rgb_gen.
@@ -33,6 +33,12 @@ inline void results_void(pccm_ctx *ctx, int dir_mask)
         ctx->nn_gen[d]++;
     }
 }
+
+// The records of direction `dir` were written again in another form under a result that stays valid (ensure_plain repeats a search
+// that left the matched rows out): the values are the same, but the job a pending reduction was bound with (ReduceWhat::job -- what
+// a later selection or count of the column would read) describes records that are gone.  Pending reductions, selections and
+// counts of the direction are recomputed from the new records by whoever asks next.
+inline void records_rewritten(pccm_ctx *ctx, int dir) { ctx->nn_gen[dir]++; }
 
 // ... and what was enqueued on them is never to be consumed (a kernel raised the device error word, a capture failed)
 inline void results_dropped(pccm_ctx *ctx)

@@ -48,6 +48,8 @@ class PrimaryMetric(AbstractMetric):                 # metric.py:32-38 -- reads 
 
 class SecondaryMetric(AbstractMetric):               # metric.py:41-50 -- pure function of its deps
     _pccm_role = 2
+    _pccm_item = None       # what the calculator tells CloudPair.prefetch_reductions about this node: "column" (EuclideanDistance),
+    #                         "ranked" (GeoRankedHausdorffDistance), "within" (GeoInlierRatio); subclasses inherit it
 
     def _get_dependencies(self) -> typing.Dict[str, "AbstractMetric"]:
         return {}
@@ -235,6 +237,8 @@ class ErrorVector(SecondaryMetric, PointToPlaneable):            # metric.py:124
 
 
 class EuclideanDistance(SecondaryMetric, PointToPlaneable):      # metric.py:156-179
+    _pccm_item = "column"
+
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         if self.point_to_plane:
             return {"error_vector": ErrorVector(is_left=self.is_left, point_to_plane=True)}
@@ -300,6 +304,7 @@ class GeoRankedHausdorffDistance(_OverEuclidean):                # no counterpar
     Hausdorff"): the rank_index(rank, n)-th smallest element of the column GeoHausdorffDistance takes the maximum of -- a
     SQUARED distance like it, and equal to it bit for bit at rank 1."""
     _pccm_waits = True      # reads a selection back from the GPU: the calculator evaluates these last
+    _pccm_item = "ranked"
 
     def __init__(self, is_left: bool, point_to_plane: bool, rank: float):
         super().__init__(is_left, point_to_plane)
@@ -313,6 +318,48 @@ class GeoRankedHausdorffDistance(_OverEuclidean):                # no counterpar
         k = rank_index(self.rank, column.shape[0])
         ranked = getattr(column, "ranked", None)              # a device column: selected in HBM
         self.value = ranked(k) if ranked is not None else np.partition(np.asarray(column), k - 1)[k - 1]
+
+
+class GeoInlierRatio(SecondaryMetric, DirectionalMetric):        # no counterpart in the reference (options.py: fscore)
+    """The share of one cloud's points that lie within ``threshold`` of the other cloud ("F-score"): the number
+    of elements of the D1 column -- squared distances -- that are <= threshold * threshold, over the number of points.  Left
+    (origin -> processed) is the recall (completeness) of the processed cloud, right its precision (accuracy)."""
+    _pccm_waits = True      # reads a count back from the GPU: the calculator evaluates these last
+    _pccm_item = "within"
+
+    def __init__(self, is_left: bool, threshold: float):
+        super().__init__(is_left)
+        self.threshold = float(threshold)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.threshold)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"euclidean_distance": EuclideanDistance(is_left=self.is_left, point_to_plane=False)}
+
+    def calculate(self, euclidean_distance: EuclideanDistance) -> None:
+        column = euclidean_distance.value
+        t2 = np.float64(self.threshold) * np.float64(self.threshold)
+        count_le = getattr(column, "count_le", None)          # a device column: counted in HBM
+        count = count_le(t2) if count_le is not None else np.count_nonzero(np.asarray(column) <= t2)
+        self.value = np.float64(count) / np.float64(column.shape[0])
+
+
+class GeoFScore(SecondaryMetric):                                # no counterpart in the reference (options.py: fscore)
+    """F-score at a distance threshold: the harmonic mean of precision (right) and recall (left), 0 when both are 0."""
+    def __init__(self, threshold: float):
+        self.threshold = float(threshold)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.threshold)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"precision": GeoInlierRatio(is_left=False, threshold=self.threshold),
+                "recall": GeoInlierRatio(is_left=True, threshold=self.threshold)}
+
+    def calculate(self, precision: GeoInlierRatio, recall: GeoInlierRatio) -> None:
+        p, r = np.float64(precision.value), np.float64(recall.value)
+        self.value = np.float64(0.0) if p + r == 0.0 else ((2.0 * p) * r) / (p + r)
 
 
 class _OverAngular(SecondaryMetric, DirectionalMetric):

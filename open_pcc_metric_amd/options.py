@@ -58,6 +58,12 @@ on the clouds' per-point scalars as given, PSNR against ``reflectance_peak``), a
   reflectance                  ReflectanceMSE L/R/sym, ReflectancePSNR L/R/sym
   reflectance & hd             ReflectanceHausdorffDistance L/R/sym, ReflectanceHausdorffDistancePSNR L/R/sym
 
+and, with ``fscore`` (no counterpart in the reference: the F-score at a distance threshold of Knapitsch et al., "Tanks and
+Temples", ACM TOG 2017, as the reconstruction and completion literature reports it beside the Chamfer distance), after every row
+above, for each threshold in ascending order:
+
+  threshold tau                GeoInlierRatio L (recall), GeoInlierRatio R (precision), GeoFScore (no symmetric row: the F-score is it)
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -69,7 +75,7 @@ import math
 import numbers
 
 from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
-                     GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
+                     GeoFScore, GeoInlierRatio, GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
                      GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
                      JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
                      MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
@@ -78,6 +84,7 @@ from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahal
 SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
 MAX_HAUSDORFF_RANKS = 4
+MAX_FSCORE_THRESHOLDS = 4
 P2D_MIN_K, P2D_MAX_K = 4, 64
 RESOLUTION_MIN_K, RESOLUTION_MAX_K = 1, 63
 
@@ -102,13 +109,33 @@ def _hausdorff_ranks(value) -> typing.Tuple[float, ...]:
     return tuple(sorted(ranks))
 
 
+def _fscore_thresholds(value) -> typing.Tuple[float, ...]:
+    """``fscore`` as a sorted tuple of distinct finite floats >= 0; ValueError for anything else."""
+    if value is None:
+        return ()
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"fscore must be a number or an iterable of numbers >= 0, not {value!r}")
+    items = [value] if isinstance(value, numbers.Real) else list(value) if hasattr(value, "__iter__") else [value]
+    thresholds = set()
+    for t in items:
+        if isinstance(t, (bool,)) or type(t).__name__ == "bool_" or not isinstance(t, numbers.Real):
+            raise ValueError(f"fscore: {t!r} is not a finite number >= 0")
+        f = float(t)
+        if not math.isfinite(f) or f < 0.0:
+            raise ValueError(f"fscore: {t!r} is not a finite number >= 0")
+        thresholds.add(f + 0.0)                               # (-0.0 is the threshold 0.0)
+    if len(thresholds) > MAX_FSCORE_THRESHOLDS:
+        raise ValueError(f"fscore: at most {MAX_FSCORE_THRESHOLDS} thresholds per report, not {len(thresholds)}")
+    return tuple(sorted(thresholds))
+
+
 class CalculateOptions:
     def __init__(self, color: typing.Optional[str] = None, hausdorff: bool = False,
                  point_to_plane: bool = False, plane_to_plane: bool = False,
                  point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
                  p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10,
-                 reflectance: bool = False, reflectance_peak: float = 65535.0):
+                 reflectance: bool = False, reflectance_peak: float = 65535.0, fscore=None):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -146,6 +173,7 @@ class CalculateOptions:
             raise ValueError(f"reflectance_peak must be a positive finite number, not {peak!r}")
         self.reflectance = bool(reflectance)
         self.reflectance_peak = float(peak)
+        self.fscore = _fscore_thresholds(fscore)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -173,6 +201,14 @@ def check_hausdorff_rank(options: CalculateOptions, *, group=None) -> None:
     A sharded pair would have to exchange the per-pass histograms across its ranks: not built."""
     if getattr(options, "hausdorff_rank", ()) and group is not None:
         raise ValueError("ranked Hausdorff rows are not available for sharded pairs (group=)")
+
+
+def check_fscore(options: CalculateOptions, *, group=None) -> None:
+    """Raise ``ValueError`` when the F-score rows ``options`` asks for cannot be computed for this pair -- before any GPU work (the
+    command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).  A sharded pair
+    would have to add its ranks' counts up: not built."""
+    if getattr(options, "fscore", ()) and group is not None:
+        raise ValueError("F-score rows are not available for sharded pairs (group=)")
 
 
 def check_point_to_distribution(options: CalculateOptions, *, group=None) -> None:
@@ -312,4 +348,7 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
         if options.hausdorff:
             metrics += (_sides(ReflectanceHausdorffDistance) + [_sym(ReflectanceHausdorffDistance, False)]
                         + _sides(ReflectanceHausdorffDistancePSNR, **kw) + [_sym(ReflectanceHausdorffDistancePSNR, True, **kw)])
+    for threshold in getattr(options, "fscore", None) or ():
+        # left: recall (how much of the origin cloud the processed one covers); right: precision; the F-score is the symmetric row
+        metrics += _sides(GeoInlierRatio, threshold=threshold) + [GeoFScore(threshold=threshold)]
     return metrics
