@@ -605,6 +605,54 @@ int pccm_nn_path(pccm_ctx *ctx, int which, char *buf, int64_t cap, int64_t *len)
  * PCCM_E_STATE before the first grid search. */
 int pccm_grid_geometry(pccm_ctx *ctx, double org[3], double h[3], int32_t dim[3]);
 
+/* What a grid build left behind, read back for inspection (diagnostics and tests; never part of a report).  Every build is one
+ * counting sort of some rows by cell; the library notes on the host, where it starts the sort, what each of these structures
+ * was last built as -- no GPU work, no wait:
+ *   PCCM_BUILD_GRID0 / _GRID1                cloud 0 / 1 of the grid the last search built (the pair's grid, or the grid over one
+ *                                            cloud alone that a k-nearest-neighbour search -- normal estimation -- builds for itself);
+ *   PCCM_BUILD_SHARD_LEFT / _RIGHT / _SELF   the cell-sorted query rows of that direction's shard in the last search (whether they
+ *                                            were sorted by the grid build's own launches or by a sort of their own);
+ *   PCCM_BUILD_SP0 / _SP1                    cloud 0 / 1 in its spatial order (made by the first pccm_drop_caches behind a search).
+ * pccm_build_plan fills plan[PCCM_BP_COUNT] (indices below) and geom = {org[3], h[3]}; pccm_build_fetch copies the structure to
+ * the host: cell_start[ncells + 1] (relative to the structure's first record), rows[n] and xyz[n][3] (the records in stored
+ * order: original row, and the stored coordinates widened to fp64 -- exact), occ[(ncells + 31) / 32] (the occupancy bitmap, when
+ * PCCM_BP_HAS_OCC); a null pointer skips that part.  The shard structures and the spatial order's cell starts live in scratch
+ * that any later build or occupancy measurement overwrites: PCCM_E_STATE for a structure that is no longer (or was never) there
+ * -- a grid never built or dropped by pccm_drop_caches, a direction that was not sharded, a cloud without a spatial order -- and,
+ * in pccm_build_fetch, for cell starts asked of a structure whose PCCM_BP_HAS_CS is 0.  Not allowed during graph capture; a
+ * captured search is described by its capture, and every replay leaves the same structures. */
+#define PCCM_BUILD_GRID0 0
+#define PCCM_BUILD_GRID1 1
+#define PCCM_BUILD_SHARD_LEFT 2
+#define PCCM_BUILD_SHARD_RIGHT 3
+#define PCCM_BUILD_SHARD_SELF 4
+#define PCCM_BUILD_SP0 5
+#define PCCM_BUILD_SP1 6
+#define PCCM_BUILD_COUNT 7
+#define PCCM_BP_REC32 0      /* records are 16 bytes {x, y, z as fp32, row}; 0: 32 bytes {x, y, z as fp64, row} */
+#define PCCM_BP_NCELLS 1
+#define PCCM_BP_N 2          /* records of the structure */
+#define PCCM_BP_ROW0 3       /* ... which are rows [row0, row0 + n) of their cloud */
+#define PCCM_BP_HAS_OCC 4    /* an occupancy bitmap was written beside the cell starts */
+#define PCCM_BP_MORTON 5     /* cells are numbered along a Z-order curve (the spatial order), not x-fastest */
+#define PCCM_BP_BITS 6       /* ... over 2^bits cells per axis */
+#define PCCM_BP_DIM 7        /* [7..9]: cells per axis */
+#define PCCM_BP_LG 10        /* the sort's plan: a bin is 2^lg consecutive cells, */
+#define PCCM_BP_NBIN 11      /* bins per job, */
+#define PCCM_BP_TILES 12     /* tiles of this structure's job */
+#define PCCM_BP_TILE_ROWS 13 /* ... and rows per tile, */
+#define PCCM_BP_SCAN 14      /* 1: hist matrix + look-back scan (PCCM_BUILD_SCAN=1), 0: bin cursors, */
+#define PCCM_BP_SCAN_TILES 15 /* workgroups of the look-back scan (0 without it), */
+#define PCCM_BP_READ_SP 16   /* the job read its cloud in spatial order instead of row order, */
+#define PCCM_BP_NJOBS 17     /* jobs the sort's launches served, */
+#define PCCM_BP_JOB 18       /* which of them made this structure, */
+#define PCCM_BP_JOB_ROW0 19  /* [19..20]: first row of job 0 / 1, */
+#define PCCM_BP_JOB_N 21     /* [21..22]: rows of job 0 / 1 */
+#define PCCM_BP_HAS_CS 23    /* the structure's cell starts are still there to fetch */
+#define PCCM_BP_COUNT 24
+int pccm_build_plan(pccm_ctx *ctx, int which, int64_t plan[PCCM_BP_COUNT], double geom[6]);
+int pccm_build_fetch(pccm_ctx *ctx, int which, uint32_t *cell_start, int32_t *rows, double *xyz, uint32_t *occ);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,7 +55,14 @@ SYMBOLS = (
     "pccm_color_transform", "pccm_lzf_decompress", "pccm_drop_caches", "pccm_graph_begin", "pccm_graph_end", "pccm_graph_launch", "pccm_graph_destroy",
     "pccm_sync",
     "pccm_profile_enable", "pccm_profile_reset", "pccm_profile_get", "pccm_nn_stats", "pccm_nn_path", "pccm_grid_geometry",
+    "pccm_build_plan", "pccm_build_fetch",
 )
+
+# structures a build leaves (pccm_build_plan / pccm_build_fetch) and the fields of a plan, in the order of PCCM_BP_*
+BUILD_GRID0, BUILD_GRID1, BUILD_SHARD_LEFT, BUILD_SHARD_RIGHT, BUILD_SHARD_SELF, BUILD_SP0, BUILD_SP1 = range(7)
+_BUILD_PLAN_FIELDS = ("rec32", "ncells", "n", "row0", "has_occ", "morton", "bits", "dim0", "dim1", "dim2", "lg", "nbin", "tiles",
+                      "tile_rows", "scan", "scan_tiles", "read_sp", "njobs", "job", "job_row0_0", "job_row0_1", "job_n_0", "job_n_1",
+                      "has_cs")
 
 COLOR_SCHEMES = {"rgb": 0, "ycc": 1, "yuv": 2}
 COLOR_OWN, COLOR_NEIGHBOUR, COLOR_DIFF, COLOR_SQUARE = 0, 1, 2, 3
@@ -180,6 +187,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_nn_stats.argtypes = [vp, i32, ctypes.POINTER(i64)]
     lib.pccm_nn_path.argtypes = [vp, i32, ctypes.c_char_p, i64, ctypes.POINTER(i64)]
     lib.pccm_grid_geometry.argtypes = [vp, dp, dp, vp]
+    lib.pccm_build_plan.argtypes = [vp, i32, lp, dp]
+    lib.pccm_build_fetch.argtypes = [vp, i32, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("pccm_last_error", "pccm_xvec_len", "pccm_cvec_len"):
@@ -849,6 +858,31 @@ class Engine:
         dim = np.empty(3, dtype=np.int32)
         _check(self._lib.pccm_grid_geometry(self._ctx, org, h, dim.ctypes.data_as(ctypes.c_void_p)))
         return np.array(org[:]), np.array(h[:]), dim
+
+    def build_plan(self, which: int) -> dict:
+        """What structure ``which`` (BUILD_*) was last built as: the fields of PCCM_BP_* by name, ``dim``, ``org`` and ``h``
+        (pccm_build_plan).  PccmStateError when the structure is not there."""
+        plan = (ctypes.c_int64 * len(_BUILD_PLAN_FIELDS))()
+        geom = (ctypes.c_double * 6)()
+        _check(self._lib.pccm_build_plan(self._ctx, int(which), plan, geom))
+        out = {k: int(v) for k, v in zip(_BUILD_PLAN_FIELDS, plan)}
+        out["dim"] = np.array([out["dim0"], out["dim1"], out["dim2"]], dtype=np.int64)
+        out["org"] = np.array(geom[0:3], dtype=np.float64)
+        out["h"] = np.array(geom[3:6], dtype=np.float64)
+        return out
+
+    def build_fetch(self, which: int) -> dict:
+        """Structure ``which`` as the build left it (pccm_build_fetch): ``plan``, ``rows`` [n], ``xyz`` [n, 3] in stored order,
+        ``cell_start`` [ncells + 1] (None when it has been overwritten) and ``occ`` (the bitmap's words, or None)."""
+        plan = self.build_plan(which)
+        n, ncells = plan["n"], plan["ncells"]
+        rows = np.empty(n, dtype=np.int32)
+        xyz = np.empty((n, 3), dtype=np.float64)
+        cs = np.empty(ncells + 1, dtype=np.uint32) if plan["has_cs"] else None
+        occ = np.empty((ncells + 31) // 32, dtype=np.uint32) if plan["has_occ"] else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        _check(self._lib.pccm_build_fetch(self._ctx, int(which), ptr(cs), ptr(rows), ptr(xyz), ptr(occ)))
+        return {"plan": plan, "rows": rows, "xyz": xyz, "cell_start": cs, "occ": occ}
 
     def tie_scan_queries(self, direction: int) -> int:
         """Queries of the last "mean" search of ``direction`` whose tie set the exact scan enumerated (PCCM_STATS_TIES)."""

@@ -2668,6 +2668,21 @@ int pccm_grid_geometry(pccm_ctx *ctx, double org[3], double h[3], int32_t dim[3]
     return PCCM_OK;
 }
 
+int pccm_build_plan(pccm_ctx *ctx, int which, int64_t plan[PCCM_BP_COUNT], double geom[6])
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (!plan || !geom) return fail(PCCM_E_ARG, "null pointer");
+    return build_plan(ctx, which, plan, geom);
+}
+
+int pccm_build_fetch(pccm_ctx *ctx, int which, uint32_t *cell_start, int32_t *rows, double *xyz, uint32_t *occ)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    return build_fetch(ctx, which, cell_start, rows, xyz, occ);
+}
+
 int pccm_nn_stats(pccm_ctx *ctx, int dir, int64_t out[3])
 {
     CHECK_CTX(ctx);

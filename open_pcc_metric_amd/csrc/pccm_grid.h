@@ -110,6 +110,7 @@ struct BuildJob {
                                  // ([ncells / 32 + 2] words; voxelised pairs, pccm_lattice.hip), or null
     const Rec32 *sp = nullptr;   // the cloud in its ingest-time spatial order ({x, y, z, original row}; Cloud::sp), read instead
                                  // of x32 when the job covers the whole cloud: the sort's scatters then stay inside a few bins
+    int tag = -1;                // PCCM_BUILD_* structure this job makes: sort_by_cell notes what it left (pccm_build_plan), or -1
 };
 
 struct BuildJobs {

@@ -749,6 +749,7 @@ static int measure_occupancy(pccm_ctx *ctx, const Cloud &c, double scale, Occupa
     int64_t ncells;
     choose_geometry(ctx, g, ncells, scale, false, solo);
     int rc;
+    ctx->scratch_gen++;                                    // g_hist is overwritten: a shard's cell starts are gone
     if ((rc = ensure(ctx, ctx->g_hist, (size_t)(ncells + 1) * sizeof(uint32_t)))) return rc;
     uint32_t *hist = (uint32_t *)ctx->g_hist.p;
     unsigned long long *counter = (unsigned long long *)ctx->stats.p;
@@ -944,6 +945,8 @@ int grid_decide(pccm_ctx *ctx, bool *hostile)
 int spatial_order(pccm_ctx *ctx, Cloud &c)
 {
     c.sp_valid = false;
+    const int which = (int)(&c - ctx->cloud);
+    ctx->builds[PCCM_BUILD_SP0 + which].valid = false;
     static const bool off = [] { const char *e = getenv("PCCM_SPATIAL"); return e && e[0] == '0'; }();
     if (off || !c.exact32 || c.n < 4096) return PCCM_OK;            // small clouds: nothing to gain
     int bits = 4;
@@ -961,12 +964,14 @@ int spatial_order(pccm_ctx *ctx, Cloud &c)
     const int64_t ncells = 1ll << (3 * bits);
     int rc;
     if ((rc = grow(&c.sp, c.cap_sp, (size_t)c.n * sizeof(Rec32)))) return rc;
+    ctx->scratch_gen++;
     if ((rc = ensure(ctx, ctx->g_hist, (size_t)3 * (ncells + 1) * sizeof(uint32_t)))) return rc;
     ProfScope ps(ctx, PCCM_K_INGEST);
     BuildJobs jobs;
     jobs.njobs = 1;
     jobs.total = c.n;
     jobs.j[0] = {c.xyz64, (const float *)c.xyz32, 0, c.n, (uint32_t *)ctx->g_hist.p};
+    jobs.j[0].tag = PCCM_BUILD_SP0 + which;
     jobs.j[1] = jobs.j[0];
     if ((rc = sort_by_cell(ctx, jobs, g, ncells, c.sp, true))) return rc;
     c.sp_valid = true;
@@ -1020,6 +1025,7 @@ struct ShardSort {
     const Cloud *it = nullptr;
     int64_t begin = 0, n = 0;
     bool done = false;
+    int tag = -1;                      // PCCM_BUILD_SHARD_* of the shard's direction
     const char *recs = nullptr;        // where the shard's cell-sorted records went
     const uint32_t *cs = nullptr;      // ... and their cell starts
 };
@@ -1047,6 +1053,7 @@ static int ensure_grid(pccm_ctx *ctx, bool need64 = false, int need_mask = 3, ui
     if (same && (gr.built & need_mask) == need_mask) return PCCM_OK;
     if (same) need_mask |= gr.built;                   // keep what is there, add what is missing
     ProfScope ps(ctx, PCCM_K_GRID_BUILD);
+    ctx->builds[PCCM_BUILD_GRID0].valid = ctx->builds[PCCM_BUILD_GRID1].valid = false;   // the grid's buffers are written (or moved) below
     GridGeom g;
     int64_t ncells;
     choose_geometry(ctx, g, ncells, gr.scale, vox);
@@ -1077,6 +1084,7 @@ static int ensure_grid(pccm_ctx *ctx, bool need64 = false, int need_mask = 3, ui
         jobs.j[jobs.njobs] = {c.xyz64, (const float *)c.xyz32, 0, c.n, cs + (size_t)k * (ncells + 1)};
         if (rec32 && c.sp_valid) jobs.j[jobs.njobs].sp = (const Rec32 *)c.sp;
         if (lattice) jobs.j[jobs.njobs].occ = (uint32_t *)gr.occ.p + (size_t)k * occ_words;
+        jobs.j[jobs.njobs].tag = PCCM_BUILD_GRID0 + k;
         ++jobs.njobs;
         jobs.total += c.n;
     }
@@ -1086,6 +1094,7 @@ static int ensure_grid(pccm_ctx *ctx, bool need64 = false, int need_mask = 3, ui
         // (16-byte records fill half of the buffer that is sized for either layout: the shard's records fit behind the cloud's)
         if ((rc = ensure(ctx, ctx->g_hist, (size_t)3 * (ncells + 1) * sizeof(uint32_t)))) return rc;
         jobs.j[1] = {shard->it->xyz64, (const float *)shard->it->xyz32, shard->begin, shard->n, (uint32_t *)ctx->g_hist.p};
+        jobs.j[1].tag = shard->tag;
         jobs.njobs = 2;
         shard->recs = first + (size_t)jobs.total * rsz;
         shard->cs = (const uint32_t *)ctx->g_hist.p;
@@ -1331,6 +1340,7 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
             ride_dir = dirs[d];
             ride.it = &it;
             ride.begin = res.begin;
+            ride.tag = PCCM_BUILD_SHARD_LEFT + dirs[d];
             ride.n = res.end - res.begin;
         }
     }
@@ -1470,6 +1480,7 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
                 const Cloud &it = ctx->cloud[dir == PCCM_DIR_RIGHT ? 1 : 0];
                 bj.j[k] = {it.xyz64, (const float *)it.xyz32, res.begin, res.end - res.begin,
                            (uint32_t *)ctx->g_hist.p + (size_t)(s0 + k) * (gr.ncells + 1)};
+                bj.j[k].tag = PCCM_BUILD_SHARD_LEFT + dir;
                 bj.total += res.end - res.begin;
             }
             if (cnt == 1) bj.j[1] = bj.j[0];
@@ -1908,6 +1919,7 @@ int grid_ensure_solo(pccm_ctx *ctx, int which)
         c.solo_scale_version = c.version;
     }
     ProfScope ps(ctx, PCCM_K_GRID_BUILD);
+    ctx->builds[PCCM_BUILD_GRID0].valid = ctx->builds[PCCM_BUILD_GRID1].valid = false;
     GridGeom g;
     int64_t ncells;
     choose_geometry(ctx, g, ncells, c.solo_scale, false, which);
@@ -1918,6 +1930,7 @@ int grid_ensure_solo(pccm_ctx *ctx, int which)
     jobs.njobs = 1;
     jobs.total = c.n;
     jobs.j[0] = {c.xyz64, (const float *)c.xyz32, 0, c.n, (uint32_t *)gr.cell_start.p + (size_t)which * (ncells + 1)};
+    jobs.j[0].tag = PCCM_BUILD_GRID0 + which;
     jobs.j[1] = jobs.j[0];
     if ((rc = sort_by_cell(ctx, jobs, g, ncells, (char *)gr.recs.p + (size_t)(which ? n0 : 0) * sizeof(GridRec), false))) return rc;
     for (int a = 0; a < 3; ++a) {
@@ -1945,10 +1958,113 @@ void grid_release(pccm_ctx *ctx)
         b->p = nullptr;
         b->bytes = 0;
     }
+    for (BuildNote &b : ctx->builds) b.valid = false;
     ctx->grid.key = 0;
 }
 
-void grid_invalidate(pccm_ctx *ctx) { ctx->grid.key = 0; }
+void grid_invalidate(pccm_ctx *ctx)
+{
+    ctx->grid.key = 0;
+    // what the searches' builds left is no longer vouched for either (pccm_build_plan): the caller dropped it, or a capture that
+    // noted it never ran; a spatial order stays with its cloud
+    for (int k = PCCM_BUILD_GRID0; k <= PCCM_BUILD_SHARD_SELF; ++k) ctx->builds[k].valid = false;
+}
+
+// ---- read-back of what a build left (pccm_build_plan / pccm_build_fetch) ----------------------------------------------------
+// The note of structure `which` when the structure is still there, else null (with the error set).  Shard structures live in
+// scratch: theirs is the note of the latest scratch generation only; a spatial order stands as long as its cloud keeps it.
+static const BuildNote *build_note(pccm_ctx *ctx, int which, bool *has_cs)
+{
+    if (which < 0 || which >= PCCM_BUILD_COUNT) {
+        fail(PCCM_E_ARG, "unknown structure %d", which);
+        return nullptr;
+    }
+    const BuildNote &b = ctx->builds[which];
+    const bool current = b.gen == ctx->scratch_gen;
+    *has_cs = true;
+    bool there = b.valid;
+    if (which >= PCCM_BUILD_SP0) {
+        const Cloud &c = ctx->cloud[which - PCCM_BUILD_SP0];
+        there = there && c.sp_valid && c.sp == b.recs && c.n == b.n;
+        *has_cs = current;                                 // its cell starts were written into g_hist
+    } else if (which >= PCCM_BUILD_SHARD_LEFT) {
+        there = there && current;
+    }
+    if (!there) {
+        fail(PCCM_E_STATE, "structure %d is not there: never built, or overwritten since", which);
+        return nullptr;
+    }
+    return &b;
+}
+
+int build_plan(pccm_ctx *ctx, int which, int64_t *plan, double *geom)
+{
+    bool has_cs;
+    const BuildNote *b = build_note(ctx, which, &has_cs);
+    if (!b) return which < 0 || which >= PCCM_BUILD_COUNT ? PCCM_E_ARG : PCCM_E_STATE;
+    for (int k = 0; k < PCCM_BP_COUNT; ++k) plan[k] = 0;
+    plan[PCCM_BP_REC32] = b->rec32;
+    plan[PCCM_BP_NCELLS] = b->ncells;
+    plan[PCCM_BP_N] = b->n;
+    plan[PCCM_BP_ROW0] = b->row0;
+    plan[PCCM_BP_HAS_OCC] = b->occ != nullptr;
+    plan[PCCM_BP_MORTON] = b->morton;
+    if (b->morton)
+        while ((1 << plan[PCCM_BP_BITS]) < b->dim[0]) ++plan[PCCM_BP_BITS];
+    for (int a = 0; a < 3; ++a) {
+        plan[PCCM_BP_DIM + a] = b->dim[a];
+        geom[a] = b->org[a];
+        geom[3 + a] = b->h[a];
+    }
+    plan[PCCM_BP_LG] = b->lg;
+    plan[PCCM_BP_NBIN] = b->nbin;
+    plan[PCCM_BP_TILES] = b->tiles;
+    plan[PCCM_BP_TILE_ROWS] = b->tile_rows;
+    plan[PCCM_BP_SCAN] = b->scan;
+    plan[PCCM_BP_SCAN_TILES] = b->scan_tiles;
+    plan[PCCM_BP_READ_SP] = b->read_sp;
+    plan[PCCM_BP_NJOBS] = b->njobs;
+    plan[PCCM_BP_JOB] = b->job;
+    for (int q = 0; q < 2; ++q) {
+        plan[PCCM_BP_JOB_ROW0 + q] = b->job_row0[q];
+        plan[PCCM_BP_JOB_N + q] = b->job_n[q];
+    }
+    plan[PCCM_BP_HAS_CS] = has_cs;
+    return PCCM_OK;
+}
+
+// raw device bytes over the stream, unpacked on the host (no kernel)
+int build_fetch(pccm_ctx *ctx, int which, uint32_t *cell_start, int32_t *rows, double *xyz, uint32_t *occ)
+{
+    bool has_cs;
+    const BuildNote *b = build_note(ctx, which, &has_cs);
+    if (!b) return which < 0 || which >= PCCM_BUILD_COUNT ? PCCM_E_ARG : PCCM_E_STATE;
+    if (cell_start && !has_cs) return fail(PCCM_E_STATE, "the cell starts of structure %d have been overwritten", which);
+    if (occ && !b->occ) return fail(PCCM_E_STATE, "structure %d has no occupancy bitmap", which);
+    const size_t rsz = b->rec32 ? sizeof(Rec32) : sizeof(GridRec);
+    std::vector<char> raw;
+    if ((rows || xyz) && b->n > 0) {
+        raw.resize((size_t)b->n * rsz);
+        PCCM_HIP(hipMemcpyAsync(raw.data(), b->recs, raw.size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (cell_start) PCCM_HIP(hipMemcpyAsync(cell_start, b->cs, (size_t)(b->ncells + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (occ) PCCM_HIP(hipMemcpyAsync(occ, b->occ, (size_t)((b->ncells + 31) / 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < (int64_t)(raw.size() / rsz); ++i) {
+        if (b->rec32) {
+            Rec32 r;
+            memcpy(&r, raw.data() + (size_t)i * rsz, sizeof(r));
+            if (rows) rows[i] = r.row;
+            if (xyz) { xyz[3 * i] = (double)r.x; xyz[3 * i + 1] = (double)r.y; xyz[3 * i + 2] = (double)r.z; }
+        } else {
+            GridRec r;
+            memcpy(&r, raw.data() + (size_t)i * rsz, sizeof(r));
+            if (rows) rows[i] = r.idx;
+            if (xyz) { xyz[3 * i] = r.x; xyz[3 * i + 1] = r.y; xyz[3 * i + 2] = r.z; }
+        }
+    }
+    return PCCM_OK;
+}
 
 int grid_ensure(pccm_ctx *ctx, bool need64, int need_mask) { return ensure_grid(ctx, need64, need_mask); }
 

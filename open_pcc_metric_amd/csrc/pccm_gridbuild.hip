@@ -527,6 +527,7 @@ static int ceil_log2(int64_t v)
 int sort_by_cell(pccm_ctx *ctx, const BuildJobs &jobs, const GridGeom &g, int64_t ncells, void *recs, bool rec32, uint32_t *zero, int nzero)
 {
     BinPlan P;
+    ctx->scratch_gen++;                                    // whatever lived in the sort's scratch is about to go
     P.zero = zero;
     P.nzero = zero ? nzero : 0;
     P.njobs = jobs.njobs;
@@ -624,6 +625,41 @@ int sort_by_cell(pccm_ctx *ctx, const BuildJobs &jobs, const GridGeom &g, int64_
     else PCCM_LAUNCH(ctx, (k_bin_sort<GridRec>), bg, dim3(256), lds_cells, ctx->stream, P, g, (const uint32_t *)hist, (const GridRec *)ctx->g_tmp.p, (GridRec *)recs);
     PCCM_HIP(hipGetLastError());
     ctx->bins_clean = true;                                // k_bin_sort has been queued: it leaves the cursors at zero
+    // what every tagged job leaves behind, for pccm_build_plan / pccm_build_fetch (host bookkeeping only)
+    for (int k = 0; k < jobs.njobs; ++k) {
+        const int tag = jobs.j[k].tag;
+        if (tag < 0 || tag >= PCCM_BUILD_COUNT) continue;
+        BuildNote &b = ctx->builds[tag];
+        const BinJob &J = P.j[k];
+        b.valid = true;
+        b.gen = ctx->scratch_gen;
+        b.recs = (const char *)recs + (size_t)J.base * rsz;
+        b.cs = J.cs;
+        b.occ = J.occ;
+        b.rec32 = rec32;
+        b.morton = g.morton != 0;
+        b.scan = !cur;
+        b.read_sp = J.sp != nullptr;
+        for (int a = 0; a < 3; ++a) {
+            b.dim[a] = g.dim[a];
+            b.org[a] = g.org[a];
+            b.h[a] = g.h[a];
+        }
+        b.ncells = ncells;
+        b.n = J.n;
+        b.row0 = J.row0;
+        b.lg = P.lg;
+        b.nbin = P.nbin;
+        b.njobs = jobs.njobs;
+        b.job = k;
+        b.tiles = J.nt;
+        b.tile_rows = J.tl;
+        b.scan_tiles = cur ? 0 : st;
+        for (int q = 0; q < 2; ++q) {
+            b.job_row0[q] = q < jobs.njobs ? P.j[q].row0 : 0;
+            b.job_n[q] = q < jobs.njobs ? P.j[q].n : 0;
+        }
+    }
     return PCCM_OK;
 }
 

@@ -200,6 +200,22 @@ struct Grid {                    // one geometry, both clouds (grid engine)
                                    // rank among the set bits of the cell's brick
 };
 
+// What the last sort_by_cell job for one PCCM_BUILD_* structure left behind, noted on the host where the sort is called
+// (pccm_build_plan / pccm_build_fetch: a diagnostic read-back; no device work)
+struct BuildNote {
+    bool valid = false;
+    uint64_t gen = 0;              // pccm_ctx::scratch_gen of that call: shard structures (and the spatial order's cell starts)
+                                   // live in scratch that later calls overwrite
+    const void *recs = nullptr;    // the job's first record
+    const uint32_t *cs = nullptr, *occ = nullptr;
+    bool rec32 = false, morton = false, scan = false, read_sp = false;
+    int dim[3] = {1, 1, 1};
+    double org[3] = {0, 0, 0}, h[3] = {1, 1, 1};
+    int64_t ncells = 0, n = 0, row0 = 0;
+    int lg = 0, nbin = 0, njobs = 0, job = 0;
+    int64_t tiles = 0, tile_rows = 0, scan_tiles = 0, job_row0[2] = {0, 0}, job_n[2] = {0, 0};
+};
+
 struct UnitCol {                // one column reduced from a job's array
     int off;                    // field of the 32-byte result record (0: squared distance, 1: projection); 0 for plain columns
     int square;                 // reduce value^2 (the D2 column from the records' signed projection; metric.py:179)
@@ -402,6 +418,8 @@ struct pccm_ctx {
     // answering wrongly in silence; every call that hands results to the caller checks it behind its wait (check_device_errors)
     uint32_t *host_err = nullptr;
     bool bins_clean = false;   // the build's bin cursors (head of g_bins) are zero on the stream
+    pccm::BuildNote builds[PCCM_BUILD_COUNT];   // what the builds left, per structure (pccm_build_plan)
+    uint64_t scratch_gen = 0;  // bumped by whatever writes g_hist / g_qrecs: sort_by_cell, measure_occupancy, spatial_order
     int want_idx = 1;                      // pccm_nn_want_idx: searches store the matched row with every result
     int fuse_mode[3] = {-1, -1, -1};       // pccm_nn_fuse: normal mode of the D2 projection fused into the search, per direction
     pccm::ReduceSlot slots[24];           // (a report with every PointSSIM and point-to-distribution row holds up to 21 columns at once)
@@ -520,6 +538,8 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx = 0);   // 
 void grid_release(pccm_ctx *ctx);
 void grid_invalidate(pccm_ctx *ctx);
 int grid_ensure(pccm_ctx *ctx, bool need64 = false, int need_mask = 3);
+int build_plan(pccm_ctx *ctx, int which, int64_t *plan, double *geom);       // pccm_build_plan / pccm_build_fetch: what a build left
+int build_fetch(pccm_ctx *ctx, int which, uint32_t *cell_start, int32_t *rows, double *xyz, uint32_t *occ);
 int grid_ensure_solo(pccm_ctx *ctx, int which);    // GridRec grid over cloud `which` alone, cells sized for it (normal estimation)   // need64: GridRec records wanted (pccm_knn.hip reads them)
 int spatial_order(pccm_ctx *ctx, Cloud &c);      // fills Cloud::sp (ingest; no-op for clouds that are not fp32-exact)
 int grid_decide(pccm_ctx *ctx, bool *hostile);   // geometry decision for the current pair (cached per pair)

@@ -101,14 +101,15 @@ UNREACHABLE = {
 
 OTHER = {
     # grid build <fp32 records, bin cursors (else round 2's look-back scan)>; the fp64 look-back build has row 'build_scan_f64'
-    "k_bin_count<false, true>": "grid build of fp64 clouds: rows 'coop_f64', 'thread_gridrec'",
-    "k_bin_count<true, false>": "look-back scan build of fp32 clouds: test_gpu_ab_paths (PCCM_BUILD_SCAN=1)",
-    "k_bin_count<true, true>": "grid build of fp32 clouds: every fp32 grid row",
-    "k_bin_scatter<pccm::GridRec, false, true>": "grid build of fp64 clouds: rows 'coop_f64', 'thread_gridrec'",
-    "k_bin_scatter<pccm::Rec32, true, false>": "look-back scan build of fp32 clouds: test_gpu_ab_paths (PCCM_BUILD_SCAN=1)",
-    "k_bin_scatter<pccm::Rec32, true, true>": "grid build of fp32 clouds: every fp32 grid row",
-    "k_bin_sort<pccm::GridRec>": "grid build: every fp64 row above",
-    "k_bin_sort<pccm::Rec32>": "grid build: every fp32 row above",
+    "k_bin_count<false, true>": "grid build of fp64 clouds: rows 'coop_f64', 'thread_gridrec'; what the build leaves, structure by structure: test_gpu_gridbuild",
+    "k_bin_count<true, false>": "look-back scan build of fp32 clouds: test_gpu_ab_paths (PCCM_BUILD_SCAN=1); test_gpu_gridbuild (its scan rows)",
+    "k_bin_count<true, true>": "grid build of fp32 clouds: every fp32 grid row; what the build leaves, structure by structure: test_gpu_gridbuild",
+    "k_bin_scatter<pccm::GridRec, false, true>": "grid build of fp64 clouds: rows 'coop_f64', 'thread_gridrec'; records, tiles and shards: test_gpu_gridbuild",
+    "k_bin_scatter<pccm::Rec32, true, false>": "look-back scan build of fp32 clouds: test_gpu_ab_paths (PCCM_BUILD_SCAN=1); test_gpu_gridbuild (its scan rows)",
+    "k_bin_scatter<pccm::Rec32, true, true>": "grid build of fp32 clouds: every fp32 grid row; records, tiles, shards and the spatial order: test_gpu_gridbuild",
+    "k_bin_sort<pccm::GridRec>": "grid build: every fp64 row above; cell starts, records and cursors left at zero: test_gpu_gridbuild",
+    "k_bin_sort<pccm::Rec32>": "grid build: every fp32 row above; cell starts, records, bitmaps and cursors left at zero: test_gpu_gridbuild",
+    "k_scan_lookback": "look-back scan of the build's histogram: row 'build_scan_f64'; one tile and tiles with predecessors: test_gpu_gridbuild (its scan rows)",
     "k_tie_mean_scan": "ties='mean': test_gpu_ties_mean",
     "k_count_isolated<pccm::Rec32>": "grid scale decision: every fp32 row above",
     "k_count_isolated<pccm::GridRec>": "grid scale decision: every fp64 row above",

@@ -74,14 +74,22 @@ def predicted_tail(d2, nvox, rows):
     return (d2 > VOX_REACH2) | (nvox > VOX_TIES) if rows else d2 > VOX_REACH2
 
 
+def cell_coords(points, org, h, dim):
+    """Per-axis cell of every point, as float64 whole numbers: the arithmetic of cell_coord in pccm_grid.h -- the subtraction and
+    the multiplication by inv_h = 1 / h each rounded once, floor, clamp to [0, dim - 1]."""
+    q = np.asarray(points, dtype=np.float64)
+    org, h, dim = np.asarray(org, np.float64), np.asarray(h, np.float64), np.asarray(dim, np.int64)
+    inv_h = 1.0 / h
+    return np.clip(np.floor((q - org) * inv_h), 0, dim - 1)
+
+
 def lattice_fallback(queries, d2, org, h, dim):
     """Queries the per-thread kernels leave to the exact rescan: the nearest neighbour lies beyond MAX_RING cells of the grid
     (org, h, dim as pccm_grid_geometry reports them).  The arithmetic of cell_coord / face_bound / settled_by in pccm_grid.h."""
     q = np.asarray(queries, dtype=np.float64)
     org, h, dim = np.asarray(org, np.float64), np.asarray(h, np.float64), np.asarray(dim, np.int64)
-    inv_h = 1.0 / h
     slack = (np.abs(org) + (dim + 2) * h) * 2.0 ** -48
-    c = np.clip(np.floor((q - org) * inv_h), 0, dim - 1)
+    c = cell_coords(q, org, h, dim)
     bound = np.full(len(q), np.inf)
     for a in range(3):
         lo = np.where(c[:, a] - MAX_RING > 0, (q[:, a] - (org[a] + (c[:, a] - MAX_RING) * h[a])) - slack[a], np.inf)
