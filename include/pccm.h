@@ -452,6 +452,29 @@ int pccm_count_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *m
 int pccm_count_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const double *xs,
                     int64_t *out /*[n]*/);
 
+/* Mapped reductions: out[3 i ..] = np.sum, np.min, np.max of f(column), bit for bit, for PCCM_METRIC_D1 or PCCM_METRIC_D2 of
+ * direction 0 or 1 under the context's tie policy, without the column or f(column) ever being stored.  maps[i] says what f is,
+ * applied in this order:
+ *   PCCM_MAP_CLAMP  min(value, xs[i])  (np.minimum(column, xs[i]); xs[i] is read with this bit alone)
+ *   PCCM_MAP_ROOT   the correctly rounded square root (np.sqrt)
+ * so PCCM_MAP_ROOT on a D1 column sums the unsquared nearest-neighbour distances (Chamfer-L1's numerator), PCCM_MAP_CLAMP at
+ * tau * tau the squared distances truncated at tau, and both bits the truncated distances, sqrt(min(value, tau * tau)).  The map
+ * is a mode of the general reduction kernel (k_unit_jobs): it reads the column once, in HBM, in whatever form the search left
+ * it, and sums in NumPy's order like the plain reduction does.  n <= 8 per call.
+ *   pccm_reduce_map_prefetch_many  enqueues the launch (and the columns' plain reductions where nobody has); capturable into
+ *                                  a hipGraph between pccm_graph_begin / pccm_graph_end like pccm_count_prefetch_many.
+ *   pccm_reduce_map_total_many     consumes them (enqueuing first what nobody prefetched) and waits once.
+ * xs[i] = +inf clamps nothing (the plain total's bits); xs[i] <= 0 is allowed.
+ * PCCM_E_ARG: PCCM_DIR_SELF, any other metric (PCCM_METRIC_PROJ has negative values), maps[i] outside 1..3 (0: use
+ * pccm_reduce_total_many), a NaN xs[i] under PCCM_MAP_CLAMP; PCCM_E_STATE: no search result yet, a sharded context;
+ * PCCM_METRIC_D2 without the normals it needs: PCCM_E_STATE / PCCM_E_RANGE exactly where pccm_reduce_total gives them. */
+#define PCCM_MAP_CLAMP 1
+#define PCCM_MAP_ROOT 2
+int pccm_reduce_map_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
+                                  const double *xs);
+int pccm_reduce_map_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
+                               const double *xs, double *out /*[3 n]*/);
+
 /* Sharded contexts whose rows start and end on whole 8192-row chunks (pccm_set_shard / pccm_set_shard_dir do that
  * whenever every rank can have a chunk): the exchange vector shrinks to ONE number per chunk -- NumPy adds the
  * chunks of a column one after the other, and the GPU has finished each chunk's pairwise tree -- plus the raw values
@@ -555,11 +578,11 @@ int pccm_color_transform(const double *rgb, int64_t n, int scheme, double *out);
 int pccm_drop_caches(pccm_ctx *ctx);
 
 /* hipGraph capture.  Between pccm_graph_begin() and pccm_graph_end() only pccm_drop_caches(),
- * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many() and pccm_count_prefetch_many() may be called; they are recorded on the
+ * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many(), pccm_count_prefetch_many() and pccm_reduce_map_prefetch_many() may be called; they are recorded on the
  * context's stream instead of executed.  The same sequence must have run once before (capture cannot allocate).
  * pccm_graph_end() instantiates the graph, runs it once and returns its id; pccm_graph_launch()
  * replays the whole sequence -- kernels and host-side bookkeeping -- with a single launch, after which
- * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
+ * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_reduce_map_total_many()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
  * clouds, normals, shard or any buffer it references change.  One report over resident clouds is
  * ~45 small launches, which an eager host cannot issue as fast as the GPU retires them. */
 int pccm_graph_begin(pccm_ctx *ctx);

@@ -27,6 +27,7 @@ NORMAL_MODES = {"row": 0, "neighbour": 1}
 TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
 DUPLICATES = {"drop": 1, "average": 2}  # PCCM_DUP_DROP / PCCM_DUP_AVERAGE
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
+MAP_CLAMP, MAP_ROOT = 1, 2          # Engine.reduce_map_*: PCCM_MAP_*
 METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
 # PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
 SSIM_ATTRS = {"geometry": 1, "normal": 2, "curvature": 4, "color": 8}
@@ -48,7 +49,7 @@ SYMBOLS = (
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours",
     "pccm_resolution_build", "pccm_get_resolution", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
-    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
+    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_reduce_map_prefetch_many", "pccm_reduce_map_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_reflectance", "pccm_set_reflectance_u16", "pccm_get_reflectance",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
@@ -158,6 +159,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_select_many.argtypes = [vp, i32, ip, ip, ip, lp, dp]
     lib.pccm_count_prefetch_many.argtypes = [vp, i32, ip, ip, ip, dp]
     lib.pccm_count_many.argtypes = [vp, i32, ip, ip, ip, dp, lp]
+    lib.pccm_reduce_map_prefetch_many.argtypes = [vp, i32, ip, ip, ip, ip, dp]
+    lib.pccm_reduce_map_total_many.argtypes = [vp, i32, ip, ip, ip, ip, dp, dp]
     lib.pccm_cvec_len.argtypes = [i64]
     lib.pccm_cvec_len.restype = i64
     lib.pccm_reduce_chunks_many.argtypes = [vp, i32, ip, ip, ip, dp, dp]
@@ -780,6 +783,30 @@ class Engine:
         out = (ctypes.c_int64 * args[0])()
         _check(self._lib.pccm_count_many(self._ctx, *args, out))
         return [int(v) for v in out]
+
+    def _map_args(self, requests, normal_mode):
+        k = len(requests)
+        arr = ctypes.c_int * k
+        return (k, arr(*[int(r[0]) for r in requests]), arr(*[int(r[1]) for r in requests]), arr(*_modes(normal_mode, k)),
+                arr(*[int(r[2]) for r in requests]), (ctypes.c_double * k)(*[float(r[3]) for r in requests]))
+
+    def reduce_map_prefetch_many(self, requests, normal_mode: str = "row") -> None:
+        """``requests``: up to 8 ``(direction, metric, map, x)``: enqueue the reduction of ``f(column)`` for each D1 / D2 column
+        without waiting (pccm_reduce_map_prefetch_many; ``map``: MAP_CLAMP -- ``min(value, x)`` -- and / or MAP_ROOT -- then the
+        square root); a later reduce_map_total_many() consumes them."""
+        if requests:
+            _check(self._lib.pccm_reduce_map_prefetch_many(self._ctx, *self._map_args(requests, normal_mode)))
+
+    def reduce_map_total_many(self, requests, normal_mode: str = "row"):
+        """-> [(sum, min, max)] of ``f(column)`` for up to 8 ``(direction, metric, map, x)``, mapped and summed in HBM
+        (pccm_reduce_map_total_many): bit for bit ``np.sum`` / ``np.min`` / ``np.max`` of ``np.sqrt(np.minimum(column, x))``
+        with the steps ``map`` names."""
+        if not requests:
+            return []
+        args = self._map_args(requests, normal_mode)
+        out = (ctypes.c_double * (3 * args[0]))()
+        _check(self._lib.pccm_reduce_map_total_many(self._ctx, *args, out))
+        return [(np.float64(out[3 * i]), np.float64(out[3 * i + 1]), np.float64(out[3 * i + 2])) for i in range(args[0])]
 
     def reduce_chunks_many(self, requests, normal_mode: str = "row"):
         """-> (one float64 array holding the chunk vectors of up to 8 columns ``(direction, metric)`` one after the other,

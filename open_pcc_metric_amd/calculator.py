@@ -40,7 +40,7 @@ class CalculateResult:
                 label += f"[{inner.rank!r}]"
             if getattr(inner, "peak", None) is not None:        # reflectance PSNR rows: the peak they were taken against
                 label += f"[{inner.peak!r}]"
-            if getattr(inner, "threshold", None) is not None:   # F-score rows: one block per distance threshold
+            if getattr(inner, "threshold", None) is not None:   # F-score and truncated-distance rows: one block per distance threshold
                 label += f"[{inner.threshold!r}]"
             if inner is not m:
                 label += "(symmetric)"
@@ -118,6 +118,8 @@ class MetricCalculator:
                     wanted.append(("ranked", metric.is_left, metric.point_to_plane, metric.rank))
                 elif item == "within":
                     wanted.append(("within", metric.is_left, metric.threshold))
+                elif item == "mapped":
+                    wanted.append(("mapped",) + tuple(metric._mapped_request()))
             resolved = {}
             for name, dep in metric._get_dependencies().items():
                 resolved[name], _, dep_waits = self._visit(dep, early, late, planned, wanted)

@@ -202,6 +202,23 @@ class DeviceColumn(_DeviceArray):
                 return value
         return int(np.count_nonzero(np.asarray(self) <= x))
 
+    def mapped(self, root: bool = False, clamp=None):
+        """``(sum, min, max)`` of ``f(column)``, f = the clamp ``np.minimum(column, clamp)`` (when ``clamp`` is given), then the
+        root ``np.sqrt`` (when ``root``): mapped and summed in HBM when the engine can (pccm_reduce_map_total_many: D1 and D2
+        columns) -- neither the column nor f(column) leaves the GPU or is stored there.  Bit for bit NumPy on the column."""
+        if clamp is not None:
+            clamp = float(clamp)
+            if clamp != clamp:
+                raise ValueError("mapped: the clamp is NaN")
+        if not root and clamp is None:
+            return self._reduced()
+        if self._kind in ("d1", "d2"):
+            which = (nat.MAP_CLAMP if clamp is not None else 0) | (nat.MAP_ROOT if root else 0)
+            value = self._pair._mapped(self._dir, self._METRIC[self._kind], which, 0.0 if clamp is None else clamp)
+            if value is not None:
+                return value
+        return mapped_on_host(np.asarray(self), root, clamp)
+
     def _fused_function(self, func, args, kwargs):
         which = _REDUCERS.get(func)
         if which is None or len(args) != 1 or args[0] is not self:
@@ -217,6 +234,16 @@ class DeviceColumn(_DeviceArray):
         if ufunc is np.square and method == "__call__" and not kwargs and self._kind == "proj":
             return DeviceColumn(self._pair, self._dir, "d2")     # metric.py:179 stays on the GPU
         return NotImplemented
+
+
+def mapped_on_host(column, root: bool = False, clamp=None):
+    """What DeviceColumn.mapped answers, for a column that is a plain array."""
+    f = np.asarray(column, dtype=np.float64)
+    if clamp is not None:
+        f = np.minimum(f, np.float64(clamp))
+    if root:
+        f = np.sqrt(f)
+    return np.sum(f), np.min(f), np.max(f)
 
 
 class DeviceFeatures(_DeviceArray):
@@ -340,6 +367,7 @@ class CloudPair:
         self._xchg, self._xchg_wanted = {}, []
         self._selections, self._sel_wanted = {}, []
         self._counts, self._cnt_wanted = {}, []
+        self._maps, self._map_wanted = {}, []
         self._colours_on_device = [False, False]
         self._reflectance_on_device = [False, False]
         self._reflectance = False           # a report asked for the reflectance columns: the searches keep the matched rows
@@ -439,6 +467,7 @@ class CloudPair:
         new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
         new._selections, new._sel_wanted = {}, []
         new._counts, new._cnt_wanted = {}, []
+        new._maps, new._map_wanted = {}, []
         new._graph_id, new._last_wanted = None, None
         keep_self = bool(self.__dict__.get("_self_done")) and bool(getattr(eng, "keeps_self_search", False))
         self_total = self.__dict__.get("_totals", {}).get((nat.DIR_SELF, nat.METRIC_D1)) if keep_self else None
@@ -538,6 +567,7 @@ class CloudPair:
         self._totals = {}
         self._selections = {}
         self._counts = {}
+        self._maps = {}
         self._colour_red = {}
         if self._use_graph and self._last_wanted is not None and hasattr(eng, "graph_begin"):
             wants_self = "boundary" in self._last_wanted
@@ -696,6 +726,26 @@ class CloudPair:
             for q, v in zip(batch, eng.count_many(batch, self.normal_index)):
                 self._counts[q] = v
         return self._counts[key]
+
+    def _check_mapped(self) -> None:
+        """options.check_chamfer / check_truncate for this pair: ValueError before any GPU work of a report."""
+        if self._coll.sharded:
+            raise ValueError("Chamfer and truncated-distance rows are not available for sharded pairs (group=)")
+
+    def _mapped(self, direction: int, metric: int, which: int, x: float):
+        """``(sum, min, max)`` of f(column) for a whole D1 / D2 column, mapped and reduced on the GPU (``which``: nat.MAP_*, ``x``:
+        the clamp).  The first one a report asks for brings back the batch of eight it was enqueued in (prefetch_reductions).
+        None: this engine has no mapped reduction (a test double): the caller maps the materialised column."""
+        self._check_mapped()
+        eng = self._engine
+        if not hasattr(eng, "reduce_map_total_many"):
+            return None
+        key = (direction, metric, which, x)
+        if key not in self._maps:
+            batch = next((b for b in _map_batches(self._map_wanted) if key in b), [key])
+            for q, v in zip(batch, eng.reduce_map_total_many(batch, self.normal_index)):
+                self._maps[q] = v
+        return self._maps[key]
 
     def tie_exposure(self, is_left: bool = True, point_to_plane: bool = True) -> dict:
         """Opt-in diagnostic (not part of any report): how far the order of EXACT ties can move the point-to-plane MSE.
@@ -1088,8 +1138,8 @@ class CloudPair:
 
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
         ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
-        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)``, ``("within", is_left, tau)`` and/or
-        the string ``"boundary"``.
+        ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)``, ``("within", is_left, tau)``,
+        ``("mapped", is_left, point_to_plane, root, clamp)`` (clamp: a number or None) and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -1118,6 +1168,10 @@ class CloudPair:
         if within_items:
             self._check_fscore()
             wanted = [item for item in wanted if item not in within_items]     # (their columns are requests of their own, EuclideanDistance's)
+        mapped_items = [item for item in wanted if item[0] == "mapped"]
+        if mapped_items:
+            self._check_mapped()
+            wanted = [item for item in wanted if item not in mapped_items]     # (their columns are requests of their own, EuclideanDistance's)
         # point-to-distribution: the check, then the columns -- built here like the features, eagerly and outside any capture
         # (one build per neighbourhood size, with the union of what the report needs at that size)
         p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] in ("p2d", "p2d_color", "p2d_joint")]
@@ -1195,6 +1249,14 @@ class CloudPair:
             column = (nat.DIR_LEFT if is_left else nat.DIR_RIGHT, nat.METRIC_D1)
             if column in requests:
                 counts.append(column + (float(np.float64(tau) * np.float64(tau)),))
+        # Chamfer and truncated-distance rows: f(column) of the D1 / D2 columns this report reduces, mapped inside the reduction
+        # kernel -- up to twenty, enqueued behind everything else, eight per call
+        maps = []
+        for _, is_left, p2p, root, clamp in mapped_items:
+            column = (nat.DIR_LEFT if is_left else nat.DIR_RIGHT, nat.METRIC_D2 if p2p else nat.METRIC_D1)
+            if column in requests:
+                which = (nat.MAP_CLAMP if clamp is not None else 0) | (nat.MAP_ROOT if root else 0)
+                maps.append(column + (which, 0.0 if clamp is None else float(clamp)))
         # the reflectance columns join the first batch -- its k_point_jobs launch and its reduction launch -- when it has room
         # for them: eight columns, of which at most four are formed by point jobs (unfused D2, angular, reflectance)
         if reflectance_requests:
@@ -1204,6 +1266,7 @@ class CloudPair:
         self._xchg_wanted = list(requests) + reflectance_requests + ssim_requests + p2d_requests
         self._sel_wanted = sorted(set(selections))
         self._cnt_wanted = sorted(set(counts)) if counts else []
+        self._map_wanted = sorted(set(maps)) if maps else []
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
@@ -1221,6 +1284,9 @@ class CloudPair:
             if self._cnt_wanted and hasattr(eng, "count_prefetch_many"):
                 for batch in _selection_batches(self._cnt_wanted):
                     eng.count_prefetch_many(batch, self.normal_index)
+            if self._map_wanted and hasattr(eng, "reduce_map_prefetch_many"):
+                for batch in _map_batches(self._map_wanted):
+                    eng.reduce_map_prefetch_many(batch, self.normal_index)
         else:
             requests = requests + reflectance_requests + ssim_requests + p2d_requests
             for direction, metric in requests:
@@ -1248,6 +1314,12 @@ def _selection_batches(selections, cap: int = 8):
     if current:
         batches.append(current)
     return batches
+
+
+def _map_batches(maps, cap: int = 8):
+    """Sorted ``(direction, metric, map, x)`` mapped reductions in batches of ``cap`` (pccm_reduce_map_total_many's limit): the
+    order keeps a column's maps next to each other, and two of them share one read of the column."""
+    return [maps[at:at + cap] for at in range(0, len(maps), cap)]
 
 
 def _has_normals(cloud) -> bool:

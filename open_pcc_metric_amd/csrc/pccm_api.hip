@@ -450,6 +450,8 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
         if (s.ev) (void)hipEventDestroy(s.ev);
         s.ev = s.wait_ev = nullptr;
     }
+    for (auto &m : ctx->map_slots)
+        if (m.host) (void)hipHostFree(m.host);
     grid_release(ctx);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     for (auto &pbuf : ctx->pin)
@@ -2341,6 +2343,175 @@ int pccm_count_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, c
     return PCCM_OK;
 }
 
+// ---- mapped reductions: np.sum / min / max of f(column) without the column (include/pccm.h) ---------------------------------
+// A request is (column, map, cap).  Like a selection it reads the column as the column's plain reduction describes it
+// (ReduceWhat::job), enqueued first where nobody has; unlike one it is a reduction launch: the job's column carries the map,
+// reduce_shape() gives such a job no lean kernel, and k_unit_jobs writes block results and the raw tail into the slot's own host
+// region.  Two requests on one column share a job -- its two columns, one read of the records.
+static uint64_t map_cap_bits(int map, double x)
+{
+    uint64_t b = 0;
+    if (map & PCCM_MAP_CLAMP) memcpy(&b, &x, sizeof b);
+    return b;
+}
+
+static MapSlot *map_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, int map, double x)
+{
+    for (auto &m : ctx->map_slots)
+        if (m.matches(dir, metric, normal_mode, ctx->nn_gen[dir], map, map_cap_bits(map, x))) return &m;
+    return nullptr;
+}
+
+static int map_check(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
+                     const double *xs)
+{
+    if (n < 0 || n > 8 || (n > 0 && (!dirs || !metrics || !normal_modes || !maps || !xs))) return fail(PCCM_E_ARG, "1..8 requests expected");
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "%s needs the whole columns on this GPU (world = 1)", who);
+    for (int i = 0; i < n; ++i) {
+        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "mapped reductions read directions 0 and 1, not %d", dirs[i]);
+        if (metrics[i] != PCCM_METRIC_D1 && metrics[i] != PCCM_METRIC_D2)
+            return fail(PCCM_E_ARG, "mapped reductions read PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", metrics[i]);
+        if (maps[i] < 1 || maps[i] > (PCCM_MAP_CLAMP | PCCM_MAP_ROOT))
+            return fail(PCCM_E_ARG, "map %d is no combination of PCCM_MAP_CLAMP and PCCM_MAP_ROOT (0: pccm_reduce_total_many)", maps[i]);
+        if ((maps[i] & PCCM_MAP_CLAMP) && xs[i] != xs[i]) return fail(PCCM_E_ARG, "a clamp's cap is a number or an infinity, not NaN");
+        const Cloud *it, *se;
+        NNResult *res;
+        int rc = need_nn(ctx, dirs[i], &it, &se, &res);
+        if (rc) return rc;
+    }
+    return PCCM_OK;
+}
+
+static int map_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps, const double *xs)
+{
+    auto same_column = [&](int a, int b) {
+        return dirs[a] == dirs[b] && metrics[a] == metrics[b] && (metrics[a] == PCCM_METRIC_D1 || normal_modes[a] == normal_modes[b]);
+    };
+    int todo[8], ntodo = 0, cd[8], cm[8], cmode[8], col_of[8], col_first[8], ncols = 0;
+    for (int i = 0; i < n; ++i) {
+        if (map_find(ctx, dirs[i], metrics[i], normal_modes[i], maps[i], xs[i])) continue;
+        bool dup = false;
+        for (int j = 0; j < ntodo; ++j)
+            dup = dup || (same_column(todo[j], i) && maps[todo[j]] == maps[i] && map_cap_bits(maps[todo[j]], xs[todo[j]]) == map_cap_bits(maps[i], xs[i]));
+        if (dup) continue;
+        int c = 0;
+        while (c < ncols && !same_column(col_first[c], i)) ++c;
+        if (c == ncols) { cd[c] = dirs[i]; cm[c] = metrics[i]; cmode[c] = normal_modes[i]; col_first[c] = i; ncols++; }
+        col_of[ntodo] = c;
+        todo[ntodo++] = i;
+    }
+    if (ntodo == 0) return PCCM_OK;
+    int rc = prefetch_many(ctx, ncols, cd, cm, cmode, false);     // the columns' plain reductions, where none is pending
+    if (rc) return rc;
+    const ReduceSlot *cslot[8];
+    for (int c = 0; c < ncols; ++c) {
+        cslot[c] = slot_find(ctx, cd[c], cm[c], cmode[c]);
+        if (!cslot[c]) return fail(PCCM_E_STATE, "reduction slot lost");
+    }
+    MapSlot *fresh[8];
+    int nfresh = 0, open_job[8];                   // open_job[c]: the job of column c that still has one column free, or -1
+    for (int c = 0; c < 8; ++c) open_job[c] = -1;
+    UnitJobs uj;
+    uj.njobs = 0; uj.uoff[0] = 0; uj.toff[0] = 0;
+    PathScope path(ctx, 1u << 3, true);            // the launch joins the log of the columns' reduction batch
+    for (int j = 0; j < ntodo; ++j) {
+        const int i = todo[j], c = col_of[j];
+        MapSlot *m = pick_free(ctx->map_slots, fresh, nfresh, ctx->nn_gen);
+        if (!m) return fail(PCCM_E_STATE, "no free mapped-reduction slot");
+        if (m->pending && !ctx->capturing && m->wait_ev && (rc = wait_batch(ctx, m->wait_seq, m->wait_ev))) return rc;
+        m->pending = false;
+        SlotShape hs = *cslot[c];                  // the column's shape; no per-leaf results cross to the host
+        hs.nunits = 0;
+        const size_t need = (size_t)hs.host_doubles() * sizeof(double);
+        if (need > m->host_cap) {
+            if (ctx->capturing) {
+                ctx->capture_failed = true;
+                return fail(PCCM_E_STATE, "a mapped-reduction slot must be allocated during graph capture: run the sequence once first");
+            }
+            ctx->epoch++;
+            if (m->host) (void)hipHostFree(m->host);
+            m->host = nullptr; m->host_cap = 0;
+            PCCM_HIP(hipHostMalloc((void **)&m->host, need, hipHostMallocCoherent));   // no XCD's L2 keeps any of it (wait_batch)
+            m->host_cap = need;
+        }
+        m->dir = dirs[i]; m->metric = metrics[i]; m->mode = normal_modes[i];
+        m->gen = ctx->nn_gen[dirs[i]];
+        m->shape = hs;
+        m->map = maps[i];
+        m->cap_bits = map_cap_bits(maps[i], xs[i]);
+        m->pending = true;
+        fresh[nfresh++] = m;
+        if (!cslot[c]->has_job) continue;          // a column without rows: nothing to launch, the total of nothing
+        UnitCol col = cslot[c]->job.c[0];
+        col.map = maps[i];
+        col.cap = (maps[i] & PCCM_MAP_CLAMP) ? xs[i] : 0.0;
+        bind_outputs(col, SlotView(hs, m->host), false);
+        if (open_job[c] >= 0) {                    // the second map over the fields the job already reads
+            uj.j[open_job[c]].c[1] = col;
+            uj.j[open_job[c]].ncols = 2;
+            open_job[c] = -1;
+        } else {
+            UnitJob &U = uj.j[uj.njobs];
+            U = cslot[c]->job;
+            U.ncols = 1;
+            U.c[0] = col; U.c[1] = col;
+            const int64_t lanes = (U.nunits * 8 + 255) / 256 * 256;
+            uj.uoff[uj.njobs + 1] = uj.uoff[uj.njobs] + lanes;
+            uj.toff[uj.njobs + 1] = uj.toff[uj.njobs] + U.tail_n;
+            open_job[c] = uj.njobs++;
+        }
+    }
+    uint64_t seq = 0;
+    if ((rc = launch_unit_jobs(ctx, uj, &seq))) return rc;
+    if (!seq && (rc = launch_publish(ctx, &seq))) return rc;      // (columns without rows: the batch still publishes)
+    for (int f = 0; f < nfresh; ++f) {
+        MapSlot &m = *fresh[f];
+        m.wait_seq = seq;                          // (while capturing: the batch's ordinal in the captured sequence)
+        m.wait_ev = ctx->capturing ? nullptr : ctx->batch_ev;
+        if (ctx->capturing) {
+            GraphOp op;
+            op.kind = 4;
+            op.dir = m.dir;
+            op.slot = (int)(&m - ctx->map_slots);
+            op.msnap = {m, m};
+            ctx->cap_ops.push_back(op);
+        }
+    }
+    if (!ctx->capturing) PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
+    return PCCM_OK;
+}
+
+int pccm_reduce_map_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
+                                  const double *xs)
+{
+    CHECK_CTX(ctx);
+    int rc = map_check(ctx, "pccm_reduce_map_prefetch_many", n, dirs, metrics, normal_modes, maps, xs);
+    if (rc) return rc;
+    return map_prefetch(ctx, n, dirs, metrics, normal_modes, maps, xs);
+}
+
+int pccm_reduce_map_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
+                               const double *xs, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (n > 0 && !out) return fail(PCCM_E_ARG, "null pointer");
+    int rc = map_check(ctx, "pccm_reduce_map_total_many", n, dirs, metrics, normal_modes, maps, xs);
+    if (!rc) rc = map_prefetch(ctx, n, dirs, metrics, normal_modes, maps, xs);
+    if (rc) return rc;
+    MapSlot *got[8];
+    for (int i = 0; i < n; ++i) {
+        MapSlot *m = map_find(ctx, dirs[i], metrics[i], normal_modes[i], maps[i], xs[i]);
+        if (!m) return fail(PCCM_E_STATE, "mapped-reduction slot lost");
+        if ((rc = wait_batch(ctx, m->wait_seq, m->wait_ev))) return rc;
+        if ((rc = check_device_errors(ctx))) return rc;
+        slot_total(m->shape, SlotView(m->shape, m->host), out + 3 * i);
+        got[i] = m;
+    }
+    for (int i = 0; i < n; ++i) got[i]->pending = false;
+    return PCCM_OK;
+}
+
 // Host helper for the colour metrics (metric.py:261-290): out[r] = M * rgb[r] for the BT.709 "ycc" (1) or
 // the "yuv" (2) matrix.  The reference maps every row with np.matmul(M, c); on the authoring host
 // (NumPy 2.2.6 / OpenBLAS dgemv) that evaluates each component as fma(m2*c2, fma(m0*c0, m1*c1)) -- pinned
@@ -2460,6 +2631,17 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
             q.gen = ctx->nn_gen[q.dir];
             q.pending = true;
             rearm(q, ctx, op.ssnap.wait_seq);
+        } else if (op.kind == 4) {
+            MapSlot &m = ctx->map_slots[op.slot];
+            if (m.pending && m.gen == ctx->nn_gen[m.dir] && m.wait_ev) {       // still in use by someone else
+                int rcw = wait_batch(ctx, m.wait_seq, m.wait_ev);
+                if (rcw) return rcw;
+            }
+            static_cast<SlotKey &>(m) = op.msnap.key;
+            static_cast<MapWhat &>(m) = op.msnap.what;
+            m.gen = ctx->nn_gen[m.dir];
+            m.pending = true;
+            rearm(m, ctx, op.msnap.key.wait_seq);
         }
     }
     ctx->batches_issued += g.batches;                            // before the launch: a failed one only delays a waiter
@@ -2476,6 +2658,7 @@ int pccm_graph_begin(pccm_ctx *ctx)
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     for (auto &s : ctx->slots) s.pending = false;      // nothing outside the graph may be half-consumed
     for (auto &q : ctx->sel_slots) q.pending = false;
+    for (auto &m : ctx->map_slots) m.pending = false;
     ctx->cap_ops.clear();
     ctx->cap_batches = 0;
     ctx->capture_failed = false;
@@ -2518,6 +2701,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     for (auto &op : g.ops)
         if (op.kind == 2) rearm(ctx->slots[op.slot], ctx, op.snap.key.wait_seq);
         else if (op.kind == 3) rearm(ctx->sel_slots[op.slot], ctx, op.ssnap.wait_seq);
+        else if (op.kind == 4) rearm(ctx->map_slots[op.slot], ctx, op.msnap.key.wait_seq);
     ctx->batches_issued += g.batches;
     PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));

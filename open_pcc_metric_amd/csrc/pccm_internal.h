@@ -222,6 +222,10 @@ struct UnitCol {                // one column reduced from a job's array
     double *out_units;          // pinned host memory [3][nunits] per-leaf sum/min/max, or null
     double *out_blocks;         // pinned host memory [3][nblocks] per-32-leaf tree sum/min/max
     double *out_tail;           // pinned host memory [tail_n]
+    // a map applied to the value behind the pick and the square (k_unit_jobs alone: reduce_shape() gives a mapped job no lean
+    // kernel): PCCM_MAP_CLAMP -- min(value, cap) -- then PCCM_MAP_ROOT -- the correctly rounded square root; 0: none
+    int map = 0;
+    double cap = 0.0;
 };
 struct UnitJob {                // one per-point array to reduce (k_unit_jobs): up to two columns per pass
     const double *val;          // plain column (stride 1) or the result records (stride 2 or 4 doubles)
@@ -286,6 +290,29 @@ struct SelectSlot : SlotKey {  // one enqueued selection (pccm_select_prefetch_m
     }
 };
 
+// One enqueued mapped reduction (pccm_reduce_map_*): np.sum / min / max of f(column) for the column a reduction slot describes
+// (ReduceWhat::job, as a selection ranks it).  It owns no device column -- only its pinned host region: block results and the
+// raw tail, laid out by SlotView for `shape`, the column's SlotShape without per-leaf results (nunits 0).  A table of its own:
+// a report's up to twenty mapped reductions never evict the plain columns they read.
+struct MapWhat {
+    SlotShape shape;
+    int map = 0;
+    uint64_t cap_bits = 0;     // the bit pattern of the cap (0 without PCCM_MAP_CLAMP)
+};
+struct MapSlot : SlotKey, MapWhat {
+    double *host = nullptr;    // pinned, shape.host_doubles() doubles at least
+    size_t host_cap = 0;
+
+    bool matches(int d, int m, int normal_mode, uint64_t gen_now, int which_map, uint64_t bits) const
+    {
+        return SlotKey::matches(d, m, normal_mode, gen_now) && map == which_map && cap_bits == bits;
+    }
+};
+struct MapSnap {               // ... its bookkeeping at capture time, without what the slot owns
+    SlotKey key;
+    MapWhat what;
+};
+
 struct ReduceSnap {            // a reduction slot's bookkeeping at capture time, without what the slot owns
     SlotKey key;
     ReduceWhat what;
@@ -303,11 +330,13 @@ struct ProfSpan {
 };
 
 struct GraphOp {               // host-side effect of one captured call, replayed by pccm_graph_launch
-    int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch / count_prefetch(slot)
+    int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch / count_prefetch(slot),
+                               // 4 reduce_map_prefetch(slot)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
     ReduceSnap snap;           // kind 2: the slot's bookkeeping at capture time
     SelectSlot ssnap;          // kind 3: likewise for a selection or count slot
+    MapSnap msnap;             // kind 4: likewise for a mapped reduction's slot
 };
 
 struct GraphRec {
@@ -429,6 +458,10 @@ struct pccm_ctx {
     pccm::SelectSlot sel_slots[kSelSlots];
     double *sel_host = nullptr;
     pccm::DevBuf sel_hist, sel_state;
+    // mapped reductions (pccm_reduce_map_*): a report asks for up to twenty (two directions x D1 / D2 roots, and per threshold
+    // the clamp and the clamped root of both directions)
+    static constexpr int kMapSlots = 32;
+    pccm::MapSlot map_slots[kMapSlots];
     uint64_t nn_gen[3] = {1, 1, 1};
     // hipGraph capture of a step (pccm_graph_*): epoch changes whenever inputs, shard or any device
     // buffer a captured kernel may reference changes, which invalidates every recorded graph
@@ -726,6 +759,7 @@ struct UnitJobs {
     int64_t toff[9];            // prefix sums of tail_n
     UnitSelect sel;             // sel.pass != 0: a selection launch (uoff / toff are not read)
 };
+static_assert(sizeof(UnitJobs) <= 4096, "UnitJobs is passed by value: it must fit the 4 KB of kernel arguments");
 // the rescan jobs of njobs <= 2 results (scratch allocated), for k2b_fallback or the rescan half of k_grid_tail
 int rescan_jobs(pccm_ctx *ctx, int njobs, const Cloud *const *its, const Cloud *const *ses, NNResult *const *ress, bool self, RescanJobs *out);
 constexpr unsigned kRescanCap = 512;   // most workgroups that ever share one job's list (sizes the split regime's partials)

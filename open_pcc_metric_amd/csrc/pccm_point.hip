@@ -249,6 +249,8 @@ int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs)
 struct UnitView {               // the fields of a job the inner loop needs, in registers (wave-uniform)
     const double *val;
     int stride, off0, off1, sq0, sq1;
+    int map0, map1;             // UnitCol::map / cap of the two columns
+    double cap0, cap1;
     int defer;                  // UnitJob::defer
     int64_t nrm_rows;           // UnitJob::nrm_rows
     const double *nrm64;
@@ -297,6 +299,8 @@ __device__ __forceinline__ UnitView unit_view(const UnitJob &J)
     w.stride = J.stride;
     w.off0 = J.c[0].off; w.off1 = J.c[1].off;
     w.sq0 = J.c[0].square; w.sq1 = J.c[1].square;
+    w.map0 = J.c[0].map; w.map1 = J.c[1].map;
+    w.cap0 = J.c[0].cap; w.cap1 = J.c[1].cap;
     w.defer = J.defer; w.nrm64 = J.nrm64; w.nrm32 = J.nrm32; w.q32 = J.q32; w.row0 = J.row0; w.nrm_rows = J.nrm_rows;
     return w;
 }
@@ -314,6 +318,15 @@ __device__ __forceinline__ void unit_load(const UnitView &J, int64_t i, double v
     }
 }
 
+// f(value) of a mapped column: the clamp is np.minimum(value, cap) for the NaN-free columns the map is defined on, the root
+// the correctly rounded one (np.sqrt), in this order
+__device__ __forceinline__ double unit_map(int map, double cap, double v)
+{
+    if (map & PCCM_MAP_CLAMP) v = (v < cap) ? v : cap;
+    if (map & PCCM_MAP_ROOT) v = __dsqrt_rn(v);
+    return v;
+}
+
 __device__ __forceinline__ void unit_pick(const UnitView &J, double v[2])                 // fields -> the job's columns
 {
     if (J.stride >= 2) {
@@ -323,6 +336,12 @@ __device__ __forceinline__ void unit_pick(const UnitView &J, double v[2])       
     }
     if (J.sq0) v[0] = __dmul_rn(v[0], v[0]);
     if (J.sq1) v[1] = __dmul_rn(v[1], v[1]);
+    // the map mode (UnitCol::map): np.sum(f(column)) without the column.  Behind one wave-uniform branch on both columns' maps,
+    // so that a job without one -- every job but pccm_reduce_map_*'s -- passes with a single scalar test per value
+    if (J.map0 | J.map1) {
+        v[0] = unit_map(J.map0, J.cap0, v[0]);
+        v[1] = unit_map(J.map1, J.cap1, v[1]);
+    }
 }
 
 

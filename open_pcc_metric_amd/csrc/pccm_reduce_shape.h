@@ -8,7 +8,8 @@ namespace pccm {
 
 // stride: doubles per record (1: a plain column).  cfg: which fields feed the columns -- 0: two columns {field 0, field 1
 // squared} (D1 + D2 of a direction in one pass over its records), 1: field 0, 2: field 1 squared, 3: field 1 (the signed
-// projection), -1: anything else.  defer: UnitJob::defer (records of layout 1, stride 2).
+// projection), -1: anything else -- a job with a mapped column (UnitCol::map) among them: only the general kernel maps.
+// defer: UnitJob::defer (records of layout 1, stride 2).
 struct ReduceShape {
     int stride, cfg, defer;
 };
@@ -21,6 +22,7 @@ inline ReduceShape reduce_shape(const UnitJob &J)
     else if (J.ncols == 2) cfg = (J.c[0].off == 0 && !J.c[0].square && J.c[1].off == 1 && J.c[1].square) ? 0 : -1;
     else if (J.c[0].off == 0) cfg = J.c[0].square ? -1 : 1;
     else cfg = J.c[0].square ? 2 : 3;
+    if (J.c[0].map || (J.ncols == 2 && J.c[1].map)) cfg = -1;
     if (cfg < 0 || (J.stride != 1 && J.stride != 2 && J.stride != 4) || (J.defer && J.stride != 2)) return {0, -1, 0};
     return {J.stride, cfg, J.defer};
 }

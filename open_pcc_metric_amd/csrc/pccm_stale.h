@@ -9,7 +9,7 @@
 //
 // The counters.  Each is only ever compared for equality with a copy taken earlier; each counts one thing:
 //   nn_gen[d]  whatever a reduction, selection or count of direction d reads has changed: the result itself, or normals, features and
-//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, selections, counts), TieCols::gen, ColorMemo::gen.
+//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, mapped reductions, selections, counts), TieCols::gen, ColorMemo::gen.
 //   nn_run[d]  searches of direction d (prepare_nn alone bumps it): WHICH result the direction holds.  Copies: Carry::run_f / run_g.
 //   nrm_gen    any cloud's normals changed.  Copies: TieCols::nrm_gen / ang_gen.
 //   rgb_gen    any cloud's colours changed.  Copies: TieCols::rgb_gen, ColorMemo::rgb_gen.
@@ -46,6 +46,7 @@ inline void results_dropped(pccm_ctx *ctx)
     results_void(ctx, kDirsAll);
     for (auto &s : ctx->slots) s.pending = false;
     for (auto &q : ctx->sel_slots) q.pending = false;
+    for (auto &m : ctx->map_slots) m.pending = false;
 }
 
 // The rows this context owns of these directions changed (pccm_set_shard, pccm_set_shard_dir): captured searches carry the old ones

@@ -3,7 +3,8 @@
     python -m open_pcc_metric_amd --ocloud A.ply --pcloud B.ply [--pcloud C.ply ...] [--color rgb|ycc] [--hausdorff]
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
                                   [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
-                                  [--resolution-psnr] [--resolution-neighbours K] [--reflectance] [--reflectance-peak P] [--fscore TAU ...] [--csv]
+                                  [--resolution-psnr] [--resolution-neighbours K] [--reflectance] [--reflectance-peak P] [--fscore TAU ...]
+                                  [--chamfer] [--truncate TAU ...] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -47,7 +48,12 @@ squared difference between each point's reflectance and its matched point's, on 
 units; no counterpart in the reference) adds, after all others, the rows the reconstruction and completion literature reports beside
 the Chamfer distance: the share of the original cloud's points within TAU of the processed cloud (recall), the share of the
 processed cloud's points within TAU of the original (precision) and their harmonic mean, the F-score -- counted on the GPU, and at
-TAU = 0 the share of points reproduced exactly ("F-score").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+TAU = 0 the share of points reproduced exactly ("F-score").  ``--chamfer`` (no counterpart in the reference) adds,
+after those, the mean UNSQUARED nearest-neighbour distance of each direction (with ``--point-to-plane`` also the mean magnitude of
+the projection), Chamfer-L1 -- their average over the two directions, PCN's convention -- and Chamfer-L2, the sum of the two D1
+GeoMSE rows.  ``--truncate TAU`` (repeatable, TAU >= 0; no counterpart in the reference) adds, last, the mean squared distance with
+every distance clipped at TAU -- and with ``--chamfer`` the clipped mean distance --, the remedy for partly overlapping clouds; all
+of them are summed inside the reduction kernel, no column is stored ("Chamfer and truncated distances").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -112,6 +118,14 @@ import click
               help="Report precision, recall and F-score at this distance threshold (>= 0, in the clouds' units) as well (may be "
                    "repeated, at most 4), after all other rows: the share of each cloud's points within TAU of the other cloud "
                    "(left: recall, right: precision) and their harmonic mean; TAU = 0 counts the points reproduced exactly.")
+@click.option("--chamfer", "chamfer", required=False, is_flag=True,
+              help="Report the mean unsquared nearest-neighbour distance of each direction (with --point-to-plane also of the "
+                   "projection's magnitude), Chamfer-L1 (their average over both directions) and Chamfer-L2 (the sum of the two "
+                   "mean squared distances) as well, after all other rows.")
+@click.option("--truncate", "truncate", type=float, multiple=True, metavar="TAU",
+              help="Report the mean squared distance with every distance clipped at this threshold (>= 0, in the clouds' units) as "
+                   "well (may be repeated, at most 4), after all other rows; with --chamfer also the clipped mean distance.  For "
+                   "partly overlapping clouds.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -126,13 +140,13 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import (CalculateOptions, check_carry_normals, check_duplicates, check_fscore, check_hausdorff_rank, check_p2d_color, check_point_ssim,
-                          check_point_to_distribution, check_reflectance, check_resolution_psnr, transform_options)
+    from .options import (CalculateOptions, check_carry_normals, check_chamfer, check_duplicates, check_fscore, check_hausdorff_rank, check_p2d_color, check_point_ssim,
+                          check_point_to_distribution, check_reflectance, check_resolution_psnr, check_truncate, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
         options = CalculateOptions(color=color, hausdorff=hausdorff, point_to_plane=point_to_plane, plane_to_plane=plane_to_plane,
@@ -140,13 +154,16 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
                                    point_to_distribution=point_to_distribution, p2d_neighbours=p2d_neighbours,
                                    p2d_color=p2d_color, resolution_psnr=resolution_psnr,
                                    resolution_neighbours=resolution_neighbours, reflectance=reflectance,
-                                   reflectance_peak=reflectance_peak, fscore=fscore or None)
+                                   reflectance_peak=reflectance_peak, fscore=fscore or None, chamfer=chamfer,
+                                   truncate=truncate or None)
         check_carry_normals(carry_normals, ties=ties)
         check_duplicates(duplicates)
     except ValueError as exc:
         raise click.UsageError(str(exc))
     check_hausdorff_rank(options)
     check_fscore(options)
+    check_chamfer(options)
+    check_truncate(options)
     check_point_to_distribution(options)
     check_resolution_psnr(options)
     ocloud_cloud = read_point_cloud(ocloud)

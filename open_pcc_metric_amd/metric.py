@@ -49,7 +49,8 @@ class PrimaryMetric(AbstractMetric):                 # metric.py:32-38 -- reads 
 class SecondaryMetric(AbstractMetric):               # metric.py:41-50 -- pure function of its deps
     _pccm_role = 2
     _pccm_item = None       # what the calculator tells CloudPair.prefetch_reductions about this node: "column" (EuclideanDistance),
-    #                         "ranked" (GeoRankedHausdorffDistance), "within" (GeoInlierRatio); subclasses inherit it
+    #                         "ranked" (GeoRankedHausdorffDistance), "within" (GeoInlierRatio), "mapped" (GeoMeanDistance,
+    #                         GeoTruncatedMSE, GeoTruncatedMeanDistance: _mapped_request() says which map); subclasses inherit it
 
     def _get_dependencies(self) -> typing.Dict[str, "AbstractMetric"]:
         return {}
@@ -360,6 +361,84 @@ class GeoFScore(SecondaryMetric):                                # no counterpar
     def calculate(self, precision: GeoInlierRatio, recall: GeoInlierRatio) -> None:
         p, r = np.float64(precision.value), np.float64(recall.value)
         self.value = np.float64(0.0) if p + r == 0.0 else ((2.0 * p) * r) / (p + r)
+
+
+def _mapped_sum(column, root: bool, clamp):
+    """np.sum(f(column)), f = np.minimum(., clamp) (when given), then np.sqrt (when ``root``): in HBM for a device column."""
+    mapped = getattr(column, "mapped", None)
+    if mapped is not None:
+        return mapped(root=root, clamp=clamp)[0]
+    f = np.asarray(column, dtype=np.float64)
+    if clamp is not None:
+        f = np.minimum(f, clamp)
+    return np.sum(np.sqrt(f) if root else f)
+
+
+class GeoMeanDistance(_OverEuclidean):                           # no counterpart in the reference (options.py: chamfer)
+    """The mean UNSQUARED nearest-neighbour distance of one direction ("Chamfer and truncated distances"):
+    np.sum(np.sqrt(column)) / n over the D1 column, or -- point_to_plane -- over the D2 column, where the root of the squared
+    projection is its magnitude."""
+    _pccm_waits = True      # reads a mapped reduction back from the GPU: the calculator evaluates these last
+    _pccm_item = "mapped"
+
+    def _mapped_request(self):
+        return self.is_left, self.point_to_plane, True, None
+
+    def calculate(self, euclidean_distance: EuclideanDistance) -> None:
+        column = euclidean_distance.value
+        self.value = _mapped_sum(column, True, None) / column.shape[0]
+
+
+class GeoChamferL1(SecondaryMetric):                             # no counterpart in the reference (options.py: chamfer)
+    """Chamfer-L1 in PCN's convention (Yuan et al., 3DV 2018): the average of the two directions' mean unsquared distances."""
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"left": GeoMeanDistance(is_left=True, point_to_plane=False), "right": GeoMeanDistance(is_left=False, point_to_plane=False)}
+
+    def calculate(self, left: GeoMeanDistance, right: GeoMeanDistance) -> None:
+        self.value = (np.float64(left.value) + np.float64(right.value)) / np.float64(2)
+
+
+class GeoChamferL2(SecondaryMetric):                             # no counterpart in the reference (options.py: chamfer)
+    """Chamfer-L2: the sum of the two directions' mean squared distances, the report's GeoMSE rows (D1)."""
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"left": GeoMSE(is_left=True, point_to_plane=False), "right": GeoMSE(is_left=False, point_to_plane=False)}
+
+    def calculate(self, left: GeoMSE, right: GeoMSE) -> None:
+        self.value = np.float64(left.value) + np.float64(right.value)
+
+
+class GeoTruncatedMSE(SecondaryMetric, DirectionalMetric):       # no counterpart in the reference (options.py: truncate)
+    """The mean squared nearest-neighbour distance of one direction with every distance clipped at ``threshold``:
+    np.sum(np.minimum(column, threshold * threshold)) / n over the D1 column -- the remedy for partly overlapping clouds, whose
+    points without a counterpart otherwise dominate the mean."""
+    _pccm_waits = True      # reads a mapped reduction back from the GPU: the calculator evaluates these last
+    _pccm_item = "mapped"
+    _root = False
+
+    def __init__(self, is_left: bool, threshold: float):
+        super().__init__(is_left)
+        self.threshold = float(threshold)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.threshold)
+
+    def _cap(self):
+        return np.float64(self.threshold) * np.float64(self.threshold)
+
+    def _mapped_request(self):
+        return self.is_left, False, self._root, float(self._cap())
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"euclidean_distance": EuclideanDistance(is_left=self.is_left, point_to_plane=False)}
+
+    def calculate(self, euclidean_distance: EuclideanDistance) -> None:
+        column = euclidean_distance.value
+        self.value = _mapped_sum(column, self._root, self._cap()) / column.shape[0]
+
+
+class GeoTruncatedMeanDistance(GeoTruncatedMSE):                 # no counterpart in the reference (options.py: chamfer + truncate)
+    """... and the mean unsquared distance clipped at ``threshold``: np.sum(np.sqrt(np.minimum(column, threshold * threshold))) / n."""
+    _root = True
 
 
 class _OverAngular(SecondaryMetric, DirectionalMetric):

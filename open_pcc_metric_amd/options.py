@@ -64,6 +64,19 @@ above, for each threshold in ascending order:
 
   threshold tau                GeoInlierRatio L (recall), GeoInlierRatio R (precision), GeoFScore (no symmetric row: the F-score is it)
 
+and, with ``chamfer`` (no counterpart in the reference: the Chamfer distance of the reconstruction and completion literature, Fan
+et al., CVPR 2017; Chamfer-L1 in the convention of PCN, Yuan et al., 3DV 2018), after every row above, F-score rows included:
+
+  chamfer                      GeoMeanDistance L/R/sym (D1: the mean UNSQUARED nearest-neighbour distance)
+  chamfer & p2plane            GeoMeanDistance L/R/sym with point_to_plane=True (the mean magnitude of the projection)
+  chamfer                      GeoChamferL1 ((L + R) / 2 of the D1 sides), GeoChamferL2 (GeoMSE L + GeoMSE R, D1)
+
+and, with ``truncate`` (no counterpart in the reference: the truncated -- clipped -- mean for partly overlapping clouds, whose
+points without a counterpart otherwise dominate every mean), after every row above, for each threshold in ascending order:
+
+  threshold tau                GeoTruncatedMSE L/R/sym (D1: the mean of min(d^2, tau^2))
+  threshold tau & chamfer      GeoTruncatedMeanDistance L/R/sym (D1: the mean of min(d, tau))
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -75,7 +88,7 @@ import math
 import numbers
 
 from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
-                     GeoFScore, GeoInlierRatio, GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
+                     GeoChamferL1, GeoChamferL2, GeoMeanDistance, GeoTruncatedMeanDistance, GeoTruncatedMSE, GeoFScore, GeoInlierRatio, GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
                      GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
                      JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
                      MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
@@ -85,6 +98,7 @@ SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row ord
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
 MAX_HAUSDORFF_RANKS = 4
 MAX_FSCORE_THRESHOLDS = 4
+MAX_TRUNCATE_THRESHOLDS = 4
 P2D_MIN_K, P2D_MAX_K = 4, 64
 RESOLUTION_MIN_K, RESOLUTION_MAX_K = 1, 63
 
@@ -109,24 +123,33 @@ def _hausdorff_ranks(value) -> typing.Tuple[float, ...]:
     return tuple(sorted(ranks))
 
 
-def _fscore_thresholds(value) -> typing.Tuple[float, ...]:
-    """``fscore`` as a sorted tuple of distinct finite floats >= 0; ValueError for anything else."""
+def _distance_thresholds(value, name: str, most: int) -> typing.Tuple[float, ...]:
+    """A distance-threshold option (``fscore``, ``truncate``) as a sorted tuple of distinct finite floats >= 0; ValueError for
+    anything else."""
     if value is None:
         return ()
     if isinstance(value, (str, bytes)):
-        raise ValueError(f"fscore must be a number or an iterable of numbers >= 0, not {value!r}")
+        raise ValueError(f"{name} must be a number or an iterable of numbers >= 0, not {value!r}")
     items = [value] if isinstance(value, numbers.Real) else list(value) if hasattr(value, "__iter__") else [value]
     thresholds = set()
     for t in items:
         if isinstance(t, (bool,)) or type(t).__name__ == "bool_" or not isinstance(t, numbers.Real):
-            raise ValueError(f"fscore: {t!r} is not a finite number >= 0")
+            raise ValueError(f"{name}: {t!r} is not a finite number >= 0")
         f = float(t)
         if not math.isfinite(f) or f < 0.0:
-            raise ValueError(f"fscore: {t!r} is not a finite number >= 0")
+            raise ValueError(f"{name}: {t!r} is not a finite number >= 0")
         thresholds.add(f + 0.0)                               # (-0.0 is the threshold 0.0)
-    if len(thresholds) > MAX_FSCORE_THRESHOLDS:
-        raise ValueError(f"fscore: at most {MAX_FSCORE_THRESHOLDS} thresholds per report, not {len(thresholds)}")
+    if len(thresholds) > most:
+        raise ValueError(f"{name}: at most {most} thresholds per report, not {len(thresholds)}")
     return tuple(sorted(thresholds))
+
+
+def _fscore_thresholds(value) -> typing.Tuple[float, ...]:
+    return _distance_thresholds(value, "fscore", MAX_FSCORE_THRESHOLDS)
+
+
+def _truncate_thresholds(value) -> typing.Tuple[float, ...]:
+    return _distance_thresholds(value, "truncate", MAX_TRUNCATE_THRESHOLDS)
 
 
 class CalculateOptions:
@@ -135,7 +158,8 @@ class CalculateOptions:
                  point_ssim: typing.Optional[typing.Iterable[str]] = None, ssim_neighbours: int = 12,
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
                  p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10,
-                 reflectance: bool = False, reflectance_peak: float = 65535.0, fscore=None):
+                 reflectance: bool = False, reflectance_peak: float = 65535.0, fscore=None, chamfer: bool = False,
+                 truncate=None):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -174,6 +198,8 @@ class CalculateOptions:
         self.reflectance = bool(reflectance)
         self.reflectance_peak = float(peak)
         self.fscore = _fscore_thresholds(fscore)
+        self.chamfer = bool(chamfer)
+        self.truncate = _truncate_thresholds(truncate)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -209,6 +235,20 @@ def check_fscore(options: CalculateOptions, *, group=None) -> None:
     would have to add its ranks' counts up: not built."""
     if getattr(options, "fscore", ()) and group is not None:
         raise ValueError("F-score rows are not available for sharded pairs (group=)")
+
+
+def check_chamfer(options: CalculateOptions, *, group=None) -> None:
+    """Raise ``ValueError`` when the Chamfer rows ``options`` asks for cannot be computed for this pair -- before any GPU work (the
+    command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).  A sharded pair
+    would have to exchange the mapped leaves across its ranks: not built."""
+    if getattr(options, "chamfer", False) and group is not None:
+        raise ValueError("Chamfer and truncated-distance rows are not available for sharded pairs (group=)")
+
+
+def check_truncate(options: CalculateOptions, *, group=None) -> None:
+    """... and likewise for the truncated-distance rows."""
+    if getattr(options, "truncate", ()) and group is not None:
+        raise ValueError("Chamfer and truncated-distance rows are not available for sharded pairs (group=)")
 
 
 def check_point_to_distribution(options: CalculateOptions, *, group=None) -> None:
@@ -351,4 +391,13 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
     for threshold in getattr(options, "fscore", None) or ():
         # left: recall (how much of the origin cloud the processed one covers); right: precision; the F-score is the symmetric row
         metrics += _sides(GeoInlierRatio, threshold=threshold) + [GeoFScore(threshold=threshold)]
+    chamfer = bool(getattr(options, "chamfer", False))
+    if chamfer:
+        # lower is better: the symmetric rows report the larger side
+        for point_to_plane in (False, True) if options.point_to_plane else (False,):
+            metrics += _sides(GeoMeanDistance, point_to_plane=point_to_plane) + [_sym(GeoMeanDistance, False, point_to_plane=point_to_plane)]
+        metrics += [GeoChamferL1(), GeoChamferL2()]
+    for threshold in getattr(options, "truncate", None) or ():
+        for cls in (GeoTruncatedMSE, GeoTruncatedMeanDistance) if chamfer else (GeoTruncatedMSE,):
+            metrics += _sides(cls, threshold=threshold) + [_sym(cls, False, threshold=threshold)]
     return metrics
