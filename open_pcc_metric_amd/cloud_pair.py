@@ -687,65 +687,50 @@ class CloudPair:
                 self._totals[key] = eng.reduce_total(direction, metric, self.normal_index)
         return self._totals[key]
 
-    def _check_ranked(self) -> None:
-        """options.check_hausdorff_rank for this pair: ValueError before any GPU work of a report."""
+    def _check_unsharded(self, rows: str) -> None:
+        """``rows`` read whole columns on one GPU: ValueError before any GPU work of a report for a sharded pair."""
         if self._coll.sharded:
-            raise ValueError("ranked Hausdorff rows are not available for sharded pairs (group=)")
+            raise ValueError(f"{rows} rows are not available for sharded pairs (group=)")
 
-    def _selected(self, direction: int, metric: int, k: int):
-        """The k-th smallest element of a whole D1 / D2 column, selected on the GPU.  The first selection a report asks for
-        brings every selection the report enqueued (prefetch_reductions) back in one call per eight.  None: this engine has no
-        selection (a test double): the caller ranks the materialised column."""
-        self._check_ranked()
-        eng = self._engine
-        if not hasattr(eng, "select_many"):
-            return None
-        key = (direction, metric, k)
-        if key not in self._selections:
-            batch = next((b for b in _selection_batches(self._sel_wanted) if key in b), [key])
-            for q, v in zip(batch, eng.select_many(batch, self.normal_index)):
-                self._selections[q] = v
-        return self._selections[key]
+    def _check_ranked(self) -> None:
+        """options.check_hausdorff_rank for this pair."""
+        self._check_unsharded("ranked Hausdorff")
 
     def _check_fscore(self) -> None:
-        """options.check_fscore for this pair: ValueError before any GPU work of a report."""
-        if self._coll.sharded:
-            raise ValueError("F-score rows are not available for sharded pairs (group=)")
-
-    def _counted(self, direction: int, metric: int, x: float):
-        """The number of rows ``<= x`` of a whole D1 / D2 column, counted on the GPU.  The first count a report asks for brings
-        every count the report enqueued (prefetch_reductions) back in one call per eight.  None: this engine has no count (a
-        test double): the caller counts the materialised column."""
-        self._check_fscore()
-        eng = self._engine
-        if not hasattr(eng, "count_many"):
-            return None
-        key = (direction, metric, x)
-        if key not in self._counts:
-            batch = next((b for b in _selection_batches(self._cnt_wanted) if key in b), [key])
-            for q, v in zip(batch, eng.count_many(batch, self.normal_index)):
-                self._counts[q] = v
-        return self._counts[key]
+        """options.check_fscore for this pair."""
+        self._check_unsharded("F-score")
 
     def _check_mapped(self) -> None:
-        """options.check_chamfer / check_truncate for this pair: ValueError before any GPU work of a report."""
-        if self._coll.sharded:
-            raise ValueError("Chamfer and truncated-distance rows are not available for sharded pairs (group=)")
+        """options.check_chamfer / check_truncate for this pair."""
+        self._check_unsharded("Chamfer and truncated-distance")
+
+    def _consumed(self, key, cache: dict, wanted, batches, method: str):
+        """The answer to request ``key`` from the engine's ``method``, through ``cache``.  The first request a report asks for
+        brings back the batch of eight (``batches(wanted)``) it was enqueued in (prefetch_reductions) in one call.  None: this
+        engine has no such method (a test double): the caller works on the materialised column."""
+        consume = getattr(self._engine, method, None)
+        if consume is None:
+            return None
+        if key not in cache:
+            batch = next((b for b in batches(wanted) if key in b), [key])
+            cache.update(zip(batch, consume(batch, self.normal_index)))
+        return cache[key]
+
+    def _selected(self, direction: int, metric: int, k: int):
+        """The k-th smallest element of a whole D1 / D2 column, selected on the GPU."""
+        self._check_ranked()
+        return self._consumed((direction, metric, k), self._selections, self._sel_wanted, _selection_batches, "select_many")
+
+    def _counted(self, direction: int, metric: int, x: float):
+        """The number of rows ``<= x`` of a whole D1 / D2 column, counted on the GPU."""
+        self._check_fscore()
+        return self._consumed((direction, metric, x), self._counts, self._cnt_wanted, _selection_batches, "count_many")
 
     def _mapped(self, direction: int, metric: int, which: int, x: float):
         """``(sum, min, max)`` of f(column) for a whole D1 / D2 column, mapped and reduced on the GPU (``which``: nat.MAP_*, ``x``:
-        the clamp).  The first one a report asks for brings back the batch of eight it was enqueued in (prefetch_reductions).
-        None: this engine has no mapped reduction (a test double): the caller maps the materialised column."""
+        the clamp)."""
         self._check_mapped()
-        eng = self._engine
-        if not hasattr(eng, "reduce_map_total_many"):
-            return None
-        key = (direction, metric, which, x)
-        if key not in self._maps:
-            batch = next((b for b in _map_batches(self._map_wanted) if key in b), [key])
-            for q, v in zip(batch, eng.reduce_map_total_many(batch, self.normal_index)):
-                self._maps[q] = v
-        return self._maps[key]
+        return self._consumed((direction, metric, which, x), self._maps, self._map_wanted, _map_batches, "reduce_map_total_many")
 
     def tie_exposure(self, is_left: bool = True, point_to_plane: bool = True) -> dict:
         """Opt-in diagnostic (not part of any report): how far the order of EXACT ties can move the point-to-plane MSE.

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <new>
 #include <thread>
+#include <type_traits>
 
 #include "pccm_stale.h"
 
@@ -379,7 +380,7 @@ int pccm_ctx_create(int device, void *hip_stream, pccm_ctx **out)
         ctx->own_stream = true;
     }
     int rc = ensure(ctx, ctx->counters, 16 * sizeof(uint32_t));      // [0..5] per-direction counters, [8..11] rescan tickets, [12..15] tail-launch counts
-    // host-coherent: the host may read it on the completion counter's word alone (wait_slot), with no end-of-stream flush
+    // host-coherent: the host may read it on the completion counter's word alone (wait_batch), with no end-of-stream flush
     if (!rc && hipHostMalloc((void **)&ctx->host_err, 64, hipHostMallocCoherent) != hipSuccess) {
         ctx->host_err = nullptr;
         rc = fail(PCCM_E_OOM, "hipHostMalloc of the device error word failed");
@@ -444,14 +445,11 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
     for (auto &g : ctx->graphs) graph_free(g);
-    for (auto &s : ctx->slots) {
-        free_buf(s.val);
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.ev) (void)hipEventDestroy(s.ev);
-        s.ev = s.wait_ev = nullptr;
-    }
-    for (auto &m : ctx->map_slots)
-        if (m.host) (void)hipHostFree(m.host);
+    for (auto &s : ctx->slots) free_buf(s.val);
+    for_each_slot(ctx, [](auto &s) {
+        if constexpr (std::is_base_of_v<SlotHost, std::remove_reference_t<decltype(s)>>)
+            if (s.host) (void)hipHostFree(s.host);
+    });
     grid_release(ctx);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     for (auto &pbuf : ctx->pin)
@@ -1781,7 +1779,125 @@ static int wait_batch(pccm_ctx *ctx, uint64_t want, hipEvent_t wait_ev)
     return PCCM_OK;
 }
 
-static int wait_slot(pccm_ctx *ctx, const ReduceSlot *s) { return wait_batch(ctx, s->wait_seq, s->wait_ev); }
+// ---- one life cycle for the slots of every table ("A reduction slot") --------------------------------------------
+extern "C++" {       // (templates)
+// The slots a call takes for its new requests.  It acquires a slot, describes the request in it and marks it pending before it
+// acquires the next (pick_free and find_pending then see it while the batch is assembled); finish() follows the last launch.
+template <class Slot, size_t N>
+struct SlotBatch {
+    pccm_ctx *ctx;
+    Slot (&table)[N];
+    Slot *fresh[8] = {};
+    int nfresh = 0;
+    SlotBatch(pccm_ctx *c, Slot (&t)[N]) : ctx(c), table(t) {}
+
+    // a slot for a new request, idle; a pending one of another call is waited for first (its kernels may still write its host outputs)
+    int acquire(const char *none_free, Slot **out)
+    {
+        Slot *s = pick_free(table, fresh, nfresh, ctx->nn_gen);
+        if (!s) return fail(PCCM_E_STATE, "%s", none_free);
+        int rc = s->pending && !ctx->capturing && s->wait_ev ? wait_batch(ctx, s->wait_seq, s->wait_ev) : PCCM_OK;
+        if (rc) return rc;
+        s->pending = false;
+        fresh[nfresh++] = s;
+        *out = s;
+        return PCCM_OK;
+    }
+
+    // seq: the batch's count on the completion counter (while capturing: its ordinal in the captured sequence).  Eagerly one record
+    // of the batch event serves every slot; a capture keeps the slots' snapshots, and whoever launches the graph arms them (rearm).
+    int finish(uint64_t seq)
+    {
+        for (int k = 0; k < nfresh; ++k) {
+            Slot &s = *fresh[k];
+            s.wait_seq = seq;
+            s.wait_ev = ctx->capturing ? nullptr : ctx->batch_ev;
+            if (!ctx->capturing) continue;
+            GraphOp op;
+            op.slot = (int)(&s - table);
+            op.snap = snapshot(s);
+            op.kind = 2 + (int)op.snap.index();
+            ctx->cap_ops.push_back(op);
+        }
+        if (!ctx->capturing) PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
+        return PCCM_OK;
+    }
+};
+
+// A captured batch runs again: its slot takes the snapshot's description back, for the generation its direction has by now.
+template <class Slot>
+static int slot_replay(pccm_ctx *ctx, Slot &s, const SlotSnap<typename Slot::What> &snap)
+{
+    const bool in_use = s.pending && s.gen == ctx->nn_gen[s.dir] && s.wait_ev;       // by someone else, still
+    int rc = in_use ? wait_batch(ctx, s.wait_seq, s.wait_ev) : PCCM_OK;
+    if (rc) return rc;
+    restore(s, snap);
+    s.gen = ctx->nn_gen[s.dir];
+    s.pending = true;
+    rearm(s, ctx, snap.key.wait_seq);
+    return PCCM_OK;
+}
+
+// Consume n <= 8 requests: find(i) is request i's pending slot (null: `lost`), read(i, slot) takes its numbers once they are on
+// the host.  The slots stay pending until every request is read.
+template <class Find, class Read>
+static int consume(pccm_ctx *ctx, int n, const char *lost, Find find, Read read)
+{
+    decltype(find(0)) got[8];
+    for (int i = 0; i < n; ++i) {
+        auto *s = find(i);
+        if (!s) return fail(PCCM_E_STATE, "%s", lost);
+        int rc = wait_batch(ctx, s->wait_seq, s->wait_ev);
+        if (!rc) rc = check_device_errors(ctx);
+        if (rc) return rc;
+        read(i, *s);
+        got[i] = s;
+    }
+    for (int i = 0; i < n; ++i) got[i]->pending = false;
+    return PCCM_OK;
+}
+
+// What selections, counts and mapped reductions (`what`) ask of their requests alike: 1..8 of them with every array there
+// (`arrays`), the whole columns on this GPU, directions 0 and 1, D1 / D2 columns, a search behind each.  Request i's own key is
+// checked by key_first(i) before the search is asked for, and by key_last(i, iterating cloud) behind it.
+template <class KeyFirst, class KeyLast>
+static int request_check(pccm_ctx *ctx, const char *who, const char *what, int n, bool arrays, const int *dirs, const int *metrics,
+                         KeyFirst key_first, KeyLast key_last)
+{
+    if (n < 0 || n > 8 || (n > 0 && !arrays)) return fail(PCCM_E_ARG, "1..8 requests expected");
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "%s needs the whole columns on this GPU (world = 1)", who);
+    for (int i = 0; i < n; ++i) {
+        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "%s read directions 0 and 1, not %d", what, dirs[i]);
+        if (metrics[i] != PCCM_METRIC_D1 && metrics[i] != PCCM_METRIC_D2)
+            return fail(PCCM_E_ARG, "%s read PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", what, metrics[i]);
+        const Cloud *it, *se;
+        NNResult *res;
+        int rc = key_first(i);
+        if (!rc) rc = need_nn(ctx, dirs[i], &it, &se, &res);
+        if (!rc) rc = key_last(i, *it);
+        if (rc) return rc;
+    }
+    return PCCM_OK;
+}
+}  // extern "C++"
+
+// A slot's pinned host block holds `doubles` doubles at least.  Growing it moves what a captured graph writes to: captured graphs
+// go stale, and a capture in progress fails with `while_capturing`.
+static int host_reserve(pccm_ctx *ctx, SlotHost &h, int64_t doubles, const char *while_capturing)
+{
+    const size_t need = (size_t)doubles * sizeof(double);
+    if (need <= h.host_cap) return PCCM_OK;
+    if (ctx->capturing) {
+        ctx->capture_failed = true;
+        return fail(PCCM_E_STATE, "%s", while_capturing);
+    }
+    ctx->epoch++;
+    if (h.host) (void)hipHostFree(h.host);
+    h.host = nullptr; h.host_cap = 0;
+    PCCM_HIP(hipHostMalloc((void **)&h.host, need, hipHostMallocCoherent));   // no XCD's L2 keeps any of it (wait_batch)
+    h.host_cap = need;
+    return PCCM_OK;
+}
 
 // Where a reduction column is read from (given the form and tie policy of the direction's search), and what has to happen before
 // it can be bound.  slot_prepare binds from the first answer; prefetch_many acts on the second for every request before binding
@@ -1881,19 +1997,8 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     static_cast<SlotShape &>(s) = slot_shape(it->n, res->begin, res->end);
     s.has_units = want_units;
     s.has_job = false;
-    const size_t need = (size_t)s.host_doubles() * sizeof(double);
-    if (ctx->capturing && (need > s.host_cap || !s.ev)) {
-        ctx->capture_failed = true;
-        return fail(PCCM_E_STATE, "a reduction slot must be allocated during graph capture: run the sequence once first");
-    }
-    if (need > s.host_cap) {
-        ctx->epoch++;
-        if (s.host) (void)hipHostFree(s.host);
-        s.host = nullptr; s.host_cap = 0;
-        PCCM_HIP(hipHostMalloc((void **)&s.host, need, hipHostMallocCoherent));   // no XCD's L2 keeps any of it (wait_slot)
-        s.host_cap = need;
-    }
-    if (!s.ev) PCCM_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if ((rc = host_reserve(ctx, s, s.host_doubles(), "a reduction slot must be allocated during graph capture: run the sequence once first")))
+        return rc;
     if (s.nunits > 0) {
         UnitCol col;
         col.off = src.off;
@@ -1933,13 +2038,6 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
     return PCCM_OK;
 }
 
-static ReduceSlot *slot_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, bool need_units = false)
-{
-    for (auto &s : ctx->slots)
-        if (s.matches(dir, metric, normal_mode, ctx->nn_gen[dir], need_units)) return &s;
-    return nullptr;
-}
-
 static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, bool want_units);
 
 int pccm_reduce_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes)
@@ -1967,8 +2065,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     uj.njobs = 0; uj.uoff[0] = 0; uj.toff[0] = 0;
     for (int k = 0; k < n; ++k)
         if (dirs[k] < 0 || dirs[k] > 2) return fail(PCCM_E_ARG, "bad direction %d", dirs[k]);
-    ReduceSlot *fresh[8];
-    int nfresh = 0;
+    SlotBatch batch(ctx, ctx->slots);
     // first, whatever may change the layout of a direction's result records: a column that needs the plain columns before
     // the batch is bound (column_source) gets them now -- when the search left the matched rows out it is repeated
     // (ensure_plain), with the rows, and with the projection fused when the normals have arrived meanwhile.  Only then are the
@@ -1983,7 +2080,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         else if (normal_mode_enters(metrics[k]) && normal_modes[k] == PCCM_NORMAL_NEIGHBOUR) tie_nrm[dirs[k]] = true;
     }
     for (int d = 0; d < 2; ++d) {
-        if (!tie_ang[d] || slot_find(ctx, d, PCCM_METRIC_ANGULAR, 0, want_units)) continue;
+        if (!tie_ang[d] || find_pending(ctx->slots, ctx->nn_gen, d, PCCM_METRIC_ANGULAR, 0, want_units)) continue;
         const Cloud *it, *se;
         NNResult *res;
         int rc = need_nn(ctx, d, &it, &se, &res);
@@ -1994,7 +2091,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     }
     for (int k = 0; k < n; ++k) {
         if (column_source(ctx, dirs[k], metrics[k], normal_modes[k]).prep != ColumnSource::kPlainFirst ||
-            slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units))
+            find_pending(ctx->slots, ctx->nn_gen, dirs[k], metrics[k], normal_modes[k], want_units))
             continue;
         int rc = ensure_plain(ctx, ctx->nn[dirs[k]], true);
         if (rc) return rc;
@@ -2002,17 +2099,14 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     const int path_kept = ctx->path_n[3];
     PathScope path(ctx, 1u << 3);          // the batch's kernels: per-point columns (slot_prepare), point and unit jobs
     for (int k = 0; k < n; ++k) {
-        if (slot_find(ctx, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
-        ReduceSlot *s = pick_free(ctx->slots, fresh, nfresh, ctx->nn_gen);
-        if (!s) return fail(PCCM_E_STATE, "no free reduction slot: more than 24 live columns in one batch");
-        if (s->pending && !ctx->capturing && s->wait_ev) { int rcw = wait_slot(ctx, s); if (rcw) return rcw; }
-        s->pending = false;
-        int rc = slot_prepare(ctx, *s, dirs[k], metrics[k], normal_modes[k], want_units, pj, uj);
+        if (find_pending(ctx->slots, ctx->nn_gen, dirs[k], metrics[k], normal_modes[k], want_units)) continue;
+        ReduceSlot *s;
+        int rc = batch.acquire("no free reduction slot: more than 24 live columns in one batch", &s);
+        if (!rc) rc = slot_prepare(ctx, *s, dirs[k], metrics[k], normal_modes[k], want_units, pj, uj);
         if (rc) return rc;
-        s->pending = true;                 // so that pick_free/slot_find see it while the batch is assembled
-        fresh[nfresh++] = s;
+        s->pending = true;
     }
-    if (nfresh == 0) {
+    if (batch.nfresh == 0) {
         ctx->path_n[3] = path_kept;        // no batch: the log still describes the last one
         return PCCM_OK;
     }
@@ -2020,22 +2114,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
     if ((rc = launch_point_jobs(ctx, pj))) return rc;
     uint64_t seq = 0;
     if ((rc = launch_unit_jobs(ctx, uj, &seq))) return rc;
-    for (int k = 0; k < nfresh; ++k) {
-        ReduceSlot &s = *fresh[k];
-        s.wait_seq = seq;                  // (while capturing: the batch's ordinal in the captured sequence)
-        if (ctx->capturing) {
-            GraphOp op;
-            op.kind = 2;
-            op.dir = s.dir;
-            op.slot = (int)(&s - ctx->slots);
-            op.snap = snapshot(s);
-            ctx->cap_ops.push_back(op);
-        } else {
-            s.wait_ev = ctx->batch_ev;
-        }
-    }
-    if (!ctx->capturing) PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));      // one record for the whole batch
-    return PCCM_OK;
+    return batch.finish(seq);
 }
 
 int pccm_reduce_prefetch(pccm_ctx *ctx, int dir, int metric, int normal_mode)
@@ -2047,19 +2126,12 @@ int pccm_reduce_prefetch(pccm_ctx *ctx, int dir, int metric, int normal_mode)
 static int take_slot(pccm_ctx *ctx, int dir, int metric, int normal_mode, bool units, ReduceSlot **out)
 {
     if (dir < 0 || dir > 2) return fail(PCCM_E_ARG, "bad direction %d", dir);
-    ReduceSlot *s = slot_find(ctx, dir, metric, normal_mode, units);
-    if (!s) {
+    auto find = [&](int) { return find_pending(ctx->slots, ctx->nn_gen, dir, metric, normal_mode, units); };
+    if (!find(0)) {
         int rc = prefetch_many(ctx, 1, &dir, &metric, &normal_mode, units);
         if (rc) return rc;
-        s = slot_find(ctx, dir, metric, normal_mode, units);
-        if (!s) return fail(PCCM_E_STATE, "reduction slot lost");
     }
-    int rc = wait_slot(ctx, s);
-    if (!rc) rc = check_device_errors(ctx);
-    if (rc) return rc;
-    s->pending = false;
-    *out = s;
-    return PCCM_OK;
+    return consume(ctx, 1, "reduction slot lost", find, [&](int, ReduceSlot &s) { *out = &s; });
 }
 
 int pccm_reduce(pccm_ctx *ctx, int dir, int metric, int normal_mode, double *xvec, double *minmax)
@@ -2151,94 +2223,77 @@ int pccm_reduce_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *met
     return PCCM_OK;
 }
 
-// ---- selections and counts: the k-th smallest element of a column, the rows of a column <= x (include/pccm.h) ---------------
-// One slot table, one enqueue path: a request is (kind, column, key) -- the key a selection's rank or the bit pattern of a count's
-// threshold -- and the two differ in the check of the key, the launches and the type of the host word.
-static SelectSlot *sel_find(pccm_ctx *ctx, int kind, int dir, int metric, int normal_mode, int64_t k)
+// The plain reductions of the columns that a call's new selections, counts or mapped reductions read, enqueued in one batch where
+// none is pending, and their slots: a column is read as its reduction's job describes it (need_job: a column without rows won't do).
+static int column_slots(pccm_ctx *ctx, const RequestGroups &g, bool need_job, const ReduceSlot **cslot)
 {
-    for (auto &q : ctx->sel_slots)
-        if (q.matches(dir, metric, normal_mode, ctx->nn_gen[dir], k, kind)) return &q;
-    return nullptr;
-}
-
-static int select_check(pccm_ctx *ctx, int kind, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes,
-                        const int64_t *ks)
-{
-    const char *what = kind == kSlotCount ? "counts" : "selections";
-    if (n < 0 || n > kSelMax || (n > 0 && (!dirs || !metrics || !normal_modes || !ks))) return fail(PCCM_E_ARG, "1..8 requests expected");
-    if (ctx->sharded()) return fail(PCCM_E_STATE, "%s needs the whole columns on this GPU (world = 1)", who);
-    for (int i = 0; i < n; ++i) {
-        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "%s read directions 0 and 1, not %d", what, dirs[i]);
-        if (metrics[i] != PCCM_METRIC_D1 && metrics[i] != PCCM_METRIC_D2)
-            return fail(PCCM_E_ARG, "%s read PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", what, metrics[i]);
-        const Cloud *it, *se;
-        NNResult *res;
-        int rc = need_nn(ctx, dirs[i], &it, &se, &res);
-        if (rc) return rc;
-        if (it->n >= ((int64_t)1 << 32)) return fail(PCCM_E_ARG, "%s count rows in 32 bits: columns of 2^32 rows or more are not supported", what);
-        if (kind == kSlotCount) {
-            double x;
-            memcpy(&x, &ks[i], sizeof x);
-            if (x != x) return fail(PCCM_E_ARG, "a count's threshold is a number or an infinity, not NaN");
-        } else if (ks[i] < 1 || ks[i] > it->n) {
-            return fail(PCCM_E_ARG, "rank %lld outside 1..%lld", (long long)ks[i], (long long)it->n);
-        }
+    int rc = prefetch_many(ctx, g.ncols, g.dir, g.metric, g.mode, false);
+    if (rc) return rc;
+    for (int c = 0; c < g.ncols; ++c) {
+        cslot[c] = find_pending(ctx->slots, ctx->nn_gen, g.dir[c], g.metric[c], g.mode[c]);
+        if (!cslot[c] || (need_job && !cslot[c]->has_job)) return fail(PCCM_E_STATE, "reduction slot lost");
     }
     return PCCM_OK;
 }
 
-static int select_prefetch(pccm_ctx *ctx, int kind, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
+// ---- selections and counts: the k-th smallest element of a column, the rows of a column <= x (include/pccm.h) ---------------
+// One slot table, one enqueue path: a request is (kind, column, key) -- the key a selection's rank or the bit pattern of a count's
+// threshold -- and the two differ in the check of the key, the launches and the type of the host word.
+static int select_check(pccm_ctx *ctx, int kind, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes,
+                        const int64_t *ks)
 {
-    // what is not enqueued yet, by column; a column's reduction is enqueued first when nobody has: the selection ranks (the
-    // count reads) the column as that reduction's job describes it
-    int todo[kSelMax], ntodo = 0, cd[kSelMax], cm[kSelMax], cmode[kSelMax], col_of[kSelMax], ncols = 0;
-    for (int i = 0; i < n; ++i) {
-        if (sel_find(ctx, kind, dirs[i], metrics[i], normal_modes[i], ks[i])) continue;
-        bool dup = false;
-        for (int j = 0; j < ntodo; ++j)
-            dup = dup || (dirs[todo[j]] == dirs[i] && metrics[todo[j]] == metrics[i] && ks[todo[j]] == ks[i] &&
-                          (metrics[i] == PCCM_METRIC_D1 || normal_modes[todo[j]] == normal_modes[i]));
-        if (dup) continue;
-        int c = 0;
-        while (c < ncols && !(cd[c] == dirs[i] && cm[c] == metrics[i] && (metrics[i] == PCCM_METRIC_D1 || cmode[c] == normal_modes[i]))) ++c;
-        if (c == ncols) { cd[c] = dirs[i]; cm[c] = metrics[i]; cmode[c] = normal_modes[i]; ncols++; }
-        col_of[ntodo] = c;
-        todo[ntodo++] = i;
-    }
-    if (ntodo == 0) return PCCM_OK;
-    int rc = ensure(ctx, ctx->sel_hist, (size_t)kSelPasses * kSelMax * kSelBins * sizeof(uint32_t));
-    if (!rc) rc = ensure(ctx, ctx->sel_state, (size_t)kSelPasses * kSelMax * sizeof(SelState));
-    if (!rc) rc = prefetch_many(ctx, ncols, cd, cm, cmode, false);
+    static_assert(kSelMax == 8, "the slot batches hold eight requests");
+    const char *what = kind == kSlotCount ? "counts" : "selections";
+    return request_check(ctx, who, what, n, dirs && metrics && normal_modes && ks, dirs, metrics, [](int) { return PCCM_OK; },
+                         [&](int i, const Cloud &it) {
+        if (it.n >= ((int64_t)1 << 32)) return fail(PCCM_E_ARG, "%s count rows in 32 bits: columns of 2^32 rows or more are not supported", what);
+        if (kind == kSlotCount) {
+            double x;
+            memcpy(&x, &ks[i], sizeof x);
+            if (x != x) return fail(PCCM_E_ARG, "a count's threshold is a number or an infinity, not NaN");
+        } else if (ks[i] < 1 || ks[i] > it.n) {
+            return fail(PCCM_E_ARG, "rank %lld outside 1..%lld", (long long)ks[i], (long long)it.n);
+        }
+        return PCCM_OK;
+    });
+}
+
+// check, then enqueue what is not enqueued yet, by column
+static int select_prefetch(pccm_ctx *ctx, int kind, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes,
+                           const int64_t *ks)
+{
+    int rc = select_check(ctx, kind, who, n, dirs, metrics, normal_modes, ks);
     if (rc) return rc;
+    const RequestGroups g = group_requests(n, dirs, metrics, normal_modes, ks, nullptr, [&](int i) {
+        return find_pending(ctx->sel_slots, ctx->nn_gen, dirs[i], metrics[i], normal_modes[i], ks[i], kind) != nullptr;
+    });
+    if (g.ntodo == 0) return PCCM_OK;
     const ReduceSlot *cslot[kSelMax];
-    for (int c = 0; c < ncols; ++c) {
-        cslot[c] = slot_find(ctx, cd[c], cm[c], cmode[c]);
-        if (!cslot[c] || !cslot[c]->has_job) return fail(PCCM_E_STATE, "reduction slot lost");
-    }
-    SelectSlot *fresh[kSelMax];
-    int nfresh = 0;
+    rc = ensure(ctx, ctx->sel_hist, (size_t)kSelPasses * kSelMax * kSelBins * sizeof(uint32_t));
+    if (!rc) rc = ensure(ctx, ctx->sel_state, (size_t)kSelPasses * kSelMax * sizeof(SelState));
+    if (!rc) rc = column_slots(ctx, g, true, cslot);
+    if (rc) return rc;
+    SlotBatch batch(ctx, ctx->sel_slots);
     bool placed[kSelMax] = {};
     PathScope path(ctx, 1u << 3, true);            // the selection's launches join the log of the column's reduction batch
-    for (int left = ntodo; left > 0;) {            // rounds of at most kSelPerCol requests per column (two at the most)
+    for (int left = g.ntodo; left > 0;) {          // rounds of at most kSelPerCol requests per column (two at the most)
         UnitJobs uj;
         uj.njobs = 0;
         for (int k = 0; k < 9; ++k) uj.uoff[k] = uj.toff[k] = 0;
         UnitSelect &S = uj.sel;
         S.hist = (uint32_t *)ctx->sel_hist.p;
         S.state = (SelState *)ctx->sel_state.p;
-        for (int c = 0; c < ncols; ++c) {
+        for (int c = 0; c < g.ncols; ++c) {
             int taken = 0;
-            for (int j = 0; j < ntodo && taken < kSelPerCol; ++j) {
-                if (placed[j] || col_of[j] != c) continue;
-                SelectSlot *q = pick_free(ctx->sel_slots, fresh, nfresh, ctx->nn_gen);      // (a live one of another call: its result is given up)
-                if (!q) return fail(PCCM_E_STATE, "no free selection slot");
-                if (q->pending && !ctx->capturing && q->wait_ev && (rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
-                const int i = todo[j];
+            for (int j = 0; j < g.ntodo && taken < kSelPerCol; ++j) {
+                if (placed[j] || g.col_of[j] != c) continue;
+                SelectSlot *q;
+                if ((rc = batch.acquire("no free selection slot", &q))) return rc;
+                const int i = g.todo[j];
                 q->kind = kind;
                 q->dir = dirs[i]; q->metric = metrics[i]; q->mode = normal_modes[i]; q->k = ks[i];
                 q->gen = ctx->nn_gen[dirs[i]];
                 q->pending = true;
-                fresh[nfresh++] = q;
                 if (taken == 0) {
                     uj.j[uj.njobs] = cslot[c]->job;
                     S.sfirst[uj.njobs] = S.nsel;
@@ -2258,49 +2313,23 @@ static int select_prefetch(pccm_ctx *ctx, int kind, int n, const int *dirs, cons
     }
     uint64_t seq = 0;
     if ((rc = launch_publish(ctx, &seq))) return rc;
-    for (int f = 0; f < nfresh; ++f) {
-        SelectSlot &q = *fresh[f];
-        q.wait_seq = seq;                          // (while capturing: the batch's ordinal in the captured sequence)
-        q.wait_ev = ctx->capturing ? nullptr : ctx->batch_ev;
-        if (ctx->capturing) {
-            GraphOp op;
-            op.kind = 3;
-            op.dir = q.dir;
-            op.slot = (int)(&q - ctx->sel_slots);
-            op.ssnap = q;
-            ctx->cap_ops.push_back(op);
-        }
-    }
-    if (!ctx->capturing) PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
-    return PCCM_OK;
+    return batch.finish(seq);
 }
 
 // consume: enqueue first what nobody prefetched, in one batch; wait once; word[i]: the host word of request i
 static int select_consume(pccm_ctx *ctx, int kind, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes,
                           const int64_t *ks, double *word)
 {
-    int rc = select_check(ctx, kind, who, n, dirs, metrics, normal_modes, ks);
-    if (!rc) rc = select_prefetch(ctx, kind, n, dirs, metrics, normal_modes, ks);
+    int rc = select_prefetch(ctx, kind, who, n, dirs, metrics, normal_modes, ks);
     if (rc) return rc;
-    SelectSlot *got[kSelMax];
-    for (int i = 0; i < n; ++i) {
-        SelectSlot *q = sel_find(ctx, kind, dirs[i], metrics[i], normal_modes[i], ks[i]);
-        if (!q) return fail(PCCM_E_STATE, "selection slot lost");
-        if ((rc = wait_batch(ctx, q->wait_seq, q->wait_ev))) return rc;
-        if ((rc = check_device_errors(ctx))) return rc;
-        word[i] = ctx->sel_host[q - ctx->sel_slots];
-        got[i] = q;
-    }
-    for (int i = 0; i < n; ++i) got[i]->pending = false;
-    return PCCM_OK;
+    auto find = [&](int i) { return find_pending(ctx->sel_slots, ctx->nn_gen, dirs[i], metrics[i], normal_modes[i], ks[i], kind); };
+    return consume(ctx, n, "selection slot lost", find, [&](int i, SelectSlot &q) { word[i] = ctx->sel_host[&q - ctx->sel_slots]; });
 }
 
 int pccm_select_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks)
 {
     CHECK_CTX(ctx);
-    int rc = select_check(ctx, kSlotSelect, "pccm_select_prefetch_many", n, dirs, metrics, normal_modes, ks);
-    if (rc) return rc;
-    return select_prefetch(ctx, kSlotSelect, n, dirs, metrics, normal_modes, ks);
+    return select_prefetch(ctx, kSlotSelect, "pccm_select_prefetch_many", n, dirs, metrics, normal_modes, ks);
 }
 
 int pccm_select_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *ks, double *out)
@@ -2324,9 +2353,8 @@ int pccm_count_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *m
     CHECK_CTX(ctx);
     int64_t keys[kSelMax];
     int rc = count_keys(n, xs, keys);
-    if (!rc) rc = select_check(ctx, kSlotCount, "pccm_count_prefetch_many", n, dirs, metrics, normal_modes, keys);
     if (rc) return rc;
-    return select_prefetch(ctx, kSlotCount, n, dirs, metrics, normal_modes, keys);
+    return select_prefetch(ctx, kSlotCount, "pccm_count_prefetch_many", n, dirs, metrics, normal_modes, keys);
 }
 
 int pccm_count_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const double *xs, int64_t *out)
@@ -2348,99 +2376,54 @@ int pccm_count_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, c
 // (ReduceWhat::job), enqueued first where nobody has; unlike one it is a reduction launch: the job's column carries the map,
 // reduce_shape() gives such a job no lean kernel, and k_unit_jobs writes block results and the raw tail into the slot's own host
 // region.  Two requests on one column share a job -- its two columns, one read of the records.
-static uint64_t map_cap_bits(int map, double x)
-{
-    uint64_t b = 0;
-    if (map & PCCM_MAP_CLAMP) memcpy(&b, &x, sizeof b);
-    return b;
-}
-
-static MapSlot *map_find(pccm_ctx *ctx, int dir, int metric, int normal_mode, int map, double x)
-{
-    for (auto &m : ctx->map_slots)
-        if (m.matches(dir, metric, normal_mode, ctx->nn_gen[dir], map, map_cap_bits(map, x))) return &m;
-    return nullptr;
-}
-
 static int map_check(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
                      const double *xs)
 {
-    if (n < 0 || n > 8 || (n > 0 && (!dirs || !metrics || !normal_modes || !maps || !xs))) return fail(PCCM_E_ARG, "1..8 requests expected");
-    if (ctx->sharded()) return fail(PCCM_E_STATE, "%s needs the whole columns on this GPU (world = 1)", who);
-    for (int i = 0; i < n; ++i) {
-        if (dirs[i] != PCCM_DIR_LEFT && dirs[i] != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "mapped reductions read directions 0 and 1, not %d", dirs[i]);
-        if (metrics[i] != PCCM_METRIC_D1 && metrics[i] != PCCM_METRIC_D2)
-            return fail(PCCM_E_ARG, "mapped reductions read PCCM_METRIC_D1 and PCCM_METRIC_D2 columns, not metric %d", metrics[i]);
+    return request_check(ctx, who, "mapped reductions", n, dirs && metrics && normal_modes && maps && xs, dirs, metrics, [&](int i) {
         if (maps[i] < 1 || maps[i] > (PCCM_MAP_CLAMP | PCCM_MAP_ROOT))
             return fail(PCCM_E_ARG, "map %d is no combination of PCCM_MAP_CLAMP and PCCM_MAP_ROOT (0: pccm_reduce_total_many)", maps[i]);
         if ((maps[i] & PCCM_MAP_CLAMP) && xs[i] != xs[i]) return fail(PCCM_E_ARG, "a clamp's cap is a number or an infinity, not NaN");
-        const Cloud *it, *se;
-        NNResult *res;
-        int rc = need_nn(ctx, dirs[i], &it, &se, &res);
-        if (rc) return rc;
-    }
-    return PCCM_OK;
+        return PCCM_OK;
+    }, [](int, const Cloud &) { return PCCM_OK; });
 }
 
-static int map_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps, const double *xs)
+static int map_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
+                        const double *xs)
 {
-    auto same_column = [&](int a, int b) {
-        return dirs[a] == dirs[b] && metrics[a] == metrics[b] && (metrics[a] == PCCM_METRIC_D1 || normal_modes[a] == normal_modes[b]);
-    };
-    int todo[8], ntodo = 0, cd[8], cm[8], cmode[8], col_of[8], col_first[8], ncols = 0;
-    for (int i = 0; i < n; ++i) {
-        if (map_find(ctx, dirs[i], metrics[i], normal_modes[i], maps[i], xs[i])) continue;
-        bool dup = false;
-        for (int j = 0; j < ntodo; ++j)
-            dup = dup || (same_column(todo[j], i) && maps[todo[j]] == maps[i] && map_cap_bits(maps[todo[j]], xs[todo[j]]) == map_cap_bits(maps[i], xs[i]));
-        if (dup) continue;
-        int c = 0;
-        while (c < ncols && !same_column(col_first[c], i)) ++c;
-        if (c == ncols) { cd[c] = dirs[i]; cm[c] = metrics[i]; cmode[c] = normal_modes[i]; col_first[c] = i; ncols++; }
-        col_of[ntodo] = c;
-        todo[ntodo++] = i;
-    }
-    if (ntodo == 0) return PCCM_OK;
-    int rc = prefetch_many(ctx, ncols, cd, cm, cmode, false);     // the columns' plain reductions, where none is pending
+    int rc = map_check(ctx, who, n, dirs, metrics, normal_modes, maps, xs);
     if (rc) return rc;
-    const ReduceSlot *cslot[8];
-    for (int c = 0; c < ncols; ++c) {
-        cslot[c] = slot_find(ctx, cd[c], cm[c], cmode[c]);
-        if (!cslot[c]) return fail(PCCM_E_STATE, "reduction slot lost");
+    int64_t which[8];
+    uint64_t bits[8];
+    for (int i = 0; i < n; ++i) {
+        which[i] = maps[i];
+        bits[i] = map_cap_bits(maps[i], xs[i]);
     }
-    MapSlot *fresh[8];
-    int nfresh = 0, open_job[8];                   // open_job[c]: the job of column c that still has one column free, or -1
+    const RequestGroups g = group_requests(n, dirs, metrics, normal_modes, which, bits, [&](int i) {
+        return find_pending(ctx->map_slots, ctx->nn_gen, dirs[i], metrics[i], normal_modes[i], maps[i], bits[i]) != nullptr;
+    });
+    if (g.ntodo == 0) return PCCM_OK;
+    const ReduceSlot *cslot[8];
+    if ((rc = column_slots(ctx, g, false, cslot))) return rc;
+    SlotBatch batch(ctx, ctx->map_slots);
+    int open_job[8];                               // open_job[c]: the job of column c that still has one column free, or -1
     for (int c = 0; c < 8; ++c) open_job[c] = -1;
     UnitJobs uj;
     uj.njobs = 0; uj.uoff[0] = 0; uj.toff[0] = 0;
     PathScope path(ctx, 1u << 3, true);            // the launch joins the log of the columns' reduction batch
-    for (int j = 0; j < ntodo; ++j) {
-        const int i = todo[j], c = col_of[j];
-        MapSlot *m = pick_free(ctx->map_slots, fresh, nfresh, ctx->nn_gen);
-        if (!m) return fail(PCCM_E_STATE, "no free mapped-reduction slot");
-        if (m->pending && !ctx->capturing && m->wait_ev && (rc = wait_batch(ctx, m->wait_seq, m->wait_ev))) return rc;
-        m->pending = false;
+    for (int j = 0; j < g.ntodo; ++j) {
+        const int i = g.todo[j], c = g.col_of[j];
+        MapSlot *m;
+        if ((rc = batch.acquire("no free mapped-reduction slot", &m))) return rc;
         SlotShape hs = *cslot[c];                  // the column's shape; no per-leaf results cross to the host
         hs.nunits = 0;
-        const size_t need = (size_t)hs.host_doubles() * sizeof(double);
-        if (need > m->host_cap) {
-            if (ctx->capturing) {
-                ctx->capture_failed = true;
-                return fail(PCCM_E_STATE, "a mapped-reduction slot must be allocated during graph capture: run the sequence once first");
-            }
-            ctx->epoch++;
-            if (m->host) (void)hipHostFree(m->host);
-            m->host = nullptr; m->host_cap = 0;
-            PCCM_HIP(hipHostMalloc((void **)&m->host, need, hipHostMallocCoherent));   // no XCD's L2 keeps any of it (wait_batch)
-            m->host_cap = need;
-        }
+        if ((rc = host_reserve(ctx, *m, hs.host_doubles(), "a mapped-reduction slot must be allocated during graph capture: run the sequence once first")))
+            return rc;
         m->dir = dirs[i]; m->metric = metrics[i]; m->mode = normal_modes[i];
         m->gen = ctx->nn_gen[dirs[i]];
         m->shape = hs;
         m->map = maps[i];
-        m->cap_bits = map_cap_bits(maps[i], xs[i]);
+        m->cap_bits = bits[i];
         m->pending = true;
-        fresh[nfresh++] = m;
         if (!cslot[c]->has_job) continue;          // a column without rows: nothing to launch, the total of nothing
         UnitCol col = cslot[c]->job.c[0];
         col.map = maps[i];
@@ -2464,30 +2447,14 @@ static int map_prefetch(pccm_ctx *ctx, int n, const int *dirs, const int *metric
     uint64_t seq = 0;
     if ((rc = launch_unit_jobs(ctx, uj, &seq))) return rc;
     if (!seq && (rc = launch_publish(ctx, &seq))) return rc;      // (columns without rows: the batch still publishes)
-    for (int f = 0; f < nfresh; ++f) {
-        MapSlot &m = *fresh[f];
-        m.wait_seq = seq;                          // (while capturing: the batch's ordinal in the captured sequence)
-        m.wait_ev = ctx->capturing ? nullptr : ctx->batch_ev;
-        if (ctx->capturing) {
-            GraphOp op;
-            op.kind = 4;
-            op.dir = m.dir;
-            op.slot = (int)(&m - ctx->map_slots);
-            op.msnap = {m, m};
-            ctx->cap_ops.push_back(op);
-        }
-    }
-    if (!ctx->capturing) PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
-    return PCCM_OK;
+    return batch.finish(seq);
 }
 
 int pccm_reduce_map_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
                                   const double *xs)
 {
     CHECK_CTX(ctx);
-    int rc = map_check(ctx, "pccm_reduce_map_prefetch_many", n, dirs, metrics, normal_modes, maps, xs);
-    if (rc) return rc;
-    return map_prefetch(ctx, n, dirs, metrics, normal_modes, maps, xs);
+    return map_prefetch(ctx, "pccm_reduce_map_prefetch_many", n, dirs, metrics, normal_modes, maps, xs);
 }
 
 int pccm_reduce_map_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
@@ -2496,20 +2463,12 @@ int pccm_reduce_map_total_many(pccm_ctx *ctx, int n, const int *dirs, const int 
     CHECK_CTX(ctx);
     NOT_CAPTURING(ctx);
     if (n > 0 && !out) return fail(PCCM_E_ARG, "null pointer");
-    int rc = map_check(ctx, "pccm_reduce_map_total_many", n, dirs, metrics, normal_modes, maps, xs);
-    if (!rc) rc = map_prefetch(ctx, n, dirs, metrics, normal_modes, maps, xs);
+    int rc = map_prefetch(ctx, "pccm_reduce_map_total_many", n, dirs, metrics, normal_modes, maps, xs);
     if (rc) return rc;
-    MapSlot *got[8];
-    for (int i = 0; i < n; ++i) {
-        MapSlot *m = map_find(ctx, dirs[i], metrics[i], normal_modes[i], maps[i], xs[i]);
-        if (!m) return fail(PCCM_E_STATE, "mapped-reduction slot lost");
-        if ((rc = wait_batch(ctx, m->wait_seq, m->wait_ev))) return rc;
-        if ((rc = check_device_errors(ctx))) return rc;
-        slot_total(m->shape, SlotView(m->shape, m->host), out + 3 * i);
-        got[i] = m;
-    }
-    for (int i = 0; i < n; ++i) got[i]->pending = false;
-    return PCCM_OK;
+    auto find = [&](int i) {
+        return find_pending(ctx->map_slots, ctx->nn_gen, dirs[i], metrics[i], normal_modes[i], maps[i], map_cap_bits(maps[i], xs[i]));
+    };
+    return consume(ctx, n, "mapped-reduction slot lost", find, [&](int i, MapSlot &m) { slot_total(m.shape, SlotView(m.shape, m.host), out + 3 * i); });
 }
 
 // Host helper for the colour metrics (metric.py:261-290): out[r] = M * rgb[r] for the BT.709 "ycc" (1) or
@@ -2605,43 +2564,14 @@ static void graph_free(GraphRec &g)
 
 static int graph_replay(pccm_ctx *ctx, GraphRec &g)
 {
-
     for (auto &op : g.ops) {
         if (op.kind == 1) {
             ctx->nn_gen[op.dir]++;
             ctx->nn[op.dir].valid = true;
             ctx->nn[op.dir].form = op.form;
-        } else if (op.kind == 2) {
-            ReduceSlot &s = ctx->slots[op.slot];
-            if (s.pending && s.gen == ctx->nn_gen[s.dir] && s.wait_ev) {      // still in use by someone else
-                int rcw = wait_slot(ctx, &s);
-                if (rcw) return rcw;
-            }
-            restore(s, op.snap);
-            s.gen = ctx->nn_gen[s.dir];
-            s.pending = true;
-            rearm(s, ctx, op.snap.key.wait_seq);
-        } else if (op.kind == 3) {
-            SelectSlot &q = ctx->sel_slots[op.slot];
-            if (q.pending && q.gen == ctx->nn_gen[q.dir] && q.wait_ev) {       // still in use by someone else
-                int rcw = wait_batch(ctx, q.wait_seq, q.wait_ev);
-                if (rcw) return rcw;
-            }
-            q = op.ssnap;
-            q.gen = ctx->nn_gen[q.dir];
-            q.pending = true;
-            rearm(q, ctx, op.ssnap.wait_seq);
-        } else if (op.kind == 4) {
-            MapSlot &m = ctx->map_slots[op.slot];
-            if (m.pending && m.gen == ctx->nn_gen[m.dir] && m.wait_ev) {       // still in use by someone else
-                int rcw = wait_batch(ctx, m.wait_seq, m.wait_ev);
-                if (rcw) return rcw;
-            }
-            static_cast<SlotKey &>(m) = op.msnap.key;
-            static_cast<MapWhat &>(m) = op.msnap.what;
-            m.gen = ctx->nn_gen[m.dir];
-            m.pending = true;
-            rearm(m, ctx, op.msnap.key.wait_seq);
+        } else if (op.kind >= 2) {                                   // (in order: a slot takes the generation a kind 1 op before it left)
+            int rc = std::visit([&](const auto &snap) { return slot_replay(ctx, table_of(ctx, snap)[op.slot], snap); }, op.snap);
+            if (rc) return rc;
         }
     }
     ctx->batches_issued += g.batches;                            // before the launch: a failed one only delays a waiter
@@ -2656,9 +2586,7 @@ int pccm_graph_begin(pccm_ctx *ctx)
     if (ctx->capturing) return fail(PCCM_E_STATE, "already capturing");
     if (ctx->ties != PCCM_TIES_PICK) return fail(PCCM_E_STATE, "searches under PCCM_TIES_MEAN run eagerly: no graph capture");
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    for (auto &s : ctx->slots) s.pending = false;      // nothing outside the graph may be half-consumed
-    for (auto &q : ctx->sel_slots) q.pending = false;
-    for (auto &m : ctx->map_slots) m.pending = false;
+    for_each_slot(ctx, [](SlotKey &k) { k.pending = false; });      // nothing outside the graph may be half-consumed
     ctx->cap_ops.clear();
     ctx->cap_batches = 0;
     ctx->capture_failed = false;
@@ -2699,9 +2627,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     g.valid = true;
     // the captured calls changed the host bookkeeping but nothing ran yet: run the graph once now
     for (auto &op : g.ops)
-        if (op.kind == 2) rearm(ctx->slots[op.slot], ctx, op.snap.key.wait_seq);
-        else if (op.kind == 3) rearm(ctx->sel_slots[op.slot], ctx, op.ssnap.wait_seq);
-        else if (op.kind == 4) rearm(ctx->map_slots[op.slot], ctx, op.msnap.key.wait_seq);
+        if (op.kind >= 2) std::visit([&](const auto &snap) { rearm(table_of(ctx, snap)[op.slot], ctx, snap.key.wait_seq); }, op.snap);
     ctx->batches_issued += g.batches;
     PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));

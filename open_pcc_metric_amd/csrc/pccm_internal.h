@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <mutex>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "pccm.h"
@@ -267,22 +268,30 @@ struct ReduceWhat : SlotShape { // what a reduction slot holds: everything a cap
     UnitJob job;               // the column as a one-column k_unit_jobs job, as bound when the reduction was enqueued
 };
 
-struct ReduceSlot : SlotKey, ReduceWhat {   // one enqueued reduction (pccm_reduce_prefetch / pccm_reduce) and what the slot owns
-    DevBuf val;
-    double *host = nullptr;    // pinned, SlotShape::host_doubles() doubles at least: SlotView names its regions
+// the pinned host block a reduction or mapped-reduction slot owns (host_reserve, pccm_api.hip, grows it)
+struct SlotHost {
+    double *host = nullptr;
     size_t host_cap = 0;
-    hipEvent_t ev = nullptr;
+};
 
-    bool matches(int d, int m, int normal_mode, uint64_t gen_now, bool need_units) const
+struct ReduceSlot : SlotKey, ReduceWhat, SlotHost {   // one enqueued reduction (pccm_reduce_prefetch / pccm_reduce) and what the slot owns
+    using What = ReduceWhat;
+    DevBuf val;                // (host: SlotShape::host_doubles() doubles at least, SlotView names its regions)
+
+    bool matches(int d, int m, int normal_mode, uint64_t gen_now, bool need_units = false) const
     {
         return SlotKey::matches(d, m, normal_mode, gen_now) && (has_units || !need_units);
     }
 };
 
-constexpr int kSlotSelect = 0, kSlotCount = 1;     // SelectSlot::kind
-struct SelectSlot : SlotKey {  // one enqueued selection (pccm_select_prefetch_many / pccm_select_many) or count (pccm_count_*)
+constexpr int kSlotSelect = 0, kSlotCount = 1;     // SelectWhat::kind
+struct SelectWhat {
     int kind = kSlotSelect;
     int64_t k = 0;             // the rank; of a count: the bit pattern of its threshold
+};
+// one enqueued selection (pccm_select_*) or count (pccm_count_*); it owns nothing: slot s answers into pccm_ctx::sel_host[s]
+struct SelectSlot : SlotKey, SelectWhat {
+    using What = SelectWhat;
 
     bool matches(int d, int m, int normal_mode, uint64_t gen_now, int64_t rank, int what = kSlotSelect) const
     {
@@ -297,32 +306,16 @@ struct SelectSlot : SlotKey {  // one enqueued selection (pccm_select_prefetch_m
 struct MapWhat {
     SlotShape shape;
     int map = 0;
-    uint64_t cap_bits = 0;     // the bit pattern of the cap (0 without PCCM_MAP_CLAMP)
+    uint64_t cap_bits = 0;     // map_cap_bits(map, cap)
 };
-struct MapSlot : SlotKey, MapWhat {
-    double *host = nullptr;    // pinned, shape.host_doubles() doubles at least
-    size_t host_cap = 0;
+struct MapSlot : SlotKey, MapWhat, SlotHost {      // (host: shape.host_doubles() doubles at least)
+    using What = MapWhat;
 
     bool matches(int d, int m, int normal_mode, uint64_t gen_now, int which_map, uint64_t bits) const
     {
         return SlotKey::matches(d, m, normal_mode, gen_now) && map == which_map && cap_bits == bits;
     }
 };
-struct MapSnap {               // ... its bookkeeping at capture time, without what the slot owns
-    SlotKey key;
-    MapWhat what;
-};
-
-struct ReduceSnap {            // a reduction slot's bookkeeping at capture time, without what the slot owns
-    SlotKey key;
-    ReduceWhat what;
-};
-inline ReduceSnap snapshot(const ReduceSlot &s) { return {s, s}; }
-inline void restore(ReduceSlot &s, const ReduceSnap &snap)
-{
-    static_cast<SlotKey &>(s) = snap.key;
-    static_cast<ReduceWhat &>(s) = snap.what;
-}
 
 struct ProfSpan {
     hipEvent_t a, b;
@@ -334,9 +327,8 @@ struct GraphOp {               // host-side effect of one captured call, replaye
                                // 4 reduce_map_prefetch(slot)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
-    ReduceSnap snap;           // kind 2: the slot's bookkeeping at capture time
-    SelectSlot ssnap;          // kind 3: likewise for a selection or count slot
-    MapSnap msnap;             // kind 4: likewise for a mapped reduction's slot
+    // kinds 2, 3, 4 (2 + index()): the slot's key and description at capture time (pccm_slot.h)
+    std::variant<SlotSnap<ReduceWhat>, SlotSnap<SelectWhat>, SlotSnap<MapWhat>> snap;
 };
 
 struct GraphRec {
@@ -493,6 +485,20 @@ inline void rearm(SlotKey &k, const pccm_ctx *ctx, uint64_t snap_seq)
     k.wait_ev = ctx->batch_ev;
     k.wait_seq = snap_seq ? ctx->batches_issued + snap_seq : 0;
 }
+
+// every slot of the three tables
+template <class F>
+inline void for_each_slot(pccm_ctx *ctx, F f)
+{
+    for (auto &s : ctx->slots) f(s);
+    for (auto &s : ctx->sel_slots) f(s);
+    for (auto &s : ctx->map_slots) f(s);
+}
+
+// ... and the table a captured op's snapshot belongs to
+inline auto &table_of(pccm_ctx *ctx, const SlotSnap<ReduceWhat> &) { return ctx->slots; }
+inline auto &table_of(pccm_ctx *ctx, const SlotSnap<SelectWhat> &) { return ctx->sel_slots; }
+inline auto &table_of(pccm_ctx *ctx, const SlotSnap<MapWhat> &) { return ctx->map_slots; }
 
 // error plumbing ---------------------------------------------------------------------
 int fail(int code, const char *fmt, ...);

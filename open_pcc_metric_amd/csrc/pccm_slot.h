@@ -1,7 +1,8 @@
 // A reduction slot's shape, the layout of its pinned host buffer and NumPy's summation order over what the kernels leave there:
-// each decided here and nowhere else ("A reduction slot: shape, host layout, summation order").  The keys and the
-// free-slot policy that reduction and selection slots share are here too.  Host-only: no HIP call, no allocation; pccm_internal.h
-// includes it.
+// each decided here and nowhere else ("A reduction slot: shape, host layout, summation order").  What the three slot
+// tables (reductions, selections and counts, mapped reductions) share is here too: the key, the snapshot a captured graph keeps,
+// the search for a pending slot, the grouping of a call's requests by column and the free-slot policy.  Host-only: no HIP call, no
+// allocation; pccm_internal.h includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -169,7 +170,7 @@ inline void slot_fill_cvec(const SlotShape &s, const SlotView &v, double *cvec, 
     fold_minmax(v.bmin, v.bmax, s.nblocks, minmax);
 }
 
-// ---- what reduction and selection slots share -------------------------------------------------------------------------------
+// ---- what the slot tables share ----------------------------------------------------------------------------------------------
 
 // normal_mode enters the column: the projection on a normal of the searched cloud and its square, nothing else
 inline bool normal_mode_enters(int metric) { return metric == PCCM_METRIC_D2 || metric == PCCM_METRIC_PROJ; }
@@ -188,6 +189,72 @@ struct SlotKey {                    // which column an enqueued result belongs t
         return pending && dir == d && metric == m && (!normal_mode_enters(m) || mode == normal_mode) && gen == gen_now;
     }
 };
+
+// A slot of any table is three parts: SlotKey, a `What` struct (Slot::What, a base of the slot) that describes the enqueued result,
+// and what the slot owns.  A captured graph keeps the first two -- whole, so a new field travels too -- and its replay puts them back.
+template <class What>
+struct SlotSnap {
+    SlotKey key;
+    What what;
+};
+template <class Slot>
+inline SlotSnap<typename Slot::What> snapshot(const Slot &s) { return {s, s}; }
+template <class Slot>
+inline void restore(Slot &s, const SlotSnap<typename Slot::What> &snap)
+{
+    static_cast<SlotKey &>(s) = snap.key;
+    static_cast<typename Slot::What &>(s) = snap.what;
+}
+
+// the pending slot of a table that answers a request (rest: what the table's matches() asks on top of the column), or null
+template <class Slot, size_t N, class... Rest>
+inline Slot *find_pending(Slot (&slots)[N], const uint64_t *nn_gen, int dir, int metric, int normal_mode, Rest... rest)
+{
+    for (auto &s : slots)
+        if (s.matches(dir, metric, normal_mode, nn_gen[dir], rest...)) return &s;
+    return nullptr;
+}
+
+// the cap of a mapped reduction as a slot key: its bit pattern (0.0 and -0.0 are two keys), and nothing where the map does not clamp
+inline uint64_t map_cap_bits(int map, double x)
+{
+    uint64_t b = 0;
+    if (map & PCCM_MAP_CLAMP) memcpy(&b, &x, sizeof b);
+    return b;
+}
+
+// Which of a call's n <= 8 requests it still has to enqueue, and the distinct columns they read, in first-seen order.  A request
+// is a column (D1 ignores the normal mode) and a key (a selection's rank, the bits of a count's threshold, a map) of one word or,
+// with key2, two (a map's cap bits).  Left out: what enqueued(i) says is pending, and a repeat of an earlier request of the call.
+struct RequestGroups {
+    int ntodo = 0, ncols = 0;
+    int todo[8] = {}, col_of[8] = {};                // todo[j]: a request to enqueue; col_of[j]: the column it reads
+    int dir[8] = {}, metric[8] = {}, mode[8] = {};   // the columns
+};
+template <class Enqueued>
+inline RequestGroups group_requests(int n, const int *dirs, const int *metrics, const int *normal_modes, const int64_t *key,
+                                    const uint64_t *key2, Enqueued enqueued)
+{
+    RequestGroups g;
+    auto same_column = [&](int d, int m, int mode, int i) {
+        return d == dirs[i] && m == metrics[i] && (!normal_mode_enters(m) || mode == normal_modes[i]);
+    };
+    for (int i = 0; i < n; ++i) {
+        if (enqueued(i)) continue;
+        bool dup = false;
+        for (int j = 0; j < g.ntodo; ++j) {
+            const int t = g.todo[j];
+            dup = dup || (same_column(dirs[t], metrics[t], normal_modes[t], i) && key[t] == key[i] && (!key2 || key2[t] == key2[i]));
+        }
+        if (dup) continue;
+        int c = 0;
+        while (c < g.ncols && !same_column(g.dir[c], g.metric[c], g.mode[c], i)) ++c;
+        if (c == g.ncols) { g.dir[c] = dirs[i]; g.metric[c] = metrics[i]; g.mode[c] = normal_modes[i]; g.ncols++; }
+        g.col_of[g.ntodo] = c;
+        g.todo[g.ntodo++] = i;
+    }
+    return g;
+}
 
 // A slot for a new request: an idle one, then a stale one (nn_gen: the directions' generations now); failing that, a pending one
 // that does NOT belong to the batch being assembled (`fresh`): its unconsumed result is given up (a later consumer recomputes

@@ -16,7 +16,7 @@
 //   version    (per cloud) its points changed.  Copies: Grid::key and its kin, Cloud::solo_scale_version.
 //   epoch      something a captured graph has baked in changed: inputs, shards, policies, or the address of a device buffer.
 //              Copy: GraphRec::epoch.  The bumps for buffers and policies stay where the buffer or policy is: ensure,
-//              prepare_nn, slot_prepare, pccm_drop_caches, pccm_set_ties, pccm_nn_want_idx, pccm_nn_fuse.
+//              prepare_nn, host_reserve, pccm_drop_caches, pccm_set_ties, pccm_nn_want_idx, pccm_nn_fuse.
 #pragma once
 #include "pccm_internal.h"
 
@@ -44,9 +44,7 @@ inline void records_rewritten(pccm_ctx *ctx, int dir) { ctx->nn_gen[dir]++; }
 inline void results_dropped(pccm_ctx *ctx)
 {
     results_void(ctx, kDirsAll);
-    for (auto &s : ctx->slots) s.pending = false;
-    for (auto &q : ctx->sel_slots) q.pending = false;
-    for (auto &m : ctx->map_slots) m.pending = false;
+    for_each_slot(ctx, [](SlotKey &k) { k.pending = false; });
 }
 
 // The rows this context owns of these directions changed (pccm_set_shard, pccm_set_shard_dir): captured searches carry the old ones

@@ -194,8 +194,8 @@ static void test_restore()
     memset(&was.job, 0, sizeof(was.job));
     was.job.val = dev_a; was.job.stride = 2; was.job.ncols = 1;
     bind_shape(was.job, was);
-    was.val.p = dev_a; was.val.bytes = 64; was.host = buf_a; was.host_cap = 32; was.ev = (hipEvent_t)dev_a;
-    const ReduceSnap snap = snapshot(was);
+    was.val.p = dev_a; was.val.bytes = 64; was.host = buf_a; was.host_cap = 32;
+    const SlotSnap<ReduceWhat> snap = snapshot(was);
 
     ReduceSlot now;                                                       // the same slot later: another column, buffers regrown
     now.dir = 0; now.metric = PCCM_METRIC_D1; now.gen = 12; now.wait_ev = (hipEvent_t)buf_b; now.wait_seq = 40;
@@ -203,10 +203,10 @@ static void test_restore()
     memset(&now.job, 0, sizeof(now.job));
     now.job.val = dev_b; now.job.stride = 1;
     bind_shape(now.job, now);
-    now.val.p = dev_b; now.val.bytes = 128; now.host = buf_b; now.host_cap = 4096; now.ev = (hipEvent_t)dev_b;
+    now.val.p = dev_b; now.val.bytes = 128; now.host = buf_b; now.host_cap = 4096;
     restore(now, snap);
 
-    EXPECT(now.val.p == dev_b && now.val.bytes == 128 && now.host == buf_b && now.host_cap == 4096 && now.ev == (hipEvent_t)dev_b);
+    EXPECT(now.val.p == dev_b && now.val.bytes == 128 && now.host == buf_b && now.host_cap == 4096);
     EXPECT(now.pending && now.dir == 1 && now.metric == PCCM_METRIC_D2 && now.mode == PCCM_NORMAL_NEIGHBOUR && now.gen == 11);
     EXPECT(now.wait_ev == (hipEvent_t)buf_a && now.wait_seq == 3);
     EXPECT(now.n_iter == 28673 && now.begin == 8192 && now.end == 28673 && now.ns == 20481 && now.nunits == 161 && now.nblocks == 6);
@@ -214,7 +214,9 @@ static void test_restore()
     EXPECT(now.job.val == dev_a && now.job.stride == 2 && now.job.ncols == 1 && now.job.ns == 20481 && now.job.nunits == 161);
     EXPECT(now.job.nblocks == 6 && now.job.tail_first == 16384 && now.job.tail_n == 4097);
     // every byte of the snapshot is one of the two parts: a field added to either travels without a line written for it
-    static_assert(sizeof(ReduceSnap) == sizeof(SlotKey) + sizeof(ReduceWhat), "the snapshot is the key and the description");
+    static_assert(sizeof(SlotSnap<ReduceWhat>) == sizeof(SlotKey) + sizeof(ReduceWhat), "the snapshot is the key and the description");
+    static_assert(sizeof(SlotSnap<SelectWhat>) == sizeof(SlotKey) + sizeof(SelectWhat), "... in the selection table");
+    static_assert(sizeof(SlotSnap<MapWhat>) == sizeof(SlotKey) + sizeof(MapWhat), "... and in the mapped reductions'");
 
     pccm_ctx *ctx = new pccm_ctx();                                       // (plain host memory until something is allocated)
     ctx->batch_ev = (hipEvent_t)dev_a;
@@ -224,6 +226,146 @@ static void test_restore()
     rearm(now, ctx, 0);                                                   // no counter: the event only
     EXPECT(now.wait_seq == 0);
     delete ctx;
+}
+
+// ... in the other two tables as well
+static void test_restore_select_and_map()
+{
+    snprintf(g_case, sizeof(g_case), "restore select / map");
+    static double buf_a[4], buf_b[4];
+    SelectSlot qwas;
+    qwas.pending = true; qwas.dir = 1; qwas.metric = PCCM_METRIC_D2; qwas.mode = PCCM_NORMAL_NEIGHBOUR; qwas.gen = 11;
+    qwas.wait_ev = (hipEvent_t)buf_a; qwas.wait_seq = 3;
+    qwas.kind = kSlotCount; qwas.k = 0x3ff0000000000000ll;
+    const SlotSnap<SelectWhat> qsnap = snapshot(qwas);
+    SelectSlot q;
+    q.dir = 0; q.metric = PCCM_METRIC_D1; q.gen = 12; q.wait_ev = (hipEvent_t)buf_b; q.wait_seq = 40; q.kind = kSlotSelect; q.k = 7;
+    restore(q, qsnap);
+    EXPECT(q.pending && q.dir == 1 && q.metric == PCCM_METRIC_D2 && q.mode == PCCM_NORMAL_NEIGHBOUR && q.gen == 11);
+    EXPECT(q.wait_ev == (hipEvent_t)buf_a && q.wait_seq == 3 && q.kind == kSlotCount && q.k == 0x3ff0000000000000ll);
+
+    MapSlot mwas;
+    mwas.pending = true; mwas.dir = 1; mwas.metric = PCCM_METRIC_D2; mwas.mode = PCCM_NORMAL_NEIGHBOUR; mwas.gen = 11;
+    mwas.wait_ev = (hipEvent_t)buf_a; mwas.wait_seq = 3;
+    mwas.shape = slot_shape(28673, 0, 28673);
+    mwas.shape.nunits = 0;
+    mwas.map = PCCM_MAP_CLAMP | PCCM_MAP_ROOT; mwas.cap_bits = map_cap_bits(mwas.map, 0.25);
+    mwas.host = buf_a; mwas.host_cap = 32;
+    const SlotSnap<MapWhat> map_snap = snapshot(mwas);
+    MapSlot m;
+    m.dir = 0; m.metric = PCCM_METRIC_D1; m.gen = 12; m.wait_ev = (hipEvent_t)buf_b; m.wait_seq = 40;
+    m.shape = slot_shape(1000, 0, 1000);
+    m.map = PCCM_MAP_ROOT; m.cap_bits = 0;
+    m.host = buf_b; m.host_cap = 4096;
+    restore(m, map_snap);
+    EXPECT(m.host == buf_b && m.host_cap == 4096);
+    EXPECT(m.pending && m.dir == 1 && m.metric == PCCM_METRIC_D2 && m.mode == PCCM_NORMAL_NEIGHBOUR && m.gen == 11);
+    EXPECT(m.wait_ev == (hipEvent_t)buf_a && m.wait_seq == 3);
+    EXPECT(m.shape.n_iter == 28673 && m.shape.begin == 0 && m.shape.end == 28673 && m.shape.ns == 28673 && m.shape.nunits == 0);
+    EXPECT(m.shape.nblocks == 8 && m.shape.t0 == 24576 && m.shape.tail_n == 4097);
+    EXPECT(m.map == (PCCM_MAP_CLAMP | PCCM_MAP_ROOT) && m.cap_bits == 0x3fd0000000000000ull);
+}
+
+// (g) one search finds the pending slot of a request in any table
+static void test_find_pending()
+{
+    snprintf(g_case, sizeof(g_case), "find_pending");
+    const uint64_t gen[3] = {5, 6, 7};
+    const int ROW = PCCM_NORMAL_ROW, NB = PCCM_NORMAL_NEIGHBOUR, D1 = PCCM_METRIC_D1, D2 = PCCM_METRIC_D2;
+    auto key = [](SlotKey &k, int dir, int metric, int mode, uint64_t g) { k.pending = true; k.dir = dir; k.metric = metric; k.mode = mode; k.gen = g; };
+    {
+        ReduceSlot r[4];
+        key(r[0], 0, D1, ROW, 5);
+        key(r[1], 1, D2, ROW, 6);
+        key(r[2], 1, D2, NB, 6);
+        r[2].has_units = true;
+        key(r[3], 0, D2, ROW, 4);                                         // (of an earlier search)
+        EXPECT(find_pending(r, gen, 0, D1, ROW) == &r[0] && find_pending(r, gen, 0, D1, NB) == &r[0]);      // D1 ignores the mode
+        EXPECT(find_pending(r, gen, 1, D2, ROW) == &r[1] && find_pending(r, gen, 1, D2, NB) == &r[2]);      // D2 does not
+        EXPECT(find_pending(r, gen, 1, D2, ROW, true) == nullptr && find_pending(r, gen, 1, D2, NB, true) == &r[2]);   // need_units
+        EXPECT(find_pending(r, gen, 0, D1, ROW, true) == nullptr && find_pending(r, gen, 1, D1, ROW) == nullptr);
+        EXPECT(find_pending(r, gen, 0, D2, ROW) == nullptr);              // stale by its direction's generation
+        r[0].pending = false;
+        EXPECT(find_pending(r, gen, 0, D1, ROW) == nullptr);
+    }
+    {
+        SelectSlot q[3];
+        key(q[0], 0, D1, ROW, 5); q[0].kind = kSlotSelect; q[0].k = 9;
+        key(q[1], 0, D1, ROW, 5); q[1].kind = kSlotCount; q[1].k = 9;     // a count whose threshold has a rank's bits: another request
+        key(q[2], 1, D2, NB, 6); q[2].kind = kSlotSelect; q[2].k = 9;
+        EXPECT(find_pending(q, gen, 0, D1, NB, (int64_t)9) == &q[0] && find_pending(q, gen, 0, D1, NB, (int64_t)9, kSlotSelect) == &q[0]);
+        EXPECT(find_pending(q, gen, 0, D1, ROW, (int64_t)9, kSlotCount) == &q[1] && find_pending(q, gen, 0, D1, ROW, (int64_t)8) == nullptr);
+        EXPECT(find_pending(q, gen, 1, D2, NB, (int64_t)9) == &q[2] && find_pending(q, gen, 1, D2, ROW, (int64_t)9) == nullptr);
+        EXPECT(find_pending(q, gen, 1, D2, NB, (int64_t)9, kSlotCount) == nullptr);
+    }
+    {
+        const int CL = PCCM_MAP_CLAMP, RT = PCCM_MAP_ROOT;
+        MapSlot m[4];
+        key(m[0], 0, D1, ROW, 5); m[0].map = CL; m[0].cap_bits = map_cap_bits(CL, 0.0);
+        key(m[1], 0, D1, ROW, 5); m[1].map = CL; m[1].cap_bits = map_cap_bits(CL, -0.0);
+        key(m[2], 0, D1, ROW, 5); m[2].map = RT; m[2].cap_bits = map_cap_bits(RT, 3.0);
+        key(m[3], 1, D2, NB, 6); m[3].map = CL | RT; m[3].cap_bits = map_cap_bits(CL | RT, 0.5);
+        EXPECT(map_cap_bits(CL, 0.0) != map_cap_bits(CL, -0.0) && map_cap_bits(RT, 3.0) == 0 && map_cap_bits(RT, -1.0) == 0);
+        EXPECT(find_pending(m, gen, 0, D1, NB, CL, map_cap_bits(CL, 0.0)) == &m[0]);          // 0.0 and -0.0: two keys
+        EXPECT(find_pending(m, gen, 0, D1, NB, CL, map_cap_bits(CL, -0.0)) == &m[1]);
+        EXPECT(find_pending(m, gen, 0, D1, ROW, RT, map_cap_bits(RT, 8.0)) == &m[2]);         // no clamp: the cap is no part of the key
+        EXPECT(find_pending(m, gen, 0, D1, ROW, CL | RT, map_cap_bits(CL | RT, 0.0)) == nullptr);
+        EXPECT(find_pending(m, gen, 1, D2, NB, CL | RT, map_cap_bits(CL | RT, 0.5)) == &m[3]);
+        EXPECT(find_pending(m, gen, 1, D2, ROW, CL | RT, map_cap_bits(CL | RT, 0.5)) == nullptr);
+        EXPECT(find_pending(m, gen, 1, D2, NB, CL | RT, map_cap_bits(CL | RT, 0.25)) == nullptr);
+    }
+}
+
+// (h) which requests of a call are enqueued, and on which columns
+struct Req {
+    int dir, metric, mode;
+    int64_t key;
+    double x;                                                             // (maps: the cap)
+};
+static bool groups_are(const std::vector<Req> &reqs, bool maps, const std::vector<int> &enqueued, const std::vector<int> &todo,
+                       const std::vector<int> &col_of, const std::vector<Req> &cols)
+{
+    int dirs[8], metrics[8], modes[8];
+    int64_t key[8];
+    uint64_t key2[8];
+    const int n = (int)reqs.size();
+    for (int i = 0; i < n; ++i) {
+        dirs[i] = reqs[i].dir; metrics[i] = reqs[i].metric; modes[i] = reqs[i].mode; key[i] = reqs[i].key;
+        key2[i] = map_cap_bits((int)reqs[i].key, reqs[i].x);
+    }
+    const RequestGroups g = group_requests(n, dirs, metrics, modes, key, maps ? key2 : nullptr, [&](int i) {
+        for (int e : enqueued)
+            if (e == i) return true;
+        return false;
+    });
+    bool ok = g.ntodo == (int)todo.size() && g.ncols == (int)cols.size() && todo.size() == col_of.size();
+    for (int j = 0; ok && j < g.ntodo; ++j) ok = g.todo[j] == todo[j] && g.col_of[j] == col_of[j];
+    for (int c = 0; ok && c < g.ncols; ++c) ok = g.dir[c] == cols[c].dir && g.metric[c] == cols[c].metric && g.mode[c] == cols[c].mode;
+    return ok;
+}
+
+static void test_group_requests()
+{
+    snprintf(g_case, sizeof(g_case), "group_requests");
+    const int ROW = PCCM_NORMAL_ROW, NB = PCCM_NORMAL_NEIGHBOUR, D1 = PCCM_METRIC_D1, D2 = PCCM_METRIC_D2;
+    const int CL = PCCM_MAP_CLAMP, RT = PCCM_MAP_ROOT;
+    std::vector<Req> eight;
+    for (int i = 0; i < 8; ++i) eight.push_back({0, D1, ROW, 10 + i, 0.0});
+    EXPECT(groups_are(eight, false, {}, {0, 1, 2, 3, 4, 5, 6, 7}, {0, 0, 0, 0, 0, 0, 0, 0}, {{0, D1, ROW}}));          // eight on one column
+    EXPECT(groups_are(eight, false, {0, 1, 2, 3, 4, 5, 6, 7}, {}, {}, {}));                                            // all enqueued already
+    EXPECT(groups_are(eight, false, {0, 2, 7}, {1, 3, 4, 5, 6}, {0, 0, 0, 0, 0}, {{0, D1, ROW}}));
+    EXPECT(groups_are({{1, D2, ROW, 5}, {1, D2, ROW, 5}}, false, {}, {0}, {0}, {{1, D2, ROW}}));                       // the same request twice
+    EXPECT(groups_are({{0, D1, ROW, 5}, {0, D1, NB, 5}, {0, D1, NB, 6}}, false, {}, {0, 2}, {0, 0}, {{0, D1, ROW}}));  // D1: one column under two modes
+    EXPECT(groups_are({{0, D2, ROW, 5}, {0, D2, NB, 5}, {0, D2, ROW, 6}}, false, {}, {0, 1, 2}, {0, 1, 0}, {{0, D2, ROW}, {0, D2, NB}}));   // D2: two
+    EXPECT(groups_are({{1, D1, ROW, 1}, {0, D1, ROW, 1}, {1, D2, ROW, 1}, {0, D1, ROW, 2}, {1, D1, ROW, 2}, {0, D2, ROW, 1}}, false, {},
+                      {0, 1, 2, 3, 4, 5}, {0, 1, 2, 1, 0, 3}, {{1, D1, ROW}, {0, D1, ROW}, {1, D2, ROW}, {0, D2, ROW}}));   // first-seen order
+    EXPECT(groups_are({{1, D1, ROW, 1}, {0, D1, ROW, 1}, {1, D1, ROW, 2}}, false, {0}, {1, 2}, {0, 1}, {{0, D1, ROW}, {1, D1, ROW}}));
+    // maps: the cap is part of the key exactly when the map clamps
+    EXPECT(groups_are({{0, D1, ROW, CL, 0.5}, {0, D1, ROW, CL, 0.25}}, true, {}, {0, 1}, {0, 0}, {{0, D1, ROW}}));
+    EXPECT(groups_are({{0, D1, ROW, CL, 0.0}, {0, D1, ROW, CL, -0.0}, {0, D1, ROW, CL, 0.0}}, true, {}, {0, 1}, {0, 0}, {{0, D1, ROW}}));
+    EXPECT(groups_are({{0, D1, ROW, RT, 0.5}, {0, D1, ROW, RT, 0.25}}, true, {}, {0}, {0}, {{0, D1, ROW}}));
+    EXPECT(groups_are({{0, D1, ROW, CL, 0.5}, {0, D1, ROW, CL | RT, 0.5}, {1, D1, NB, CL, 0.5}}, true, {}, {0, 1, 2}, {0, 0, 1},
+                      {{0, D1, ROW}, {1, D1, NB}}));
 }
 
 int main(int argc, char **argv)
@@ -243,6 +385,9 @@ int main(int argc, char **argv)
     for (int a = 3; a < argc; ++a) run_world(col, atoi(argv[a]));
     test_pick_free();
     test_restore();
+    test_restore_select_and_map();
+    test_find_pending();
+    test_group_requests();
     printf("%d checks, %d failed\n", g_checked, g_failed);
     return g_failed ? 1 : 0;
 }
