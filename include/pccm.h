@@ -475,6 +475,38 @@ int pccm_reduce_map_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const i
 int pccm_reduce_map_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
                                const double *xs, double *out /*[3 n]*/);
 
+/* Match counts: out[j] = the number of shard rows of direction dir (0 or 1) whose matched row is j --
+ * np.bincount(idx, minlength=n_searched) over the idx pccm_nn_fetch gives, as n_searched uint32 words (the searched cloud's
+ * rows).  Counted on the GPU with integer atomics, once per search and direction and kept until the direction's results change;
+ * the matched rows are read where the search left them (result records or the plain idx column), and a search that left them out
+ * (pccm_nn_want_idx off, the voxel-brick search) is repeated with the rows on, as for pccm_carry_normals.
+ * PCCM_E_ARG: dir is not 0 or 1, a null out.  PCCM_E_STATE: no search result yet, a sharded context, a search that ran under
+ * PCCM_TIES_MEAN (a virtual neighbour has no row), a call during graph capture. */
+int pccm_match_counts(pccm_ctx *ctx, int dir, uint32_t *out /*[n_searched]*/);
+
+/* Density-aware Chamfer terms (Wu et al., NeurIPS 2021): out[3 i ..] = np.sum, np.min, np.max of
+ *   t = 1 - exp(-alphas[i] * s) / m[idx]        s = sqrt(d2) (squared[i] == 0: the paper's equation) or d2 (squared[i] == 1)
+ * over the PCCM_METRIC_D1 column d2 of direction dirs[i] (0 or 1), idx its matched rows and m the direction's match counts
+ * (pccm_match_counts).  On the device: s = squared ? d2 : sqrt_rn(d2); a = mul_rn(-alpha, s); e = exp(a) (the fp64 device exp);
+ * q = div_rn(e, (double)m); t = sub_rn(1.0, q) -- every operation but exp correctly rounded --, summed in NumPy's order.  So
+ * alpha = 0 gives np.sum(1.0 - 1.0 / m[idx]) bit for bit (the left row / n = 1 - distinct matched rows / n: a coverage number),
+ * a huge alpha (1e300) np.sum(np.where(s > 0, 1.0, 1.0 - 1.0 / m[idx])) bit for bit, and any other alpha differs from NumPy by
+ * what the two exp implementations differ by.  Every m that is gathered is >= 1 (the row that gathers it counted itself), so
+ * every term lies in [0, 1].  The term is the map PCCM_MAP_DENSITY of the general reduction kernel (k_unit_jobs), applied behind
+ * the optional root and never combined with a clamp: it reads the column once, in HBM, gathers the counts through the matched
+ * rows, and stores no column; pccm_reduce_map_* keeps refusing maps outside 1..3.  n <= 8 per call (n == 0: PCCM_OK).
+ *   pccm_reduce_density_prefetch_many  makes the counts where the search's are not there yet (a memset and one launch) and
+ *                                      enqueues the mapped launch behind them; capturable between pccm_graph_begin /
+ *                                      pccm_graph_end like pccm_reduce_map_prefetch_many (a search without matched rows cannot
+ *                                      be repeated there: PCCM_E_STATE).
+ *   pccm_reduce_density_total_many     consumes them (enqueuing first what nobody prefetched) and waits once.
+ * PCCM_E_ARG: n outside 0..8, a null array with n > 0 or a null out, PCCM_DIR_SELF, squared[i] outside 0 / 1, alphas[i] NaN,
+ * negative or infinite.  PCCM_E_STATE: no search result yet, a sharded context, a search that ran under PCCM_TIES_MEAN. */
+#define PCCM_MAP_DENSITY 4
+int pccm_reduce_density_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *squared, const double *alphas);
+int pccm_reduce_density_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *squared, const double *alphas,
+                                   double *out /*[3 n]: np.sum, np.min, np.max of the terms*/);
+
 /* Sharded contexts whose rows start and end on whole 8192-row chunks (pccm_set_shard / pccm_set_shard_dir do that
  * whenever every rank can have a chunk): the exchange vector shrinks to ONE number per chunk -- NumPy adds the
  * chunks of a column one after the other, and the GPU has finished each chunk's pairwise tree -- plus the raw values
@@ -578,11 +610,11 @@ int pccm_color_transform(const double *rgb, int64_t n, int scheme, double *out);
 int pccm_drop_caches(pccm_ctx *ctx);
 
 /* hipGraph capture.  Between pccm_graph_begin() and pccm_graph_end() only pccm_drop_caches(),
- * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many(), pccm_count_prefetch_many() and pccm_reduce_map_prefetch_many() may be called; they are recorded on the
+ * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many(), pccm_count_prefetch_many(), pccm_reduce_map_prefetch_many() and pccm_reduce_density_prefetch_many() may be called; they are recorded on the
  * context's stream instead of executed.  The same sequence must have run once before (capture cannot allocate).
  * pccm_graph_end() instantiates the graph, runs it once and returns its id; pccm_graph_launch()
  * replays the whole sequence -- kernels and host-side bookkeeping -- with a single launch, after which
- * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_reduce_map_total_many()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
+ * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_reduce_map_total_many()/pccm_reduce_density_total_many()/pccm_match_counts()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
  * clouds, normals, shard or any buffer it references change.  One report over resident clouds is
  * ~45 small launches, which an eager host cannot issue as fast as the GPU retires them. */
 int pccm_graph_begin(pccm_ctx *ctx);

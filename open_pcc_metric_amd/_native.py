@@ -28,6 +28,7 @@ TIES = {"pick": 0, "mean": 1}          # PCCM_TIES_PICK / PCCM_TIES_MEAN
 DUPLICATES = {"drop": 1, "average": 2}  # PCCM_DUP_DROP / PCCM_DUP_AVERAGE
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
 MAP_CLAMP, MAP_ROOT = 1, 2          # Engine.reduce_map_*: PCCM_MAP_*
+MAP_DENSITY = 4                     # PCCM_MAP_DENSITY: the map behind Engine.reduce_density_* (reduce_map_* refuses it)
 METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
 # PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
 SSIM_ATTRS = {"geometry": 1, "normal": 2, "curvature": 4, "color": 8}
@@ -49,7 +50,7 @@ SYMBOLS = (
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours",
     "pccm_resolution_build", "pccm_get_resolution", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
-    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_reduce_map_prefetch_many", "pccm_reduce_map_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
+    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_reduce_map_prefetch_many", "pccm_reduce_map_total_many", "pccm_match_counts", "pccm_reduce_density_prefetch_many", "pccm_reduce_density_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_reflectance", "pccm_set_reflectance_u16", "pccm_get_reflectance",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
@@ -161,6 +162,9 @@ def load() -> ctypes.CDLL:
     lib.pccm_count_many.argtypes = [vp, i32, ip, ip, ip, dp, lp]
     lib.pccm_reduce_map_prefetch_many.argtypes = [vp, i32, ip, ip, ip, ip, dp]
     lib.pccm_reduce_map_total_many.argtypes = [vp, i32, ip, ip, ip, ip, dp, dp]
+    lib.pccm_match_counts.argtypes = [vp, i32, vp]
+    lib.pccm_reduce_density_prefetch_many.argtypes = [vp, i32, ip, ip, dp]
+    lib.pccm_reduce_density_total_many.argtypes = [vp, i32, ip, ip, dp, dp]
     lib.pccm_cvec_len.argtypes = [i64]
     lib.pccm_cvec_len.restype = i64
     lib.pccm_reduce_chunks_many.argtypes = [vp, i32, ip, ip, ip, dp, dp]
@@ -806,6 +810,38 @@ class Engine:
         args = self._map_args(requests, normal_mode)
         out = (ctypes.c_double * (3 * args[0]))()
         _check(self._lib.pccm_reduce_map_total_many(self._ctx, *args, out))
+        return [(np.float64(out[3 * i]), np.float64(out[3 * i + 1]), np.float64(out[3 * i + 2])) for i in range(args[0])]
+
+    def match_counts(self, direction: int) -> np.ndarray:
+        """How many shard rows of ``direction`` (0 or 1) matched each row of the searched cloud (pccm_match_counts):
+        ``np.bincount(idx, minlength=n_searched)`` as uint32, counted on the GPU."""
+        out = np.empty(self.n_iter(DIR_RIGHT if int(direction) == DIR_LEFT else DIR_LEFT), dtype=np.uint32)
+        _check(self._lib.pccm_match_counts(self._ctx, int(direction), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    @staticmethod
+    def _density_args(requests):
+        k = len(requests)
+        arr = ctypes.c_int * k
+        return (k, arr(*[int(r[0]) for r in requests]), arr(*[int(bool(r[2])) for r in requests]),
+                (ctypes.c_double * k)(*[float(r[1]) for r in requests]))
+
+    def reduce_density_prefetch_many(self, requests, normal_mode: str = "row") -> None:
+        """``requests``: up to 8 ``(direction, alpha, squared)``: enqueue the density-aware Chamfer terms of each direction's D1
+        column without waiting (pccm_reduce_density_prefetch_many; the match counts are made first where the search's are not
+        there yet); a later reduce_density_total_many() consumes them.  ``normal_mode`` does not enter."""
+        if requests:
+            _check(self._lib.pccm_reduce_density_prefetch_many(self._ctx, *self._density_args(requests)))
+
+    def reduce_density_total_many(self, requests, normal_mode: str = "row"):
+        """-> [(sum, min, max)] of ``1 - exp(-alpha * s) / m[idx]`` for up to 8 ``(direction, alpha, squared)``, s the D1 column
+        (``squared``) or its root, m the direction's match counts: gathered, mapped and summed in HBM
+        (pccm_reduce_density_total_many)."""
+        if not requests:
+            return []
+        args = self._density_args(requests)
+        out = (ctypes.c_double * (3 * args[0]))()
+        _check(self._lib.pccm_reduce_density_total_many(self._ctx, *args, out))
         return [(np.float64(out[3 * i]), np.float64(out[3 * i + 1]), np.float64(out[3 * i + 2])) for i in range(args[0])]
 
     def reduce_chunks_many(self, requests, normal_mode: str = "row"):

@@ -42,6 +42,8 @@ class CalculateResult:
                 label += f"[{inner.peak!r}]"
             if getattr(inner, "threshold", None) is not None:   # F-score and truncated-distance rows: one block per distance threshold
                 label += f"[{inner.threshold!r}]"
+            if getattr(inner, "alpha", None) is not None:       # density-aware Chamfer rows: one block per alpha
+                label += f"[{inner.alpha!r}, squared]" if getattr(inner, "squared", False) else f"[{inner.alpha!r}]"
             if inner is not m:
                 label += "(symmetric)"
             rows["label"].append(label)
@@ -120,6 +122,8 @@ class MetricCalculator:
                     wanted.append(("within", metric.is_left, metric.threshold))
                 elif item == "mapped":
                     wanted.append(("mapped",) + tuple(metric._mapped_request()))
+                elif item == "density":
+                    wanted.append(("density", metric.is_left, metric.alpha, metric.squared))
             resolved = {}
             for name, dep in metric._get_dependencies().items():
                 resolved[name], _, dep_waits = self._visit(dep, early, late, planned, wanted)

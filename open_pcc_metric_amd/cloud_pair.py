@@ -219,6 +219,24 @@ class DeviceColumn(_DeviceArray):
                 return value
         return mapped_on_host(np.asarray(self), root, clamp)
 
+    def density(self, alpha, squared: bool = False):
+        """``(sum, min, max)`` of the density-aware Chamfer terms ``1 - exp(-alpha * s) / m[idx]`` of a ``d1`` column: s the
+        column (``squared``) or its root, idx the direction's matched rows, m how many rows matched each row of the searched
+        cloud (CloudPair.match_counts).  Counted, gathered, mapped and summed in HBM when the engine can
+        (pccm_reduce_density_total_many) -- neither the column, the rows nor the terms leave the GPU or are stored there."""
+        alpha = float(alpha)
+        if not (alpha >= 0.0) or alpha == float("inf"):
+            raise ValueError("density: alpha is a finite number >= 0")
+        if self._kind != "d1" or self._dir not in (nat.DIR_LEFT, nat.DIR_RIGHT):
+            raise ValueError("density: defined on the d1 columns of the two directions")
+        value = self._pair._density(self._dir, alpha + 0.0, bool(squared))
+        if value is not None:
+            return value
+        pair = self._pair
+        rows = pair._neighbour_index(self._dir)
+        counts = np.bincount(rows, minlength=pair._engine.n_iter(nat.DIR_RIGHT if self._dir == nat.DIR_LEFT else nat.DIR_LEFT))
+        return density_on_host(np.asarray(self), rows, counts, alpha, squared)
+
     def _fused_function(self, func, args, kwargs):
         which = _REDUCERS.get(func)
         if which is None or len(args) != 1 or args[0] is not self:
@@ -244,6 +262,15 @@ def mapped_on_host(column, root: bool = False, clamp=None):
     if root:
         f = np.sqrt(f)
     return np.sum(f), np.min(f), np.max(f)
+
+
+def density_on_host(column, rows, counts, alpha, squared: bool = False):
+    """What DeviceColumn.density answers, for a column, matched rows and match counts that are plain arrays."""
+    d2 = np.asarray(column, dtype=np.float64)
+    s = d2 if squared else np.sqrt(d2)
+    m = np.asarray(counts)[np.asarray(rows)].astype(np.float64)
+    t = 1.0 - np.exp(-np.float64(alpha) * s) / m
+    return np.sum(t), np.min(t), np.max(t)
 
 
 class DeviceFeatures(_DeviceArray):
@@ -368,6 +395,8 @@ class CloudPair:
         self._selections, self._sel_wanted = {}, []
         self._counts, self._cnt_wanted = {}, []
         self._maps, self._map_wanted = {}, []
+        self._dens, self._dens_wanted = {}, []
+        self._density_rows = False          # a report asked for density-aware Chamfer rows: the searches keep the matched rows
         self._colours_on_device = [False, False]
         self._reflectance_on_device = [False, False]
         self._reflectance = False           # a report asked for the reflectance columns: the searches keep the matched rows
@@ -468,6 +497,7 @@ class CloudPair:
         new._selections, new._sel_wanted = {}, []
         new._counts, new._cnt_wanted = {}, []
         new._maps, new._map_wanted = {}, []
+        new._dens, new._dens_wanted = {}, []
         new._graph_id, new._last_wanted = None, None
         keep_self = bool(self.__dict__.get("_self_done")) and bool(getattr(eng, "keeps_self_search", False))
         self_total = self.__dict__.get("_totals", {}).get((nat.DIR_SELF, nat.METRIC_D1)) if keep_self else None
@@ -550,6 +580,7 @@ class CloudPair:
             eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or self.__dict__.get("_ssim", False)
                             or self.__dict__.get("_reflectance", False)        # (each point's reflectance against its matched point's)
                             or self.__dict__.get("_carry_normals", False)      # (the carry reads both directions' matched rows)
+                            or self.__dict__.get("_density_rows", False)       # (the match counts and the density map likewise)
                             or any(_has_colors(c) for c in self.clouds))
 
     def _colours_for_ties(self) -> None:
@@ -568,6 +599,7 @@ class CloudPair:
         self._selections = {}
         self._counts = {}
         self._maps = {}
+        self._dens = {}
         self._colour_red = {}
         if self._use_graph and self._last_wanted is not None and hasattr(eng, "graph_begin"):
             wants_self = "boundary" in self._last_wanted
@@ -704,6 +736,12 @@ class CloudPair:
         """options.check_chamfer / check_truncate for this pair."""
         self._check_unsharded("Chamfer and truncated-distance")
 
+    def _check_density(self) -> None:
+        """options.check_dcd for this pair: ValueError before any GPU work of a report."""
+        if self.ties == "mean":
+            raise ValueError("density-aware Chamfer rows are not defined under ties='mean': a virtual neighbour has no row to count")
+        self._check_unsharded("density-aware Chamfer")
+
     def _consumed(self, key, cache: dict, wanted, batches, method: str):
         """The answer to request ``key`` from the engine's ``method``, through ``cache``.  The first request a report asks for
         brings back the batch of eight (``batches(wanted)``) it was enqueued in (prefetch_reductions) in one call.  None: this
@@ -731,6 +769,22 @@ class CloudPair:
         the clamp)."""
         self._check_mapped()
         return self._consumed((direction, metric, which, x), self._maps, self._map_wanted, _map_batches, "reduce_map_total_many")
+
+    def _density(self, direction: int, alpha: float, squared: bool):
+        """``(sum, min, max)`` of the density-aware Chamfer terms of a whole D1 column, gathered, mapped and reduced on the GPU."""
+        self._check_density()
+        return self._consumed((direction, alpha, squared), self._dens, self._dens_wanted, _map_batches, "reduce_density_total_many")
+
+    def match_counts(self, is_left: bool = True) -> np.ndarray:
+        """How many points of the iterating cloud (left: the origin cloud) matched each point of the searched cloud:
+        ``np.bincount(matched rows, minlength=len(searched cloud))``, counted on the GPU (pccm_match_counts), uint32.  Ties go to
+        the smallest row (``ties="pick"``); ``1 - np.count_nonzero(counts) / n`` is the left density row at alpha = 0."""
+        self._check_density()
+        direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
+        if hasattr(self._engine, "match_counts"):
+            return self._engine.match_counts(direction)
+        n_searched = self._engine.n_iter(nat.DIR_RIGHT if is_left else nat.DIR_LEFT)
+        return np.bincount(self._neighbour_index(direction), minlength=n_searched).astype(np.uint32)
 
     def tie_exposure(self, is_left: bool = True, point_to_plane: bool = True) -> dict:
         """Opt-in diagnostic (not part of any report): how far the order of EXACT ties can move the point-to-plane MSE.
@@ -1124,7 +1178,8 @@ class CloudPair:
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
         ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
         ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)``, ``("within", is_left, tau)``,
-        ``("mapped", is_left, point_to_plane, root, clamp)`` (clamp: a number or None) and/or the string ``"boundary"``.
+        ``("mapped", is_left, point_to_plane, root, clamp)`` (clamp: a number or None), ``("density", is_left, alpha, squared)``
+        and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -1157,6 +1212,13 @@ class CloudPair:
         if mapped_items:
             self._check_mapped()
             wanted = [item for item in wanted if item not in mapped_items]     # (their columns are requests of their own, EuclideanDistance's)
+        density_items = [item for item in wanted if item[0] == "density"]
+        if density_items:
+            self._check_density()
+            wanted = [item for item in wanted if item not in density_items]    # (their columns are requests of their own, EuclideanDistance's)
+            if not self._density_rows:
+                self._density_rows = True
+                self._update_fusion()         # later searches keep the matched rows (this one's are recovered once)
         # point-to-distribution: the check, then the columns -- built here like the features, eagerly and outside any capture
         # (one build per neighbourhood size, with the union of what the report needs at that size)
         p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] in ("p2d", "p2d_color", "p2d_joint")]
@@ -1242,6 +1304,13 @@ class CloudPair:
             if column in requests:
                 which = (nat.MAP_CLAMP if clamp is not None else 0) | (nat.MAP_ROOT if root else 0)
                 maps.append(column + (which, 0.0 if clamp is None else float(clamp)))
+        # density-aware Chamfer rows: per direction and alpha one density map of the D1 column this report reduces, behind the
+        # direction's match counts (made once per search) -- up to eight, in one call
+        dens = []
+        for _, is_left, alpha, squared in density_items:
+            direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
+            if (direction, nat.METRIC_D1) in requests:
+                dens.append((direction, float(alpha) + 0.0, bool(squared)))
         # the reflectance columns join the first batch -- its k_point_jobs launch and its reduction launch -- when it has room
         # for them: eight columns, of which at most four are formed by point jobs (unfused D2, angular, reflectance)
         if reflectance_requests:
@@ -1252,6 +1321,7 @@ class CloudPair:
         self._sel_wanted = sorted(set(selections))
         self._cnt_wanted = sorted(set(counts)) if counts else []
         self._map_wanted = sorted(set(maps)) if maps else []
+        self._dens_wanted = sorted(set(dens)) if dens else []
         if not can_prefetch:
             return
         if hasattr(eng, "reduce_prefetch_many"):
@@ -1272,6 +1342,9 @@ class CloudPair:
             if self._map_wanted and hasattr(eng, "reduce_map_prefetch_many"):
                 for batch in _map_batches(self._map_wanted):
                     eng.reduce_map_prefetch_many(batch, self.normal_index)
+            if self._dens_wanted and hasattr(eng, "reduce_density_prefetch_many"):
+                for batch in _map_batches(self._dens_wanted):
+                    eng.reduce_density_prefetch_many(batch, self.normal_index)
         else:
             requests = requests + reflectance_requests + ssim_requests + p2d_requests
             for direction, metric in requests:

@@ -440,7 +440,8 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_refl, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state};
+                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_refl, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state,
+                      &ctx->match[0].buf, &ctx->match[1].buf};
     for (DevBuf *b : bufs) free_buf(*b);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
@@ -2387,11 +2388,74 @@ static int map_check(pccm_ctx *ctx, const char *who, int n, const int *dirs, con
     }, [](int, const Cloud &) { return PCCM_OK; });
 }
 
+// Where the matched rows of a direction's result are read (matched_row, pccm_internal.h): in place from records that carry them
+// (idx null), else from the plain idx column.  A search that left the rows out -- NNForm::kPair, pccm_nn_want_idx off;
+// kMatchedNoRows, the voxel-brick search -- is repeated with the rows on (ensure_plain, records_rewritten included; PCCM_E_STATE
+// during graph capture), as for the colour calls and pccm_carry_normals; records that have the rows are never unpacked for this.
+struct RowSource {
+    const int32_t *idx = nullptr;
+    const double *rec = nullptr;
+    int stride = 0;
+};
+static int row_source(pccm_ctx *ctx, NNResult &res, RowSource *out)
+{
+    int rc = res.form.rows_need_repeat() ? ensure_plain(ctx, res, true) : PCCM_OK;
+    if (rc) return rc;
+    if (res.form.has_rows()) *out = {nullptr, (const double *)res.rec.p, res.form.stride()};
+    else if (res.form.plain_ready(true)) *out = {res.idx, nullptr, 0};
+    else return fail(PCCM_E_STATE, "no matched rows to read");
+    return PCCM_OK;
+}
+
+// The match counts of direction dir (pccm_ctx::match): made once per search -- valid while their generation is the direction's --
+// by a memset and a launch of the carry's count pass on the stream.  A capture records both, and an op that gives the counts the
+// generation the replayed search leaves (graph_replay), once per captured search.
+static int match_counts_ensure(pccm_ctx *ctx, int dir, const Cloud &se, const NNResult &res, const RowSource &src)
+{
+    pccm_ctx::MatchCounts &mc = ctx->match[dir];
+    bool there = mc.gen == ctx->nn_gen[dir];
+    if (there && ctx->capturing) {                     // ... by this capture, behind its last search of the direction?
+        there = false;
+        for (size_t k = ctx->cap_ops.size(); k-- > 0 && !there;) {
+            const GraphOp &op = ctx->cap_ops[k];
+            if (op.dir != dir) continue;
+            if (op.kind == 1) break;
+            there = op.kind == 5;
+        }
+    }
+    if (there) return PCCM_OK;
+    const void *was = mc.buf.p;
+    int rc = ensure(ctx, mc.buf, (size_t)(se.n > 0 ? se.n : 1) * sizeof(uint32_t));
+    if (rc) return rc;
+    if (was && was != mc.buf.p) column_moved(ctx);
+    mc.gen = 0;
+    if ((rc = launch_match_counts(ctx, src.idx, src.rec, src.stride, res.end - res.begin, se.n, (uint32_t *)mc.buf.p))) return rc;
+    mc.gen = ctx->nn_gen[dir];
+    if (ctx->capturing) {
+        GraphOp op;
+        op.kind = 5;
+        op.dir = dir;
+        ctx->cap_ops.push_back(op);
+    }
+    return PCCM_OK;
+}
+
+static int map_enqueue(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps, const double *xs,
+                       const RowSource *rows);
+
 static int map_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps,
                         const double *xs)
 {
     int rc = map_check(ctx, who, n, dirs, metrics, normal_modes, maps, xs);
     if (rc) return rc;
+    return map_enqueue(ctx, n, dirs, metrics, normal_modes, maps, xs, nullptr);
+}
+
+// enqueue what is not enqueued yet of n checked requests; rows[d]: where a density map of direction d reads the matched rows
+static int map_enqueue(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps, const double *xs,
+                       const RowSource *rows)
+{
+    int rc;
     int64_t which[8];
     uint64_t bits[8];
     for (int i = 0; i < n; ++i) {
@@ -2428,6 +2492,7 @@ static int map_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, 
         UnitCol col = cslot[c]->job.c[0];
         col.map = maps[i];
         col.cap = (maps[i] & PCCM_MAP_CLAMP) ? xs[i] : 0.0;
+        col.alpha = (maps[i] & PCCM_MAP_DENSITY) ? xs[i] : 0.0;
         bind_outputs(col, SlotView(hs, m->host), false);
         if (open_job[c] >= 0) {                    // the second map over the fields the job already reads
             uj.j[open_job[c]].c[1] = col;
@@ -2438,6 +2503,12 @@ static int map_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, 
             U = cslot[c]->job;
             U.ncols = 1;
             U.c[0] = col; U.c[1] = col;
+            if (maps[i] & PCCM_MAP_DENSITY) {      // (a call's maps are all density maps or none is: a job's two columns agree)
+                const int d = dirs[i];
+                U.rows = rows[d].idx;
+                U.cnt = (const uint32_t *)ctx->match[d].buf.p;
+                U.cnt_rows = ctx->cloud[d == PCCM_DIR_LEFT ? 1 : 0].n;
+            }
             const int64_t lanes = (U.nunits * 8 + 255) / 256 * 256;
             uj.uoff[uj.njobs + 1] = uj.uoff[uj.njobs] + lanes;
             uj.toff[uj.njobs + 1] = uj.toff[uj.njobs] + U.tail_n;
@@ -2469,6 +2540,100 @@ int pccm_reduce_map_total_many(pccm_ctx *ctx, int n, const int *dirs, const int 
         return find_pending(ctx->map_slots, ctx->nn_gen, dirs[i], metrics[i], normal_modes[i], maps[i], map_cap_bits(maps[i], xs[i]));
     };
     return consume(ctx, n, "mapped-reduction slot lost", find, [&](int i, MapSlot &m) { slot_total(m.shape, SlotView(m.shape, m.host), out + 3 * i); });
+}
+
+// ---- match counts and the density-aware Chamfer terms (include/pccm.h) -------------------------------------------------------
+// A density request is a mapped reduction of the direction's D1 column whose map is PCCM_MAP_DENSITY, with PCCM_MAP_ROOT in front
+// of it unless `squared`, and whose key is alpha: it lives in the mapped-reduction slots and shares their life cycle.  In front of
+// the mapped launch go, per direction and where the search's are not there yet, the match counts.
+static int density_maps(int n, const int *dirs, const int *squared, const double *alphas, int *metrics, int *modes, int *maps)
+{
+    if (n < 0 || n > 8 || (n > 0 && (!dirs || !squared || !alphas))) return fail(PCCM_E_ARG, "0..8 requests expected");
+    for (int i = 0; i < n; ++i) {
+        metrics[i] = PCCM_METRIC_D1;
+        modes[i] = PCCM_NORMAL_ROW;
+        maps[i] = PCCM_MAP_DENSITY | (squared[i] ? 0 : PCCM_MAP_ROOT);
+    }
+    return PCCM_OK;
+}
+
+static int density_ties_check(const pccm_ctx *ctx, int dir)
+{
+    if (ctx->nn[dir].ties == PCCM_TIES_MEAN)
+        return fail(PCCM_E_STATE, "the search of direction %d ran under PCCM_TIES_MEAN: a virtual neighbour has no row to count", dir);
+    return PCCM_OK;
+}
+
+static int density_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *squared, const double *alphas, int *metrics,
+                            int *modes, int *maps)
+{
+    int rc = density_maps(n, dirs, squared, alphas, metrics, modes, maps);
+    if (!rc)
+        rc = request_check(ctx, who, "density reductions", n, true, dirs, metrics, [&](int i) {
+            if (squared[i] != 0 && squared[i] != 1) return fail(PCCM_E_ARG, "squared is 0 or 1, not %d", squared[i]);
+            if (!(alphas[i] >= 0.0) || alphas[i] == INFINITY) return fail(PCCM_E_ARG, "alpha is a finite number >= 0");
+            return PCCM_OK;
+        }, [&](int i, const Cloud &) { return density_ties_check(ctx, dirs[i]); });
+    if (rc || n == 0) return rc;
+    // the rows first (a repeated search rewrites the records the columns are bound to), then the counts, then the columns
+    RowSource rows[2];
+    bool seen[2] = {false, false};
+    for (int i = 0; i < n; ++i) {
+        const int d = dirs[i];
+        if (seen[d]) continue;
+        seen[d] = true;
+        const Cloud *it, *se;
+        NNResult *res;
+        if ((rc = need_nn(ctx, d, &it, &se, &res)) || (rc = row_source(ctx, *res, &rows[d]))) return rc;
+    }
+    for (int d = 0; d < 2; ++d) {
+        if (!seen[d]) continue;
+        const Cloud *it, *se;
+        NNResult *res;
+        if ((rc = need_nn(ctx, d, &it, &se, &res)) || (rc = match_counts_ensure(ctx, d, *se, *res, rows[d]))) return rc;
+    }
+    return map_enqueue(ctx, n, dirs, metrics, modes, maps, alphas, rows);
+}
+
+int pccm_reduce_density_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *squared, const double *alphas)
+{
+    CHECK_CTX(ctx);
+    int metrics[8], modes[8], maps[8];
+    return density_prefetch(ctx, "pccm_reduce_density_prefetch_many", n, dirs, squared, alphas, metrics, modes, maps);
+}
+
+int pccm_reduce_density_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *squared, const double *alphas, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    int metrics[8], modes[8], maps[8];
+    int rc = density_prefetch(ctx, "pccm_reduce_density_total_many", n, dirs, squared, alphas, metrics, modes, maps);
+    if (rc || n == 0) return rc;
+    auto find = [&](int i) {
+        return find_pending(ctx->map_slots, ctx->nn_gen, dirs[i], metrics[i], modes[i], maps[i], map_cap_bits(maps[i], alphas[i]));
+    };
+    return consume(ctx, n, "mapped-reduction slot lost", find, [&](int i, MapSlot &m) { slot_total(m.shape, SlotView(m.shape, m.host), out + 3 * i); });
+}
+
+int pccm_match_counts(pccm_ctx *ctx, int dir, uint32_t *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (dir != PCCM_DIR_LEFT && dir != PCCM_DIR_RIGHT) return fail(PCCM_E_ARG, "match counts exist for directions 0 and 1, not %d", dir);
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "pccm_match_counts needs the whole column on this GPU (world = 1)");
+    const Cloud *it, *se;
+    NNResult *res;
+    RowSource rows;
+    int rc = need_nn(ctx, dir, &it, &se, &res);
+    if (!rc) rc = density_ties_check(ctx, dir);
+    if (!rc) rc = row_source(ctx, *res, &rows);
+    if (!rc) rc = match_counts_ensure(ctx, dir, *se, *res, rows);
+    if (rc) return rc;
+    if (se->n > 0 && (rc = d2h(ctx, out, ctx->match[dir].buf.p, (size_t)se->n * sizeof(uint32_t)))) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    return check_device_errors(ctx);
 }
 
 // Host helper for the colour metrics (metric.py:261-290): out[r] = M * rgb[r] for the BT.709 "ycc" (1) or
@@ -2569,6 +2734,8 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
             ctx->nn_gen[op.dir]++;
             ctx->nn[op.dir].valid = true;
             ctx->nn[op.dir].form = op.form;
+        } else if (op.kind == 5) {                                   // (the graph counts again, behind the search)
+            ctx->match[op.dir].gen = ctx->nn_gen[op.dir];
         } else if (op.kind >= 2) {                                   // (in order: a slot takes the generation a kind 1 op before it left)
             int rc = std::visit([&](const auto &snap) { return slot_replay(ctx, table_of(ctx, snap)[op.slot], snap); }, op.snap);
             if (rc) return rc;
@@ -2627,7 +2794,7 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     g.valid = true;
     // the captured calls changed the host bookkeeping but nothing ran yet: run the graph once now
     for (auto &op : g.ops)
-        if (op.kind >= 2) std::visit([&](const auto &snap) { rearm(table_of(ctx, snap)[op.slot], ctx, snap.key.wait_seq); }, op.snap);
+        if (op.kind >= 2 && op.kind <= 4) std::visit([&](const auto &snap) { rearm(table_of(ctx, snap)[op.slot], ctx, snap.key.wait_seq); }, op.snap);
     ctx->batches_issued += g.batches;
     PCCM_HIP(hipGraphLaunch(g.exec, ctx->stream));
     PCCM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));

@@ -30,6 +30,8 @@ __host__ __device__ constexpr int64_t whole_waves(int64_t rows) { return (rows +
 // cnt[n_to], fill[n_to], base[n_to], list[n_from], queue[n_from / (kCarryLong + 1) + 1]
 struct CarryView {
     const int32_t *nn_f, *nn_g;     // nn_F [n_from]: matched rows of the direction that iterates the source cloud; nn_G [n_to] or null
+    const double *rec;              // the count pass alone (launch_match_counts): nn_F null -- the rows are read in place from
+    int rec_stride;                 // these result records (matched_row, pccm_internal.h)
     const double *src;              // the source rows [n_from][nc]: normals or colours (nc 3), or a scalar column (nc 1)
     double *out;                    // the target rows [n_to][nc]
     int nc;
@@ -44,6 +46,8 @@ static CarryView carry_view(const int32_t *nn_f, const int32_t *nn_g, const doub
     V.nc = nc;
     V.nn_f = nn_f;
     V.nn_g = nn_g;
+    V.rec = nullptr;
+    V.rec_stride = 0;
     V.src = src;
     V.out = out;
     V.n_from = n_from;
@@ -90,7 +94,7 @@ __device__ __forceinline__ void carry_count(const CarryView &V, int64_t i, int l
     // every row's add on the same few words
     int32_t j = -1;
     if (i < V.n_from) {
-        j = V.nn_f[i];
+        j = matched_row(V.nn_f, V.rec, V.rec_stride, i);
         if (j < 0 || (int64_t)j >= V.n_to) j = -1;                  // (no search writes such a row)
     }
     unsigned long long todo = __ballot(j >= 0);
@@ -262,6 +266,27 @@ int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const 
     PCCM_LAUNCH(ctx, k_carry_place, blocks(whole_waves(n_to)), dim3(256), 0, ctx->stream, V);
     PCCM_LAUNCH(ctx, k_carry_scatter_walk, blocks(whole_waves(n_from) + walk_lanes), dim3(256), 0, ctx->stream, V);
     PCCM_LAUNCH(ctx, k_carry_sum, blocks(whole_waves(n_to)), dim3(256), 0, ctx->stream, V);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+// A direction's match counts (pccm_match_counts, the density map of k_unit_jobs): the count pass above on its own -- cnt zeroed on
+// the stream, then k_carry_count over the shard's rows padded to whole waves.  Of the view only the rows' source, the two row
+// counts and cnt are read.
+int launch_match_counts(pccm_ctx *ctx, const int32_t *idx, const double *rec, int stride, int64_t ns, int64_t n_to, uint32_t *cnt)
+{
+    if (n_to <= 0) return PCCM_OK;
+    ProfScope ps(ctx, PCCM_K_POINT);
+    PCCM_HIP(hipMemsetAsync(cnt, 0, (size_t)n_to * sizeof(uint32_t), ctx->stream));
+    if (ns <= 0) return PCCM_OK;
+    CarryView V = {};
+    V.nn_f = idx;
+    V.rec = rec;
+    V.rec_stride = stride;
+    V.n_from = ns;
+    V.n_to = n_to;
+    V.cnt = cnt;
+    PCCM_LAUNCH(ctx, k_carry_count, dim3((unsigned)((whole_waves(ns) + 255) / 256)), dim3(256), 0, ctx->stream, V);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

@@ -224,9 +224,12 @@ struct UnitCol {                // one column reduced from a job's array
     double *out_blocks;         // pinned host memory [3][nblocks] per-32-leaf tree sum/min/max
     double *out_tail;           // pinned host memory [tail_n]
     // a map applied to the value behind the pick and the square (k_unit_jobs alone: reduce_shape() gives a mapped job no lean
-    // kernel): PCCM_MAP_CLAMP -- min(value, cap) -- then PCCM_MAP_ROOT -- the correctly rounded square root; 0: none
+    // kernel): PCCM_MAP_CLAMP -- min(value, cap) -- then PCCM_MAP_ROOT -- the correctly rounded square root -- then
+    // PCCM_MAP_DENSITY -- 1 - exp(-alpha value) / m, m the match count of the row's matched row (UnitJob::rows / cnt; never
+    // with a clamp); 0: none
     int map = 0;
     double cap = 0.0;
+    double alpha = 0.0;
 };
 struct UnitJob {                // one per-point array to reduce (k_unit_jobs): up to two columns per pass
     const double *val;          // plain column (stride 1) or the result records (stride 2 or 4 doubles)
@@ -246,6 +249,11 @@ struct UnitJob {                // one per-point array to reduce (k_unit_jobs): 
     int64_t ns, nunits;
     int64_t tail_first, tail_n; // rows [tail_first, tail_first + tail_n) are copied out raw
     int64_t nblocks;            // ceil(nunits / 32)
+    // PCCM_MAP_DENSITY: where the matched row of shard row i is read (matched_row below: the plain idx column, or null -- the
+    // records `val` of stride 2 or 4) and the direction's match counts [cnt_rows] (pccm_ctx::match), gathered through it
+    const int32_t *rows = nullptr;
+    const uint32_t *cnt = nullptr;
+    int64_t cnt_rows = 0;
 };
 
 // the shape SlotShape describes, as the kernels are told it: a job's rows, units and tail ...
@@ -306,7 +314,7 @@ struct SelectSlot : SlotKey, SelectWhat {
 struct MapWhat {
     SlotShape shape;
     int map = 0;
-    uint64_t cap_bits = 0;     // map_cap_bits(map, cap)
+    uint64_t cap_bits = 0;     // map_cap_bits(map, cap) (PCCM_MAP_DENSITY: of alpha)
 };
 struct MapSlot : SlotKey, MapWhat, SlotHost {      // (host: shape.host_doubles() doubles at least)
     using What = MapWhat;
@@ -324,7 +332,7 @@ struct ProfSpan {
 
 struct GraphOp {               // host-side effect of one captured call, replayed by pccm_graph_launch
     int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch / count_prefetch(slot),
-                               // 4 reduce_map_prefetch(slot)
+                               // 4 reduce_map_prefetch / reduce_density_prefetch(slot), 5 match counts(dir)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
     // kinds 2, 3, 4 (2 + index()): the slot's key and description at capture time (pccm_slot.h)
@@ -454,6 +462,12 @@ struct pccm_ctx {
     // the clamp and the clamped root of both directions)
     static constexpr int kMapSlots = 32;
     pccm::MapSlot map_slots[kMapSlots];
+    // match counts (pccm_match_counts, the density-aware Chamfer terms): per direction 0 / 1 one uint32 per row of the SEARCHED
+    // cloud -- how many shard rows matched it --, made once per search and valid while gen equals nn_gen[dir] (0: not made)
+    struct MatchCounts {
+        pccm::DevBuf buf;
+        uint64_t gen = 0;
+    } match[2];
     uint64_t nn_gen[3] = {1, 1, 1};
     // hipGraph capture of a step (pccm_graph_*): epoch changes whenever inputs, shard or any device
     // buffer a captured kernel may reference changes, which invalidates every recorded graph
@@ -636,6 +650,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)
     return v;
 }
 
+// The matched row of shard row i of a direction's result, read where the search left it: the plain idx column (the brute-force
+// engine; results unpacked by ensure_plain), or -- idx null -- in place from the result records: the row word of a matched record
+// (stride 2, NNForm::kMatched: rec.w, as matched_fields reads it) or the row field of a pair record (stride 4,
+// NNForm::kPairRows: the low word of field 2, as k_unpack reads it).  The match-count pass and the density map both read through it.
+__device__ __forceinline__ int32_t matched_row(const int32_t *idx, const double *rec, int stride, int64_t i)
+{
+    if (idx) return idx[i];
+    if (stride == 4) return *reinterpret_cast<const int32_t *>(rec + 4 * i + 2);
+    return __float_as_int(reinterpret_cast<const float4 *>(rec)[i].w);
+}
+
 // PCCM_METRIC_ANGULAR of one pair of normals (include/pccm.h): every operation separately rounded, as NumPy's element-wise ops
 __device__ __forceinline__ double angular_similarity(const double *a, const double *b)
 {
@@ -777,6 +802,9 @@ size_t carry_ws_bytes(int64_t n_from, int64_t n_to);
 // nc: the doubles per row of n_from64 and out -- 3 (normals, colours) or 1 (a scalar column: the reflectance)
 int launch_carry(pccm_ctx *ctx, const int32_t *nn_f, const int32_t *nn_g, const double *n_from64, int64_t n_from, int64_t n_to,
                  uint32_t *ws, double *out, int nc);
+// the carry's count pass alone, for a direction's match counts: cnt [n_to] zeroed on the stream (a memset), then k_carry_count
+// over the ns shard rows, whose matched rows are read through matched_row(idx, rec, stride, i)
+int launch_match_counts(pccm_ctx *ctx, const int32_t *idx, const double *rec, int stride, int64_t ns, int64_t n_to, uint32_t *cnt);
 inline size_t merge_ws_bytes(int64_t n) { return merge_layout(n).bytes(); }
 // pccm_merge_duplicates on the stream, in two halves with the caller's read of n' (head[0] of the workspace's words) between them:
 // table filled, insert | find | the two scans; then -- rows were merged away -- the gather into `out` (rgb: the colours to keep

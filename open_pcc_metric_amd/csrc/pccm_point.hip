@@ -249,8 +249,12 @@ int launch_point_jobs(pccm_ctx *ctx, const PointJobs &jobs)
 struct UnitView {               // the fields of a job the inner loop needs, in registers (wave-uniform)
     const double *val;
     int stride, off0, off1, sq0, sq1;
-    int map0, map1;             // UnitCol::map / cap of the two columns
+    int map0, map1;             // UnitCol::map / cap / alpha of the two columns
     double cap0, cap1;
+    double alpha0, alpha1;
+    const int32_t *rows;        // UnitJob::rows / cnt / cnt_rows (PCCM_MAP_DENSITY)
+    const uint32_t *cnt;
+    int64_t cnt_rows;
     int defer;                  // UnitJob::defer
     int64_t nrm_rows;           // UnitJob::nrm_rows
     const double *nrm64;
@@ -301,6 +305,8 @@ __device__ __forceinline__ UnitView unit_view(const UnitJob &J)
     w.sq0 = J.c[0].square; w.sq1 = J.c[1].square;
     w.map0 = J.c[0].map; w.map1 = J.c[1].map;
     w.cap0 = J.c[0].cap; w.cap1 = J.c[1].cap;
+    w.alpha0 = J.c[0].alpha; w.alpha1 = J.c[1].alpha;
+    w.rows = J.rows; w.cnt = J.cnt; w.cnt_rows = J.cnt_rows;
     w.defer = J.defer; w.nrm64 = J.nrm64; w.nrm32 = J.nrm32; w.q32 = J.q32; w.row0 = J.row0; w.nrm_rows = J.nrm_rows;
     return w;
 }
@@ -318,16 +324,36 @@ __device__ __forceinline__ void unit_load(const UnitView &J, int64_t i, double v
     }
 }
 
+// PCCM_MAP_DENSITY: the density-aware Chamfer term of s (the distance, or its square) for a row whose matched row m rows share --
+// 1 - exp(-alpha s) / m, every operation but the fp64 exp correctly rounded and in this order (include/pccm.h)
+__device__ __forceinline__ double unit_density(double alpha, double s, uint32_t m)
+{
+    const double e = exp(__dmul_rn(-alpha, s));
+    return __dsub_rn(1.0, __ddiv_rn(e, (double)m));
+}
+
 // f(value) of a mapped column: the clamp is np.minimum(value, cap) for the NaN-free columns the map is defined on, the root
-// the correctly rounded one (np.sqrt), in this order
-__device__ __forceinline__ double unit_map(int map, double cap, double v)
+// the correctly rounded one (np.sqrt), the density term the one above (m: the row's match count), in this order
+__device__ __forceinline__ double unit_map(int map, double cap, double alpha, double v, uint32_t m)
 {
     if (map & PCCM_MAP_CLAMP) v = (v < cap) ? v : cap;
     if (map & PCCM_MAP_ROOT) v = __dsqrt_rn(v);
+    if (map & PCCM_MAP_DENSITY) v = unit_density(alpha, v, m);
     return v;
 }
 
-__device__ __forceinline__ void unit_pick(const UnitView &J, double v[2])                 // fields -> the job's columns
+// a density job (wave-uniform), and the match count its row i gathers: through the matched row, read where the search left it
+__device__ __forceinline__ bool unit_dense(const UnitView &J) { return ((J.map0 | J.map1) & PCCM_MAP_DENSITY) != 0; }
+__device__ __forceinline__ int32_t unit_row(const UnitView &J, int64_t i) { return matched_row(J.rows, J.val, J.stride, i); }
+__device__ __forceinline__ uint32_t unit_count_of(const UnitView &J, int32_t row)
+{
+    // (a row outside the searched cloud cannot be in a result the searches wrote: clamped all the same, as matched_fields does)
+    const int64_t r = row < 0 ? 0 : ((int64_t)row >= J.cnt_rows ? J.cnt_rows - 1 : (int64_t)row);
+    return J.cnt[r];
+}
+
+// fields -> the job's columns (m: the row's match count, read by a density map alone)
+__device__ __forceinline__ void unit_pick(const UnitView &J, double v[2], uint32_t m = 1u)
 {
     if (J.stride >= 2) {
         const double x = v[0], y = v[1];
@@ -337,10 +363,11 @@ __device__ __forceinline__ void unit_pick(const UnitView &J, double v[2])       
     if (J.sq0) v[0] = __dmul_rn(v[0], v[0]);
     if (J.sq1) v[1] = __dmul_rn(v[1], v[1]);
     // the map mode (UnitCol::map): np.sum(f(column)) without the column.  Behind one wave-uniform branch on both columns' maps,
-    // so that a job without one -- every job but pccm_reduce_map_*'s -- passes with a single scalar test per value
+    // so that a job without one -- every job but pccm_reduce_map_*'s and pccm_reduce_density_*'s -- passes with a single scalar test
+    // per value
     if (J.map0 | J.map1) {
-        v[0] = unit_map(J.map0, J.cap0, v[0]);
-        v[1] = unit_map(J.map1, J.cap1, v[1]);
+        v[0] = unit_map(J.map0, J.cap0, J.alpha0, v[0], m);
+        v[1] = unit_map(J.map1, J.cap1, J.alpha1, v[1], m);
     }
 }
 
@@ -584,7 +611,11 @@ struct UnitCols {
     __device__ __forceinline__ bool live(int c) const { return c < ncols; }
     static __device__ __forceinline__ double min(double a, double b) { return fmin(a, b); }
     static __device__ __forceinline__ double max(double a, double b) { return fmax(a, b); }
-    __device__ __forceinline__ void one(int64_t i, double v[2]) const { unit_load(V, i, v); unit_pick(V, v); }
+    __device__ __forceinline__ void one(int64_t i, double v[2]) const
+    {
+        unit_load(V, i, v);
+        unit_pick(V, v, unit_dense(V) ? unit_count_of(V, unit_row(V, i)) : 1u);
+    }
     __device__ __forceinline__ void leaf(int64_t base, int k, double v[kLeaf / 8][2]) const
     {
         __builtin_assume((base & (kLeaf - 1)) == 0 && k >= 0 && k < 8);       // (see LeanCols::leaf)
@@ -602,6 +633,19 @@ struct UnitCols {
         } else {
 #pragma unroll
             for (int j = 0; j < kLeaf / 8; ++j) v[j][0] = v[j][1] = V.val[base + 8 * j + k];
+        }
+        if (unit_dense(V)) {
+            // the density map: the sixteen rows come with (or beside) the sixteen records above, then the sixteen gathers of
+            // their counts go out together -- no gather waits on its own record alone
+            int32_t row[kLeaf / 8];
+            uint32_t m[kLeaf / 8];
+#pragma unroll
+            for (int j = 0; j < kLeaf / 8; ++j) row[j] = unit_row(V, base + 8 * j + k);
+#pragma unroll
+            for (int j = 0; j < kLeaf / 8; ++j) m[j] = unit_count_of(V, row[j]);
+#pragma unroll
+            for (int j = 0; j < kLeaf / 8; ++j) unit_pick(V, v[j], m[j]);
+            return;
         }
 #pragma unroll
         for (int j = 0; j < kLeaf / 8; ++j) unit_pick(V, v[j]);

@@ -4,12 +4,14 @@
 // The products: the searches' results (NNResult::valid, NNForm::fused), normals carried to a cloud (pccm_ctx::carry), the
 // merge maps (merge_n), PointSSIM features (Cloud::ssim_attrs / ssim_k), point spacings (Cloud::res_k), the point-to-distribution
 // columns (p2d_k, p2d_color), a cloud's reflectance (Cloud::n_refl), and everything keyed on a counter: pending reductions, selections and counts, tie columns, the colour memo,
+// the directions' match counts (pccm_ctx::match),
 // captured graphs, grid caches.  What ESTABLISHES a product stays with its builder (ssim_attrs = attrs, res_k = K, p2d_k = k,
 // carry.to = to, merge_n = n, valid = true, form = ...).
 //
 // The counters.  Each is only ever compared for equality with a copy taken earlier; each counts one thing:
 //   nn_gen[d]  whatever a reduction, selection or count of direction d reads has changed: the result itself, or normals, features and
-//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, mapped reductions, selections, counts), TieCols::gen, ColorMemo::gen.
+//              stored columns under a result that stays.  Copies: SlotKey::gen (reductions, mapped reductions, selections, counts), TieCols::gen, ColorMemo::gen,
+//              MatchCounts::gen (the counts read the matched rows alone: a bump for normals or features recounts them needlessly, never wrongly).
 //   nn_run[d]  searches of direction d (prepare_nn alone bumps it): WHICH result the direction holds.  Copies: Carry::run_f / run_g.
 //   nrm_gen    any cloud's normals changed.  Copies: TieCols::nrm_gen / ang_gen.
 //   rgb_gen    any cloud's colours changed.  Copies: TieCols::rgb_gen, ColorMemo::rgb_gen.
@@ -71,7 +73,7 @@ inline void column_rebuild(pccm_ctx *ctx, Stored col, int which = 0)
     for (int d = 0; d < ndirs; ++d) ctx->nn_gen[d]++;
 }
 
-// ... and its buffer was reallocated on the way: captured graphs that read the old one are stale
+// ... and its buffer was reallocated on the way (the match counts' buffer likewise): captured graphs that read the old one are stale
 inline void column_moved(pccm_ctx *ctx) { ctx->epoch++; }
 
 // forget the content, keep the allocations

@@ -4,7 +4,7 @@
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
                                   [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
                                   [--resolution-psnr] [--resolution-neighbours K] [--reflectance] [--reflectance-peak P] [--fscore TAU ...]
-                                  [--chamfer] [--truncate TAU ...] [--csv]
+                                  [--chamfer] [--truncate TAU ...] [--dcd ALPHA ...] [--dcd-squared] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -53,7 +53,12 @@ after those, the mean UNSQUARED nearest-neighbour distance of each direction (wi
 the projection), Chamfer-L1 -- their average over the two directions, PCN's convention -- and Chamfer-L2, the sum of the two D1
 GeoMSE rows.  ``--truncate TAU`` (repeatable, TAU >= 0; no counterpart in the reference) adds, last, the mean squared distance with
 every distance clipped at TAU -- and with ``--chamfer`` the clipped mean distance --, the remedy for partly overlapping clouds; all
-of them are summed inside the reduction kernel, no column is stored ("Chamfer and truncated distances").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+of them are summed inside the reduction kernel, no column is stored ("Chamfer and truncated distances").  ``--dcd ALPHA`` (repeatable, ALPHA >= 0; no counterpart in the reference) adds,
+after every other row, the density-aware Chamfer distance of Wu et al. (NeurIPS 2021): per direction the mean of
+1 - exp(-ALPHA d) / m over a cloud's points -- d the distance to the matched point, m the number of points that share it, counted on
+the GPU -- and the average of the two directions; every row lies in [0, 1], and a cloud that piles its points onto a few places is
+penalised where the Chamfer distance is blind.  ``--dcd-squared`` feeds d^2 in d's place; ``--ties mean`` with ``--dcd`` is a usage
+error ("Density-aware Chamfer distance").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -126,6 +131,13 @@ import click
               help="Report the mean squared distance with every distance clipped at this threshold (>= 0, in the clouds' units) as "
                    "well (may be repeated, at most 4), after all other rows; with --chamfer also the clipped mean distance.  For "
                    "partly overlapping clouds.")
+@click.option("--dcd", "dcd", type=float, multiple=True, metavar="ALPHA",
+              help="Report the density-aware Chamfer distance at this alpha (>= 0, in 1 / the clouds' units) as well (may be "
+                   "repeated, at most 4), after all other rows: per direction the mean of 1 - exp(-ALPHA d) / m, d the distance "
+                   "to the matched point and m the number of points that share it, and the average of both directions; in "
+                   "[0, 1], lower is better.  ALPHA = 0: the share of points that share their matched point.  Not with --ties mean.")
+@click.option("--dcd-squared", "dcd_squared", required=False, is_flag=True,
+              help="With --dcd: feed the squared distance d^2 in d's place.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -140,12 +152,12 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, dcd, dcd_squared, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import (CalculateOptions, check_carry_normals, check_chamfer, check_duplicates, check_fscore, check_hausdorff_rank, check_p2d_color, check_point_ssim,
+    from .options import (CalculateOptions, check_carry_normals, check_chamfer, check_dcd, check_duplicates, check_fscore, check_hausdorff_rank, check_p2d_color, check_point_ssim,
                           check_point_to_distribution, check_reflectance, check_resolution_psnr, check_truncate, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
@@ -155,7 +167,8 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
                                    p2d_color=p2d_color, resolution_psnr=resolution_psnr,
                                    resolution_neighbours=resolution_neighbours, reflectance=reflectance,
                                    reflectance_peak=reflectance_peak, fscore=fscore or None, chamfer=chamfer,
-                                   truncate=truncate or None)
+                                   truncate=truncate or None, dcd=dcd or None, dcd_squared=dcd_squared)
+        check_dcd(options, ties=ties)
         check_carry_normals(carry_normals, ties=ties)
         check_duplicates(duplicates)
     except ValueError as exc:

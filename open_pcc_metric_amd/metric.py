@@ -50,7 +50,8 @@ class SecondaryMetric(AbstractMetric):               # metric.py:41-50 -- pure f
     _pccm_role = 2
     _pccm_item = None       # what the calculator tells CloudPair.prefetch_reductions about this node: "column" (EuclideanDistance),
     #                         "ranked" (GeoRankedHausdorffDistance), "within" (GeoInlierRatio), "mapped" (GeoMeanDistance,
-    #                         GeoTruncatedMSE, GeoTruncatedMeanDistance: _mapped_request() says which map); subclasses inherit it
+    #                         GeoTruncatedMSE, GeoTruncatedMeanDistance: _mapped_request() says which map), "density"
+    #                         (GeoDensityAwareDistance); subclasses inherit it
 
     def _get_dependencies(self) -> typing.Dict[str, "AbstractMetric"]:
         return {}
@@ -196,6 +197,20 @@ class ReflectanceErrors(PrimaryMetric, DirectionalMetric):       # no counterpar
     PCCM_METRIC_REFLECTANCE; INTEGRATION.md, "Reflectance"): (a - b)^2 on the values as given."""
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, cloud_pair.get_left_reflectance_errors, cloud_pair.get_right_reflectance_errors)
+
+
+class MatchedRows(PrimaryMetric, DirectionalMetric):             # no counterpart in the reference (options.py: dcd)
+    """Which row of the searched cloud every point of the iterating cloud matched (ties: the smallest row).  For a pair whose
+    results live in HBM the value is the direction's lazy DeviceRows -- a handle on the result that is never copied to the host:
+    the match counts and the density map read the rows where the search left them -- and for any other pair the plain index
+    array."""
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        getter = getattr(cloud_pair, "get_left_error_vector" if self.is_left else "get_right_error_vector", None)
+        rows = getter() if getter is not None else None
+        if isinstance(rows, DeviceRows):
+            self.value = rows
+        else:
+            self.value = np.asarray(cloud_pair._neighbour_index(0 if self.is_left else 1))
 
 
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
@@ -439,6 +454,57 @@ class GeoTruncatedMSE(SecondaryMetric, DirectionalMetric):       # no counterpar
 class GeoTruncatedMeanDistance(GeoTruncatedMSE):                 # no counterpart in the reference (options.py: chamfer + truncate)
     """... and the mean unsquared distance clipped at ``threshold``: np.sum(np.sqrt(np.minimum(column, threshold * threshold))) / n."""
     _root = True
+
+
+class GeoDensityAwareDistance(SecondaryMetric, DirectionalMetric):   # no counterpart in the reference (options.py: dcd)
+    """One direction of the density-aware Chamfer distance (Wu et al., NeurIPS 2021; INTEGRATION.md, "Density-aware Chamfer
+    distance"): the mean over the iterating cloud's points of 1 - exp(-alpha * s) / m, s the distance to the matched point
+    (``squared``: its square) and m the number of points that share that matched point.  In [0, 1]; at alpha = 0 it is
+    1 - (distinct matched rows) / n."""
+    _pccm_waits = True      # reads a mapped reduction back from the GPU: the calculator evaluates these last
+    _pccm_item = "density"
+
+    def __init__(self, is_left: bool, alpha: float, squared: bool = False):
+        super().__init__(is_left)
+        self.alpha = float(alpha) + 0.0
+        self.squared = bool(squared)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.alpha, self.squared)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"euclidean_distance": EuclideanDistance(is_left=self.is_left, point_to_plane=False),
+                "matched_rows": MatchedRows(is_left=self.is_left)}
+
+    def calculate(self, euclidean_distance: EuclideanDistance, matched_rows: MatchedRows) -> None:
+        column = euclidean_distance.value
+        density = getattr(column, "density", None)            # a device column: counted, gathered and summed in HBM
+        if density is not None:
+            total = density(self.alpha, self.squared)[0]
+        else:
+            d2 = np.asarray(column, dtype=np.float64)
+            idx = np.asarray(matched_rows.value)
+            m = np.bincount(idx)
+            s = d2 if self.squared else np.sqrt(d2)
+            total = np.sum(1.0 - np.exp(-np.float64(self.alpha) * s) / m[idx].astype(np.float64))
+        self.value = total / column.shape[0]
+
+
+class GeoDensityAwareChamfer(SecondaryMetric):                   # no counterpart in the reference (options.py: dcd)
+    """The density-aware Chamfer distance: the average of the two directions' rows."""
+    def __init__(self, alpha: float, squared: bool = False):
+        self.alpha = float(alpha) + 0.0
+        self.squared = bool(squared)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.alpha, self.squared)
+
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"left": GeoDensityAwareDistance(is_left=True, alpha=self.alpha, squared=self.squared),
+                "right": GeoDensityAwareDistance(is_left=False, alpha=self.alpha, squared=self.squared)}
+
+    def calculate(self, left: GeoDensityAwareDistance, right: GeoDensityAwareDistance) -> None:
+        self.value = (np.float64(left.value) + np.float64(right.value)) / np.float64(2)
 
 
 class _OverAngular(SecondaryMetric, DirectionalMetric):

@@ -77,6 +77,12 @@ points without a counterpart otherwise dominate every mean), after every row abo
   threshold tau                GeoTruncatedMSE L/R/sym (D1: the mean of min(d^2, tau^2))
   threshold tau & chamfer      GeoTruncatedMeanDistance L/R/sym (D1: the mean of min(d, tau))
 
+and, with ``dcd`` (no counterpart in the reference: the density-aware Chamfer distance of Wu et al., NeurIPS 2021 -- every point's
+term 1 - exp(-alpha d) / m, m the number of points that share its matched point; ``dcd_squared`` puts d^2 in d's place), after
+every row above, truncated rows included, for each alpha in ascending order:
+
+  alpha                        GeoDensityAwareDistance L, GeoDensityAwareDistance R, GeoDensityAwareChamfer ((L + R) / 2; no symmetric row)
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -88,7 +94,7 @@ import math
 import numbers
 
 from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
-                     GeoChamferL1, GeoChamferL2, GeoMeanDistance, GeoTruncatedMeanDistance, GeoTruncatedMSE, GeoFScore, GeoInlierRatio, GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
+                     GeoChamferL1, GeoChamferL2, GeoDensityAwareChamfer, GeoDensityAwareDistance, GeoMeanDistance, GeoTruncatedMeanDistance, GeoTruncatedMSE, GeoFScore, GeoInlierRatio, GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
                      GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
                      JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
                      MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
@@ -99,6 +105,7 @@ SSIM_MIN_K, SSIM_MAX_K = 2, 64
 MAX_HAUSDORFF_RANKS = 4
 MAX_FSCORE_THRESHOLDS = 4
 MAX_TRUNCATE_THRESHOLDS = 4
+MAX_DCD_ALPHAS = 4
 P2D_MIN_K, P2D_MAX_K = 4, 64
 RESOLUTION_MIN_K, RESOLUTION_MAX_K = 1, 63
 
@@ -124,7 +131,7 @@ def _hausdorff_ranks(value) -> typing.Tuple[float, ...]:
 
 
 def _distance_thresholds(value, name: str, most: int) -> typing.Tuple[float, ...]:
-    """A distance-threshold option (``fscore``, ``truncate``) as a sorted tuple of distinct finite floats >= 0; ValueError for
+    """A distance-threshold option (``fscore``, ``truncate``; the alphas of ``dcd`` obey the same rules) as a sorted tuple of distinct finite floats >= 0; ValueError for
     anything else."""
     if value is None:
         return ()
@@ -159,7 +166,7 @@ class CalculateOptions:
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
                  p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10,
                  reflectance: bool = False, reflectance_peak: float = 65535.0, fscore=None, chamfer: bool = False,
-                 truncate=None):
+                 truncate=None, dcd=None, dcd_squared: bool = False):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -200,6 +207,10 @@ class CalculateOptions:
         self.fscore = _fscore_thresholds(fscore)
         self.chamfer = bool(chamfer)
         self.truncate = _truncate_thresholds(truncate)
+        self.dcd = _distance_thresholds(dcd, "dcd", MAX_DCD_ALPHAS)
+        if dcd_squared and not self.dcd:
+            raise ValueError("dcd_squared says what the density-aware Chamfer rows are fed: it needs dcd=")
+        self.dcd_squared = bool(dcd_squared)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -249,6 +260,19 @@ def check_truncate(options: CalculateOptions, *, group=None) -> None:
     """... and likewise for the truncated-distance rows."""
     if getattr(options, "truncate", ()) and group is not None:
         raise ValueError("Chamfer and truncated-distance rows are not available for sharded pairs (group=)")
+
+
+def check_dcd(options: CalculateOptions, *, ties: str = "pick", group=None) -> None:
+    """Raise ``ValueError`` when the density-aware Chamfer rows ``options`` asks for cannot be computed for this pair -- before any
+    GPU work (the command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).
+    Under ``ties="mean"`` the matched point is a virtual one that has no row to count; a sharded pair would have to add its ranks'
+    match counts up: not built."""
+    if not getattr(options, "dcd", ()):
+        return
+    if ties != "pick":
+        raise ValueError("density-aware Chamfer rows are not defined under ties='mean': a virtual neighbour has no row to count")
+    if group is not None:
+        raise ValueError("density-aware Chamfer rows are not available for sharded pairs (group=)")
 
 
 def check_point_to_distribution(options: CalculateOptions, *, group=None) -> None:
@@ -400,4 +424,7 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
     for threshold in getattr(options, "truncate", None) or ():
         for cls in (GeoTruncatedMSE, GeoTruncatedMeanDistance) if chamfer else (GeoTruncatedMSE,):
             metrics += _sides(cls, threshold=threshold) + [_sym(cls, False, threshold=threshold)]
+    squared = bool(getattr(options, "dcd_squared", False))
+    for alpha in getattr(options, "dcd", None) or ():
+        metrics += _sides(GeoDensityAwareDistance, alpha=alpha, squared=squared) + [GeoDensityAwareChamfer(alpha=alpha, squared=squared)]
     return metrics
