@@ -327,11 +327,13 @@ def test_long_runs_inside_the_lds_budget_stay_exact(engine):
 
 
 @pytest.mark.parametrize("margin,note", [(0.012, "several thousand tails: more than one entry per wave at both ends of the wave range"),
-                                         (0.05, "tens of thousands: the thread-per-query path")])
+                                         (0.05, "tens of thousands: still one wave per entry, many entries per wave")])
 def test_many_tail_queries_stay_exact(engine, margin, note):
     """Queries in a rim where the other cloud has no points cannot be settled by ring 1: they go through k_grid_tail
-    (one wave per entry, the two directions' lists handed out from opposite ends) or, past 2^18 entries, through the
-    per-thread search; a few fall through to the exact rescan.  Every row is still the oracle's."""
+    (one wave per entry, the two directions' lists handed out from opposite ends); a few fall through to the exact rescan.
+    Every row is still the oracle's.  Both margins stay far below kTailWaveMax = 2^18 tail entries (300 000 queries per
+    direction, a rim of at most 5 %): the thread-per-query half of k_grid_tail, which takes longer lists, is reached by
+    tests/test_gpu_grid_planted.py's long-tail case instead."""
     rng = np.random.default_rng(31)
     n = 300_000
     a = (rng.random((n, 3), dtype=np.float32) * np.float32(1.0 + margin)).astype(np.float32)   # A pokes out of B's box

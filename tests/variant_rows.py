@@ -45,6 +45,9 @@ ROWS = {
     # unequal sizes: more staged records per brick of the denser cloud, from the data alone
     "brick42_unequal": dict(kind="brick", env="", gen=dict(n=240_007, m=40_009), expect=[_brick(False, 4, 2, 3584), _brick(False, 4, 2, 3584, False)]),
     # ---- the other query kernels ----------------------------------------------------------------------------------------
+    # (these rows run seeded random clouds; what the stop rule of k_grid_query*, k_brick_query and k_grid_tail must settle, must
+    # not settle and must hand to the exact rescan, query by query and count by count, and the thread-per-query half of
+    # k_grid_tail behind a tail list longer than 2^18: tests/test_gpu_grid_planted.py)
     # fp64 volumetric clouds (not fp32-exact): the cooperative kernel on GridRec records, tails on GridRec
     "coop_f64": dict(kind="search", env="", gen=dict(n=200_001, m=190_003, f64=True),
                      expect=["k_grid_query_coop<false>", "k_grid_query_coop<true>", "k_grid_tail<pccm::GridRec, false>",
