@@ -14,9 +14,7 @@ import typing
 import pandas as pd
 
 from .cloud_pair import CloudPair
-from .metric import (AbstractMetric, AngularSimilarities, BoundarySqrtDistances, ColorMahalanobisDistances,
-                     JointMahalanobisDistances, MahalanobisDistances, PointSpacings, PrimaryMetric,
-                     ReflectanceErrors, SecondaryMetric, SSIMSimilarities, SymmetricMetric)
+from .metric import AbstractMetric, PrimaryMetric, SecondaryMetric, SymmetricMetric
 
 _COLUMNS = ("label", "is_left", "point-to-plane", "value")
 
@@ -93,44 +91,17 @@ class MetricCalculator:
         role = getattr(metric, "_pccm_role", 0) or (1 if isinstance(metric, PrimaryMetric) else
                                                     2 if isinstance(metric, SecondaryMetric) else 0)
         waits = bool(getattr(metric, "_pccm_waits", False))
-        if role == 1:
-            if isinstance(metric, BoundarySqrtDistances):
-                wanted.append("boundary")
-            elif isinstance(metric, AngularSimilarities):
-                wanted.append(("angular", metric.is_left))
-            elif isinstance(metric, SSIMSimilarities):
-                wanted.append(("ssim", metric.attribute, metric.is_left, metric.k))
-            elif isinstance(metric, ColorMahalanobisDistances):
-                wanted.append(("p2d_color", metric.is_left, metric.k))
-            elif isinstance(metric, JointMahalanobisDistances):
-                wanted.append(("p2d_joint", metric.is_left, metric.k))
-            elif isinstance(metric, MahalanobisDistances):
-                wanted.append(("p2d", metric.is_left, metric.k))
-            elif isinstance(metric, PointSpacings):
-                wanted.append(("spacing", metric.is_left, metric.k))
-            elif isinstance(metric, ReflectanceErrors):
-                wanted.append(("reflectance", metric.is_left))
-            (late if waits else early).append((metric, None, key))
-        elif role == 2:
-            item = getattr(metric, "_pccm_item", None)      # (one attribute, not an isinstance per case: ~1 us each on an ABC)
-            if item is not None:
-                if item == "column":
-                    wanted.append((metric.is_left, metric.point_to_plane))
-                elif item == "ranked":
-                    wanted.append(("ranked", metric.is_left, metric.point_to_plane, metric.rank))
-                elif item == "within":
-                    wanted.append(("within", metric.is_left, metric.threshold))
-                elif item == "mapped":
-                    wanted.append(("mapped",) + tuple(metric._mapped_request()))
-                elif item == "density":
-                    wanted.append(("density", metric.is_left, metric.alpha, metric.squared))
-            resolved = {}
+        if role not in (1, 2):
+            raise RuntimeError(f"Metric of unknown AbstractMetric subclass {type(metric).__name__}")
+        resolved = {} if role == 2 else None
+        if role == 2:
             for name, dep in metric._get_dependencies().items():
                 resolved[name], _, dep_waits = self._visit(dep, early, late, planned, wanted)
                 waits = waits or dep_waits
-            (late if waits else early).append((metric, resolved, key))
-        else:
-            raise RuntimeError(f"Metric of unknown AbstractMetric subclass {type(metric).__name__}")
+        item = metric._pccm_request()       # what the node wants enqueued ahead of its evaluation (prefetch_reductions)
+        if item is not None:
+            wanted.append(item)
+        (late if waits else early).append((metric, resolved, key))
         planned[key] = (metric, key, waits)
         return planned[key]
 

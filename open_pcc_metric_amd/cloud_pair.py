@@ -391,20 +391,14 @@ class CloudPair:
         self._duplicates = duplicates
         self._merged = [False, False]           # the cloud lost rows to pccm_merge_duplicates: its arrays are the engine's, not the caller's
         self.duplicates_removed = (0, 0)
-        self._xchg, self._xchg_wanted = {}, []
-        self._selections, self._sel_wanted = {}, []
-        self._counts, self._cnt_wanted = {}, []
-        self._maps, self._map_wanted = {}, []
-        self._dens, self._dens_wanted = {}, []
-        self._density_rows = False          # a report asked for density-aware Chamfer rows: the searches keep the matched rows
+        self._drop_results(plan=True)
+        # why the searches keep the matched rows (_keep_matched_rows): "carry" (the carry reads them), and the columns a report has asked
+        # for that compare a point with its matched point ("angular", "ssim", "reflectance") or count who shares one ("density")
+        self._keep_rows = {"carry"} if self._carry_normals else set()
         self._colours_on_device = [False, False]
         self._reflectance_on_device = [False, False]
-        self._reflectance = False           # a report asked for the reflectance columns: the searches keep the matched rows
-        self._colour_red = {}
         self._graph_id = None
         self._last_wanted = None
-        self._angular = False               # a report asked for the angular columns: the searches keep the matched rows
-        self._ssim = False                  # ... or for PointSSIM columns (likewise)
         self._extent = None if extent is None else np.asarray(extent, dtype=np.float64)
         self._coll = Collective(group)
         self._owns_engine = False
@@ -493,11 +487,8 @@ class CloudPair:
         new._reflectance_on_device = [self._reflectance_on_device[0], False]     # (the origin cloud's column stays in HBM)
         new._merged = [self._merged[0], False]           # (cloud 0 stays merged and resident: only the new cloud 1 is merged)
         new.duplicates_removed = (self.duplicates_removed[0], 0)
-        new._xchg, new._xchg_wanted, new._colour_red = {}, [], {}
-        new._selections, new._sel_wanted = {}, []
-        new._counts, new._cnt_wanted = {}, []
-        new._maps, new._map_wanted = {}, []
-        new._dens, new._dens_wanted = {}, []
+        new._keep_rows = set(self._keep_rows)
+        new._drop_results(plan=True)
         new._graph_id, new._last_wanted = None, None
         keep_self = bool(self.__dict__.get("_self_done")) and bool(getattr(eng, "keeps_self_search", False))
         self_total = self.__dict__.get("_totals", {}).get((nat.DIR_SELF, nat.METRIC_D1)) if keep_self else None
@@ -575,13 +566,29 @@ class CloudPair:
             eng.nn_fuse(direction, self.normal_index if self._normals_ready(other) and not mean else None)
         # the matched rows (cloud_pair.py:34-42) are only read by the colour metrics and the error-vector / neighbour
         # getters: clouds without colours leave them out of the result records (a getter that asks later still gets them)
-        # (and so do the angular columns, which compare each point's normal with its matched point's)
+        # (and so do the columns and passes named in _keep_rows)
         if hasattr(eng, "nn_want_idx"):
-            eng.nn_want_idx(mean or self.__dict__.get("_angular", False) or self.__dict__.get("_ssim", False)
-                            or self.__dict__.get("_reflectance", False)        # (each point's reflectance against its matched point's)
-                            or self.__dict__.get("_carry_normals", False)      # (the carry reads both directions' matched rows)
-                            or self.__dict__.get("_density_rows", False)       # (the match counts and the density map likewise)
-                            or any(_has_colors(c) for c in self.clouds))
+            eng.nn_want_idx(mean or bool(self.__dict__.get("_keep_rows")) or any(_has_colors(c) for c in self.clouds))
+
+    def _keep_matched_rows(self, reason: str) -> None:
+        """From now on the searches keep the matched rows, for ``reason`` (one of those listed in __init__); the rows of the search
+        that has already run are recovered once."""
+        if reason not in self._keep_rows:
+            self._keep_rows.add(reason)
+            self._update_fusion()
+
+    def _drop_results(self, plan: bool = False) -> None:
+        """Forget every result read back from the GPU -- new searches are about to run -- and, with ``plan``, which results the last
+        report enqueued (the batches they come back in): a new pair."""
+        self._idx_cache, self._xchg, self._totals, self._colour_red = {}, {}, {}, {}
+        if plan:
+            self._xchg_wanted = []
+        # per row family of _FAMILIES: (the answers by request, the requests the last report enqueued in sorted order)
+        self._results = {tag: ({}, [] if plan else self._results[tag][1]) for tag in _FAMILIES}
+
+    def _drop_totals(self, metrics) -> None:
+        """Forget the totals of the columns of ``metrics``: what they were reduced from has been built again or replaced."""
+        self._totals = {key: v for key, v in self._totals.items() if key[1] not in metrics}
 
     def _colours_for_ties(self) -> None:
         """Under ``ties="mean"`` the colours go up before the searches, so that the one averaging pass per direction (pccm_set_ties)
@@ -593,14 +600,7 @@ class CloudPair:
         """Run both directional sweeps again on the clouds already resident in HBM
         (cloud_pair.py:67-78 does this once, eagerly, in the constructor) and drop cached results."""
         eng = self._engine
-        self._idx_cache = {}
-        self._xchg = {}
-        self._totals = {}
-        self._selections = {}
-        self._counts = {}
-        self._maps = {}
-        self._dens = {}
-        self._colour_red = {}
+        self._drop_results()
         if self._use_graph and self._last_wanted is not None and hasattr(eng, "graph_begin"):
             wants_self = "boundary" in self._last_wanted
             if self._graph_id is not None:
@@ -707,16 +707,16 @@ class CloudPair:
         done = self._totals.get(key)
         if done is not None:
             return done
-        if True:
-            eng = self._engine
-            batch = [k for k in self._xchg_wanted if k not in self._totals]
-            if key not in batch:
-                batch.append(key)
-            if hasattr(eng, "reduce_total_many") and len(batch) > 1:
-                for k, v in zip(batch[:8], eng.reduce_total_many(batch[:8], self.normal_index)):
-                    self._totals[k] = v
-            if key not in self._totals:
-                self._totals[key] = eng.reduce_total(direction, metric, self.normal_index)
+        eng = self._engine
+        batch = [k for k in self._xchg_wanted if k not in self._totals]
+        if key not in batch:
+            batch.append(key)
+        if hasattr(eng, "reduce_total_many") and len(batch) > 1:
+            batch = batch[:_MAX_REQUESTS]
+            for k, v in zip(batch, eng.reduce_total_many(batch, self.normal_index)):
+                self._totals[k] = v
+        if key not in self._totals:
+            self._totals[key] = eng.reduce_total(direction, metric, self.normal_index)
         return self._totals[key]
 
     def _check_unsharded(self, rows: str) -> None:
@@ -724,56 +724,43 @@ class CloudPair:
         if self._coll.sharded:
             raise ValueError(f"{rows} rows are not available for sharded pairs (group=)")
 
-    def _check_ranked(self) -> None:
-        """options.check_hausdorff_rank for this pair."""
-        self._check_unsharded("ranked Hausdorff")
-
-    def _check_fscore(self) -> None:
-        """options.check_fscore for this pair."""
-        self._check_unsharded("F-score")
-
-    def _check_mapped(self) -> None:
-        """options.check_chamfer / check_truncate for this pair."""
-        self._check_unsharded("Chamfer and truncated-distance")
-
     def _check_density(self) -> None:
         """options.check_dcd for this pair: ValueError before any GPU work of a report."""
         if self.ties == "mean":
             raise ValueError("density-aware Chamfer rows are not defined under ties='mean': a virtual neighbour has no row to count")
         self._check_unsharded("density-aware Chamfer")
 
-    def _consumed(self, key, cache: dict, wanted, batches, method: str):
-        """The answer to request ``key`` from the engine's ``method``, through ``cache``.  The first request a report asks for
-        brings back the batch of eight (``batches(wanted)``) it was enqueued in (prefetch_reductions) in one call.  None: this
-        engine has no such method (a test double): the caller works on the materialised column."""
-        consume = getattr(self._engine, method, None)
+    def _consumed(self, tag: str, key):
+        """The answer to request ``key`` of row family ``tag`` (_FAMILIES), after the family's check.  The first request a report
+        asks for brings back the batch it was enqueued in (prefetch_reductions) in one call.  None: this engine has no such method
+        (a test double): the caller works on the materialised column."""
+        family = _FAMILIES[tag]
+        family.check(self)
+        consume = getattr(self._engine, family.consume, None)
         if consume is None:
             return None
+        cache, wanted = self._results[tag]
         if key not in cache:
-            batch = next((b for b in batches(wanted) if key in b), [key])
+            batch = next((b for b in family.batches(wanted) if key in b), [key])
             cache.update(zip(batch, consume(batch, self.normal_index)))
         return cache[key]
 
     def _selected(self, direction: int, metric: int, k: int):
         """The k-th smallest element of a whole D1 / D2 column, selected on the GPU."""
-        self._check_ranked()
-        return self._consumed((direction, metric, k), self._selections, self._sel_wanted, _selection_batches, "select_many")
+        return self._consumed("ranked", (direction, metric, k))
 
     def _counted(self, direction: int, metric: int, x: float):
         """The number of rows ``<= x`` of a whole D1 / D2 column, counted on the GPU."""
-        self._check_fscore()
-        return self._consumed((direction, metric, x), self._counts, self._cnt_wanted, _selection_batches, "count_many")
+        return self._consumed("within", (direction, metric, x))
 
     def _mapped(self, direction: int, metric: int, which: int, x: float):
         """``(sum, min, max)`` of f(column) for a whole D1 / D2 column, mapped and reduced on the GPU (``which``: nat.MAP_*, ``x``:
         the clamp)."""
-        self._check_mapped()
-        return self._consumed((direction, metric, which, x), self._maps, self._map_wanted, _map_batches, "reduce_map_total_many")
+        return self._consumed("mapped", (direction, metric, which, x))
 
     def _density(self, direction: int, alpha: float, squared: bool):
         """``(sum, min, max)`` of the density-aware Chamfer terms of a whole D1 column, gathered, mapped and reduced on the GPU."""
-        self._check_density()
-        return self._consumed((direction, alpha, squared), self._dens, self._dens_wanted, _map_batches, "reduce_density_total_many")
+        return self._consumed("density", (direction, alpha, squared))
 
     def match_counts(self, is_left: bool = True) -> np.ndarray:
         """How many points of the iterating cloud (left: the origin cloud) matched each point of the searched cloud:
@@ -976,10 +963,8 @@ class CloudPair:
         for which in (0, 1):
             built = self._engine.ssim_features(which, int(k), attributes) or built
         if built:                                         # totals of earlier features are stale
-            self._totals = {key: v for key, v in self._totals.items() if key[1] not in nat.METRIC_SSIM.values()}
-        if not self._ssim:
-            self._ssim = True
-            self._update_fusion()     # later searches keep the matched rows (this one's are recovered once)
+            self._drop_totals(nat.METRIC_SSIM.values())
+        self._keep_matched_rows("ssim")
 
     def get_ssim_features(self, which: int, attribute: str, k: int = 12):
         """Per point of cloud ``which`` (0 origin, 1 reconstructed): its PointSSIM feature of ``attribute`` over its k
@@ -1024,7 +1009,7 @@ class CloudPair:
             self._ensure_colours()
         built = self._engine.p2d_build(int(k), nat.P2D_GEOMETRY | (nat.P2D_COLOR if color else 0))
         if built or self.__dict__.get("_p2d_k") != int(k):    # totals of earlier columns are stale
-            self._totals = {key: v for key, v in self._totals.items() if key[1] not in self._P2D_METRICS}
+            self._drop_totals(self._P2D_METRICS)
         self._p2d_k = int(k)
 
     def _p2d_column(self, direction: int, k: int, kind: str = "p2d") -> DeviceColumn:
@@ -1075,7 +1060,7 @@ class CloudPair:
         for which in (0, 1):
             built = self._engine.resolution_build(which, int(k)) or built
         if built or self.__dict__.get("_resolution_k") != int(k):     # totals of earlier columns are stale
-            self._totals = {key: v for key, v in self._totals.items() if key[1] != nat.METRIC_RESOLUTION}
+            self._drop_totals((nat.METRIC_RESOLUTION,))
         self._resolution_k = int(k)
 
     def _spacing_column(self, direction: int, k: int) -> DeviceColumn:
@@ -1118,9 +1103,7 @@ class CloudPair:
         for k in range(2):
             if not self._reflectance_on_device[k]:
                 self._upload_reflectance(k)
-        if not self._reflectance:
-            self._reflectance = True
-            self._update_fusion()     # later searches keep the matched rows (this one's are recovered once)
+        self._keep_matched_rows("reflectance")
 
     def set_reflectance(self, which: int, reflectance) -> None:
         """Replace the reflectance the pair holds for cloud ``which`` (the caller's cloud object is not touched): the searches,
@@ -1138,7 +1121,7 @@ class CloudPair:
                     " row, see merge_map)") if self._merged[which] else ""
             raise ValueError(f"cloud {which} has {rows} rows but {values.shape[0]} reflectance values were given{hint}")
         self._reflectance_on_device[which] = False
-        self._totals = {key: v for key, v in self._totals.items() if key[1] != nat.METRIC_REFLECTANCE}
+        self._drop_totals((nat.METRIC_REFLECTANCE,))
         self._graph_id = None                                        # (a captured point job read the old column)
         self._engine.set_reflectance(which, values)
         self._reflectance_on_device[which] = True
@@ -1191,164 +1174,107 @@ class CloudPair:
                 eng.graph_destroy(self._graph_id)             # a different report: capture anew next time
                 self._graph_id = None
             self._last_wanted = wanted
-        # PointSSIM: every check first (ValueError before any GPU work of the report), then the features -- built here, eagerly
-        # and outside any graph capture, the first time a report asks for them; found in HBM every time after that
-        ssim_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "ssim"]
+        groups = _by_family(wanted)
+        self._prepare_families(groups)
+        plan = _plan_report(groups, self._prepare_columns(groups.get("column", ())), eng.n_iter)
+        self._xchg_wanted = plan.columns
+        self._results = {tag: (self._results[tag][0], plan.rows[tag]) for tag in _FAMILIES}
+        if can_prefetch:
+            self._enqueue(plan)
+
+    def _prepare_families(self, groups) -> None:
+        """What a report's row families need before anything is enqueued, family by family: its check (ValueError before any GPU
+        work of the family), then what it reads in HBM -- built or uploaded here, eagerly and outside any graph capture, the first
+        time a report asks for it, and found there every time after that."""
+        if groups.keys() <= {"column"}:
+            return                      # (the usual report: D1 / D2, angular and boundary rows only)
+        # PointSSIM: both clouds' features, one build per neighbourhood size
         by_k = {}
-        for _, attribute, _, k in ssim_items:
+        for _, attribute, _, k in groups.get("ssim", ()):
             by_k.setdefault(k, []).append(attribute)
         for k, attributes in by_k.items():
             self._check_ssim(attributes, k)
         for k, attributes in by_k.items():
             self._ensure_ssim(sorted(set(attributes)), k)
-        ranked_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "ranked"]
-        if ranked_items:
-            self._check_ranked()
-        within_items = [item for item in wanted if item[0] == "within"]
-        if within_items:
-            self._check_fscore()
-            wanted = [item for item in wanted if item not in within_items]     # (their columns are requests of their own, EuclideanDistance's)
-        mapped_items = [item for item in wanted if item[0] == "mapped"]
-        if mapped_items:
-            self._check_mapped()
-            wanted = [item for item in wanted if item not in mapped_items]     # (their columns are requests of their own, EuclideanDistance's)
-        density_items = [item for item in wanted if item[0] == "density"]
-        if density_items:
-            self._check_density()
-            wanted = [item for item in wanted if item not in density_items]    # (their columns are requests of their own, EuclideanDistance's)
-            if not self._density_rows:
-                self._density_rows = True
-                self._update_fusion()         # later searches keep the matched rows (this one's are recovered once)
-        # point-to-distribution: the check, then the columns -- built here like the features, eagerly and outside any capture
-        # (one build per neighbourhood size, with the union of what the report needs at that size)
-        p2d_items = [item for item in wanted if isinstance(item, tuple) and item[0] in ("p2d", "p2d_color", "p2d_joint")]
-        p2d_color = {k: any(item[0] != "p2d" for item in p2d_items if item[2] == k) for k in sorted({item[2] for item in p2d_items})}
-        for k, color in p2d_color.items():
-            self._check_p2d(k, color)
-        for k, color in p2d_color.items():
-            self._ensure_p2d(k, color)
-        # point spacings: likewise, one build per cloud and neighbour count; their requests ride with the other stored columns
-        spacing_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "spacing"]
-        for k in sorted({item[2] for item in spacing_items}):
+        # ranked Hausdorff, F-score, Chamfer / truncated and density-aware Chamfer rows: they read the D1 / D2 columns
+        for tag, family in _FAMILIES.items():
+            if tag in groups:
+                family.check(self)
+                if family.keeps_rows:
+                    self._keep_matched_rows(tag)
+        # point-to-distribution: one build per neighbourhood size, with the union of what the report needs at that size
+        colour_at = {}
+        for kind, _, k in groups.get("p2d", ()):
+            colour_at[k] = colour_at.get(k, False) or kind != "p2d"
+        for k in sorted(colour_at):
+            self._check_p2d(k, colour_at[k])
+        for k in sorted(colour_at):
+            self._ensure_p2d(k, colour_at[k])
+        # point spacings: one build per cloud and neighbour count
+        sizes = sorted({item[2] for item in groups.get("spacing", ())})
+        for k in sizes:
             self._check_resolution(k)
-        for k in sorted({item[2] for item in spacing_items}):
+        for k in sizes:
             self._ensure_resolution(k)
-        # reflectance: the check, then both clouds' columns in HBM (uploaded here the first time, outside any capture)
-        reflectance_items = [item for item in wanted if isinstance(item, tuple) and item[0] == "reflectance"]
-        if reflectance_items:
+        # reflectance: both clouds' columns in HBM
+        if "reflectance" in groups:
             self._ensure_reflectance()
-        reflectance_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_REFLECTANCE) for item in reflectance_items]
-        requests, ssim_requests, selections, counts = [], [], [], []
-        stored_items = p2d_items + spacing_items
-        p2d_requests = [(nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, DeviceColumn._METRIC[item[0]]) for item in stored_items]
-        for item in wanted:
-            if item in ranked_items or item in stored_items or item in reflectance_items:
-                continue              # (ranked: their columns are requests of their own, EuclideanDistance's)
-            if item in ssim_items:
-                ssim_requests.append((nat.DIR_LEFT if item[2] else nat.DIR_RIGHT, nat.METRIC_SSIM[item[1]]))
-                continue
-            if item == "boundary":
-                if self._self_done and (nat.DIR_SELF, nat.METRIC_D1) in self._totals:
-                    continue                              # inherited with the origin cloud (with_reconst): nothing to reduce again
-                if not self._self_done:
-                    eng.nn(nat.DIR_SELF, self.nn_engine)
-                    self._self_done = True
-                requests.append((nat.DIR_SELF, nat.METRIC_D1))
-                continue
-            if item[0] == "angular":
-                try:
-                    self._require_normals(0)
-                    self._require_normals(1)
-                except ValueError:
-                    continue          # surfaces when the column is evaluated
-                if not self._angular:
-                    self._angular = True
-                    self._update_fusion()     # later searches keep the matched rows (this one's are recovered once)
-                requests.append((nat.DIR_LEFT if item[1] else nat.DIR_RIGHT, nat.METRIC_ANGULAR))
-                continue
-            is_left, p2p = item
-            direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
-            if not p2p:
-                requests.append((direction, nat.METRIC_D1))
-            else:
-                other = 1 if is_left else 0
-                try:
-                    self._require_normals(other)
-                except ValueError:
-                    continue          # surfaces when the column is evaluated
-                n_other = self._engine.n_iter(nat.DIR_RIGHT if other else nat.DIR_LEFT) if self._estimated[other] or self._carried[other] \
-                    or self._merged[other] else len(self.clouds[other].normals)
-                if self.normal_index == "row" and eng.n_iter(direction) > n_other:
-                    continue      # row-indexed normals out of range (the WHOLE cloud decides, so that every rank of a
-                    #               sharded pair agrees): surfaces, on every rank, where the reference raises
-                requests.append((direction, nat.METRIC_D2))
-        # ranked Hausdorff rows: the selections of every column this report reduces (a column that was left out above -- no
-        # normals, row-indexed normals out of range -- surfaces when the row is evaluated), by column, then rank
-        from .metric import rank_index
-        for _, is_left, p2p, rank in ranked_items:
-            direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
-            column = (direction, nat.METRIC_D2 if p2p else nat.METRIC_D1)
-            if column in requests:
-                selections.append(column + (rank_index(rank, eng.n_iter(direction)),))
-        # F-score rows: the points within tau of the other cloud, counted on the D1 column of each direction at tau * tau (the
-        # product GeoInlierRatio forms) -- both directions and every threshold, eight counts at the most, in one batch
-        for _, is_left, tau in within_items:
-            column = (nat.DIR_LEFT if is_left else nat.DIR_RIGHT, nat.METRIC_D1)
-            if column in requests:
-                counts.append(column + (float(np.float64(tau) * np.float64(tau)),))
-        # Chamfer and truncated-distance rows: f(column) of the D1 / D2 columns this report reduces, mapped inside the reduction
-        # kernel -- up to twenty, enqueued behind everything else, eight per call
-        maps = []
-        for _, is_left, p2p, root, clamp in mapped_items:
-            column = (nat.DIR_LEFT if is_left else nat.DIR_RIGHT, nat.METRIC_D2 if p2p else nat.METRIC_D1)
-            if column in requests:
-                which = (nat.MAP_CLAMP if clamp is not None else 0) | (nat.MAP_ROOT if root else 0)
-                maps.append(column + (which, 0.0 if clamp is None else float(clamp)))
-        # density-aware Chamfer rows: per direction and alpha one density map of the D1 column this report reduces, behind the
-        # direction's match counts (made once per search) -- up to eight, in one call
-        dens = []
-        for _, is_left, alpha, squared in density_items:
-            direction = nat.DIR_LEFT if is_left else nat.DIR_RIGHT
-            if (direction, nat.METRIC_D1) in requests:
-                dens.append((direction, float(alpha) + 0.0, bool(squared)))
-        # the reflectance columns join the first batch -- its k_point_jobs launch and its reduction launch -- when it has room
-        # for them: eight columns, of which at most four are formed by point jobs (unfused D2, angular, reflectance)
-        if reflectance_requests:
-            point_jobs = sum(1 for _, m in requests if m in (nat.METRIC_D2, nat.METRIC_ANGULAR))
-            if len(requests) + len(reflectance_requests) <= 8 and point_jobs + len(reflectance_requests) <= 4:
-                requests, reflectance_requests = requests + reflectance_requests, []
-        self._xchg_wanted = list(requests) + reflectance_requests + ssim_requests + p2d_requests
-        self._sel_wanted = sorted(set(selections))
-        self._cnt_wanted = sorted(set(counts)) if counts else []
-        self._map_wanted = sorted(set(maps)) if maps else []
-        self._dens_wanted = sorted(set(dens)) if dens else []
-        if not can_prefetch:
-            return
-        if hasattr(eng, "reduce_prefetch_many"):
-            ride = len(requests) + len(p2d_requests) <= 8     # (stored columns: they join the first batch when it has room)
-            eng.reduce_prefetch_many((requests + p2d_requests if ride else requests)[:8], self.normal_index)
-            if reflectance_requests:
-                eng.reduce_prefetch_many(reflectance_requests, self.normal_index)
-            for b in range(0, len(ssim_requests), 4):     # (at most four matched-row columns per batch: k_point_jobs)
-                eng.reduce_prefetch_many(ssim_requests[b:b + 4], self.normal_index)
-            if not ride:
-                eng.reduce_prefetch_many(p2d_requests, self.normal_index)
-            if hasattr(eng, "select_prefetch_many"):
-                for batch in _selection_batches(self._sel_wanted):
-                    eng.select_prefetch_many(batch, self.normal_index)
-            if self._cnt_wanted and hasattr(eng, "count_prefetch_many"):
-                for batch in _selection_batches(self._cnt_wanted):
-                    eng.count_prefetch_many(batch, self.normal_index)
-            if self._map_wanted and hasattr(eng, "reduce_map_prefetch_many"):
-                for batch in _map_batches(self._map_wanted):
-                    eng.reduce_map_prefetch_many(batch, self.normal_index)
-            if self._dens_wanted and hasattr(eng, "reduce_density_prefetch_many"):
-                for batch in _map_batches(self._dens_wanted):
-                    eng.reduce_density_prefetch_many(batch, self.normal_index)
-        else:
-            requests = requests + reflectance_requests + ssim_requests + p2d_requests
-            for direction, metric in requests:
+
+    def _prepare_columns(self, items):
+        """The requests of the columns formed from the searches' results -- ``"boundary"``, ``("angular", is_left)`` and
+        ``(is_left, point_to_plane)`` -- in the order given, after what each needs (the self search, normals).  A column that
+        cannot be formed is left out: its error surfaces when the column is evaluated."""
+        found = (self._boundary_request() if item == "boundary" else self._angular_request(item[1]) if item[0] == "angular"
+                 else self._distance_request(*item) for item in items)
+        return [request for request in found if request is not None]
+
+    def _boundary_request(self):
+        if self._self_done and (nat.DIR_SELF, nat.METRIC_D1) in self._totals:
+            return None                                   # inherited with the origin cloud (with_reconst): nothing to reduce again
+        if not self._self_done:
+            self._engine.nn(nat.DIR_SELF, self.nn_engine)
+            self._self_done = True
+        return nat.DIR_SELF, nat.METRIC_D1
+
+    def _angular_request(self, is_left: bool):
+        try:
+            self._require_normals(0)
+            self._require_normals(1)
+        except ValueError:
+            return None
+        self._keep_matched_rows("angular")
+        return _direction(is_left), nat.METRIC_ANGULAR
+
+    def _distance_request(self, is_left: bool, point_to_plane: bool):
+        direction = _direction(is_left)
+        if not point_to_plane:
+            return direction, nat.METRIC_D1
+        other = 1 if is_left else 0
+        try:
+            self._require_normals(other)
+        except ValueError:
+            return None
+        n_other = self._engine.n_iter(nat.DIR_RIGHT if other else nat.DIR_LEFT) if self._estimated[other] or self._carried[other] \
+            or self._merged[other] else len(self.clouds[other].normals)
+        if self.normal_index == "row" and self._engine.n_iter(direction) > n_other:
+            return None           # row-indexed normals out of range (the WHOLE cloud decides, so that every rank of a sharded
+            #                       pair agrees): surfaces, on every rank, where the reference raises
+        return direction, nat.METRIC_D2
+
+    def _enqueue(self, plan: "_Plan") -> None:
+        """Hand a report's plan to the engine: the column batches in order, then each row family's batches."""
+        eng = self._engine
+        if not hasattr(eng, "reduce_prefetch_many"):
+            for direction, metric in plan.columns:
                 eng.reduce_prefetch(direction, metric, self.normal_index)
+            return
+        for batch in plan.batches:
+            eng.reduce_prefetch_many(batch, self.normal_index)
+        for tag, rows in plan.rows.items():
+            prefetch = getattr(eng, _FAMILIES[tag].prefetch, None) if rows else None
+            if prefetch is not None:
+                for batch in _FAMILIES[tag].batches(rows):
+                    prefetch(batch, self.normal_index)
 
     # -- fused projection used by metric.ErrorVector ------------------------------------------------
     def point_to_plane_column(self, is_left: bool) -> DeviceColumn:
@@ -1356,16 +1282,41 @@ class CloudPair:
         return DeviceColumn(self, nat.DIR_LEFT if is_left else nat.DIR_RIGHT, "proj")
 
 
-def _selection_batches(selections, cap: int = 8):
-    """Sorted ``(direction, metric, k)`` selections in batches of at most ``cap`` (pccm_select_many's limit) that keep the ranks
-    of a column together: every pass of a batch streams each of its columns once, whatever the number of ranks.  Counts
-    ``(direction, metric, x)`` are batched the same way (pccm_count_many)."""
+# -- how a report becomes launches ("How a report becomes launches") ----------------------------------------------------
+_MAX_REQUESTS = 8       # what one pccm_*_many call takes: every batch below, and every batch read back, has at most eight requests
+_MAX_POINT_JOBS = 4     # columns one k_point_jobs launch forms from the matched rows: unfused D2, angular, reflectance, PointSSIM
+
+_GROUP = {"ssim": "ssim", "ranked": "ranked", "within": "within", "mapped": "mapped", "density": "density", "p2d": "p2d",
+          "p2d_color": "p2d", "p2d_joint": "p2d", "spacing": "spacing", "reflectance": "reflectance"}
+
+
+def _by_family(wanted):
+    """The items of ``wanted`` (prefetch_reductions) grouped by what prepares them, each group in the order given: the tag's group
+    of _GROUP, or "column" for ``"boundary"``, ``("angular", is_left)`` and ``(is_left, point_to_plane)``."""
+    groups = {}
+    for item in wanted:
+        groups.setdefault(_GROUP.get(item[0] if isinstance(item, tuple) else item, "column"), []).append(item)
+    return groups
+
+
+def _direction(is_left: bool) -> int:
+    return nat.DIR_LEFT if is_left else nat.DIR_RIGHT
+
+
+def _side_column(is_left: bool, point_to_plane: bool = False):
+    return _direction(is_left), nat.METRIC_D2 if point_to_plane else nat.METRIC_D1
+
+
+def _selection_batches(selections):
+    """Sorted ``(direction, metric, k)`` selections in batches of at most _MAX_REQUESTS that keep the ranks of a column together:
+    every pass of a batch streams each of its columns once, whatever the number of ranks.  Counts ``(direction, metric, x)`` are
+    batched the same way."""
     batches, current = [], []
     for column in sorted({q[:2] for q in selections}):
         ranks = [q for q in selections if q[:2] == column]
-        for at in range(0, len(ranks), cap):
-            part = ranks[at:at + cap]
-            if current and len(current) + len(part) > cap:
+        for at in range(0, len(ranks), _MAX_REQUESTS):
+            part = ranks[at:at + _MAX_REQUESTS]
+            if current and len(current) + len(part) > _MAX_REQUESTS:
                 batches.append(current)
                 current = []
             current = current + part
@@ -1374,10 +1325,95 @@ def _selection_batches(selections, cap: int = 8):
     return batches
 
 
-def _map_batches(maps, cap: int = 8):
-    """Sorted ``(direction, metric, map, x)`` mapped reductions in batches of ``cap`` (pccm_reduce_map_total_many's limit): the
-    order keeps a column's maps next to each other, and two of them share one read of the column."""
-    return [maps[at:at + cap] for at in range(0, len(maps), cap)]
+def _map_batches(maps):
+    """Sorted ``(direction, metric, map, x)`` mapped reductions in batches of _MAX_REQUESTS: the order keeps a column's maps next
+    to each other, and two of them share one read of the column.  Density maps ``(direction, alpha, squared)`` likewise."""
+    return [maps[at:at + _MAX_REQUESTS] for at in range(0, len(maps), _MAX_REQUESTS)]
+
+
+def _ranked_request(item, column, n_iter):
+    from .metric import rank_index
+    return column + (rank_index(item[3], n_iter(column[0])),)
+
+
+def _within_request(item, column, n_iter):
+    return column + (float(np.float64(item[2]) * np.float64(item[2])),)       # tau * tau, the product GeoInlierRatio forms
+
+
+def _mapped_request(item, column, n_iter):
+    root, clamp = item[3], item[4]
+    return column + ((nat.MAP_CLAMP if clamp is not None else 0) | (nat.MAP_ROOT if root else 0), 0.0 if clamp is None else float(clamp))
+
+
+def _density_request(item, column, n_iter):
+    return column[0], float(item[2]) + 0.0, bool(item[3])
+
+
+class _Family(typing.NamedTuple):
+    """A family of report rows answered from a whole D1 / D2 column by calls of its own, up to _MAX_REQUESTS requests each."""
+    check: typing.Callable          # (pair): ValueError where the pair cannot have these rows -- before any GPU work of the family
+    column: typing.Callable         # (item) -> the (direction, metric) column the item of ``wanted`` reads
+    request: typing.Callable        # (item, column, n_iter) -> the engine's request
+    batches: typing.Callable        # (sorted requests) -> the batches they are enqueued and read back in
+    prefetch: str                   # the engine method that enqueues a batch
+    consume: str                    # ... and the one that brings its answers back
+    keeps_rows: bool = False        # the searches have to keep the matched rows
+
+
+# by the tag of the family's items in ``wanted``; the order is the order of the checks and of the launches
+_FAMILIES = {
+    "ranked": _Family(lambda pair: pair._check_unsharded("ranked Hausdorff"), lambda item: _side_column(item[1], item[2]),
+                      _ranked_request, _selection_batches, "select_prefetch_many", "select_many"),
+    "within": _Family(lambda pair: pair._check_unsharded("F-score"), lambda item: _side_column(item[1]),
+                      _within_request, _selection_batches, "count_prefetch_many", "count_many"),
+    "mapped": _Family(lambda pair: pair._check_unsharded("Chamfer and truncated-distance"), lambda item: _side_column(item[1], item[2]),
+                      _mapped_request, _map_batches, "reduce_map_prefetch_many", "reduce_map_total_many"),
+    "density": _Family(CloudPair._check_density, lambda item: _side_column(item[1]),
+                       _density_request, _map_batches, "reduce_density_prefetch_many", "reduce_density_total_many", keeps_rows=True),
+}
+
+
+class _Plan(typing.NamedTuple):
+    """What one report enqueues."""
+    batches: list       # the column requests (direction, metric), one reduce_prefetch_many call each, in launch order
+    columns: list       # the same requests in the order they are read back in, _MAX_REQUESTS per call (CloudPair._total)
+    rows: dict          # per family of _FAMILIES, its requests in sorted order: batched by the family's ``batches``
+
+
+def _plan_report(groups, requests, n_iter) -> _Plan:
+    """The plan of a report from its items by family (_by_family) and the requests of its columns that can be formed
+    (CloudPair._prepare_columns).  Asks the engine for nothing but row counts.  Every packing rule is here:
+
+    * a call takes _MAX_REQUESTS requests, and a batch at most _MAX_POINT_JOBS columns formed by point jobs;
+    * the reflectance columns join the first batch -- its k_point_jobs launch and its reduction launch -- when it has room for them
+      under both limits, and are a batch of their own otherwise;
+    * PointSSIM columns, all formed by point jobs, go in batches of _MAX_POINT_JOBS;
+    * the stored columns (point-to-distribution, spacings) ride in the first batch when it has room, and follow last otherwise;
+    * a row family's requests are those whose column this report reduces (one that was left out surfaces when the row is
+      evaluated), sorted, so that a column's ranks stay together and its maps next to each other (_selection_batches, _map_batches)."""
+    reduced = set(requests)
+    reflectance = [(_direction(item[1]), nat.METRIC_REFLECTANCE) for item in groups.get("reflectance", ())]
+    ssim = [(_direction(item[2]), nat.METRIC_SSIM[item[1]]) for item in groups.get("ssim", ())]
+    stored = [(_direction(item[1]), DeviceColumn._METRIC[item[0]]) for item in groups.get("p2d", []) + groups.get("spacing", [])]
+    first = list(requests)
+    if reflectance and len(first) + len(reflectance) <= _MAX_REQUESTS:
+        point_jobs = sum(1 for _, m in first if m in (nat.METRIC_D2, nat.METRIC_ANGULAR))
+        if point_jobs + len(reflectance) <= _MAX_POINT_JOBS:
+            first, reflectance = first + reflectance, []
+    columns = first + reflectance + ssim + stored
+    ride = len(first) + len(stored) <= _MAX_REQUESTS
+    batches = [(first + stored if ride else first)[:_MAX_REQUESTS]]
+    if reflectance:
+        batches.append(reflectance)
+    batches += [ssim[at:at + _MAX_POINT_JOBS] for at in range(0, len(ssim), _MAX_POINT_JOBS)]
+    if not ride:
+        batches.append(stored)
+    rows = {}
+    for tag, family in _FAMILIES.items():
+        items = groups.get(tag)
+        rows[tag] = sorted({family.request(item, column, n_iter) for item in items
+                            if (column := family.column(item)) in reduced}) if items else []
+    return _Plan(batches, columns, rows)
 
 
 def _has_normals(cloud) -> bool:

@@ -30,6 +30,11 @@ class AbstractMetric(abc.ABC):                       # metric.py:14-29
     def _key(self) -> typing.Tuple:
         return (type(self).__name__,)
 
+    def _pccm_request(self):
+        """What this node asks CloudPair.prefetch_reductions to enqueue ahead of its evaluation -- one of the items listed there --
+        or None.  The calculator collects these while it plans a report."""
+        return None
+
     @abc.abstractmethod
     def calculate(self, cloud_pair: CloudPair, **kwargs) -> None:
         raise NotImplementedError("calculate is not implemented")
@@ -48,10 +53,6 @@ class PrimaryMetric(AbstractMetric):                 # metric.py:32-38 -- reads 
 
 class SecondaryMetric(AbstractMetric):               # metric.py:41-50 -- pure function of its deps
     _pccm_role = 2
-    _pccm_item = None       # what the calculator tells CloudPair.prefetch_reductions about this node: "column" (EuclideanDistance),
-    #                         "ranked" (GeoRankedHausdorffDistance), "within" (GeoInlierRatio), "mapped" (GeoMeanDistance,
-    #                         GeoTruncatedMSE, GeoTruncatedMeanDistance: _mapped_request() says which map), "density"
-    #                         (GeoDensityAwareDistance); subclasses inherit it
 
     def _get_dependencies(self) -> typing.Dict[str, "AbstractMetric"]:
         return {}
@@ -84,6 +85,20 @@ class PointToPlaneable(DirectionalMetric):           # metric.py:63-71
 
 def _side(metric: DirectionalMetric, left, right):
     return left() if metric.is_left else right()
+
+
+def _column_reducer(slot: int, on_host):
+    """np.sum / np.min / np.max (``on_host``) of a column along axis 0.  A device column answers from ``slot`` of its fused
+    (sum, min, max) -- what NumPy would dispatch to, called directly -- unless it has none there (the boundary column's sum); a
+    plain array goes to NumPy."""
+    def reduce(column):
+        fused = getattr(column, "_reduced", None)
+        value = fused()[slot] if fused is not None else None
+        return on_host(column, axis=0) if value is None else value
+    return reduce
+
+
+_column_sum, _column_min, _column_max = _column_reducer(0, np.sum), _column_reducer(1, np.min), _column_reducer(2, np.max)
 
 
 # --------------------------------------------------------------------------- primaries
@@ -126,6 +141,9 @@ class NeighbourColors(PrimaryMetric, DirectionalMetric):         # metric.py:115
 class AngularSimilarities(PrimaryMetric, DirectionalMetric):     # no counterpart in the reference (options.py: plane_to_plane)
     """Per point of the iterating cloud, the angular similarity of its normal and its matched neighbour's (include/pccm.h,
     PCCM_METRIC_ANGULAR): 1 - 2 acos(min(|a . b| / (|a| |b|), 1)) / pi, 0 for a zero-length normal."""
+    def _pccm_request(self):
+        return "angular", self.is_left
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, cloud_pair.get_left_angular_similarities, cloud_pair.get_right_angular_similarities)
 
@@ -140,6 +158,9 @@ class SSIMSimilarities(PrimaryMetric, DirectionalMetric):        # no counterpar
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.attribute, self.is_left, self.k)
 
+    def _pccm_request(self):
+        return "ssim", self.attribute, self.is_left, self.k
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, lambda: cloud_pair.get_left_ssim_similarities(self.attribute, self.k),
                            lambda: cloud_pair.get_right_ssim_similarities(self.attribute, self.k))
@@ -148,12 +169,17 @@ class SSIMSimilarities(PrimaryMetric, DirectionalMetric):        # no counterpar
 class MahalanobisDistances(PrimaryMetric, DirectionalMetric):    # no counterpart in the reference (options.py: point_to_distribution)
     """Per point of the iterating cloud, its Mahalanobis distance to the distribution (mean and ridged covariance) of its k
     nearest points in the OTHER cloud (include/pccm.h, pccm_p2d_build; INTEGRATION.md, "Point-to-distribution")."""
+    _pccm_column = "p2d"    # which of the stored columns: the colour and joint subclasses name their own
+
     def __init__(self, is_left: bool, k: int = 30):
         super().__init__(is_left)
         self.k = int(k)
 
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.is_left, self.k)
+
+    def _pccm_request(self):
+        return self._pccm_column, self.is_left, self.k
 
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, lambda: cloud_pair.get_left_mahalanobis_distances(self.k),
@@ -164,6 +190,8 @@ class ColorMahalanobisDistances(MahalanobisDistances):           # no counterpar
     """Per point of the iterating cloud, the distance of its luma to the luma distribution of the same k nearest points in the
     OTHER cloud, in ridged standard deviations (include/pccm.h, pccm_p2d_build_attrs; INTEGRATION.md, "Point-to-distribution:
     colour and joint")."""
+    _pccm_column = "p2d_color"
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, lambda: cloud_pair.get_left_color_mahalanobis_distances(self.k),
                            lambda: cloud_pair.get_right_color_mahalanobis_distances(self.k))
@@ -172,6 +200,8 @@ class ColorMahalanobisDistances(MahalanobisDistances):           # no counterpar
 class JointMahalanobisDistances(MahalanobisDistances):           # no counterpart in the reference (options.py: p2d_color)
     """Per point of the iterating cloud, sqrt(M_G^2 + M_Y^2) of its geometry and colour point-to-distribution values: the
     Mahalanobis distance in (x, y, z, Y) under a block-diagonal covariance."""
+    _pccm_column = "p2d_joint"
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, lambda: cloud_pair.get_left_joint_mahalanobis_distances(self.k),
                            lambda: cloud_pair.get_right_joint_mahalanobis_distances(self.k))
@@ -187,6 +217,9 @@ class PointSpacings(PrimaryMetric, DirectionalMetric):           # no counterpar
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.is_left, self.k)
 
+    def _pccm_request(self):
+        return "spacing", self.is_left, self.k
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, lambda: cloud_pair.get_left_point_spacings(self.k),
                            lambda: cloud_pair.get_right_point_spacings(self.k))
@@ -195,6 +228,9 @@ class PointSpacings(PrimaryMetric, DirectionalMetric):           # no counterpar
 class ReflectanceErrors(PrimaryMetric, DirectionalMetric):       # no counterpart in the reference (options.py: reflectance)
     """Per point of the iterating cloud, the squared difference of its reflectance and its matched point's (include/pccm.h,
     PCCM_METRIC_REFLECTANCE; INTEGRATION.md, "Reflectance"): (a - b)^2 on the values as given."""
+    def _pccm_request(self):
+        return "reflectance", self.is_left
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         self.value = _side(self, cloud_pair.get_left_reflectance_errors, cloud_pair.get_right_reflectance_errors)
 
@@ -215,6 +251,10 @@ class MatchedRows(PrimaryMetric, DirectionalMetric):             # no counterpar
 
 class BoundarySqrtDistances(PrimaryMetric):                      # metric.py:182-188
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
+
+    def _pccm_request(self):
+        return "boundary"
+
     def calculate(self, cloud_pair: CloudPair) -> None:
         spacing = cloud_pair.get_boundary_sqrt_distances()
         self.value = (np.min(spacing), np.max(spacing))
@@ -253,7 +293,8 @@ class ErrorVector(SecondaryMetric, PointToPlaneable):            # metric.py:124
 
 
 class EuclideanDistance(SecondaryMetric, PointToPlaneable):      # metric.py:156-179
-    _pccm_item = "column"
+    def _pccm_request(self):
+        return self.is_left, self.point_to_plane
 
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         if self.point_to_plane:
@@ -295,17 +336,13 @@ class GeoMSE(_OverEuclidean):                                    # metric.py:213
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, euclidean_distance: EuclideanDistance) -> None:
         column = euclidean_distance.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
-        total = fused()[0] if fused is not None else None
-        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+        self.value = _column_sum(column) / column.shape[0]
 
 
 class GeoHausdorffDistance(_OverEuclidean):                      # metric.py:353-366 (a SQUARED distance)
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, euclidean_distance: EuclideanDistance) -> None:
-        column = euclidean_distance.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
-        self.value = fused()[2] if fused is not None else np.max(column, axis=0)
+        self.value = _column_max(euclidean_distance.value)
 
 
 def rank_index(rank: float, n: int) -> int:
@@ -320,7 +357,6 @@ class GeoRankedHausdorffDistance(_OverEuclidean):                # no counterpar
     Hausdorff"): the rank_index(rank, n)-th smallest element of the column GeoHausdorffDistance takes the maximum of -- a
     SQUARED distance like it, and equal to it bit for bit at rank 1."""
     _pccm_waits = True      # reads a selection back from the GPU: the calculator evaluates these last
-    _pccm_item = "ranked"
 
     def __init__(self, is_left: bool, point_to_plane: bool, rank: float):
         super().__init__(is_left, point_to_plane)
@@ -328,6 +364,9 @@ class GeoRankedHausdorffDistance(_OverEuclidean):                # no counterpar
 
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.is_left, self.point_to_plane, self.rank)
+
+    def _pccm_request(self):
+        return "ranked", self.is_left, self.point_to_plane, self.rank
 
     def calculate(self, euclidean_distance: EuclideanDistance) -> None:
         column = euclidean_distance.value
@@ -341,7 +380,6 @@ class GeoInlierRatio(SecondaryMetric, DirectionalMetric):        # no counterpar
     of elements of the D1 column -- squared distances -- that are <= threshold * threshold, over the number of points.  Left
     (origin -> processed) is the recall (completeness) of the processed cloud, right its precision (accuracy)."""
     _pccm_waits = True      # reads a count back from the GPU: the calculator evaluates these last
-    _pccm_item = "within"
 
     def __init__(self, is_left: bool, threshold: float):
         super().__init__(is_left)
@@ -349,6 +387,9 @@ class GeoInlierRatio(SecondaryMetric, DirectionalMetric):        # no counterpar
 
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.is_left, self.threshold)
+
+    def _pccm_request(self):
+        return "within", self.is_left, self.threshold
 
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         return {"euclidean_distance": EuclideanDistance(is_left=self.is_left, point_to_plane=False)}
@@ -394,10 +435,9 @@ class GeoMeanDistance(_OverEuclidean):                           # no counterpar
     np.sum(np.sqrt(column)) / n over the D1 column, or -- point_to_plane -- over the D2 column, where the root of the squared
     projection is its magnitude."""
     _pccm_waits = True      # reads a mapped reduction back from the GPU: the calculator evaluates these last
-    _pccm_item = "mapped"
 
-    def _mapped_request(self):
-        return self.is_left, self.point_to_plane, True, None
+    def _pccm_request(self):
+        return "mapped", self.is_left, self.point_to_plane, True, None
 
     def calculate(self, euclidean_distance: EuclideanDistance) -> None:
         column = euclidean_distance.value
@@ -427,7 +467,6 @@ class GeoTruncatedMSE(SecondaryMetric, DirectionalMetric):       # no counterpar
     np.sum(np.minimum(column, threshold * threshold)) / n over the D1 column -- the remedy for partly overlapping clouds, whose
     points without a counterpart otherwise dominate the mean."""
     _pccm_waits = True      # reads a mapped reduction back from the GPU: the calculator evaluates these last
-    _pccm_item = "mapped"
     _root = False
 
     def __init__(self, is_left: bool, threshold: float):
@@ -440,8 +479,8 @@ class GeoTruncatedMSE(SecondaryMetric, DirectionalMetric):       # no counterpar
     def _cap(self):
         return np.float64(self.threshold) * np.float64(self.threshold)
 
-    def _mapped_request(self):
-        return self.is_left, False, self._root, float(self._cap())
+    def _pccm_request(self):
+        return "mapped", self.is_left, False, self._root, float(self._cap())
 
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         return {"euclidean_distance": EuclideanDistance(is_left=self.is_left, point_to_plane=False)}
@@ -462,7 +501,6 @@ class GeoDensityAwareDistance(SecondaryMetric, DirectionalMetric):   # no counte
     (``squared``: its square) and m the number of points that share that matched point.  In [0, 1]; at alpha = 0 it is
     1 - (distinct matched rows) / n."""
     _pccm_waits = True      # reads a mapped reduction back from the GPU: the calculator evaluates these last
-    _pccm_item = "density"
 
     def __init__(self, is_left: bool, alpha: float, squared: bool = False):
         super().__init__(is_left)
@@ -471,6 +509,9 @@ class GeoDensityAwareDistance(SecondaryMetric, DirectionalMetric):   # no counte
 
     def _key(self) -> typing.Tuple:
         return (type(self).__name__, self.is_left, self.alpha, self.squared)
+
+    def _pccm_request(self):
+        return "density", self.is_left, self.alpha, self.squared
 
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         return {"euclidean_distance": EuclideanDistance(is_left=self.is_left, point_to_plane=False),
@@ -517,18 +558,14 @@ class AngularSimilarity(_OverAngular):
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, angular_similarities: AngularSimilarities) -> None:
         column = angular_similarities.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
-        total = fused()[0] if fused is not None else None
-        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+        self.value = _column_sum(column) / column.shape[0]
 
 
 class MinAngularSimilarity(_OverAngular):
     """The worst point of one direction (reported with hausdorff)."""
     _pccm_waits = True      # reads a reduction back from the GPU: the calculator evaluates these last
     def calculate(self, angular_similarities: AngularSimilarities) -> None:
-        column = angular_similarities.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.min would dispatch to, called directly
-        self.value = fused()[1] if fused is not None else np.min(column, axis=0)
+        self.value = _column_min(angular_similarities.value)
 
 
 class _PointSSIM(SecondaryMetric, DirectionalMetric):
@@ -549,9 +586,7 @@ class _PointSSIM(SecondaryMetric, DirectionalMetric):
 
     def calculate(self, ssim_similarities: SSIMSimilarities) -> None:
         column = ssim_similarities.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
-        total = fused()[0] if fused is not None else None
-        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+        self.value = _column_sum(column) / column.shape[0]
 
 
 class GeometrySSIM(_PointSSIM):
@@ -596,17 +631,13 @@ class MahalanobisDistance(_OverMahalanobis):
     point is not at."""
     def calculate(self, mahalanobis_distances: MahalanobisDistances) -> None:
         column = mahalanobis_distances.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
-        total = fused()[0] if fused is not None else None
-        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+        self.value = _column_sum(column) / column.shape[0]
 
 
 class MaxMahalanobisDistance(_OverMahalanobis):
     """The worst point of one direction (reported with hausdorff)."""
     def calculate(self, mahalanobis_distances: MahalanobisDistances) -> None:
-        column = mahalanobis_distances.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
-        self.value = fused()[2] if fused is not None else np.max(column, axis=0)
+        self.value = _column_max(mahalanobis_distances.value)
 
 
 class ColorMahalanobisDistance(MahalanobisDistance):
@@ -699,9 +730,7 @@ class IntrinsicResolution(SecondaryMetric, DirectionalMetric):   # no counterpar
 
     def calculate(self, point_spacings: PointSpacings) -> None:
         column = point_spacings.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
-        total = fused()[0] if fused is not None else None
-        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+        self.value = _column_sum(column) / column.shape[0]
 
 
 class _ResolutionPSNR(SecondaryMetric, PointToPlaneable):
@@ -748,17 +777,13 @@ class ReflectanceMSE(_OverReflectance):                          # no counterpar
     differences (sum / n, NumPy's pairwise sum), in the units of the values as given."""
     def calculate(self, reflectance_errors: ReflectanceErrors) -> None:
         column = reflectance_errors.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.sum would dispatch to, called directly
-        total = fused()[0] if fused is not None else None
-        self.value = (np.sum(column, axis=0) if total is None else total) / column.shape[0]
+        self.value = _column_sum(column) / column.shape[0]
 
 
 class ReflectanceHausdorffDistance(_OverReflectance):
     """The worst point of one direction (reported with hausdorff): a SQUARED difference, like GeoHausdorffDistance."""
     def calculate(self, reflectance_errors: ReflectanceErrors) -> None:
-        column = reflectance_errors.value
-        fused = getattr(column, "_reduced", None)             # a device column: what np.max would dispatch to, called directly
-        self.value = fused()[2] if fused is not None else np.max(column, axis=0)
+        self.value = _column_max(reflectance_errors.value)
 
 
 def _reflectance_psnr(peak: float, distortion):

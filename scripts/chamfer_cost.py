@@ -87,7 +87,7 @@ def main():
             out["profile_" + k] = profiled(pairs[k], metrics[k])
         if "with" in runs:
             out["reduce_path_with"] = pairs["with"]._engine.last_path(nat.PATH_REDUCE)
-            out["mapped_reductions"] = len(pairs["with"]._map_wanted)
+            out["mapped_reductions"] = len(pairs["with"]._results["mapped"][1])
     finally:
         for p in pairs.values():
             p.close()

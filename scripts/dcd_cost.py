@@ -90,7 +90,7 @@ def main():
             out["profile_" + k] = profiled(pairs[k], metrics[k])
         if "with" in runs:
             out["reduce_path_with"] = pairs["with"]._engine.last_path(nat.PATH_REDUCE)
-            out["density_reductions"] = len(pairs["with"]._dens_wanted)
+            out["density_reductions"] = len(pairs["with"]._results["density"][1])
     finally:
         for p in pairs.values():
             p.close()

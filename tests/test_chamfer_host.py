@@ -127,11 +127,11 @@ def test_dependencies_and_keys():
     euclid = GeoTruncatedMSE(True, 0.5)._get_dependencies()["euclidean_distance"]
     assert euclid._key() == GeoHausdorffDistance(True, False)._get_dependencies()["euclidean_distance"]._key()
     # what the calculator tells prefetch_reductions: (is_left, point_to_plane, root, clamp) with the clamp tau * tau in fp64
-    assert GeoMeanDistance(False, True)._mapped_request() == (False, True, True, None)
-    assert GeoTruncatedMSE(True, 0.1)._mapped_request() == (True, False, False, float(np.float64(0.1) * np.float64(0.1)))
-    assert GeoTruncatedMeanDistance(False, 0.1)._mapped_request() == (False, False, True, float(np.float64(0.1) * np.float64(0.1)))
+    assert GeoMeanDistance(False, True)._pccm_request() == ("mapped", False, True, True, None)
+    assert GeoTruncatedMSE(True, 0.1)._pccm_request() == ("mapped", True, False, False, float(np.float64(0.1) * np.float64(0.1)))
+    assert GeoTruncatedMeanDistance(False, 0.1)._pccm_request() == ("mapped", False, False, True, float(np.float64(0.1) * np.float64(0.1)))
     for cls in (GeoMeanDistance, GeoTruncatedMSE, GeoTruncatedMeanDistance):
-        assert cls._pccm_waits is True and cls._pccm_item == "mapped"
+        assert cls._pccm_waits is True
 
 
 # ---- the nodes over plain arrays ---------------------------------------------------------------------------------------------

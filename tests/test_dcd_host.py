@@ -137,7 +137,8 @@ def test_dependencies_and_keys():
     assert MatchedRows(True)._key() == ("MatchedRows", True) and MatchedRows(False)._key() == ("MatchedRows", False)
     assert issubclass(MatchedRows, PrimaryMetric) and issubclass(MatchedRows, DirectionalMetric)
     assert issubclass(GeoDensityAwareDistance, SecondaryMetric) and issubclass(GeoDensityAwareDistance, DirectionalMetric)
-    assert GeoDensityAwareDistance._pccm_waits is True and GeoDensityAwareDistance._pccm_item == "density"
+    assert GeoDensityAwareDistance._pccm_waits is True
+    assert GeoDensityAwareDistance(False, 40, squared=True)._pccm_request() == ("density", False, 40.0, True)
     deps = GeoDensityAwareDistance(False, 40.0)._get_dependencies()
     assert [d._key() for d in deps.values()] == [EuclideanDistance(False, False)._key(), ("MatchedRows", False)]
     assert deps["euclidean_distance"]._key() == GeoHausdorffDistance(False, False)._get_dependencies()["euclidean_distance"]._key()
