@@ -622,6 +622,18 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id);
 int pccm_graph_launch(pccm_ctx *ctx, int graph_id);
 int pccm_graph_destroy(pccm_ctx *ctx, int graph_id);
 
+/* Filed tails.  A capture may leave the tail launch of pccm_nn_pair() out: the brick search files the queries ring 1 did not settle
+ * under their block of 4096 rows, and the reduction workgroup that owns those rows settles them (rings 2-3, the tail launch's own
+ * search) before it reduces.  It does so only when the eager step in front of the capture, on the same resident clouds, handed no
+ * query to the exact rescan, filled no block beyond the lists' capacity and reduced D1 + row-indexed D2 of every searched
+ * direction in one batch behind the search (and searched every direction the capture searches); otherwise, and whenever anything but such a reduction reads the results first, the
+ * graph holds the tail launch as ever.  Results are bit-identical either way.  pccm_set_tail_filing(ctx, 0), between
+ * pccm_graph_begin() and the captured search, keeps the tail launch in that capture (on: the default of every capture);
+ * PCCM_TAIL_FILED=0 in the environment keeps it always (A/B runs).
+ * pccm_graph_tail_filed(): *filed = 1 when graph `graph_id` was captured without the tail launch. */
+int pccm_set_tail_filing(pccm_ctx *ctx, int on);
+int pccm_graph_tail_filed(pccm_ctx *ctx, int graph_id, int *filed);
+
 /* Wait for everything queued on the context's stream. */
 int pccm_sync(pccm_ctx *ctx);
 

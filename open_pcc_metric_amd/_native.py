@@ -55,6 +55,7 @@ SYMBOLS = (
     "pccm_set_reflectance", "pccm_set_reflectance_u16", "pccm_get_reflectance",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
     "pccm_color_transform", "pccm_lzf_decompress", "pccm_drop_caches", "pccm_graph_begin", "pccm_graph_end", "pccm_graph_launch", "pccm_graph_destroy",
+    "pccm_set_tail_filing", "pccm_graph_tail_filed",
     "pccm_sync",
     "pccm_profile_enable", "pccm_profile_reset", "pccm_profile_get", "pccm_nn_stats", "pccm_nn_path", "pccm_grid_geometry",
     "pccm_build_plan", "pccm_build_fetch",
@@ -188,6 +189,8 @@ def load() -> ctypes.CDLL:
     lib.pccm_graph_end.argtypes = [vp, ctypes.POINTER(i32)]
     lib.pccm_graph_launch.argtypes = [vp, i32]
     lib.pccm_graph_destroy.argtypes = [vp, i32]
+    lib.pccm_set_tail_filing.argtypes = [vp, i32]
+    lib.pccm_graph_tail_filed.argtypes = [vp, i32, ctypes.POINTER(i32)]
     lib.pccm_profile_enable.argtypes = [vp, i32]
     lib.pccm_profile_reset.argtypes = [vp]
     lib.pccm_profile_get.argtypes = [vp, i32, dp, ctypes.POINTER(i64)]
@@ -879,6 +882,17 @@ class Engine:
         """Leave capture mode after a captured call failed (the partial graph is discarded)."""
         gid = ctypes.c_int(-1)
         self._lib.pccm_graph_end(self._ctx, ctypes.byref(gid))      # reports the failure; nothing to keep
+
+    def set_tail_filing(self, on: bool) -> None:
+        """Inside a capture, before its search: ``False`` keeps the tail launch in this capture whatever the eager step showed
+        (every capture starts with filing switched on; pccm_set_tail_filing)."""
+        _check(self._lib.pccm_set_tail_filing(self._ctx, int(bool(on))))
+
+    def graph_tail_filed(self, graph_id: int) -> bool:
+        """Whether the graph was captured without the tail launch (pccm_set_tail_filing)."""
+        filed = ctypes.c_int(0)
+        _check(self._lib.pccm_graph_tail_filed(self._ctx, int(graph_id), ctypes.byref(filed)))
+        return bool(filed.value)
 
     def graph_launch(self, graph_id: int) -> None:
         _check(self._lib.pccm_graph_launch(self._ctx, int(graph_id)))

@@ -68,9 +68,10 @@ int check_device_errors(pccm_ctx *ctx)
     const uint32_t e = __atomic_exchange_n(ctx->host_err, 0u, __ATOMIC_RELAXED);
     if (!e) return PCCM_OK;
     results_dropped(ctx);
-    return fail(PCCM_E_STATE, "a search kernel reported an inconsistent state (device error word 0x%x: %s%s%s): the results of this search were "
+    return fail(PCCM_E_STATE, "a search kernel reported an inconsistent state (device error word 0x%x: %s%s%s%s): the results of this search were "
                               "dropped, run it again", e, (e & 1u) ? "the tail launch's wait for its own workgroups ran out; " : "",
-                (e & 2u) ? "a voxel brick contradicts its cell start; " : "", (e & kErrMergeTable) ? "the duplicate table overflowed" : "");
+                (e & 2u) ? "a voxel brick contradicts its cell start; " : "", (e & kErrMergeTable) ? "the duplicate table overflowed; " : "",
+                (e & 8u) ? "a filed tail list overflowed or a filed query was not settled within three rings" : "");
 }
 
 static hipEvent_t take_event(pccm_ctx *ctx)
@@ -1368,12 +1369,16 @@ int pccm_nn_pair(pccm_ctx *ctx, int engine)
     return run_nn(ctx, 2, dirs, engine);
 }
 
-static int need_nn(pccm_ctx *ctx, int dir, const Cloud **it, const Cloud **se, NNResult **res)
+// The result of direction `dir`, for a reader.  A direction whose tails lie filed (NNForm::tails_filed: a capture left the tail
+// launch out for the settling reduction) has the classic tail launch settle them first, for every reader but the reduction batch
+// itself (binds: slot_prepare -- launch_unit_jobs decides there, job by job).
+static int need_nn(pccm_ctx *ctx, int dir, const Cloud **it, const Cloud **se, NNResult **res, bool binds = false)
 {
     int rc = dir_clouds(ctx, dir, it, se);
     if (rc) return rc;
     *res = &ctx->nn[dir];
     if (!(*res)->valid) return fail(PCCM_E_STATE, "pccm_nn(dir=%d) has not run for the current clouds/shard", dir);
+    if ((*res)->form.tails_filed && !binds) return filed_tails_resolve(ctx);
     return PCCM_OK;
 }
 
@@ -1381,6 +1386,10 @@ static int need_nn(pccm_ctx *ctx, int dir, const Cloud **it, const Cloud **se, N
 // wants columns (getters, colour kernels, the separate point kernel)
 static int ensure_plain(pccm_ctx *ctx, NNResult &res, bool need_idx)
 {
+    if (res.form.tails_filed) {                    // (the records are about to be read or rewritten: need_nn)
+        const int rc = filed_tails_resolve(ctx);
+        if (rc) return rc;
+    }
     if (res.form.plain_ready(need_idx)) return PCCM_OK;
     if (!res.form.has_records()) return fail(PCCM_E_STATE, "no nearest-neighbour result to read");
     const int dir = (int)(&res - ctx->nn);
@@ -1963,11 +1972,13 @@ static int slot_prepare(pccm_ctx *ctx, ReduceSlot &s, int dir, int metric, int n
 {
     const Cloud *it, *se;
     NNResult *res;
-    int rc = need_nn(ctx, dir, &it, &se, &res);
+    int rc = need_nn(ctx, dir, &it, &se, &res, /*binds=*/true);
     if (rc) return rc;
     const int64_t ns = res->end - res->begin;
     if ((rc = column_check(ctx, dir, metric, normal_mode, *it, *se, *res))) return rc;
     const ColumnSource src = column_source(ctx, dir, metric, normal_mode);
+    // (filed tails: a column that is not reduced straight from the records reads them in a kernel of its own first)
+    if (res->form.tails_filed && src.from != ColumnSource::kRecords && (rc = filed_tails_resolve(ctx))) return rc;
     const double *dev = (const double *)res->rec.p;
     int stride = 1;
     switch (src.from) {
@@ -2112,6 +2123,7 @@ static int prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *metri
         return PCCM_OK;
     }
     int rc;
+    if (pj.njobs > 0 && (rc = filed_tails_resolve(ctx))) return rc;      // (point jobs read matched records in place)
     if ((rc = launch_point_jobs(ctx, pj))) return rc;
     uint64_t seq = 0;
     if ((rc = launch_unit_jobs(ctx, uj, &seq))) return rc;
@@ -2747,12 +2759,35 @@ static int graph_replay(pccm_ctx *ctx, GraphRec &g)
     return PCCM_OK;
 }
 
+int pccm_set_tail_filing(pccm_ctx *ctx, int on)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->capturing) return fail(PCCM_E_STATE, "pccm_set_tail_filing speaks of the capture in progress: call pccm_graph_begin first");
+    ctx->tail_file.wish = on != 0;
+    return PCCM_OK;
+}
+
+int pccm_graph_tail_filed(pccm_ctx *ctx, int graph_id, int *filed)
+{
+    CHECK_CTX(ctx);
+    if (!filed) return fail(PCCM_E_ARG, "null pointer");
+    if (graph_id < 0 || graph_id >= (int)ctx->graphs.size() || !ctx->graphs[graph_id].valid)
+        return fail(PCCM_E_ARG, "unknown graph %d", graph_id);
+    *filed = ctx->graphs[graph_id].tails_filed ? 1 : 0;
+    return PCCM_OK;
+}
+
 int pccm_graph_begin(pccm_ctx *ctx)
 {
     CHECK_CTX(ctx);
     if (ctx->capturing) return fail(PCCM_E_STATE, "already capturing");
     if (ctx->ties != PCCM_TIES_PICK) return fail(PCCM_E_STATE, "searches under PCCM_TIES_MEAN run eagerly: no graph capture");
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    // filed tails: what the eager step in front of this capture left decides whether the capture may file (pccm_tail_wave.h)
+    ctx->tail_file.wish = true;
+    ctx->tail_file.left_out = ctx->tail_file.resolved = false;
+    int rcf = tail_facts(ctx, &ctx->tail_file.allowed, &ctx->tail_file.fact_dirs);
+    if (rcf) return rcf;
     for_each_slot(ctx, [](SlotKey &k) { k.pending = false; });      // nothing outside the graph may be half-consumed
     ctx->cap_ops.clear();
     ctx->cap_batches = 0;
@@ -2767,8 +2802,14 @@ int pccm_graph_end(pccm_ctx *ctx, int *graph_id)
     CHECK_CTX(ctx);
     if (!graph_id) return fail(PCCM_E_ARG, "null pointer");
     if (!ctx->capturing) return fail(PCCM_E_STATE, "pccm_graph_begin was not called");
+    // filed tails nobody has consumed (no reduction of that direction in the sequence): the classic tail launch ends the graph
+    const int rct = ctx->capture_failed ? PCCM_OK : filed_tails_resolve(ctx);
+    if (rct) ctx->capture_failed = true;
+    ctx->nn[PCCM_DIR_LEFT].form.tails_filed = ctx->nn[PCCM_DIR_RIGHT].form.tails_filed = false;
     ctx->capturing = false;
     GraphRec g;
+    g.tails_filed = ctx->tail_file.left_out && !ctx->tail_file.resolved;
+    ctx->tail_file.wish = ctx->tail_file.left_out = ctx->tail_file.resolved = false;
     hipError_t e = hipStreamEndCapture(ctx->stream, &g.graph);
     if (e != hipSuccess || ctx->capture_failed || !g.graph) {
         (void)hipGetLastError();
@@ -2833,6 +2874,11 @@ int pccm_graph_destroy(pccm_ctx *ctx, int graph_id)
 int pccm_ctx_reset(pccm_ctx *ctx)
 {
     CHECK_CTX(ctx);
+    ctx->nn[PCCM_DIR_LEFT].form.tails_filed = ctx->nn[PCCM_DIR_RIGHT].form.tails_filed = false;
+    ctx->tail_file.wish = ctx->tail_file.allowed = ctx->tail_file.left_out = ctx->tail_file.resolved = false;
+    ctx->tail_file.fact_dirs = 0;
+    ctx->tail_file.brick_key = 0;
+    ctx->tail_file.eager_ok = ctx->tail_file.eager_bad = 0;
     if (ctx->capturing) {                              // an abandoned capture: end it, discard what it recorded
         hipGraph_t g = nullptr;
         (void)hipStreamEndCapture(ctx->stream, &g);

@@ -38,6 +38,7 @@
 // instructions) is what a shorter kernel has to remove.  Reported against HBM as the contract asks.
 // Neighbouring bricks share runs through the XCD's L2 (XCD-aware brick order, as in round 1).
 #include "pccm_brick.h"
+#include "pccm_tail_wave.h"
 
 namespace pccm {
 
@@ -61,6 +62,27 @@ __device__ __forceinline__ void load_normal(const NNOut &o, int row, double &a, 
     } else {
         const double *np = o.nrm + 3 * (int64_t)row;
         a = np[0]; b = np[1]; c = np[2];
+    }
+}
+
+// A query ring 1 did not settle goes on the direction's tail list (k_grid_tail reads it) and -- when the step files its tails
+// (QueryJob::blk_cnt) -- under the 4096 rows of the reduction workgroup that will settle it.  A list that is full raises the device
+// error word: the capture rule has seen every block's count on the same clouds (pccm_tail_wave.h), so this never happens, and if
+// it does no sum is handed out.  A filed query's own result record is void until somebody settles it -- and the buffer still
+// holds whatever the last search of the direction left at that row, on resident clouds the very record a settle would store -- so
+// the row is overwritten here with a record no search produces (NaN coordinates, row -1): a settle that is missing, or whose store
+// does not reach the reader, shows as NaN in every sum and as row -1 in every column instead of passing on old bytes.
+__device__ __forceinline__ void tail_append(const QueryJobs &jobs, const QueryJob &J, const float4 q)
+{
+    const uint32_t pos = atomicAdd(&J.counters[1], 1u);
+    reinterpret_cast<float4 *>(J.tail)[pos] = q;
+    if (J.blk_cnt) {
+        const uint32_t blk = (uint32_t)(__float_as_int(q.w) - (int)J.row_base) >> kTailBlockShift;
+        const uint32_t slot = atomicAdd(&J.blk_cnt[blk], 1u);
+        if (slot < (uint32_t)kTailBlockCap) J.blk_list[(size_t)blk * kTailBlockCap + slot] = q;
+        else if (jobs.err) atomicOr(jobs.err, kErrTailFiled);
+        const float nan = __int_as_float(0x7fc00000);
+        store_result_rec(J.out, __float_as_int(q.w), nan, nan, nan, -1);      // (filing is for matched records: NNOut::layout 1)
     }
 }
 
@@ -178,8 +200,7 @@ __device__ __forceinline__ void brick_body(const QueryJobs &jobs, const GridGeom
         // clumped data: more candidates than the LDS budget holds -- the general kernels take this brick's queries
         for (uint32_t qi = tid; qi < NQ; qi += NT) {
             const float4 q = load_query(qi, query_row(qi));
-            const uint32_t pos = atomicAdd(&J.counters[1], 1u);
-            reinterpret_cast<float4 *>(J.tail)[pos] = q;
+            tail_append(jobs, J, q);
         }
         return;
     }
@@ -486,10 +507,7 @@ __device__ __forceinline__ void brick_body(const QueryJobs &jobs, const GridGeom
                 store_result(out, qrow, d64, p, wrow);
             }
         }
-        if (!settled) {
-            const uint32_t pos = atomicAdd(&J.counters[1], 1u);
-            reinterpret_cast<float4 *>(J.tail)[pos] = q;
-        }
+        if (!settled) tail_append(jobs, J, q);
         if (hn) {                                                      // fetched only now: keeps the scan's registers free
             rn = query_row(qnext);
             qn = load_query(qnext, rn);

@@ -123,7 +123,8 @@ struct BuildJobs {
 // cs[c] holds the position of the first record of cell c RELATIVE to the job's first record and cs[ncells] the
 // number of records of the job.
 int sort_by_cell(pccm_ctx *ctx, const BuildJobs &jobs, const GridGeom &g, int64_t ncells, void *recs, bool rec32,
-                 uint32_t *zero = nullptr, int nzero = 0);   // zero: up to 256 words the last kernel clears for the caller
+                 uint32_t *zero = nullptr, int nzero = 0,    // zero: up to 256 words the last kernel clears for the caller
+                 uint32_t *zero2 = nullptr, int64_t nzero2 = 0);   // zero2: any number of words more
 
 // scratch sizes (so that callers can allocate before a graph capture)
 int64_t scan_tiles(int64_t m);
@@ -218,6 +219,11 @@ struct QueryJob {
     uint32_t *counters;         // [0] = queries handed to the exact full rescan (k2b_fallback), [1] = tail length
     int32_t *flagged;           // ... their rows (relative to row_base) and fp32 filter thresholds
     float *flag_thr;
+    // filed tails (pccm_tail_wave.h; the brick kernel alone): every tail entry is also filed under its block of 4096 rows --
+    // blk_cnt[row >> 12] counts, blk_list[row >> 12][kTailBlockCap] holds the queries -- for the reduction workgroup that owns
+    // those rows to settle.  Null: not filed
+    uint32_t *blk_cnt = nullptr;
+    float4 *blk_list = nullptr;
 };
 
 struct QueryJobs {
@@ -229,6 +235,7 @@ struct QueryJobs {
 // bits of the device error word: a kernel that meets a state it cannot be in raises one instead of answering wrongly in silence
 constexpr uint32_t kErrTailWait = 1u;      // k_grid_tail: the rescan's wait for the tail workgroups ran out
 constexpr uint32_t kErrVoxState = 2u;      // pccm_vox.hip: a record outside its tile / a query outside its cell
+constexpr uint32_t kErrTailFiled = 8u;     // (4: kErrMergeTable, pccm_internal.h) filed tails: a block's list overflowed, or three rings did not settle a filed query
 
 constexpr int kMaxRing = 3;
 

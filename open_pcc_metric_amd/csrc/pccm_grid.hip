@@ -24,6 +24,8 @@
 //             otherwise: k_grid_query_coop (per-wave staging, segment-local fp32)
 //             -> k_grid_tail, first half: few unsettled queries one wave each (wave_tail), many one thread each
 //                (thread_search), rings 2..kMaxRing; second half of the same launch: the exact rescan below
+//                (a captured step of a pair may leave this launch out and file the unsettled queries by row block for the
+//                reduction's workgroups to settle: pccm_tail_wave.h, "filed tails")
 //           surfaces and integer lattices (decide_scale, use_coop):
 //             k_grid_query = thread_search for every query, fp64 throughout
 //           -> the exact rescan (pccm_rescan.h; behind the per-thread kernels as k2b_fallback, pccm_brute.hip): scan of the whole
@@ -35,6 +37,7 @@
 // "<" after shrinking the bound by 2^-30, so a stop is never taken on a rounding coincidence.
 #include "pccm_grid.h"
 #include "pccm_rescan.h"
+#include "pccm_tail_wave.h"
 
 namespace pccm {
 
@@ -83,35 +86,6 @@ __device__ __forceinline__ void scan_range(const REC *__restrict__ recs, uint32_
         for (int j = 0; j < kBatch; ++j) a[j] = load_rec(recs, (p + j < e) ? p + j : e - 1);
 #pragma unroll
         for (int j = 0; j < kBatch; ++j) consider(a[j], qx, qy, qz, qrow, SELF, b);
-    }
-}
-
-// ... the same with the winner's coordinates kept (wave_tail: what the result record or the fused projection needs is then in
-// registers when the search ends)
-struct BestAt {
-    double d, x, y, z;
-    int idx;
-};
-
-template <typename REC, bool SELF, int kBatch>
-__device__ __forceinline__ void scan_range_at(const REC *__restrict__ recs, uint32_t s, uint32_t e, double qx, double qy, double qz, int qrow,
-                                              BestAt &b)
-{
-    for (uint32_t p = s; p < e; p += kBatch) {
-        P3 a[kBatch];
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) a[j] = load_rec(recs, (p + j < e) ? p + j : e - 1);
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-            const double d = gdist64(qx, qy, qz, a[j].x, a[j].y, a[j].z);
-            bool better = d < b.d || (d == b.d && a[j].row < b.idx);
-            if (SELF) better = better && (a[j].row != qrow);
-            b.d = better ? d : b.d;
-            b.idx = better ? a[j].row : b.idx;
-            b.x = better ? a[j].x : b.x;
-            b.y = better ? a[j].y : b.y;
-            b.z = better ? a[j].z : b.z;
-        }
     }
 }
 
@@ -405,7 +379,6 @@ __device__ __forceinline__ void wave_tail(const QueryJobs &jobs, const GridGeom 
 {
     const int lane = threadIdx.x & 63;
     const uint32_t wave0 = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = nblocks * 4u;      // (the launch's tail workgroups, not gridDim.x)
-    const int dimx = g.dim[0], dimy = g.dim[1], dimz = g.dim[2];
     // The first job's tail is handed out to the waves from the front, the second job's from the back (a wave that took an
     // entry of each job in turn walked the chain of dependent round trips -- tail record, cell starts, records, winner --
     // twice), and the list lengths travel together with the wave's first candidate entry of every job (an entry beyond
@@ -434,43 +407,8 @@ __device__ __forceinline__ void wave_tail(const QueryJobs &jobs, const GridGeom 
             const P3 qa = (qi == start[jb]) ? first[jb] : load_rec((const REC *)J.tail, qi);   // wave-uniform
             const double qx = qa.x, qy = qa.y, qz = qa.z;
             const int qrow = qa.row;
-            const int cx = cell_coord(qx, g.org[0], g.inv_h[0], dimx);
-            const int cy = cell_coord(qy, g.org[1], g.inv_h[1], dimy);
-            const int cz = cell_coord(qz, g.org[2], g.inv_h[2], dimz);
             BestAt b;                                          // (the winner's coordinates travel with it: no look-up behind the search)
-            b.d = INFINITY;
-            b.idx = 0x7fffffff;
-            b.x = b.y = b.z = 0.0;
-            bool done = false;
-            // every query on the tail list has been through a ring-1 kernel that could not settle it -- mostly because the
-            // stop rule failed, which a second look at ring 1 cannot change: start with the 5 x 5 x 5 cube (it contains
-            // ring 1, scanned here in exact fp64, so uncertified near ties are resolved too)
-            for (int r = 2; r <= kMaxRing && !done; ++r) {
-                const int side = 2 * r + 1;
-                if (lane < side * side) {
-                    const int z = cz + lane / side - r, y = cy + lane % side - r;
-                    if (z >= 0 && z < dimz && y >= 0 && y < dimy) {
-                        const uint32_t row = ((uint32_t)z * dimy + y) * dimx;
-                        const int x0 = max(cx - r, 0), x1 = min(cx + r, dimx - 1);
-                        scan_range_at<REC, SELF, 8>(srecs, cell_start[row + x0], cell_start[row + x1 + 1], qx, qy, qz, qrow, b);
-                    }
-                }
-                double wm = b.d;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) wm = fmin(wm, __shfl_xor(wm, off));
-                int wi = (b.d == wm) ? b.idx : 0x7fffffff;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) wi = min(wi, __shfl_xor(wi, off));
-                // a lane that holds the winner hands its coordinates to everybody (rows are unique per record: one such lane)
-                const unsigned long long holds = __ballot(b.d == wm && b.idx == wi);
-                const int src = holds ? __ffsll((long long)holds) - 1 : 0;
-                b.x = __shfl(b.x, src);
-                b.y = __shfl(b.y, src);
-                b.z = __shfl(b.z, src);
-                b.d = wm;
-                b.idx = wi;
-                done = settled_by(face_bound(g, qx, qy, qz, cx, cy, cz, r), b.d);
-            }
+            const bool done = wave_settle<REC, SELF>(g, cell_start, srecs, qa, lane, b);      // rings 2..kMaxRing: pccm_tail_wave.h
             if (lane == 0) {
                 if (!done) {                                 // (wave-uniform)
                     defer_rescan(J, qrow, b.d);
@@ -1031,7 +969,8 @@ struct ShardSort {
 };
 
 static int ensure_grid(pccm_ctx *ctx, bool need64 = false, int need_mask = 3, uint32_t *zero = nullptr, int nzero = 0, bool *rebuilt = nullptr,
-                       ShardSort *shard = nullptr, int want_vox = 0)     // want_vox: 1 voxel bricks, 2 ... with the rows' table
+                       ShardSort *shard = nullptr, int want_vox = 0,     // want_vox: 1 voxel bricks, 2 ... with the rows' table
+                       uint32_t *zero2 = nullptr, int64_t nzero2 = 0)
 {
     if (rebuilt) *rebuilt = false;
     Grid &gr = ctx->grid;
@@ -1051,6 +990,9 @@ static int ensure_grid(pccm_ctx *ctx, bool need64 = false, int need_mask = 3, ui
     const bool same = gr.key == key && gr.n[0] == ctx->cloud[0].n && gr.n[1] == ctx->cloud[1].n && gr.recs.p && gr.rec32 == rec32 &&
                       gr.vox == vox && (!vox_rows || gr.vox_rows) && (!rec32 || gr.lattice == lattice_pair(ctx, geom_of(gr), rec32));
     if (same && (gr.built & need_mask) == need_mask) return PCCM_OK;
+    // (filed tails nobody has consumed hold pointers into the cell starts and records about to be rewritten: the classic launch
+    // reads them now)
+    if (const int rcf = filed_tails_resolve(ctx)) return rcf;
     if (same) need_mask |= gr.built;                   // keep what is there, add what is missing
     ProfScope ps(ctx, PCCM_K_GRID_BUILD);
     ctx->builds[PCCM_BUILD_GRID0].valid = ctx->builds[PCCM_BUILD_GRID1].valid = false;   // the grid's buffers are written (or moved) below
@@ -1101,7 +1043,7 @@ static int ensure_grid(pccm_ctx *ctx, bool need64 = false, int need_mask = 3, ui
         jobs.total += shard->n;
         shard->done = true;
     }
-    if (jobs.total > 0 && (rc = sort_by_cell(ctx, jobs, g, ncells, first, rec32, zero, nzero))) return rc;
+    if (jobs.total > 0 && (rc = sort_by_cell(ctx, jobs, g, ncells, first, rec32, zero, nzero, zero2, nzero2))) return rc;
 #ifdef PCCM_DIAG
     // diagnostic builds only (tests/test_gpu_device_errors.py): a cell start that contradicts the records, so that the brick
     // build meets records outside its tile -- the state pccm_vox.hip reports through the device error word
@@ -1302,6 +1244,77 @@ static int launch_tail(pccm_ctx *ctx, const QueryJobs &jobs, const GridGeom &g, 
     return PCCM_OK;
 }
 
+// ---- filed tails: the host side (pccm_tail_wave.h) ------------------------------------------------------------------------------
+// The classic tail launch, put back for a reader that is not the settling reduction: the global tail lists and their counters are
+// written by the filing brick kernel as ever, so k_grid_tail runs on them as it would have.  (A direction whose reduction has
+// settled it already is searched again with the same results.)
+int filed_tails_resolve(pccm_ctx *ctx)
+{
+    pccm_ctx::TailFile &tf = ctx->tail_file;
+    if (!ctx->nn[PCCM_DIR_LEFT].form.tails_filed && !ctx->nn[PCCM_DIR_RIGHT].form.tails_filed) return PCCM_OK;
+    ctx->nn[PCCM_DIR_LEFT].form.tails_filed = ctx->nn[PCCM_DIR_RIGHT].form.tails_filed = false;
+    if (!tf.state) return fail(PCCM_E_STATE, "filed tails without their search");
+    const FiledTails &st = *tf.state;
+    const Cloud *its[2], *ses[2];
+    NNResult *ress[2];
+    for (int k = 0; k < 2; ++k) {
+        its[k] = &ctx->cloud[st.dirs[k] == PCCM_DIR_RIGHT ? 1 : 0];
+        ses[k] = &ctx->cloud[st.dirs[k] == PCCM_DIR_LEFT ? 1 : 0];
+        ress[k] = &ctx->nn[st.dirs[k]];
+    }
+    tf.resolved = true;
+    return launch_tail(ctx, st.jobs, st.g, false, true, st.nqmax, its, ses, ress);
+}
+
+const TailSettle *filed_tails_settle(const pccm_ctx *ctx, int dir, int *entry)
+{
+    *entry = -1;
+    const FiledTails *st = ctx->tail_file.state;
+    if (!st || dir < 0 || dir > 1 || !ctx->nn[dir].form.tails_filed) return nullptr;
+    for (int k = 0; k < st->jobs.njobs; ++k)
+        if (st->dirs[k] == dir) *entry = k;
+    return *entry >= 0 ? &st->settle : nullptr;
+}
+
+// The capture rule (tail_filing_allowed) on what the last eager step left on the device: per direction the flagged count, and the
+// tail list binned by row block.  Two small copies and a wait -- in front of a capture, never inside a step.
+int tail_facts(pccm_ctx *ctx, bool *allowed, int *dirs)
+{
+    *dirs = 0;
+    static const bool on = [] { const char *e = getenv("PCCM_TAIL_FILED"); return !(e && e[0] == '0'); }();   // A/B: =0 keeps the tail launch
+    *allowed = false;
+    if (!on || ctx->ties != PCCM_TIES_PICK || ctx->sharded() || ctx->tail_file.brick_key == 0) return PCCM_OK;
+    TailFacts facts[2];
+    std::vector<Rec32> list;
+    std::vector<int32_t> rows;
+    for (int d = 0; d < 2; ++d) {
+        const NNResult &res = ctx->nn[d];
+        const Cloud &it = ctx->cloud[d == PCCM_DIR_RIGHT ? 1 : 0];
+        if (!res.valid) continue;
+        if (res.form.recs != NNForm::kMatched || res.begin != 0 || res.end != it.n || !res.nflag_dev || !res.tail.p) return PCCM_OK;
+        uint32_t c[2] = {0, 0};
+        PCCM_HIP(hipMemcpyAsync(c, res.nflag_dev, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+        PCCM_HIP(hipStreamSynchronize(ctx->stream));
+        if ((int64_t)c[1] > it.n || (size_t)c[1] * sizeof(Rec32) > res.tail.bytes) return PCCM_OK;
+        list.resize(c[1]);
+        if (c[1]) {
+            PCCM_HIP(hipMemcpyAsync(list.data(), res.tail.p, (size_t)c[1] * sizeof(Rec32), hipMemcpyDeviceToHost, ctx->stream));
+            PCCM_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        rows.resize(c[1]);
+        for (size_t i = 0; i < list.size(); ++i) rows[i] = list[i].row;
+        // (what the eager step reduced behind this search is what the capture will: a direction no batch could have settled,
+        // or that a batch read in another way, keeps the tail launch for everybody)
+        if (!(ctx->tail_file.eager_ok & (1 << d)) || (ctx->tail_file.eager_bad & (1 << d))) return PCCM_OK;
+        facts[d].searched = true;
+        facts[d].flagged = c[0];
+        facts[d].block_max = tail_block_max(rows.data(), (int64_t)rows.size(), it.n);
+    }
+    *allowed = tail_filing_allowed(facts, 2, true);
+    for (int d = 0; d < 2; ++d) *dirs |= (*allowed && facts[d].searched) ? 1 << d : 0;
+    return PCCM_OK;
+}
+
 // Exact 1-NN for `ndirs` directions (LEFT and RIGHT fused into the same launches when both are asked for).
 int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
 {
@@ -1363,13 +1376,43 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
         if (rows && dir == PCCM_DIR_SELF) want_vox = 0;
         else if (rows) want_vox = 2;
     }
+    // Filed tails (pccm_tail_wave.h): whole clouds, no self search in the call.  The per-block counts of both directions live side
+    // by side (direction 0's blocks, then direction 1's) and are cleared by the build's last kernel, like the counters above; the
+    // buffers are sized by eager searches, so that a capture finds them in place (or does not file).
+    pccm_ctx::TailFile &tf = ctx->tail_file;
+    const int64_t tblk[2] = {(ctx->cloud[0].n + (1ll << kTailBlockShift) - 1) >> kTailBlockShift,
+                             (ctx->cloud[1].n + (1ll << kTailBlockShift) - 1) >> kTailBlockShift};
+    const int64_t tblocks = tblk[0] + tblk[1];
+    bool may_file = nsh == 0 && ndirs > 0 && tblocks > 0 && ctx->ties == PCCM_TIES_PICK && !ctx->sharded();
+    for (int d = 0; d < ndirs; ++d) {
+        const NNResult &res = ctx->nn[dirs[d]];
+        const Cloud &it = ctx->cloud[dirs[d] == PCCM_DIR_RIGHT ? 1 : 0];
+        may_file = may_file && dirs[d] != PCCM_DIR_SELF && res.begin == 0 && res.end == it.n && it.n > 0;
+    }
+    if (may_file && !ctx->capturing) {
+        if ((rc = ensure(ctx, tf.cnt, (size_t)tblocks * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(ctx, tf.list, (size_t)tblocks * kTailBlockCap * sizeof(float4)))) return rc;
+    }
+    may_file = may_file && tf.cnt.bytes >= (size_t)tblocks * sizeof(uint32_t) && tf.list.bytes >= (size_t)tblocks * kTailBlockCap * sizeof(float4);
     if ((rc = ensure_grid(ctx, false, need, side_by_side ? (uint32_t *)ctx->counters.p + 2 * dlo : nullptr, 2 * ndirs, &rebuilt,
-                          ride_dir >= 0 ? &ride : nullptr, want_vox))) return rc;
+                          ride_dir >= 0 ? &ride : nullptr, want_vox, may_file ? (uint32_t *)tf.cnt.p : nullptr, tblocks))) return rc;
     const Grid &gr = ctx->grid;
     const GridGeom g = geom_of(gr);
     const uint32_t *cs_all = (const uint32_t *)gr.cell_start.p;
     const char *recs_all = (const char *)gr.recs.p;
     const size_t rsz = gr.rec32 ? sizeof(Rec32) : sizeof(GridRec);
+    // this call files its tails: a capture that was told to (pccm_set_tail_filing) behind an eager step that passed the capture
+    // rule, on the brick kernel, with the counts just cleared by the build -- and (below) matched records in every direction
+    const bool brick_pair = may_file && gr.rec32 && !gr.vox && use_coop(ctx);
+    bool file = brick_pair && ctx->capturing && tf.wish && tf.allowed && rebuilt && gr.key == tf.brick_key && gr.ncells == tf.brick_ncells;
+    for (int d = 0; d < ndirs; ++d) file = file && (tf.fact_dirs & (1 << dirs[d]));      // (a direction the eager step did not search: no facts, no filing)
+    bool pair_dirs = false;                          // (a self search in between leaves what the pair's search noted alone)
+    for (int d = 0; d < ndirs; ++d) pair_dirs = pair_dirs || dirs[d] != PCCM_DIR_SELF;
+    if (!ctx->capturing && pair_dirs) {
+        tf.brick_key = brick_pair ? gr.key : 0;
+        tf.brick_ncells = gr.ncells;
+        tf.eager_ok = tf.eager_bad = 0;
+    }
 
     QueryJobs normal, selfj;
     normal.njobs = 0;
@@ -1445,6 +1488,11 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
         J.out.layout = res.form.layout();
         J.tail = res.tail.p;
         J.counters = res.nflag_dev;                         // [0] full rescans, [1] tail length
+        file = file && recs == NNForm::kMatched;
+        if (file) {
+            J.blk_cnt = (uint32_t *)tf.cnt.p + (ii ? tblk[0] : 0);
+            J.blk_list = (float4 *)tf.list.p + (size_t)(ii ? tblk[0] : 0) * kTailBlockCap;
+        }
         if ((rc = ensure(ctx, res.flagged, (size_t)nq * sizeof(int32_t)))) return rc;
         if ((rc = ensure(ctx, res.flag_thr, (size_t)nq * sizeof(float)))) return rc;
         J.flagged = (int32_t *)res.flagged.p;
@@ -1498,8 +1546,10 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
     for (int pass = 0; pass < 2; ++pass) {
         QueryJobs &jobs = pass ? selfj : normal;
         if (jobs.njobs == 0) continue;
-        if (jobs.njobs == 1) jobs.j[1] = jobs.j[0];
         const bool self = pass == 1;
+        if (!file)                                       // (one direction's form said no: nobody files)
+            for (int k = 0; k < jobs.njobs; ++k) jobs.j[k].blk_cnt = nullptr;
+        if (jobs.njobs == 1) jobs.j[1] = jobs.j[0];
         int64_t chunks = 0, nqmax = 0;
         for (int k = 0; k < jobs.njobs; ++k) {
             chunks += jobs.j[k].nchunks;
@@ -1537,7 +1587,25 @@ int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx)
             tail_launch = false;                 // the per-thread kernels walk all three rings themselves
         }
         PCCM_HIP(hipGetLastError());
-        if (tail_launch) {
+        if (tail_launch && file && !self) {
+            // no tail launch: the lists are consumed by each direction's settling reduction, or by the classic launch put back for
+            // any other reader (filed_tails_resolve) -- the directions' forms say so until then
+            if (!tf.state) tf.state = new FiledTails;
+            FiledTails &st = *tf.state;
+            st.jobs = jobs;
+            st.g = g;
+            st.nqmax = nqmax;
+            st.settle.g = g;
+            st.settle.err = ctx->host_err;
+            st.settle.on = 1u;
+            for (int k = 0; k < 2; ++k) {
+                const QueryJob &J = jobs.j[k < jobs.njobs ? k : 0];
+                st.dirs[k] = pd[k < jobs.njobs ? k : 0];
+                st.settle.d[k] = {J.cs, (const Rec32 *)J.srecs, J.blk_list, J.blk_cnt, (float4 *)J.out.rec};
+                if (k < jobs.njobs) ress[k]->form.tails_filed = true;
+            }
+            tf.left_out = true;
+        } else if (tail_launch) {
             if ((rc = launch_tail(ctx, jobs, g, self, gr.rec32, nqmax, its, ses, ress))) return rc;
         } else {
             // whatever the rings could not settle: exact rescan, list lengths read on the device (an empty list is an early exit)
@@ -1952,12 +2020,15 @@ int grid_ensure_solo(pccm_ctx *ctx, int which)
 void grid_release(pccm_ctx *ctx)
 {
     DevBuf *bufs[] = {&ctx->grid.cell_start, &ctx->grid.occ, &ctx->grid.recs, &ctx->grid.vbricks, &ctx->grid.vlist, &ctx->grid.vcount, &ctx->grid.vminrow,
-                      &ctx->g_cell_of, &ctx->g_rank, &ctx->g_hist, &ctx->g_blocksum, &ctx->g_qrecs, &ctx->g_bins, &ctx->g_tmp};
+                      &ctx->g_cell_of, &ctx->g_rank, &ctx->g_hist, &ctx->g_blocksum, &ctx->g_qrecs, &ctx->g_bins, &ctx->g_tmp,
+                      &ctx->tail_file.cnt, &ctx->tail_file.list};
     for (DevBuf *b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
         b->bytes = 0;
     }
+    delete ctx->tail_file.state;
+    ctx->tail_file.state = nullptr;
     for (BuildNote &b : ctx->builds) b.valid = false;
     ctx->grid.key = 0;
 }

@@ -175,6 +175,8 @@ struct BinPlan {
     int64_t nstate;        // scan tiles + 1 (the ticket)
     uint32_t *zero;        // words the last build kernel clears for the caller (the searches' counters), or null
     int nzero;
+    uint32_t *zero2;       // ... and a longer run of them (the filed tails' per-block counts), or null
+    int64_t nzero2;
     // cursor variant (default): no scan kernel.  cursor[job][bin] = running total of the bin (zero on entry; k_bin_sort
     // leaves it zero again), toff[tile][bin] = where the tile's share starts inside the bin, bstart[job][bin] (+ sentinel)
     // = first record of the bin, written by the first tile of each job in k_bin_scatter
@@ -515,6 +517,8 @@ __global__ __launch_bounds__(256, sizeof(REC) == 16 ? 6 : 4) void k_bin_sort(Bin
     }
     if (b == P.nbin - 1 && tid == 0) J.cs[P.ncells] = e - j0;   // number of records of the job
     if (blockIdx.x == 0 && tid < P.nzero) P.zero[tid] = 0u;     // saves the caller a memset node
+    if (blockIdx.x == 0)
+        for (int64_t i = tid; i < P.nzero2; i += 256) P.zero2[i] = 0u;
 }
 
 static int ceil_log2(int64_t v)
@@ -524,12 +528,15 @@ static int ceil_log2(int64_t v)
     return l;
 }
 
-int sort_by_cell(pccm_ctx *ctx, const BuildJobs &jobs, const GridGeom &g, int64_t ncells, void *recs, bool rec32, uint32_t *zero, int nzero)
+int sort_by_cell(pccm_ctx *ctx, const BuildJobs &jobs, const GridGeom &g, int64_t ncells, void *recs, bool rec32, uint32_t *zero, int nzero,
+                 uint32_t *zero2, int64_t nzero2)
 {
     BinPlan P;
     ctx->scratch_gen++;                                    // whatever lived in the sort's scratch is about to go
     P.zero = zero;
     P.nzero = zero ? nzero : 0;
+    P.zero2 = zero2;
+    P.nzero2 = zero2 ? nzero2 : 0;
     P.njobs = jobs.njobs;
     P.ncells = ncells;
     // bins of 2^10 cells while that keeps the bins of a cloud below 8192 (the tiles' LDS histogram): a bin of ~1400 records

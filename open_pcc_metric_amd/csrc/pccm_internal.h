@@ -109,6 +109,9 @@ struct NNForm {
     } recs = kNone;
     enum Plain { kNoPlain, kPlainD2, kPlainAll } plain = kNoPlain;   // unpacked into d2 / idx: nothing, d2 alone, both
     int fused = -1;               // normal mode of the projection fused into the search, -1: none
+    // the records of the queries ring 1 did not settle are not written yet: the queries lie filed by row block (pccm_tail_wave.h)
+    // for the settling reduction; every other reader has the classic tail launch settle them first (filed_tails_resolve)
+    bool tails_filed = false;
 
     static NNForm columns() { return {kNone, kPlainAll, -1}; }
     bool has_records() const { return recs != kNone; }
@@ -254,6 +257,8 @@ struct UnitJob {                // one per-point array to reduce (k_unit_jobs): 
     const int32_t *rows = nullptr;
     const uint32_t *cnt = nullptr;
     int64_t cnt_rows = 0;
+    // k_unit_lean alone: 1 + the entry of TailSettle::d whose filed tails this job's workgroups settle before they reduce, 0: none
+    int settle = 0;
 };
 
 // the shape SlotShape describes, as the kernels are told it: a job's rows, units and tail ...
@@ -345,8 +350,12 @@ struct GraphRec {
     std::vector<GraphOp> ops;
     uint64_t epoch = 0;        // pccm_ctx::epoch it was captured under
     uint64_t batches = 0;      // reduction batches in it that publish on the completion counter (each replay adds as many)
+    bool tails_filed = false;  // the searches' tails are settled by the reductions: no tail launch in it (pccm_set_tail_filing)
     bool valid = false;
 };
+
+struct FiledTails;               // pccm_tail_wave.h
+struct TailSettle;
 
 }  // namespace pccm
 
@@ -417,6 +426,24 @@ struct pccm_ctx {
     bool p2d_color = false;
     pccm::DevBuf tail_sync;               // k_grid_tail: retired-entry counts + ticket, for the normal and the self pass
     bool tail_sync_clean = false;
+    // filed tails (pccm_tail_wave.h): inside a capture the pair's brick search files its unsettled queries by row block and leaves
+    // the tail launch out; the reduction of each direction settles them (k_unit_lean's settling head)
+    struct TailFile {
+        bool wish = false;                // the capture in progress may file (on from pccm_graph_begin; pccm_set_tail_filing)
+        bool allowed = false;             // the capture rule held for the eager step in front of this capture (pccm_graph_begin) ...
+        int fact_dirs = 0;                // ... bit d: direction d's lists were among those it read (a search of any other files nothing)
+        bool left_out = false;            // the capture in progress has left a tail launch out ...
+        bool resolved = false;            // ... and put it back for a reader other than the settling reduction
+        pccm::DevBuf cnt, list;           // uint32 [blocks of dir 0 | of dir 1], float4 [the same][kTailBlockCap]
+        uint64_t brick_key = 0;           // Grid::key / ncells of the last eager pair search when the brick kernel ran it on whole
+        int64_t brick_ncells = 0;         // clouds (0: it did not): the lists the capture rule reads are that search's
+        int eager_ok = 0, eager_bad = 0;  // bit d: since that search, a reduction batch read direction d's records and could have
+                                          // settled its tails / could not (launch_unit_jobs).  A hint for speed alone: it keeps a
+                                          // capture from filing what its reductions will not settle (the brick kernel would file
+                                          // and the classic launch run all the same).  A wrong value costs time, never a result:
+                                          // whoever reads a filed direction settles it or has it resolved first
+        pccm::FiledTails *state = nullptr; // what the search left for whoever consumes the lists
+    } tail_file;
     pccm::DevBuf color_cols, color_idx;   // colour pass: squares as three columns / caller-supplied neighbour rows
     pccm::DevBuf colsum_scratch;          // ... the column sums' chunk guesses and sub-chunk totals (pccm_color.hip)
     bool colsum_configured = false;       // k_colsum_chain's LDS opt-in was set on this context's device
@@ -588,6 +615,12 @@ int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, 
 int nn_brute(pccm_ctx *ctx, const Cloud &it, const Cloud &se, bool self, NNResult &res);
 // grid engine
 int nn_grid(pccm_ctx *ctx, int ndirs, const int *dirs, int force_idx = 0);   // force_idx: records carry the matched row whatever pccm_nn_want_idx says
+// filed tails: the classic tail launch over the lists nobody has consumed (every direction that says tails_filed), for a reader
+// other than the settling reduction; no-op when there are none
+int filed_tails_resolve(pccm_ctx *ctx);
+// ... the kernel argument of the settling reduction and the entry of it that direction `dir` is (-1: not filed)
+const TailSettle *filed_tails_settle(const pccm_ctx *ctx, int dir, int *entry);
+int tail_facts(pccm_ctx *ctx, bool *allowed, int *dirs);      // the capture rule on the last eager step's lists (pccm_graph_begin)
 void grid_release(pccm_ctx *ctx);
 void grid_invalidate(pccm_ctx *ctx);
 int grid_ensure(pccm_ctx *ctx, bool need64 = false, int need_mask = 3);
@@ -821,6 +854,8 @@ int launch_ingest_reflectance(pccm_ctx *ctx, const void *src, int dtype, int64_t
 int launch_unpack(pccm_ctx *ctx, const double *rec, int stride, int layout, const float4 *q32, int64_t row0, int64_t ns, int32_t *idx, double *d2);
 // *seq: the value the context's completion counter reaches once the batch's host outputs are complete (k_publish), or 0 when
 // nothing was launched
+// (a direction whose tails lie filed is settled by the batch's own kernels where they can, by the classic tail launch in front of
+// them otherwise: pccm_tail_wave.h)
 int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq);
 // the selection launches of jobs.sel (memset of the histograms, kSelPasses histogram passes, resolve); nothing is published
 int launch_unit_select(pccm_ctx *ctx, UnitJobs &jobs);

@@ -1,6 +1,7 @@
 // Ingest, the per-point column kernel (K3) and the NumPy-ordered leaf reduction (K5).
 #include "pccm_internal.h"
 #include "pccm_reduce_shape.h"
+#include "pccm_tail_wave.h"
 
 namespace pccm {
 
@@ -831,15 +832,80 @@ __global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
         unit_tail<UnitCols>(jobs, t - unit_threads);
 }
 
-template <int STRIDE, int CFG, int DEFER = 0>
-__global__ __launch_bounds__(256) void k_unit_lean(UnitJobs jobs)
+// The settling head of k_unit_lean (filed tails, pccm_tail_wave.h): jobs over matched records whose direction's search left the tail
+// launch out.  A workgroup owns 4096 consecutive rows of its job; the queries ring 1 did not settle among them lie filed under that
+// block, a handful at most.  The workgroup reads its block's count (uniform: a scalar load), wave w settles entries w, w + 4, ...
+// with the tail kernel's own search (wave_settle) and stores their matched records, and only then runs the unchanged leaf
+// reduction over records that are all there.  The workgroups that copy the raw rows of the column's last, partial chunk
+// (unit_tail) read rows of blocks that leaf workgroups own: they settle the entries of the (at most two per job) blocks their
+// rows lie in for themselves -- the same stores, bit for bit.  So every workgroup reads only records that the search kernel
+// wrote before the launch or that its own waves wrote: the hand-over is between waves of one workgroup (drained stores, then the
+// barrier, whose workgroup-scope release / acquire is all one CU's L1 needs), nothing is waited for, nothing is polled, and no
+// agent-scope fence writes an L2 back (k_grid_tail's notes: 57 against 12 us with one per workgroup).  A query three rings do not
+// settle has no exact rescan behind it here (the capture rule saw none on these clouds): it raises the device error word.
+// -> whether the block held entries (block-uniform)
+__device__ __forceinline__ bool settle_block(const TailSettle &ts, const TailSettleDir &D, int64_t blk)
 {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t n = D.cnt[blk];                               // block-uniform: a scalar load
+    if (!n) return false;
+    n = n < (uint32_t)kTailBlockCap ? n : (uint32_t)kTailBlockCap;      // (a longer list raised the error word when it was filed)
+    const int lane = threadIdx.x & 63;
+    for (uint32_t e = threadIdx.x >> 6; e < n; e += 4) {
+        const float4 q = D.list[blk * kTailBlockCap + e];  // wave-uniform
+        P3 qa;
+        qa.x = (double)q.x; qa.y = (double)q.y; qa.z = (double)q.z;
+        qa.row = __float_as_int(q.w);
+        BestAt b;
+        const bool done = wave_settle<Rec32, false>(ts.g, D.cs, D.srecs, qa, lane, b);
+        if (lane == 0) {
+            if (done && b.idx != 0x7fffffff) D.out[qa.row] = make_float4((float)b.x, (float)b.y, (float)b.z, __int_as_float(b.idx));
+            else if (ts.err) atomicOr(ts.err, kErrTailFiled);
+        }
+    }
+    return true;
+}
+
+// The shapes that settle: those whose kernel loses no occupancy to the search's registers (VGPRs without -> with the settling head,
+// waves per SIMD): <2, 0, 1> 102 -> 117, 4 -> 4 (D1 + D2 of a direction in one pass, fp32-exact normals: what a report reduces);
+// <2, 0, 2> 112 -> 126 and <2, 2, 2> 118 -> 127, 4 -> 4 (fp64 normals).  The single-column shapes would fall from 6 waves to 4
+// (<2, 1, *> 74 -> 113) or 3 (<2, 2, 1> 78 -> 134): a batch of those keeps the tail launch.
+constexpr bool lean_settles(int stride, int cfg, int defer)
+{
+    return stride == 2 && ((cfg == 0 && (defer == 1 || defer == 2)) || (cfg == 2 && defer == 2));
+}
+
+template <int STRIDE, int CFG, int DEFER = 0>
+__global__ __launch_bounds__(256) void k_unit_lean(UnitJobs jobs, TailSettle ts)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, t0 = (int64_t)blockIdx.x * 256;
     const int64_t unit_threads = jobs.uoff[jobs.njobs];
-    if ((int64_t)blockIdx.x * 256 < unit_threads)          // block-uniform: jobs start at multiples of 256 lanes
-        unit_leaves<LeanCols<STRIDE, CFG, DEFER>>(jobs, unit_job_at(jobs.uoff, jobs.njobs, (int64_t)blockIdx.x * 256), t);
-    else
-        unit_tail<LeanCols<STRIDE, CFG, DEFER>>(jobs, t - unit_threads);
+    const bool leaves = t0 < unit_threads;                 // block-uniform: jobs start at multiples of 256 lanes
+    const int jb = leaves ? unit_job_at(jobs.uoff, jobs.njobs, t0) : 0;
+    if constexpr (lean_settles(STRIDE, CFG, DEFER)) {
+        if (ts.on) {                                       // (a kernel argument: launches that settle nothing pay one scalar branch)
+            bool stored = false;
+            if (leaves) {
+                const int entry = jobs.j[jb].settle - 1;
+                if (entry >= 0) stored = settle_block(ts, ts.d[entry], (t0 - jobs.uoff[jb]) >> 8);      // 256 lanes = 32 leaves = 4096 rows
+            } else {
+                const int64_t c0 = t0 - unit_threads, c1 = c0 + 255;           // this workgroup's raw rows, counted over all jobs
+                for (int k = 0; k < jobs.njobs; ++k) {
+                    const UnitJob &J = jobs.j[k];
+                    const int64_t lo = c0 > jobs.toff[k] ? c0 : jobs.toff[k], hi = c1 < jobs.toff[k + 1] - 1 ? c1 : jobs.toff[k + 1] - 1;
+                    if (lo > hi || !J.settle) continue;
+                    const int64_t r_lo = J.tail_first + (lo - jobs.toff[k]), r_hi = J.tail_first + (hi - jobs.toff[k]);
+                    for (int64_t blk = r_lo >> kTailBlockShift; blk <= r_hi >> kTailBlockShift; ++blk)
+                        stored = settle_block(ts, ts.d[J.settle - 1], blk) || stored;
+                }
+            }
+            if (stored) {                                  // block-uniform
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+        }
+    }
+    if (leaves) unit_leaves<LeanCols<STRIDE, CFG, DEFER>>(jobs, jb, t);
+    else unit_tail<LeanCols<STRIDE, CFG, DEFER>>(jobs, t - unit_threads);
 }
 
 // A batch's completion, published to the host: one wave launched behind the batch's last reduction kernel on the same stream
@@ -862,7 +928,7 @@ __global__ __launch_bounds__(64) void k_publish(unsigned long long *done)
 // the kernel of every shape pccm_reduce_shape.h lists, row for row: adding a shape is a row there and a row here
 struct LeanKernel {
     ReduceShape shape;
-    void (*stub)(UnitJobs);
+    void (*stub)(UnitJobs, TailSettle);
 };
 template <int STRIDE, int CFG, int DEFER>
 constexpr LeanKernel lean() { return {{STRIDE, CFG, DEFER}, k_unit_lean<STRIDE, CFG, DEFER>}; }
@@ -895,18 +961,24 @@ constexpr bool lean_rows_match()
 }
 static_assert(lean_rows_match(), "kLeanKernels and kLeanShapes (pccm_reduce_shape.h) must list the same shapes in the same order");
 
+static bool shape_settles(const ReduceShape &s) { return lean_settles(s.stride, s.cfg, s.defer); }
+
 // one launch for jobs of one shape (lean: row of kLeanShapes, or -1: the general kernel)
-static void launch_unit_shape(pccm_ctx *ctx, const UnitJobs &jobs, int lean)
+static void launch_unit_shape(pccm_ctx *ctx, const UnitJobs &jobs, int lean, const TailSettle *settle = nullptr)
 {
     const int64_t total = jobs.uoff[jobs.njobs] + jobs.toff[jobs.njobs];
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (lean >= 0) PCCM_LAUNCH_STUB(ctx, kLeanKernels[lean].stub, grid, block, 0, ctx->stream, jobs);
+    TailSettle ts{};                                       // (on = 0: nothing to settle)
+    for (int k = 0; k < jobs.njobs && settle; ++k)
+        if (jobs.j[k].settle) ts = *settle;
+    if (lean >= 0) PCCM_LAUNCH_STUB(ctx, kLeanKernels[lean].stub, grid, block, 0, ctx->stream, jobs, ts);
     else PCCM_LAUNCH(ctx, k_unit_jobs, grid, block, 0, ctx->stream, jobs);      // signed projections (min / max of -0.0 and 0.0: fmin / fmax there), other shapes
 }
 
-int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
+int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs_in, uint64_t *seq)
 {
     *seq = 0;
+    UnitJobs jobs = jobs_in;                  // (filed tails: the settle fields are set here)
     const int64_t total = jobs.uoff[jobs.njobs] + jobs.toff[jobs.njobs];
     if (total <= 0) return PCCM_OK;
     ProfScope ps(ctx, PCCM_K_REDUCE);
@@ -920,10 +992,43 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
         for (int j = 0; j < nshapes; ++j) seen = seen || shape[first_of[j]] == shape[k];
         if (!seen) first_of[nshapes++] = k;
     }
+    // Filed tails (pccm_tail_wave.h).  A direction whose search left its tail launch out is settled by this batch when every
+    // job that reads the direction's records covers all of its rows and has a settling kernel: those jobs are marked, and the
+    // direction's form no longer says filed.  A batch that reads such records any other way has the classic tail launch first.
+    // An eager batch notes per direction whether it could have (pccm_ctx::TailFile::eager_ok / eager_bad): the capture behind it
+    // files only what its reductions will settle.
+    const TailSettle *settle = nullptr;
+    bool classic = false;
+    for (int d = 0; d < 2; ++d) {
+        int entry = -1;
+        const TailSettle *ts = filed_tails_settle(ctx, d, &entry);
+        if (!ts && ctx->capturing) continue;
+        NNResult &res = ctx->nn[d];
+        if (!res.valid || !res.rec.p) continue;
+        bool ok = all_lean;
+        int readers = 0;
+        for (int k = 0; k < jobs.njobs; ++k) {
+            if (jobs.j[k].val != (const double *)res.rec.p) continue;
+            ++readers;
+            ok = ok && shape[k] >= 0 && shape_settles(kLeanShapes[shape[k]]) && jobs.j[k].row0 == 0 && jobs.j[k].ns == res.end - res.begin;
+        }
+        if (readers == 0) continue;            // (not this batch's direction: it stays filed)
+        if (!ctx->capturing) (ok ? ctx->tail_file.eager_ok : ctx->tail_file.eager_bad) |= 1 << d;
+        if (!ts) continue;
+        if (!ok) { classic = true; continue; }
+        for (int k = 0; k < jobs.njobs; ++k)
+            if (jobs.j[k].val == (const double *)res.rec.p) jobs.j[k].settle = entry + 1;
+        res.form.tails_filed = false;
+        settle = ts;
+    }
+    if (classic) {
+        const int rc = filed_tails_resolve(ctx);
+        if (rc) return rc;
+    }
     if (!all_lean) {                          // one shape nobody specialised: the general kernel takes the whole batch
         launch_unit_shape(ctx, jobs, -1);
     } else if (nshapes == 1) {
-        launch_unit_shape(ctx, jobs, shape[0]);
+        launch_unit_shape(ctx, jobs, shape[0], settle);
     } else {
         // jobs of different shapes (the pair's two directions with the projection, the self search without): one specialised launch
         // per shape -- the general kernel costs more than a second launch (53 against 20 + 9 us on the 0.8M-point content pair)
@@ -943,7 +1048,7 @@ int launch_unit_jobs(pccm_ctx *ctx, const UnitJobs &jobs, uint64_t *seq)
                 sub.uoff[k + 1] = sub.uoff[sub.njobs];
                 sub.toff[k + 1] = sub.toff[sub.njobs];
             }
-            launch_unit_shape(ctx, sub, shape[first_of[g]]);
+            launch_unit_shape(ctx, sub, shape[first_of[g]], settle);
         }
     }
     return launch_publish(ctx, seq);
