@@ -507,6 +507,49 @@ int pccm_reduce_density_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, con
 int pccm_reduce_density_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *squared, const double *alphas,
                                    double *out /*[3 n]: np.sum, np.min, np.max of the terms*/);
 
+/* Alignment moments: the sums a Kabsch step of point-to-point ICP is made from.  For shard row i of direction dirs[r] (0 or 1),
+ * j its matched row (PCCM_TIES_PICK), d2 the PCCM_METRIC_D1 value the plain reduction forms and w = (d2 <= caps[r]) -- the IEEE
+ * comparison, so a cap of +inf keeps every row --, with u_a = sub_rn(x_it[i][a], pivot[a]) and v_b = sub_rn(x_se[j][b], pivot[b])
+ * from the two clouds' stored fp64 coordinates, the term of kinds[r] is
+ *   0..2       w ? u_a : 0.0                    (a = kind)
+ *   3..5       w ? v_b : 0.0                    (b = kind - 3)
+ *   6 + 3a + b w ? mul_rn(u_a, v_b) : 0.0
+ *   15         w ? d2 : 0.0
+ * and out[3 r ..] = np.sum, np.min, np.max of that term column -- np.sum(np.where(w, term, 0.0)) bit for bit: the terms are
+ * summed in NumPy's pairwise order by the leaf reduction like every other column (the extrema order -0.0 below 0.0, which NumPy's
+ * do not: a product column holds both as soon as a point has a coordinate of the pivot).  The term is the map PCCM_MAP_MOMENT of the
+ * general reduction kernel (k_unit_jobs): it reads the D1 column once, gathers the matched point through the matched row (read
+ * where the search left it; a search that left the rows out is repeated, as for the density map) and stores no column.  The
+ * requests of one call share the pivot; pending requests made with another pivot are given up.  n <= 8 per call (n == 0:
+ * PCCM_OK); prefetch and total behave like pccm_reduce_density_*_many, capture included.
+ * PCCM_E_ARG: n outside 0..8, a null array with n > 0 or a null out, PCCM_DIR_SELF, a kind outside 0..15, a NaN cap, a null or
+ * non-finite pivot.  PCCM_E_STATE: no search result yet, a sharded context, a search that ran under PCCM_TIES_MEAN, a search
+ * that has to be repeated during graph capture. */
+#define PCCM_MAP_MOMENT 8
+int pccm_reduce_moment_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *kinds, const double *caps, const double pivot[3]);
+int pccm_reduce_moment_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *kinds, const double *caps, const double pivot[3],
+                                  double *out /*[3 n]: np.sum, np.min, np.max of the terms*/);
+
+/* Move a resident cloud: every row of cloud `which` (0 or 1) becomes A x + t for the row-major 3 x 4 matrix m = [A | t], in fp64 on
+ * the stored coordinates and with one rounding per operation:
+ *   x' = ((a00 x + a01 y) + a02 z) + t0, likewise y' and z'.
+ * A cloud with one normal per point has them mapped by A alone, n' = (a00 nx + a01 ny) + a02 nz per component (announced normals
+ * -- pccm_set_normals_deferred -- are uploaded first).  That is right for a rotation; the call does NOT test that A is orthogonal.
+ * The context is left as pccm_set_cloud(which, X', n, PCCM_F64, ...) followed by pccm_set_normals(N') would leave it -- the ingest
+ * statistics (fp32-exactness, integer coordinates, largest magnitude, bounding box), the fp32 copies and their padding are made
+ * again by the ingest kernels, which do the arithmetic as a mode --, except that colours, packed colours, reflectance and the
+ * merge map STAY.  Search results of every direction that touches the cloud are dropped (moving cloud 1 keeps the self search of
+ * cloud 0), with PointSSIM features, spacings, point-to-distribution columns, the spatial order and carried normals of either cloud.
+ * An m that is exactly the identity (==) is a no-op: nothing is rewritten and nothing goes stale.
+ * PCCM_E_ARG: which is not 0 or 1, m is null or has a non-finite entry, or a coordinate could exceed 1e15 -- judged on the host
+ * from the cloud's largest magnitude and the rows' absolute sums, before anything is written.  PCCM_E_STATE: no such cloud, a
+ * normal count that is neither 0 nor n, a sharded context, a call between pccm_graph_begin and pccm_graph_end. */
+int pccm_transform_cloud(pccm_ctx *ctx, int which, const double m[12]);
+
+/* The bounding box of cloud `which` (0 or 1) as the ingest found it: lo[a] / hi[a] = the smallest / largest fp64 coordinate of
+ * axis a (-0.0 orders below 0.0).  No device work.  PCCM_E_ARG: which is not 0 or 1, a null pointer.  PCCM_E_STATE: no such cloud. */
+int pccm_get_bounds(pccm_ctx *ctx, int which, double lo[3], double hi[3]);
+
 /* Sharded contexts whose rows start and end on whole 8192-row chunks (pccm_set_shard / pccm_set_shard_dir do that
  * whenever every rank can have a chunk): the exchange vector shrinks to ONE number per chunk -- NumPy adds the
  * chunks of a column one after the other, and the GPU has finished each chunk's pairwise tree -- plus the raw values
@@ -610,11 +653,11 @@ int pccm_color_transform(const double *rgb, int64_t n, int scheme, double *out);
 int pccm_drop_caches(pccm_ctx *ctx);
 
 /* hipGraph capture.  Between pccm_graph_begin() and pccm_graph_end() only pccm_drop_caches(),
- * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many(), pccm_count_prefetch_many(), pccm_reduce_map_prefetch_many() and pccm_reduce_density_prefetch_many() may be called; they are recorded on the
+ * pccm_nn(), pccm_reduce_prefetch[_many](), pccm_select_prefetch_many(), pccm_count_prefetch_many(), pccm_reduce_map_prefetch_many(), pccm_reduce_density_prefetch_many() and pccm_reduce_moment_prefetch_many() may be called; they are recorded on the
  * context's stream instead of executed.  The same sequence must have run once before (capture cannot allocate).
  * pccm_graph_end() instantiates the graph, runs it once and returns its id; pccm_graph_launch()
  * replays the whole sequence -- kernels and host-side bookkeeping -- with a single launch, after which
- * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_reduce_map_total_many()/pccm_reduce_density_total_many()/pccm_match_counts()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
+ * pccm_reduce()/pccm_select_many()/pccm_count_many()/pccm_reduce_map_total_many()/pccm_reduce_density_total_many()/pccm_reduce_moment_total_many()/pccm_match_counts()/pccm_nn_fetch() read the fresh results.  A graph goes stale (PCCM_E_STATE) when
  * clouds, normals, shard or any buffer it references change.  One report over resident clouds is
  * ~45 small launches, which an eager host cannot issue as fast as the GPU retires them. */
 int pccm_graph_begin(pccm_ctx *ctx);

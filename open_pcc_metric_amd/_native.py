@@ -29,6 +29,8 @@ DUPLICATES = {"drop": 1, "average": 2}  # PCCM_DUP_DROP / PCCM_DUP_AVERAGE
 METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
 MAP_CLAMP, MAP_ROOT = 1, 2          # Engine.reduce_map_*: PCCM_MAP_*
 MAP_DENSITY = 4                     # PCCM_MAP_DENSITY: the map behind Engine.reduce_density_* (reduce_map_* refuses it)
+MAP_MOMENT = 8                      # PCCM_MAP_MOMENT: the map behind Engine.reduce_moment_* (likewise)
+MOMENT_KINDS = 16                   # kinds 0..15 of an alignment moment (include/pccm.h)
 METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
 # PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
 SSIM_ATTRS = {"geometry": 1, "normal": 2, "curvature": 4, "color": 8}
@@ -50,7 +52,7 @@ SYMBOLS = (
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours",
     "pccm_resolution_build", "pccm_get_resolution", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
-    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_reduce_map_prefetch_many", "pccm_reduce_map_total_many", "pccm_match_counts", "pccm_reduce_density_prefetch_many", "pccm_reduce_density_total_many", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
+    "pccm_reduce_total", "pccm_reduce_total_many", "pccm_select_prefetch_many", "pccm_select_many", "pccm_count_prefetch_many", "pccm_count_many", "pccm_reduce_map_prefetch_many", "pccm_reduce_map_total_many", "pccm_match_counts", "pccm_reduce_density_prefetch_many", "pccm_reduce_density_total_many", "pccm_reduce_moment_prefetch_many", "pccm_reduce_moment_total_many", "pccm_transform_cloud", "pccm_get_bounds", "pccm_cvec_len", "pccm_reduce_chunks_many", "pccm_finish_chunks",
     "pccm_set_wait", "pccm_wait_counter",
     "pccm_set_reflectance", "pccm_set_reflectance_u16", "pccm_get_reflectance",
     "pccm_set_colors", "pccm_set_colors_u8", "pccm_color_reduce", "pccm_color_rows", "pccm_seq_colsum", "pccm_obb_frames", "pccm_extreme_rows", "pccm_rows_outside",
@@ -166,6 +168,10 @@ def load() -> ctypes.CDLL:
     lib.pccm_match_counts.argtypes = [vp, i32, vp]
     lib.pccm_reduce_density_prefetch_many.argtypes = [vp, i32, ip, ip, dp]
     lib.pccm_reduce_density_total_many.argtypes = [vp, i32, ip, ip, dp, dp]
+    lib.pccm_reduce_moment_prefetch_many.argtypes = [vp, i32, ip, ip, dp, dp]
+    lib.pccm_reduce_moment_total_many.argtypes = [vp, i32, ip, ip, dp, dp, dp]
+    lib.pccm_transform_cloud.argtypes = [vp, i32, dp]
+    lib.pccm_get_bounds.argtypes = [vp, i32, dp, dp]
     lib.pccm_cvec_len.argtypes = [i64]
     lib.pccm_cvec_len.restype = i64
     lib.pccm_reduce_chunks_many.argtypes = [vp, i32, ip, ip, ip, dp, dp]
@@ -846,6 +852,46 @@ class Engine:
         out = (ctypes.c_double * (3 * args[0]))()
         _check(self._lib.pccm_reduce_density_total_many(self._ctx, *args, out))
         return [(np.float64(out[3 * i]), np.float64(out[3 * i + 1]), np.float64(out[3 * i + 2])) for i in range(args[0])]
+
+    @staticmethod
+    def _moment_args(requests, pivot):
+        k = len(requests)
+        arr = ctypes.c_int * k
+        return (k, arr(*[int(r[0]) for r in requests]), arr(*[int(r[1]) for r in requests]),
+                (ctypes.c_double * k)(*[float(r[2]) for r in requests]), (ctypes.c_double * 3)(*[float(v) for v in pivot]))
+
+    def reduce_moment_prefetch_many(self, requests, pivot) -> None:
+        """``requests``: up to 8 ``(direction, kind, cap)``: enqueue the alignment moments of each direction's D1 column
+        relative to ``pivot`` without waiting (pccm_reduce_moment_prefetch_many); a later reduce_moment_total_many() with the
+        same pivot consumes them."""
+        if requests:
+            _check(self._lib.pccm_reduce_moment_prefetch_many(self._ctx, *self._moment_args(requests, pivot)))
+
+    def reduce_moment_total_many(self, requests, pivot):
+        """-> [(sum, min, max)] of the alignment moment terms for up to 8 ``(direction, kind, cap)``: with w = (d2 <= cap), u the
+        row's point and v its matched point, both minus ``pivot``, kinds 0..2 are u_a, 3..5 v_b, 6 + 3 a + b u_a * v_b and 15
+        d2, each ``np.where(w, term, 0.0)``; gathered, multiplied and summed in HBM (pccm_reduce_moment_total_many)."""
+        if not requests:
+            return []
+        args = self._moment_args(requests, pivot)
+        out = (ctypes.c_double * (3 * args[0]))()
+        _check(self._lib.pccm_reduce_moment_total_many(self._ctx, *args, out))
+        return [(np.float64(out[3 * i]), np.float64(out[3 * i + 1]), np.float64(out[3 * i + 2])) for i in range(args[0])]
+
+    def transform_cloud(self, which: int, matrix) -> None:
+        """Move resident cloud ``which`` by the 3 x 4 (or 4 x 4, whose last row is not read) matrix ``[A | t]``: points become
+        ``A x + t``, per-point normals ``A n``, in fp64 on the GPU (pccm_transform_cloud).  Colours, reflectance and the merge map
+        stay; search results that touch the cloud go.  The exact identity is a no-op."""
+        m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64)[:3, :4])
+        if m.shape != (3, 4):
+            raise ValueError("transform_cloud: a 3 x 4 or 4 x 4 matrix expected")
+        _check(self._lib.pccm_transform_cloud(self._ctx, int(which), m.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+
+    def get_bounds(self, which: int):
+        """-> (lo, hi): the bounding box of cloud ``which`` as its ingest found it (pccm_get_bounds), two float64 triples."""
+        lo, hi = (ctypes.c_double * 3)(), (ctypes.c_double * 3)()
+        _check(self._lib.pccm_get_bounds(self._ctx, int(which), lo, hi))
+        return np.array(lo[:]), np.array(hi[:])
 
     def reduce_chunks_many(self, requests, normal_mode: str = "row"):
         """-> (one float64 array holding the chunk vectors of up to 8 columns ``(direction, metric)`` one after the other,

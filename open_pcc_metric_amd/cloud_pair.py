@@ -47,6 +47,7 @@ Differences from the reference, all deliberate:
 """
 from __future__ import annotations
 
+import math
 import os
 import typing
 
@@ -369,7 +370,8 @@ class CloudPair:
                  use_graph: bool = False, estimate_normals: bool = True, normals_knn: int = 30,
                  shard_mode: str = "direction", _engine=None, _uploads_first: bool = False,
                  staged_io: typing.Optional[bool] = None, ties: str = "pick", carry_normals: bool = False,
-                 duplicates: str = "keep"):
+                 duplicates: str = "keep", transform=None, align: typing.Optional[str] = None, align_distance=None,
+                 align_iterations: int = 30, align_tolerance: float = 1e-6):
         if normal_index not in nat.NORMAL_MODES:
             raise ValueError("normal_index must be 'row' or 'neighbour'")
         if not isinstance(ties, str) or ties not in nat.TIES:
@@ -379,6 +381,11 @@ class CloudPair:
         from .options import check_carry_normals, check_duplicates
         check_carry_normals(carry_normals, ties=ties, group=group)       # (ValueError before any GPU work)
         check_duplicates(duplicates, group=group)
+        from .align import check_align
+        # (transform 4 x 4 or None, "icp" or None, squared distance, iterations, tolerance) -- with_reconst hands them on
+        self._align = check_align(align, align_distance, align_iterations, align_tolerance, transform=transform, group=group)
+        self.alignment = None                   # align.Alignment once cloud 1 has been moved
+        self._moved = [False, False]            # the cloud was moved on the device (transform=, align=): its normals are the engine's
         self.clouds = (origin_cloud, reconst_cloud)
         self.normal_index = normal_index
         self.nn_engine = nn_engine
@@ -413,6 +420,8 @@ class CloudPair:
             raise ValueError("this engine cannot carry normals from one cloud to the other")
         if duplicates != "keep" and not hasattr(_engine, "merge_duplicates"):
             raise ValueError("this engine cannot merge duplicate points")
+        if (self._align[0] is not None or self._align[1] is not None) and not hasattr(_engine, "transform_cloud"):
+            raise ValueError("this engine cannot move a cloud")
         if hasattr(_engine, "set_ties"):
             _engine.set_ties(ties)                # (every time: a pooled context comes back with the default, pccm_ctx_reset)
         elif ties != "pick":
@@ -447,6 +456,7 @@ class CloudPair:
                     _engine.set_shard_dir(direction, *self._plan[direction][self._coll.rank])
             else:
                 _engine.set_shard(self._coll.rank, self._coll.world)
+        self._move_reconst()
         self._update_fusion()
         if deferred and _uploads_first:
             _engine.flush_uploads()                       # (A/B for bench.py: everything uploaded before the first search starts)
@@ -470,7 +480,7 @@ class CloudPair:
             # (a sharded pair keeps nothing that pays: every rank would have to agree on what is resident)
             kw = dict(nn_engine=self.nn_engine, normal_index=self.normal_index, extent=self._extent, use_graph=self._use_graph,
                       estimate_normals=self._estimate_normals, normals_knn=self._normals_knn, ties=self.ties,
-                      carry_normals=self._carry_normals, duplicates=self._duplicates)
+                      carry_normals=self._carry_normals, duplicates=self._duplicates, **self._align_kwargs())
             group, owns = self._coll.group, self._owns_engine
             self.__dict__.pop("_engine")
             if owns:
@@ -485,6 +495,7 @@ class CloudPair:
         #                                                   drops them with it, and the next consumer carries from the new one)
         new._colours_on_device = [self._colours_on_device[0], False]
         new._reflectance_on_device = [self._reflectance_on_device[0], False]     # (the origin cloud's column stays in HBM)
+        new._moved, new.alignment = [False, False], None # (only cloud 1 ever moves; the new one is moved itself: _move_reconst)
         new._merged = [self._merged[0], False]           # (cloud 0 stays merged and resident: only the new cloud 1 is merged)
         new.duplicates_removed = (self.duplicates_removed[0], 0)
         new._keep_rows = set(self._keep_rows)
@@ -503,6 +514,7 @@ class CloudPair:
             new._merge_duplicates(1)
         elif _has_normals(reconst_cloud):
             (eng.set_normals_deferred if deferred else eng.set_normals)(1, reconst_cloud.normals)
+        new._move_reconst()
         new._update_fusion()
         new._colours_for_ties()
         new.recompute()
@@ -530,6 +542,41 @@ class CloudPair:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _align_kwargs(self) -> dict:
+        """The alignment settings as the constructor takes them."""
+        transform, align, tau2, iterations, tolerance = self._align
+        return dict(transform=transform, align=align, align_distance=None if math.isinf(tau2) else math.sqrt(tau2),
+                    align_iterations=iterations, align_tolerance=tolerance)
+
+    def _move_reconst(self) -> None:
+        """``transform=`` and ``align=``: move resident cloud 1 -- after the uploads and the merge of duplicates, before normals
+        are estimated or carried and before the pair's searches (align.py).  Without either nothing is called."""
+        transform, align, tau2, iterations, tolerance = self._align
+        if transform is None and align is None:
+            return
+        from . import align as al
+        eng = self._engine
+        if transform is not None:
+            eng.transform_cloud(1, transform)
+        result = al.Alignment(np.eye(4) if transform is None else transform.copy(), 0, None, None, False)
+        if align is not None:
+            if self.__dict__.get("_align_pivot") is None:             # (the original never moves: with_reconst keeps it)
+                # (the ingest has the box already; np.min over a million rows on the host costs more than the whole alignment)
+                self._align_pivot = (al.centre_of(*eng.get_bounds(0)) if hasattr(eng, "get_bounds")
+                                     else al.bounding_box_centre(_host_rows(self.clouds[0].points)))
+            if self.ties != "pick" and hasattr(eng, "set_ties"):
+                eng.set_ties("pick")                                  # (alignment always matches under "pick")
+            if hasattr(eng, "nn_want_idx"):
+                eng.nn_want_idx(True)                                 # (the moments read the matched rows; _update_fusion follows)
+            try:
+                result = al.icp(eng, eng.n_iter(nat.DIR_RIGHT), self._align_pivot, tau2, iterations, tolerance,
+                                nn_engine=self.nn_engine, start=result.transformation)
+            finally:
+                if self.ties != "pick" and hasattr(eng, "set_ties"):
+                    eng.set_ties(self.ties)
+        self.alignment = result
+        self._moved[1] = True
 
     def _merge_duplicates(self, which: int) -> None:
         """``duplicates="drop" | "average"``: the cloud's normals and colours go up now, then its rows that share their coordinates
@@ -879,7 +926,7 @@ class CloudPair:
     def get_normals(self, which: int):
         """np.asarray(clouds[which].normals), tagged for the fused projection (metric.py:92-98)."""
         self._require_normals(which)
-        if self._estimated[which] or self._carried[which] or self._merged[which]:
+        if self._estimated[which] or self._carried[which] or self._merged[which] or self._moved[which]:
             host = self._engine.get_normals(which)
         else:
             host = np.asarray(_host_rows(self.clouds[which].normals))

@@ -444,6 +444,7 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
                       &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_refl, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state,
                       &ctx->match[0].buf, &ctx->match[1].buf};
     for (DevBuf *b : bufs) free_buf(*b);
+    if (ctx->xf_scratch) (void)hipFree(ctx->xf_scratch);
     for (pccm_ctx::TieCols *t : {&ctx->tie[0], &ctx->tie[1], &ctx->tie_rows})
         for (DevBuf *b : {&t->pos, &t->nrm, &t->rgb, &t->k, &t->ang}) free_buf(*b);
     for (auto &g : ctx->graphs) graph_free(g);
@@ -460,6 +461,37 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
         if (pe) (void)hipEventDestroy(pe);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
+    return PCCM_OK;
+}
+
+// behind launch_ingest_points: the ten statistics read back (one wait) and written into the cloud -- pccm_set_cloud and
+// pccm_transform_cloud end alike
+static int ingest_points_finish(pccm_ctx *ctx, Cloud &c, int which, int64_t n, int64_t n_pad, const unsigned long long *stats)
+{
+    unsigned long long h[10];
+    PCCM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    double maxabs;
+    memcpy(&maxabs, &h[0], sizeof(double));
+    if (h[2] != 0 || !(maxabs <= kMaxAbsCoord)) {
+        drop_cloud(c);
+        return fail(PCCM_E_ARG, "cloud %d has non-finite coordinates or |x| > 1e15", which);
+    }
+    c.n = n;
+    c.n_pad = n_pad;
+    c.maxabs = maxabs;
+    c.exact32 = (h[1] == 0);
+    c.all_int = (h[1] == 0 && h[9] == 0);
+    for (int k = 0; k < 3; ++k) {
+        auto unkey = [](unsigned long long b) {
+            b = (b >> 63) ? (b & 0x7fffffffffffffffull) : ~b;
+            double v;
+            memcpy(&v, &b, sizeof(v));
+            return v;
+        };
+        c.bb_min[k] = unkey(h[3 + k]);
+        c.bb_max[k] = unkey(h[6 + k]);
+    }
     return PCCM_OK;
 }
 
@@ -488,31 +520,7 @@ int pccm_set_cloud(pccm_ctx *ctx, int which, const void *xyz, int64_t n, int dty
     PCCM_HIP(hipMemsetAsync(stats + 3, 0xff, 3 * sizeof(unsigned long long), ctx->stream));
     rc = launch_ingest_points(ctx, dsrc, dtype, n, n_pad, c.xyz32, c.xyz64, c.xyz32r, stats);
     if (rc) return rc;
-    unsigned long long h[10];
-    PCCM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    PCCM_HIP(hipStreamSynchronize(ctx->stream));
-    double maxabs;
-    memcpy(&maxabs, &h[0], sizeof(double));
-    if (h[2] != 0 || !(maxabs <= kMaxAbsCoord)) {
-        drop_cloud(c);
-        return fail(PCCM_E_ARG, "cloud %d has non-finite coordinates or |x| > 1e15", which);
-    }
-    c.n = n;
-    c.n_pad = n_pad;
-    c.maxabs = maxabs;
-    c.exact32 = (h[1] == 0);
-    c.all_int = (h[1] == 0 && h[9] == 0);
-    for (int k = 0; k < 3; ++k) {
-        auto unkey = [](unsigned long long b) {
-            b = (b >> 63) ? (b & 0x7fffffffffffffffull) : ~b;
-            double v;
-            memcpy(&v, &b, sizeof(v));
-            return v;
-        };
-        c.bb_min[k] = unkey(h[3 + k]);
-        c.bb_max[k] = unkey(h[6 + k]);
-    }
-    return PCCM_OK;
+    return ingest_points_finish(ctx, c, which, n, n_pad, stats);
 }
 
 // the front of the two normals setters: arguments, the stream drained, everything made from the old normals forgotten
@@ -550,6 +558,83 @@ int pccm_set_normals_deferred(pccm_ctx *ctx, int which, const void *nrm, int64_t
     c.nrm_host = nrm;
     c.nrm_host_dtype = dtype;
     c.nrm_deferred = true;
+    return PCCM_OK;
+}
+
+// pccm_transform_cloud (include/pccm.h).  The two ingest kernels in their moving mode read the cloud's own fp64 rows and write the
+// moved rows into a scratch buffer, which is then swapped with the cloud's: source and destination never alias (the kernels'
+// pointers stay __restrict__, and a normal's three threads each read the whole row).  The buffer the points leave behind is the
+// scratch the normals are moved into.
+int pccm_transform_cloud(pccm_ctx *ctx, int which, const double *m)
+{
+    CHECK_CTX(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!m) return fail(PCCM_E_ARG, "null pointer");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(m[k])) return fail(PCCM_E_ARG, "the matrix has a non-finite entry");
+    NOT_CAPTURING(ctx);
+    Cloud &c = ctx->cloud[which];
+    if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "moving a cloud needs the whole cloud on this GPU (world = 1)");
+    if (c.n_nrm != 0 && c.n_nrm != c.n)
+        return fail(PCCM_E_STATE, "cloud %d has %lld points but %lld normals: they cannot be moved with it", which, (long long)c.n, (long long)c.n_nrm);
+    bool identity = true;
+    for (int k = 0; k < 12; ++k) identity = identity && m[k] == ((k % 4 == k / 4) ? 1.0 : 0.0);
+    if (identity) return PCCM_OK;                          // nothing is rewritten, nothing goes stale
+    // no coordinate can leave the range the ingest accepts: |x'| <= (|a0| + |a1| + |a2|) maxabs + |t| per row, with room for the
+    // four roundings (refused before anything is written)
+    for (int a = 0; a < 3; ++a) {
+        const double bound = (fabs(m[4 * a]) + fabs(m[4 * a + 1]) + fabs(m[4 * a + 2])) * c.maxabs + fabs(m[4 * a + 3]);
+        if (!(bound * (1.0 + 0x1p-48) <= kMaxAbsCoord))
+            return fail(PCCM_E_ARG, "moving cloud %d could take a coordinate beyond |x| = 1e15", which);
+    }
+    int rc = normals_ready(ctx, c);
+    if (rc) return rc;
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    points_moved(ctx, which);                              // (normals carried to this cloud are gone now: they are not moved)
+    const int64_t n = c.n, n_pad = c.n_pad;
+    if ((rc = grow((void **)&ctx->xf_scratch, ctx->cap_xf, (size_t)n * 3 * sizeof(double)))) return rc;
+    IngestMove mv;
+    mv.on = 1;
+    memcpy(mv.m, m, sizeof mv.m);
+    unsigned long long *stats = (unsigned long long *)ctx->stats.p;
+    PCCM_HIP(hipMemsetAsync(stats, 0, 10 * sizeof(unsigned long long), ctx->stream));
+    PCCM_HIP(hipMemsetAsync(stats + 3, 0xff, 3 * sizeof(unsigned long long), ctx->stream));
+    if ((rc = launch_ingest_points(ctx, c.xyz64, PCCM_F64, n, n_pad, c.xyz32, ctx->xf_scratch, c.xyz32r, stats, &mv))) return rc;
+    std::swap(c.xyz64, ctx->xf_scratch);
+    std::swap(c.cap64, ctx->cap_xf);
+    if ((rc = ingest_points_finish(ctx, c, which, n, n_pad, stats))) return rc;
+    if (c.n_nrm == n) {
+        if ((rc = grow((void **)&ctx->xf_scratch, ctx->cap_xf, (size_t)n * 3 * sizeof(double)))) return rc;
+        // (estimated and carried normals come without the fp32 words: the ingest writes them, so they must be there)
+        if ((rc = grow((void **)&c.nrm32, c.cap_nrm32, (size_t)n * sizeof(float4)))) return rc;
+        PCCM_HIP(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        if ((rc = launch_ingest_normals(ctx, c.nrm64, PCCM_F64, n, ctx->xf_scratch, (float *)c.nrm32, stats, &mv))) return rc;
+        std::swap(c.nrm64, ctx->xf_scratch);
+        std::swap(c.cap_nrm, ctx->cap_xf);
+        unsigned long long h[3];
+        PCCM_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        PCCM_HIP(hipStreamSynchronize(ctx->stream));
+        if (h[2] != 0) {
+            drop_normals(c);
+            return fail(PCCM_E_ARG, "the moved normals of cloud %d are not finite", which);
+        }
+        c.nrm_exact32 = h[1] == 0;
+    }
+    return PCCM_OK;
+}
+
+int pccm_get_bounds(pccm_ctx *ctx, int which, double *lo, double *hi)
+{
+    CHECK_CTX(ctx);
+    if (which != 0 && which != 1) return fail(PCCM_E_ARG, "cloud index must be 0 or 1");
+    if (!lo || !hi) return fail(PCCM_E_ARG, "null pointer");
+    const Cloud &c = ctx->cloud[which];
+    if (c.n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", which);
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = c.bb_min[a];
+        hi[a] = c.bb_max[a];
+    }
     return PCCM_OK;
 }
 
@@ -2463,7 +2548,7 @@ static int map_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, 
     return map_enqueue(ctx, n, dirs, metrics, normal_modes, maps, xs, nullptr);
 }
 
-// enqueue what is not enqueued yet of n checked requests; rows[d]: where a density map of direction d reads the matched rows
+// enqueue what is not enqueued yet of n checked requests; rows[d]: where a density or moment map of direction d reads the matched rows
 static int map_enqueue(pccm_ctx *ctx, int n, const int *dirs, const int *metrics, const int *normal_modes, const int *maps, const double *xs,
                        const RowSource *rows)
 {
@@ -2503,7 +2588,7 @@ static int map_enqueue(pccm_ctx *ctx, int n, const int *dirs, const int *metrics
         if (!cslot[c]->has_job) continue;          // a column without rows: nothing to launch, the total of nothing
         UnitCol col = cslot[c]->job.c[0];
         col.map = maps[i];
-        col.cap = (maps[i] & PCCM_MAP_CLAMP) ? xs[i] : 0.0;
+        col.cap = (maps[i] & (PCCM_MAP_CLAMP | PCCM_MAP_MOMENT)) ? xs[i] : 0.0;
         col.alpha = (maps[i] & PCCM_MAP_DENSITY) ? xs[i] : 0.0;
         bind_outputs(col, SlotView(hs, m->host), false);
         if (open_job[c] >= 0) {                    // the second map over the fields the job already reads
@@ -2520,6 +2605,15 @@ static int map_enqueue(pccm_ctx *ctx, int n, const int *dirs, const int *metrics
                 U.rows = rows[d].idx;
                 U.cnt = (const uint32_t *)ctx->match[d].buf.p;
                 U.cnt_rows = ctx->cloud[d == PCCM_DIR_LEFT ? 1 : 0].n;
+            }
+            if (maps[i] & PCCM_MAP_MOMENT) {       // (likewise: a call's maps are all moment maps or none is)
+                const int d = dirs[i];
+                const Cloud &it = ctx->cloud[d == PCCM_DIR_LEFT ? 0 : 1], &se = ctx->cloud[d == PCCM_DIR_LEFT ? 1 : 0];
+                U.rows = rows[d].idx;
+                U.cnt_rows = se.n;
+                U.mom_it = it.xyz64;
+                U.mom_se = se.xyz64;
+                for (int a = 0; a < 3; ++a) memcpy(&U.pivot[a], &ctx->moment_pivot[a], sizeof(double));
             }
             const int64_t lanes = (U.nunits * 8 + 255) / 256 * 256;
             uj.uoff[uj.njobs + 1] = uj.uoff[uj.njobs] + lanes;
@@ -2646,6 +2740,73 @@ int pccm_match_counts(pccm_ctx *ctx, int dir, uint32_t *out)
     if (se->n > 0 && (rc = d2h(ctx, out, ctx->match[dir].buf.p, (size_t)se->n * sizeof(uint32_t)))) return rc;
     PCCM_HIP(hipStreamSynchronize(ctx->stream));
     return check_device_errors(ctx);
+}
+
+// ---- alignment moments (include/pccm.h) ---------------------------------------------------------------------------------------
+// A moment request is a mapped reduction of the direction's D1 column whose map is PCCM_MAP_MOMENT | kind << 8 and whose key is the
+// inlier bound: it lives in the mapped-reduction slots and shares their life cycle.  The pivot is the call's, not the request's:
+// pending moments made with another pivot are given up before the call looks for its own.
+static int moment_prefetch(pccm_ctx *ctx, const char *who, int n, const int *dirs, const int *kinds, const double *caps, const double *pivot,
+                           int *metrics, int *modes, int *maps)
+{
+    if (n < 0 || n > 8 || (n > 0 && (!dirs || !kinds || !caps))) return fail(PCCM_E_ARG, "0..8 requests expected");
+    if (!pivot || !std::isfinite(pivot[0]) || !std::isfinite(pivot[1]) || !std::isfinite(pivot[2]))
+        return fail(PCCM_E_ARG, "the pivot is three finite numbers");
+    for (int i = 0; i < n; ++i) {
+        metrics[i] = PCCM_METRIC_D1;
+        modes[i] = PCCM_NORMAL_ROW;
+        maps[i] = PCCM_MAP_MOMENT | ((kinds[i] & 0xff) << 8);
+    }
+    int rc = request_check(ctx, who, "alignment moments", n, true, dirs, metrics, [&](int i) {
+        if (kinds[i] < 0 || kinds[i] > 15) return fail(PCCM_E_ARG, "a moment's kind is 0..15, not %d", kinds[i]);
+        if (caps[i] != caps[i]) return fail(PCCM_E_ARG, "a moment's inlier bound is a number or an infinity, not NaN");
+        return PCCM_OK;
+    }, [&](int i, const Cloud &) {
+        if (ctx->nn[dirs[i]].ties == PCCM_TIES_MEAN)
+            return fail(PCCM_E_STATE, "the search of direction %d ran under PCCM_TIES_MEAN: a virtual neighbour is no row of the cloud", dirs[i]);
+        return PCCM_OK;
+    });
+    if (rc || n == 0) return rc;
+    uint64_t pv[3];
+    memcpy(pv, pivot, sizeof pv);
+    if (pv[0] != ctx->moment_pivot[0] || pv[1] != ctx->moment_pivot[1] || pv[2] != ctx->moment_pivot[2]) {
+        for (MapSlot &m : ctx->map_slots)
+            if (m.map & PCCM_MAP_MOMENT) m.pending = false;
+        memcpy(ctx->moment_pivot, pv, sizeof pv);
+    }
+    // the rows first (a repeated search rewrites the records the columns are bound to), then the columns
+    RowSource rows[2];
+    bool seen[2] = {false, false};
+    for (int i = 0; i < n; ++i) {
+        const int d = dirs[i];
+        if (seen[d]) continue;
+        seen[d] = true;
+        const Cloud *it, *se;
+        NNResult *res;
+        if ((rc = need_nn(ctx, d, &it, &se, &res)) || (rc = row_source(ctx, *res, &rows[d]))) return rc;
+    }
+    return map_enqueue(ctx, n, dirs, metrics, modes, maps, caps, rows);
+}
+
+int pccm_reduce_moment_prefetch_many(pccm_ctx *ctx, int n, const int *dirs, const int *kinds, const double *caps, const double *pivot)
+{
+    CHECK_CTX(ctx);
+    int metrics[8], modes[8], maps[8];
+    return moment_prefetch(ctx, "pccm_reduce_moment_prefetch_many", n, dirs, kinds, caps, pivot, metrics, modes, maps);
+}
+
+int pccm_reduce_moment_total_many(pccm_ctx *ctx, int n, const int *dirs, const int *kinds, const double *caps, const double *pivot, double *out)
+{
+    CHECK_CTX(ctx);
+    NOT_CAPTURING(ctx);
+    if (!out) return fail(PCCM_E_ARG, "null pointer");
+    int metrics[8], modes[8], maps[8];
+    int rc = moment_prefetch(ctx, "pccm_reduce_moment_total_many", n, dirs, kinds, caps, pivot, metrics, modes, maps);
+    if (rc || n == 0) return rc;
+    auto find = [&](int i) {
+        return find_pending(ctx->map_slots, ctx->nn_gen, dirs[i], metrics[i], modes[i], maps[i], map_cap_bits(maps[i], caps[i]));
+    };
+    return consume(ctx, n, "mapped-reduction slot lost", find, [&](int i, MapSlot &m) { slot_total(m.shape, SlotView(m.shape, m.host), out + 3 * i); });
 }
 
 // Host helper for the colour metrics (metric.py:261-290): out[r] = M * rgb[r] for the BT.709 "ycc" (1) or

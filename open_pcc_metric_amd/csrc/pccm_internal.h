@@ -229,7 +229,8 @@ struct UnitCol {                // one column reduced from a job's array
     // a map applied to the value behind the pick and the square (k_unit_jobs alone: reduce_shape() gives a mapped job no lean
     // kernel): PCCM_MAP_CLAMP -- min(value, cap) -- then PCCM_MAP_ROOT -- the correctly rounded square root -- then
     // PCCM_MAP_DENSITY -- 1 - exp(-alpha value) / m, m the match count of the row's matched row (UnitJob::rows / cnt; never
-    // with a clamp); 0: none
+    // with a clamp); 0: none.  PCCM_MAP_MOMENT | kind << 8 -- the alignment moment `kind` of the row (include/pccm.h), the value
+    // being d2 and `cap` the inlier bound it is compared with (UnitJob::rows / mom_it / mom_se / pivot); alone
     int map = 0;
     double cap = 0.0;
     double alpha = 0.0;
@@ -257,6 +258,10 @@ struct UnitJob {                // one per-point array to reduce (k_unit_jobs): 
     const int32_t *rows = nullptr;
     const uint32_t *cnt = nullptr;
     int64_t cnt_rows = 0;
+    // PCCM_MAP_MOMENT: the matched rows as above (rows; cnt_rows: the searched cloud's rows), the fp64 coordinates of the iterating
+    // cloud (row row0 + i) and of the searched one, and the pivot both are taken relative to
+    const double *mom_it = nullptr, *mom_se = nullptr;
+    double pivot[3] = {0.0, 0.0, 0.0};
     // k_unit_lean alone: 1 + the entry of TailSettle::d whose filed tails this job's workgroups settle before they reduce, 0: none
     int settle = 0;
 };
@@ -337,7 +342,7 @@ struct ProfSpan {
 
 struct GraphOp {               // host-side effect of one captured call, replayed by pccm_graph_launch
     int kind = 0;              // 0 drop_caches, 1 nn(dir), 2 reduce_prefetch(slot), 3 select_prefetch / count_prefetch(slot),
-                               // 4 reduce_map_prefetch / reduce_density_prefetch(slot), 5 match counts(dir)
+                               // 4 reduce_map_prefetch / reduce_density_prefetch / reduce_moment_prefetch(slot), 5 match counts(dir)
     int dir = 0, slot = -1;
     NNForm form;               // kind 1: where the direction's results live once the graph has run
     // kinds 2, 3, 4 (2 + index()): the slot's key and description at capture time (pccm_slot.h)
@@ -495,6 +500,12 @@ struct pccm_ctx {
         pccm::DevBuf buf;
         uint64_t gen = 0;
     } match[2];
+    // the pivot (bit patterns) the pending alignment moments among the mapped-reduction slots were made with: a call with another
+    // pivot gives them up (pccm_reduce_moment_*)
+    uint64_t moment_pivot[3] = {0, 0, 0};
+    // pccm_transform_cloud writes the moved rows here and swaps the buffer with the cloud's (grow() allocates both)
+    double *xf_scratch = nullptr;
+    size_t cap_xf = 0;
     uint64_t nn_gen[3] = {1, 1, 1};
     // hipGraph capture of a step (pccm_graph_*): epoch changes whenever inputs, shard or any device
     // buffer a captured kernel may reference changes, which invalidates every recorded graph
@@ -606,10 +617,18 @@ struct ProfScope {   // records a HIP-event pair around a launch group when prof
 };
 
 // kernel launchers (each returns PCCM_OK or an error) -----------------------------------
+// The transforming mode of the two ingest kernels (pccm_transform_cloud): on != 0 -- every row read from `src` is mapped by the
+// row-major 3 x 4 matrix m = [A | t] before it is ingested (normals: by A alone), one rounding per operation.  The source rows
+// are the context's own fp64 rows, so the launcher is given a destination that is NOT the source (the kernels' pointers are
+// __restrict__, and a normal's thread reads its whole row).
+struct IngestMove {
+    int on = 0;
+    double m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+};
 int launch_ingest_points(pccm_ctx *ctx, const void *src, int dtype, int64_t n, int64_t n_pad, float4 *x32,
-                         double *x64, float4 *x32r, unsigned long long *stats /*[3] device*/);
+                         double *x64, float4 *x32r, unsigned long long *stats /*[3] device*/, const IngestMove *move = nullptr);
 int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, double *out, float *out32,
-                          unsigned long long *stats);
+                          unsigned long long *stats, const IngestMove *move = nullptr);
 
 // brute-force engine: fills res.idx / res.d2 for rows [res.begin, res.end) of `it` searched in `se`
 int nn_brute(pccm_ctx *ctx, const Cloud &it, const Cloud &se, bool self, NNResult &res);

@@ -22,7 +22,7 @@ __device__ __forceinline__ unsigned long long order_key(double v)
 template <typename T>
 __global__ __launch_bounds__(256) void k_ingest_points(const T *__restrict__ src, int64_t n, int64_t n_pad,
                                                        float *__restrict__ x32, double *__restrict__ x64, float4 *__restrict__ x32r,
-                                                       unsigned long long *__restrict__ stats)
+                                                       unsigned long long *__restrict__ stats, const IngestMove mv)
 {
     __shared__ unsigned long long s_mx[4], s_lo[4][3], s_hi[4][3];
     __shared__ int s_cnt[4][3];
@@ -37,8 +37,16 @@ __global__ __launch_bounds__(256) void k_ingest_points(const T *__restrict__ src
             double v[3];
             float f[3];
 #pragma unroll
+            for (int a = 0; a < 3; ++a) v[a] = (double)src[3 * i + a];
+            if (mv.on) {                                   // (a kernel argument: an ingest that moves nothing pays one scalar branch per row)
+                const double x = v[0], y = v[1], z = v[2];
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+                    v[a] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(mv.m[4 * a], x), __dmul_rn(mv.m[4 * a + 1], y)), __dmul_rn(mv.m[4 * a + 2], z)),
+                                     mv.m[4 * a + 3]);
+            }
+#pragma unroll
             for (int a = 0; a < 3; ++a) {
-                v[a] = (double)src[3 * i + a];
                 f[a] = (float)v[a];
                 inexact += ((double)f[a] != v[a]) ? 1 : 0;
                 frac += (floor(v[a]) != v[a]) ? 1 : 0;
@@ -107,12 +115,23 @@ __global__ __launch_bounds__(256) void k_ingest_points(const T *__restrict__ src
 template <typename T>
 __global__ __launch_bounds__(256) void k_ingest_normals(const T *__restrict__ src, int64_t n3,
                                                         double *__restrict__ out, float *__restrict__ out32,
-                                                        unsigned long long *__restrict__ stats)
+                                                        unsigned long long *__restrict__ stats, const IngestMove mv)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int bad = 0, inexact = 0;
     if (i < n3) {
-        double v = (double)src[i];
+        double v;
+        if (mv.on) {                                       // component a of A n for the row this component belongs to
+            const int64_t r = i / 3;
+            const int a = (int)(i - 3 * r);
+            const double nx = (double)src[3 * r], ny = (double)src[3 * r + 1], nz = (double)src[3 * r + 2];
+            const double m0 = a == 0 ? mv.m[0] : (a == 1 ? mv.m[4] : mv.m[8]);
+            const double m1 = a == 0 ? mv.m[1] : (a == 1 ? mv.m[5] : mv.m[9]);
+            const double m2 = a == 0 ? mv.m[2] : (a == 1 ? mv.m[6] : mv.m[10]);
+            v = __dadd_rn(__dadd_rn(__dmul_rn(m0, nx), __dmul_rn(m1, ny)), __dmul_rn(m2, nz));
+        } else {
+            v = (double)src[i];
+        }
         out[i] = v;
         const float f = (float)v;
         if (out32) out32[(i / 3) * 4 + (i % 3)] = f;      // stats[1] says whether this copy may stand for `out`
@@ -124,28 +143,31 @@ __global__ __launch_bounds__(256) void k_ingest_normals(const T *__restrict__ sr
 }
 
 int launch_ingest_points(pccm_ctx *ctx, const void *src, int dtype, int64_t n, int64_t n_pad, float4 *x32,
-                         double *x64, float4 *x32r, unsigned long long *stats)
+                         double *x64, float4 *x32r, unsigned long long *stats, const IngestMove *move)
 {
+    const IngestMove mv = move ? *move : IngestMove();
     ProfScope ps(ctx, PCCM_K_INGEST);
     const int64_t blocks = (n_pad + 255) / 256;
     dim3 grid((unsigned)(blocks < 256 ? blocks : 256));
     if (dtype == PCCM_F32)
-        PCCM_LAUNCH(ctx, (k_ingest_points<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n, n_pad, (float *)x32, x64, x32r, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_points<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n, n_pad, (float *)x32, x64, x32r, stats, mv);
     else
-        PCCM_LAUNCH(ctx, (k_ingest_points<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n, n_pad, (float *)x32, x64, x32r, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_points<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n, n_pad, (float *)x32, x64, x32r, stats, mv);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
 
-int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, double *out, float *out32, unsigned long long *stats)
+int launch_ingest_normals(pccm_ctx *ctx, const void *src, int dtype, int64_t n, double *out, float *out32, unsigned long long *stats,
+                          const IngestMove *move)
 {
+    const IngestMove mv = move ? *move : IngestMove();
     ProfScope ps(ctx, PCCM_K_INGEST);
     const int64_t n3 = 3 * n;
     dim3 grid((unsigned)((n3 + 255) / 256));
     if (dtype == PCCM_F32)
-        PCCM_LAUNCH(ctx, (k_ingest_normals<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n3, out, out32, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_normals<float>), grid, dim3(256), 0, ctx->stream, (const float *)src, n3, out, out32, stats, mv);
     else
-        PCCM_LAUNCH(ctx, (k_ingest_normals<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n3, out, out32, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_normals<double>), grid, dim3(256), 0, ctx->stream, (const double *)src, n3, out, out32, stats, mv);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -157,9 +179,9 @@ int launch_ingest_reflectance(pccm_ctx *ctx, const void *src, int dtype, int64_t
     ProfScope ps(ctx, PCCM_K_INGEST);
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (dtype == PCCM_F32)
-        PCCM_LAUNCH(ctx, (k_ingest_normals<float>), grid, block, 0, ctx->stream, (const float *)src, n, out, (float *)nullptr, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_normals<float>), grid, block, 0, ctx->stream, (const float *)src, n, out, (float *)nullptr, stats, IngestMove());
     else
-        PCCM_LAUNCH(ctx, (k_ingest_normals<double>), grid, block, 0, ctx->stream, (const double *)src, n, out, (float *)nullptr, stats);
+        PCCM_LAUNCH(ctx, (k_ingest_normals<double>), grid, block, 0, ctx->stream, (const double *)src, n, out, (float *)nullptr, stats, IngestMove());
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }
@@ -370,6 +392,37 @@ __device__ __forceinline__ void unit_pick(const UnitView &J, double v[2], uint32
         v[0] = unit_map(J.map0, J.cap0, J.alpha0, v[0], m);
         v[1] = unit_map(J.map1, J.cap1, J.alpha1, v[1], m);
     }
+}
+
+
+// PCCM_MAP_MOMENT (include/pccm.h; MomentCols below): the term of kind map >> 8 for row i, whose D1 value is d2 and whose matched row is `row`: the components it needs -- at most one of either
+// cloud -- are read from the stored fp64 rows, taken relative to the pivot, multiplied where the kind says so, and kept or
+// replaced by 0.0 by the IEEE comparison d2 <= cap.  The kind is a kernel argument: the branches are scalar.  The clouds' rows and
+// the pivot are read from the job (U, kernel-argument memory) where they are used, not carried in the view: ten more scalar
+// registers live across the sixteen loads of a plain leaf made the kernel spill.
+__device__ __forceinline__ double unit_moment_term(const UnitView &J, const UnitJob &U, int map, double cap, double d2, int64_t i, int32_t row)
+{
+    const int kind = map >> 8;
+    double t = d2;
+    if (kind < 15) {
+        const int a = kind < 3 ? kind : (kind < 6 ? -1 : (kind - 6) / 3);
+        const int b = kind < 3 ? -1 : (kind < 6 ? kind - 3 : (kind - 6) % 3);
+        double u = 0.0, v = 0.0;
+        if (a >= 0) u = __dsub_rn(U.mom_it[3 * (J.row0 + i) + a], a == 0 ? U.pivot[0] : (a == 1 ? U.pivot[1] : U.pivot[2]));
+        if (b >= 0) {
+            // (a row outside the searched cloud cannot be in a result the searches wrote: clamped all the same)
+            const int64_t r = row < 0 ? 0 : ((int64_t)row >= J.cnt_rows ? J.cnt_rows - 1 : (int64_t)row);
+            v = __dsub_rn(U.mom_se[3 * r + b], b == 0 ? U.pivot[0] : (b == 1 ? U.pivot[1] : U.pivot[2]));
+        }
+        t = a < 0 ? v : (b < 0 ? u : __dmul_rn(u, v));
+    }
+    return d2 <= cap ? t : 0.0;
+}
+__device__ __forceinline__ void unit_moment_pick(const UnitView &J, const UnitJob &U, double v[2], int64_t i, int32_t row)
+{
+    unit_pick(J, v);                                       // (both columns: the D1 value; unit_map passes a moment map through)
+    v[0] = unit_moment_term(J, U, J.map0, J.cap0, v[0], i, row);
+    v[1] = unit_moment_term(J, U, J.map1, J.cap1, v[1], i, row);
 }
 
 
@@ -610,6 +663,7 @@ struct UnitCols {
     const int ncols;
     __device__ __forceinline__ explicit UnitCols(const UnitJob &J) : V(unit_view(J)), ncols(J.ncols) {}
     __device__ __forceinline__ bool live(int c) const { return c < ncols; }
+    static constexpr bool rowwise() { return false; }
     static __device__ __forceinline__ double min(double a, double b) { return fmin(a, b); }
     static __device__ __forceinline__ double max(double a, double b) { return fmax(a, b); }
     __device__ __forceinline__ void one(int64_t i, double v[2]) const
@@ -653,6 +707,29 @@ struct UnitCols {
     }
 };
 
+// The alignment moments (PCCM_MAP_MOMENT; a launch's jobs are all moment jobs or none is): UnitCols' records, read the same way,
+// and the moment term in the map's place.  A policy and a branch of its own in k_unit_jobs, so that the registers the term needs
+// -- the two clouds' rows, the pivot, two kinds -- are live in that branch alone: carried through UnitCols they made the other
+// jobs' sixteen-load leaf spill.  Row-wise: every row gathers up to four doubles of the two clouds, so a full leaf is formed one
+// row at a time by unit_leaves' sequential path (leaf() is never called).  fmin / fmax: a term can be -0.0.
+struct MomentCols {
+    static constexpr int NC = 2;
+    const UnitView V;
+    const UnitJob &U;              // (the term's operands are read from the job itself: unit_moment_term)
+    const int ncols;
+    __device__ __forceinline__ explicit MomentCols(const UnitJob &J) : V(unit_view(J)), U(J), ncols(J.ncols) {}
+    __device__ __forceinline__ bool live(int c) const { return c < ncols; }
+    static constexpr bool rowwise() { return true; }
+    static __device__ __forceinline__ double min(double a, double b) { return fmin(a, b); }
+    static __device__ __forceinline__ double max(double a, double b) { return fmax(a, b); }
+    __device__ __forceinline__ void one(int64_t i, double v[2]) const
+    {
+        unit_load(V, i, v);
+        unit_moment_pick(V, U, v, i, unit_row(V, i));
+    }
+    __device__ __forceinline__ void leaf(int64_t, int, double[kLeaf / 8][2]) const {}
+};
+
 // The jobs' shape fixed at compile time (every report's jobs share one shape; ReduceShape, pccm_reduce_shape.h): record stride
 // and which field feeds which column are template arguments, so the sixteen loads of a lane are one base address + immediate
 // offsets and no value passes through a select.  CFG 0: two columns {field 0, field 1 squared} (D1 + D2 of a direction in
@@ -669,6 +746,7 @@ struct LeanCols {
     __device__ __forceinline__ explicit LeanCols(const UnitJob &J)
         : val(J.val), nrm64(J.nrm64), nrm32(J.nrm32), q32(J.q32), row0(J.row0), nrm_rows(J.nrm_rows) {}
     __device__ __forceinline__ bool live(int) const { return true; }
+    static constexpr bool rowwise() { return false; }
     static __device__ __forceinline__ double min(double a, double b) { return dmin_raw(a, b); }
     static __device__ __forceinline__ double max(double a, double b) { return dmax_raw(a, b); }
     __device__ __forceinline__ void one(int64_t i, double out[NC]) const { at(val + i * STRIDE, i, out); }
@@ -725,7 +803,7 @@ __device__ __forceinline__ void unit_leaves(const UnitJobs &jobs, int jb, int64_
     const bool live = u < nunits;
     const int64_t cnt = !live ? 0 : ((ns - base < kLeaf) ? ns - base : kLeaf);
     double r[NC], mn[NC], mx[NC];
-    if (cnt == kLeaf) {
+    if (cnt == kLeaf && !P::rowwise()) {
         double v[kLeaf / 8][NC];
         cols.leaf(base, k, v);
 #pragma unroll
@@ -741,7 +819,9 @@ __device__ __forceinline__ void unit_leaves(const UnitJobs &jobs, int jb, int64_
         }
     } else {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) { r[c] = 0.0; mn[c] = INFINITY; mx[c] = -INFINITY; }
+        // (a row-wise job's full leaves come here too: from -0.0, the identity of the addition, its lane adds the same sixteen
+        // values in the same order as the unrolled path, which starts from the first of them)
+        for (int c = 0; c < NC; ++c) { r[c] = P::rowwise() ? -0.0 : 0.0; mn[c] = INFINITY; mx[c] = -INFINITY; }
         for (int64_t e = k; e < cnt; e += 8) {
             double w[NC];
             cols.one(base + e, w);
@@ -825,6 +905,11 @@ __global__ __launch_bounds__(256) void k_unit_jobs(UnitJobs jobs)
     }
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t unit_threads = jobs.uoff[jobs.njobs];
+    if (jobs.j[0].c[0].map & PCCM_MAP_MOMENT) {            // launch-uniform (a kernel argument): pccm_reduce_moment_*'s launches
+        if (t < unit_threads) unit_leaves<MomentCols>(jobs, __builtin_amdgcn_readfirstlane(unit_job_at(jobs.uoff, jobs.njobs, t)), t);
+        else unit_tail<MomentCols>(jobs, t - unit_threads);
+        return;
+    }
     if (t < unit_threads)                                  // block-uniform: jobs start at multiples of 256 lanes
         // (the job index is block-uniform by construction: readfirstlane makes the job's fields scalar loads)
         unit_leaves<UnitCols>(jobs, __builtin_amdgcn_readfirstlane(unit_job_at(jobs.uoff, jobs.njobs, t)), t);

@@ -216,11 +216,11 @@ inline Slot *find_pending(Slot (&slots)[N], const uint64_t *nn_gen, int dir, int
 }
 
 // the cap of a mapped reduction as a slot key: its bit pattern (0.0 and -0.0 are two keys), and nothing where the map does not
-// clamp; of a density map: the bit pattern of its alpha
+// clamp; of a density map: the bit pattern of its alpha; of a moment map: of its inlier bound
 inline uint64_t map_cap_bits(int map, double x)
 {
     uint64_t b = 0;
-    if (map & (PCCM_MAP_CLAMP | PCCM_MAP_DENSITY)) memcpy(&b, &x, sizeof b);
+    if (map & (PCCM_MAP_CLAMP | PCCM_MAP_DENSITY | PCCM_MAP_MOMENT)) memcpy(&b, &x, sizeof b);
     return b;
 }
 

@@ -116,6 +116,29 @@ inline void points_changed(pccm_ctx *ctx, int which)
     ctx->cloud[which].version++;
 }
 
+// Cloud `which` is being moved in place (pccm_transform_cloud): the same rows at new coordinates, its own normals rotated with
+// them.  What was made from the coordinates goes as in points_changed -- results of every direction that touches the cloud (the
+// self search of cloud 0 survives a move of cloud 1), PointSSIM features, spacings, the point-to-distribution columns, the spatial
+// order, normals carried to either cloud (the cloud's own, which stay, are rotated by the caller).  What is keyed on the ROWS
+// stays: colours, packed colours, reflectance and the merge map.
+inline void points_moved(pccm_ctx *ctx, int which)
+{
+    if (ctx->carry.to >= 0) {                          // both clouds' points enter a carry: the carried normals go, whoever holds them
+        drop_normals(ctx->cloud[ctx->carry.to]);
+        ctx->carry.to = -1;
+    }
+    Cloud &c = ctx->cloud[which];
+    c.sp_valid = c.sp_tried = false;
+    c.ssim_attrs = c.ssim_k = 0;
+    c.res_k = 0;
+    ctx->p2d_k = 0;
+    ctx->p2d_color = false;
+    results_void(ctx, which == 1 ? kDirsPair : kDirsAll);
+    if (c.n_nrm > 0) ctx->nrm_gen++;                   // (averaged normals of PCCM_TIES_MEAN are stale)
+    ctx->epoch++;
+    c.version++;
+}
+
 // Cloud `which` is getting new normals: uploaded (pccm_set_normals), announced (pccm_set_normals_deferred -- everything moves
 // now; the upload behind it, normals_ready, changes nothing anybody could have read in between, because whoever reads normals
 // makes them ready first), estimated (estimate_normals) or carried (pccm_carry_normals, which records the new carry afterwards).

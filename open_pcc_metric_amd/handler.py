@@ -4,7 +4,7 @@
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
                                   [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
                                   [--resolution-psnr] [--resolution-neighbours K] [--reflectance] [--reflectance-peak P] [--fscore TAU ...]
-                                  [--chamfer] [--truncate TAU ...] [--dcd ALPHA ...] [--dcd-squared] [--csv]
+                                  [--chamfer] [--truncate TAU ...] [--dcd ALPHA ...] [--dcd-squared] [--transform FILE] [--align icp] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -138,6 +138,22 @@ import click
                    "[0, 1], lower is better.  ALPHA = 0: the share of points that share their matched point.  Not with --ties mean.")
 @click.option("--dcd-squared", "dcd_squared", required=False, is_flag=True,
               help="With --dcd: feed the squared distance d^2 in d's place.")
+@click.option("--transform", "transform", type=str, default=None, metavar="FILE",
+              help="Move every processed cloud by the rigid motion in FILE (12 or 16 whitespace-separated numbers: the rows of a "
+                   "3 x 4 or 4 x 4 matrix) before comparing, on the GPU; file normals are rotated with it.")
+@click.option("--align", "align", type=str, default=None, metavar="[icp]",
+              help="Register every processed cloud onto the original before comparing: point-to-point ICP on the GPU's exact "
+                   "nearest-neighbour search, starting from --transform (or the identity).  Adds AlignmentFitness and "
+                   "AlignmentRMSE after all other rows.")
+@click.option("--align-distance", "align_distance", type=float, default=None, metavar="D",
+              help="With --align: only points within D of the original take part (for partly overlapping clouds).")
+@click.option("--align-iterations", "align_iterations", type=int, default=30, show_default=True, metavar="N",
+              help="With --align: at most N searches (1..1000).")
+@click.option("--align-tolerance", "align_tolerance", type=float, default=1e-6, show_default=True, metavar="X",
+              help="With --align: stop when fitness and inlier RMSE both change by less than X.")
+@click.option("--align-out", "align_out", type=str, default=None, metavar="FILE",
+              help="Write the 4 x 4 motion each processed cloud was given (--transform included) to FILE, 17 significant digits; "
+                   "with several --pcloud the matrices follow one another.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -152,7 +168,7 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, dcd, dcd_squared, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, dcd, dcd_squared, transform, align, align_distance, align_iterations, align_tolerance, align_out, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
@@ -167,8 +183,14 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
                                    p2d_color=p2d_color, resolution_psnr=resolution_psnr,
                                    resolution_neighbours=resolution_neighbours, reflectance=reflectance,
                                    reflectance_peak=reflectance_peak, fscore=fscore or None, chamfer=chamfer,
-                                   truncate=truncate or None, dcd=dcd or None, dcd_squared=dcd_squared)
+                                   truncate=truncate or None, dcd=dcd or None, dcd_squared=dcd_squared, align=align)
         check_dcd(options, ties=ties)
+        from .align import check_align, read_transform_file
+        check_align(align, align_distance, align_iterations, align_tolerance)
+        if align_distance is not None and align is None:
+            raise ValueError("--align-distance needs --align")
+        if align_out is not None and align is None and transform is None:
+            raise ValueError("--align-out needs --align or --transform")
         check_carry_normals(carry_normals, ties=ties)
         check_duplicates(duplicates)
     except ValueError as exc:
@@ -179,8 +201,13 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
     check_truncate(options)
     check_point_to_distribution(options)
     check_resolution_psnr(options)
+    try:                                       # (the one file a usage error may come from: read before any cloud)
+        transform_matrix = None if transform is None else read_transform_file(transform)
+    except (OSError, ValueError) as exc:
+        raise click.UsageError(str(exc))
     ocloud_cloud = read_point_cloud(ocloud)
     cloud_pair = None
+    motions = []
     for path in pcloud:
         pcloud_cloud = read_point_cloud(path)
         check_point_ssim(options, ocloud_cloud, pcloud_cloud, ties=ties)       # (before the GPU context, for every processed cloud)
@@ -194,7 +221,8 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
             # is read --: their bytes go through the context's own pinned buffers, see CloudPair's staged_io; 0.6 ms for a pair)
             cloud_pair = CloudPair(ocloud_cloud, pcloud_cloud, device=device, nn_engine=engine, normal_index=normal_index,
                                    extent=list(extent) if extent else None, staged_io=True, ties=ties,
-                                   carry_normals=carry_normals, duplicates=duplicates)
+                                   carry_normals=carry_normals, duplicates=duplicates, transform=transform_matrix, align=align,
+                                   align_distance=align_distance, align_iterations=align_iterations, align_tolerance=align_tolerance)
             merged_logs = ((0, ocloud, ocloud_cloud), (1, path, pcloud_cloud))
         else:
             cloud_pair = cloud_pair.with_reconst(pcloud_cloud)     # the original cloud stays in HBM with all that belongs to it
@@ -203,6 +231,10 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
             for which, name, given in merged_logs:
                 click.echo(f"duplicates ({duplicates}): {name}: {cloud_pair.duplicates_removed[which]} of {len(given.points)} rows "
                            "merged away", err=True)
+        if align_out is not None:
+            from .align import write_transform_file
+            motions.append(cloud_pair.alignment.transformation)
+            write_transform_file(align_out, motions)
         calculator = MetricCalculator(cloud_pair)
         result = calculator.calculate(transform_options(options)).as_df()
         print(result.to_csv() if csv else result.to_string())

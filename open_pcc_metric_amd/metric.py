@@ -548,6 +548,29 @@ class GeoDensityAwareChamfer(SecondaryMetric):                   # no counterpar
         self.value = (np.float64(left.value) + np.float64(right.value)) / np.float64(2)
 
 
+class _AlignmentRow(PrimaryMetric):                              # no counterpart in the reference (options.py: align)
+    """A number of the registration that moved the processed cloud (``CloudPair(align="icp")``, align.py), as it stood at ICP's
+    last search."""
+    _field = ""
+
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        alignment = getattr(cloud_pair, "alignment", None)
+        value = None if alignment is None else getattr(alignment, self._field)
+        if value is None:
+            raise ValueError(f"{type(self).__name__}: the pair was not aligned (CloudPair(align='icp'))")
+        self.value = np.float64(value)
+
+
+class AlignmentFitness(_AlignmentRow):
+    """The share of the processed cloud's points within ``align_distance`` of the original (1.0 without a distance)."""
+    _field = "fitness"
+
+
+class AlignmentRMSE(_AlignmentRow):
+    """The root mean squared distance of those points to their nearest points of the original."""
+    _field = "inlier_rmse"
+
+
 class _OverAngular(SecondaryMetric, DirectionalMetric):
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         return {"angular_similarities": AngularSimilarities(is_left=self.is_left)}

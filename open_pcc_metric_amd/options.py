@@ -83,6 +83,11 @@ every row above, truncated rows included, for each alpha in ascending order:
 
   alpha                        GeoDensityAwareDistance L, GeoDensityAwareDistance R, GeoDensityAwareChamfer ((L + R) / 2; no symmetric row)
 
+and, with ``align`` (no counterpart in the reference: the pair was registered by ``CloudPair(align="icp")``, align.py), after
+every row above:
+
+  align                        AlignmentFitness (inliers / points of the processed cloud), AlignmentRMSE (of the inliers)
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -93,7 +98,7 @@ import typing
 import math
 import numbers
 
-from .metric import (SSIM_CLASSES, AbstractMetric, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
+from .metric import (SSIM_CLASSES, AbstractMetric, AlignmentFitness, AlignmentRMSE, AngularSimilarity, ColorMahalanobisDistance, ColorMSE, ColorPSNR,
                      GeoChamferL1, GeoChamferL2, GeoDensityAwareChamfer, GeoDensityAwareDistance, GeoMeanDistance, GeoTruncatedMeanDistance, GeoTruncatedMSE, GeoFScore, GeoInlierRatio, GeoHausdorffDistance, GeoHausdorffDistancePSNR, GeoHausdorffResolutionPSNR, GeoMSE, GeoPSNR,
                      GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
                      JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
@@ -166,7 +171,7 @@ class CalculateOptions:
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
                  p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10,
                  reflectance: bool = False, reflectance_peak: float = 65535.0, fscore=None, chamfer: bool = False,
-                 truncate=None, dcd=None, dcd_squared: bool = False):
+                 truncate=None, dcd=None, dcd_squared: bool = False, align=None):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -211,6 +216,10 @@ class CalculateOptions:
         if dcd_squared and not self.dcd:
             raise ValueError("dcd_squared says what the density-aware Chamfer rows are fed: it needs dcd=")
         self.dcd_squared = bool(dcd_squared)
+        # the pair was registered (CloudPair(align="icp")): AlignmentFitness and AlignmentRMSE after every other row
+        if align is not None and (not isinstance(align, str) or align not in ("icp",)):
+            raise ValueError('align must be None or "icp"')
+        self.align = align
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -427,4 +436,6 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
     squared = bool(getattr(options, "dcd_squared", False))
     for alpha in getattr(options, "dcd", None) or ():
         metrics += _sides(GeoDensityAwareDistance, alpha=alpha, squared=squared) + [GeoDensityAwareChamfer(alpha=alpha, squared=squared)]
+    if getattr(options, "align", None) is not None:
+        metrics += [AlignmentFitness(), AlignmentRMSE()]
     return metrics
