@@ -225,6 +225,18 @@ int pccm_get_merge_map(pccm_ctx *ctx, int which, int32_t *out, int64_t *n_before
 int pccm_get_points(pccm_ctx *ctx, int which, double *out);
 int pccm_get_colors(pccm_ctx *ctx, int which, double *out);
 
+/* Voxel occupancy of the two resident clouds ("Voxel occupancy"), without any search.
+ * For each of n voxel sizes (finite, > 0): out[3*k+0] = occupied voxels of cloud 0, [3*k+1] = of cloud 1, [3*k+2] = occupied by both.
+ * Voxel (a, b, c) is [a v, (a+1) v) x ... on the absolute lattice: floor(coordinate / v).
+ * The key of a row is floor(c / v) + 0.0 per component of its stored fp64 coordinates: the correctly rounded quotient (never a
+ * product with 1 / v), -0.0 folded onto 0.0, kept and compared as doubles -- what np.floor(x / v) gives.  Both clouds' rows go into
+ * one open-addressed table per size (the table of pccm_merge_duplicates with this key); every count is an integer and none depends
+ * on scheduling.  The sizes run one after the other on the stream and the call waits once.  It keeps nothing in the context,
+ * changes no cloud and no result, and does not depend on the tie policy.
+ * PCCM_E_ARG: a null pointer; n outside 1..4; a voxel size that is not finite and > 0; clouds of 2^32 - 1 rows or more together.
+ * PCCM_E_STATE: a cloud is missing; a sharded context; a call between pccm_graph_begin and pccm_graph_end. */
+int pccm_voxel_occupancy(pccm_ctx *ctx, int n, const double *voxels, int64_t *out);
+
 /* PointSSIM features ("PointSSIM") of cloud `which`: per point p, N_k(p) = the k points of the same cloud first
  * in ascending (d2, row) order (p itself included; all of them when the cloud has fewer than k), and per attribute the variance
  * with divisor m - 1 of m values over N_k(p), fp64, sums left to right in neighbourhood order, every operation separately rounded:

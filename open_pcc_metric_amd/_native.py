@@ -30,6 +30,7 @@ METRIC_D1, METRIC_D2, METRIC_PROJ = 0, 1, 2
 MAP_CLAMP, MAP_ROOT = 1, 2          # Engine.reduce_map_*: PCCM_MAP_*
 MAP_DENSITY = 4                     # PCCM_MAP_DENSITY: the map behind Engine.reduce_density_* (reduce_map_* refuses it)
 MAP_MOMENT = 8                      # PCCM_MAP_MOMENT: the map behind Engine.reduce_moment_* (likewise)
+MAX_OCCUPANCY = 4                   # voxel sizes per Engine.voxel_occupancy call (pccm_voxel_occupancy)
 MOMENT_KINDS = 16                   # kinds 0..15 of an alignment moment (include/pccm.h)
 METRIC_ANGULAR = 3       # plane-to-plane angular similarity (normal_mode does not apply)
 # PointSSIM: feature attributes (PCCM_SSIM_* bit flags) and the similarity column of each (PCCM_METRIC_SSIM_*)
@@ -48,7 +49,7 @@ KERNEL_CLASSES = {"ingest": 0, "scan": 1, "refine": 2, "fallback": 3, "point": 4
 SYMBOLS = (
     "pccm_version", "pccm_last_error", "pccm_device_count", "pccm_ctx_create", "pccm_ctx_destroy", "pccm_ctx_reset",
     "pccm_set_cloud", "pccm_set_normals", "pccm_set_normals_deferred", "pccm_flush_uploads", "pccm_set_io_staged", "pccm_estimate_normals", "pccm_get_normals", "pccm_carry_normals",
-    "pccm_merge_duplicates", "pccm_get_merge_map", "pccm_get_points", "pccm_get_colors",
+    "pccm_merge_duplicates", "pccm_get_merge_map", "pccm_get_points", "pccm_get_colors", "pccm_voxel_occupancy",
     "pccm_ssim_features", "pccm_get_ssim_features", "pccm_p2d_build", "pccm_p2d_build_attrs", "pccm_get_p2d_neighbours",
     "pccm_resolution_build", "pccm_get_resolution", "pccm_set_shard", "pccm_set_shard_dir", "pccm_shard_range", "pccm_nn", "pccm_nn_pair", "pccm_nn_fuse", "pccm_nn_want_idx", "pccm_nn_fetch",
     "pccm_error_vectors", "pccm_point_metric", "pccm_tie_exposure", "pccm_set_ties", "pccm_tie_counts", "pccm_xvec_len", "pccm_reduce_prefetch", "pccm_reduce_prefetch_many", "pccm_reduce", "pccm_finish_sum",
@@ -131,6 +132,7 @@ def load() -> ctypes.CDLL:
     lib.pccm_get_merge_map.argtypes = [vp, i32, vp, ctypes.POINTER(i64)]
     lib.pccm_get_points.argtypes = [vp, i32, vp]
     lib.pccm_get_colors.argtypes = [vp, i32, vp]
+    lib.pccm_voxel_occupancy.argtypes = [vp, i32, dp, ctypes.POINTER(i64)]
     lib.pccm_ssim_features.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i32)]
     lib.pccm_get_ssim_features.argtypes = [vp, i32, i32, vp]
     lib.pccm_p2d_build.argtypes = [vp, i32, ctypes.POINTER(i32)]
@@ -550,6 +552,16 @@ class Engine:
         out = np.empty(int(nb.value), dtype=np.int32)
         _check(self._lib.pccm_get_merge_map(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p), None))
         return out
+
+    def voxel_occupancy(self, voxels) -> list:
+        """For each of up to MAX_OCCUPANCY voxel sizes: ``(nA, nB, nAB)`` -- the voxels of the absolute lattice
+        floor(coordinate / voxel) that resident cloud 0 occupies, that cloud 1 occupies, and that both do (pccm_voxel_occupancy:
+        one table over both clouds per size, every count an integer).  One call, one wait."""
+        sizes = np.ascontiguousarray(list(voxels), dtype=np.float64)
+        out = np.zeros(3 * max(len(sizes), 1), dtype=np.int64)
+        _check(self._lib.pccm_voxel_occupancy(self._ctx, len(sizes), sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return [(int(out[3 * k]), int(out[3 * k + 1]), int(out[3 * k + 2])) for k in range(len(sizes))]
 
     def get_points(self, which: int) -> np.ndarray:
         out = np.empty((self._n[which], 3), dtype=np.float64)

@@ -42,6 +42,8 @@ class CalculateResult:
                 label += f"[{inner.threshold!r}]"
             if getattr(inner, "alpha", None) is not None:       # density-aware Chamfer rows: one block per alpha
                 label += f"[{inner.alpha!r}, squared]" if getattr(inner, "squared", False) else f"[{inner.alpha!r}]"
+            if getattr(inner, "voxel", None) is not None:       # voxel-occupancy rows: one block per voxel size
+                label += f"[{inner.voxel!r}]"
             if inner is not m:
                 label += "(symmetric)"
             rows["label"].append(label)

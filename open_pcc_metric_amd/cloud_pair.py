@@ -48,6 +48,7 @@ Differences from the reference, all deliberate:
 from __future__ import annotations
 
 import math
+import numbers
 import os
 import typing
 
@@ -577,6 +578,7 @@ class CloudPair:
                     eng.set_ties(self.ties)
         self.alignment = result
         self._moved[1] = True
+        self._occupancy = {}            # (the voxels were counted where the cloud stood: whoever moves resident points drops them)
 
     def _merge_duplicates(self, which: int) -> None:
         """``duplicates="drop" | "average"``: the cloud's normals and colours go up now, then its rows that share their coordinates
@@ -591,6 +593,7 @@ class CloudPair:
             self._upload_reflectance(which)
         after = eng.merge_duplicates(which, self._duplicates)
         self._merged[which] = after < before
+        self._occupancy = {}            # (new rows; the counts would come out the same, but they are the old rows')
         removed = list(self.duplicates_removed)
         removed[which] = before - after
         self.duplicates_removed = tuple(removed)
@@ -630,6 +633,9 @@ class CloudPair:
         self._idx_cache, self._xchg, self._totals, self._colour_red = {}, {}, {}, {}
         if plan:
             self._xchg_wanted = []
+            self._occupancy = {}        # voxel size -> (nA, nB, nAB) of the resident points: kept across recompute(), which searches
+            #                             the same points again; dropped by everything that changes them (a new pair here,
+            #                             _merge_duplicates, _move_reconst)
         # per row family of _FAMILIES: (the answers by request, the requests the last report enqueued in sorted order)
         self._results = {tag: ({}, [] if plan else self._results[tag][1]) for tag in _FAMILIES}
 
@@ -808,6 +814,33 @@ class CloudPair:
     def _density(self, direction: int, alpha: float, squared: bool):
         """``(sum, min, max)`` of the density-aware Chamfer terms of a whole D1 column, gathered, mapped and reduced on the GPU."""
         return self._consumed("density", (direction, alpha, squared))
+
+    def voxel_occupancy(self, voxel: float) -> typing.Tuple[int, int, int]:
+        """``(nA, nB, nAB)``: how many voxels of edge ``voxel`` -- cells of the absolute lattice ``floor(coordinate / voxel)`` --
+        the origin cloud occupies, the processed cloud occupies, and both occupy, counted on the GPU's voxel table
+        (pccm_voxel_occupancy) over the points as they are compared: after ``duplicates=`` and ``transform=`` / ``align=``.  Python
+        ints, kept per voxel size for the life of the pair's points."""
+        return self._voxel_occupancy((voxel,))[0]
+
+    def _voxel_occupancy(self, voxels) -> list:
+        """The triples of ``voxels``; those the pair does not hold yet come from ONE engine call."""
+        self._check_unsharded("voxel-occupancy")
+        sizes = []
+        for v in voxels:
+            if isinstance(v, bool) or type(v).__name__ == "bool_" or not isinstance(v, numbers.Real) \
+                    or not math.isfinite(v) or not float(v) > 0.0:
+                raise ValueError(f"voxel_occupancy: {v!r} is not a finite voxel size > 0")
+            sizes.append(float(v))
+        missing = sorted({f for f in sizes if f not in self._occupancy})
+        if missing:
+            eng = self._engine
+            if not hasattr(eng, "voxel_occupancy"):
+                raise ValueError("this engine cannot count occupied voxels")
+            for at in range(0, len(missing), nat.MAX_OCCUPANCY):
+                part = missing[at:at + nat.MAX_OCCUPANCY]
+                for f, triple in zip(part, eng.voxel_occupancy(part)):
+                    self._occupancy[f] = tuple(int(c) for c in triple)
+        return [self._occupancy[f] for f in sizes]
 
     def match_counts(self, is_left: bool = True) -> np.ndarray:
         """How many points of the iterating cloud (left: the origin cloud) matched each point of the searched cloud:
@@ -1208,8 +1241,8 @@ class CloudPair:
         ``wanted``: iterable of ``(is_left, point_to_plane)`` pairs, ``("angular", is_left)``, ``("ssim", attribute, is_left, k)``,
         ``("ranked", is_left, point_to_plane, rank)``, ``("p2d", is_left, k)``, ``("p2d_color", is_left, k)``,
         ``("p2d_joint", is_left, k)``, ``("spacing", is_left, k)``, ``("reflectance", is_left)``, ``("within", is_left, tau)``,
-        ``("mapped", is_left, point_to_plane, root, clamp)`` (clamp: a number or None), ``("density", is_left, alpha, squared)``
-        and/or the string ``"boundary"``.
+        ``("mapped", is_left, point_to_plane, root, clamp)`` (clamp: a number or None), ``("density", is_left, alpha, squared)``,
+        ``("occupancy", voxel)`` and/or the string ``"boundary"``.
         MetricCalculator.calculate() calls this after walking the DAG of the requested metrics, so
         that the host waits for the GPU once per report instead of once per column.  Purely an
         optimisation: columns that were not prefetched are reduced on demand."""
@@ -1266,6 +1299,9 @@ class CloudPair:
         # reflectance: both clouds' columns in HBM
         if "reflectance" in groups:
             self._ensure_reflectance()
+        # voxel occupancy: every size the pair does not hold yet, in one call; a replayed report finds them all held
+        if "occupancy" in groups:
+            self._voxel_occupancy(sorted({item[1] for item in groups["occupancy"]}))
 
     def _prepare_columns(self, items):
         """The requests of the columns formed from the searches' results -- ``"boundary"``, ``("angular", is_left)`` and
@@ -1334,7 +1370,7 @@ _MAX_REQUESTS = 8       # what one pccm_*_many call takes: every batch below, an
 _MAX_POINT_JOBS = 4     # columns one k_point_jobs launch forms from the matched rows: unfused D2, angular, reflectance, PointSSIM
 
 _GROUP = {"ssim": "ssim", "ranked": "ranked", "within": "within", "mapped": "mapped", "density": "density", "p2d": "p2d",
-          "p2d_color": "p2d", "p2d_joint": "p2d", "spacing": "spacing", "reflectance": "reflectance"}
+          "p2d_color": "p2d", "p2d_joint": "p2d", "spacing": "spacing", "reflectance": "reflectance", "occupancy": "occupancy"}
 
 
 def _by_family(wanted):

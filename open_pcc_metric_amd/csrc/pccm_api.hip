@@ -441,7 +441,7 @@ int pccm_ctx_destroy(pccm_ctx *ctx)
     for (int d = 0; d < 3; ++d) free_nn(ctx->nn[d]);
     DevBuf *bufs[] = {&ctx->part_b1, &ctx->part_g, &ctx->part_b2, &ctx->val, &ctx->stats, &ctx->staging, &ctx->staging2,
                       &ctx->counters, &ctx->color_cols, &ctx->color_idx, &ctx->colsum_scratch, &ctx->rescan_part, &ctx->tail_sync,
-                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->merge_refl, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state,
+                      &ctx->ssim_scratch, &ctx->carry_ws, &ctx->merge_ws, &ctx->occupancy_ws, &ctx->merge_refl, &ctx->merge_map[0], &ctx->merge_map[1], &ctx->tie_list, &ctx->sel_hist, &ctx->sel_state,
                       &ctx->match[0].buf, &ctx->match[1].buf};
     for (DevBuf *b : bufs) free_buf(*b);
     if (ctx->xf_scratch) (void)hipFree(ctx->xf_scratch);
@@ -1180,6 +1180,45 @@ int pccm_get_merge_map(pccm_ctx *ctx, int which, int32_t *out, int64_t *n_before
         return PCCM_OK;
     }
     return fetch(ctx, out, ctx->merge_map[which].p, (size_t)nb * sizeof(int32_t));
+}
+
+int pccm_voxel_occupancy(pccm_ctx *ctx, int n, const double *voxels, int64_t *out)
+{
+    CHECK_CTX(ctx);
+    if (!voxels || !out) return fail(PCCM_E_ARG, "null pointer");
+    if (n < 1 || n > kOccupancyMax) return fail(PCCM_E_ARG, "a call takes 1..%d voxel sizes, not %d", kOccupancyMax, n);
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(voxels[k]) || !(voxels[k] > 0.0)) return fail(PCCM_E_ARG, "voxel size %d is not a finite number > 0", k);
+    NOT_CAPTURING(ctx);
+    const Cloud &c0 = ctx->cloud[0], &c1 = ctx->cloud[1];
+    for (int k = 0; k < 2; ++k)
+        if (ctx->cloud[k].n <= 0) return fail(PCCM_E_STATE, "cloud %d is not set", k);
+    if (ctx->sharded()) return fail(PCCM_E_STATE, "voxel occupancy needs the whole clouds on this GPU (world = 1)");
+    if ((uint64_t)c0.n + (uint64_t)c1.n >= 0xffffffffull)
+        return fail(PCCM_E_ARG, "voxel occupancy stores rows in 32-bit words: %lld + %lld rows are too many", (long long)c0.n, (long long)c1.n);
+    const OccupancyLayout L = occupancy_layout(c0.n, c1.n);
+    int rc;
+    // behind the layout (whose end is 8-byte aligned): the tallies of each size, gathered for one copy back
+    if ((rc = ensure(ctx, ctx->occupancy_ws, L.bytes() + (size_t)kOccupancyMax * 3 * sizeof(unsigned long long)))) return rc;
+    uint32_t *ww = (uint32_t *)ctx->occupancy_ws.p;
+    unsigned long long *all = (unsigned long long *)(ww + L.words);
+    for (int k = 0; k < n; ++k) {
+        if ((rc = launch_occupancy(ctx, c0.xyz64, c0.n, c1.xyz64, c1.n, voxels[k], ww))) return rc;
+        PCCM_HIP(hipMemcpyAsync(all + 3 * k, ww + L.tally, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    unsigned long long t[3 * kOccupancyMax] = {};
+    PCCM_HIP(hipMemcpyAsync(t, all, (size_t)n * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    PCCM_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_errors(ctx))) return rc;
+    for (int k = 0; k < n; ++k) {
+        const unsigned long long uni = t[3 * k], a = t[3 * k + 1], both = t[3 * k + 2];
+        if (a == 0 || a > uni || both > a || uni > (unsigned long long)(c0.n + c1.n))
+            return fail(PCCM_E_HIP, "voxel occupancy counted %llu voxels, %llu of cloud 0 and %llu shared", uni, a, both);
+        out[3 * k] = (int64_t)a;
+        out[3 * k + 1] = (int64_t)(uni - a + both);       // |B| = |A u B| - |A| + |A n B|
+        out[3 * k + 2] = (int64_t)both;
+    }
+    return PCCM_OK;
 }
 
 int pccm_get_points(pccm_ctx *ctx, int which, double *out)

@@ -14,6 +14,9 @@
 // k_merge_scan_waves (one lane per wave of rows) and k_merge_scan_top (one wave) turn the counts into exclusive prefixes -- the
 // ordered scan -- and leave n' in head[0]; k_merge_gather (n) writes map[i] = the position of rep[i] and, for a representative, its
 // merged row.  A reflectance column is averaged by the same passes over rows of one double (CarryView::nc).
+//
+// pccm_voxel_occupancy runs the two k_merge_probe launches alone, in their occupancy mode (MergeArgs::voxel != 0, uniform over a
+// launch): the table over the rows of BOTH clouds, keyed by a row's voxel, and three integer tallies instead of rep / bits / wpre.
 #include "pccm_internal.h"
 
 namespace pccm {
@@ -308,6 +311,16 @@ struct MergeArgs {
     int32_t *map;                   // [n] (written)
     uint32_t *err;                  // the device error word, or null
     int64_t n;
+    // occupancy mode (voxel != 0; launch-uniform): the joint rows 0 .. n-1 are x's n1 rows, then x2's n - n1; ws is an
+    // OccupancyLayout, whose table has cap slots and whose seen [n1] and tally [3] these are.  voxel 0: pccm_merge_duplicates,
+    // none of the others read.  voxel stands next to n: the kernels read both in their first load of the arguments, and the
+    // merge's path does not wait for a second one before it starts
+    double voxel;
+    const double *x2;
+    int64_t n1;
+    uint64_t cap;
+    uint32_t *seen;
+    unsigned long long *tally;      // |A u B|, |A|, |A n B| in voxels
 };
 
 __device__ __forceinline__ uint32_t merge_hash(double x, double y, double z)
@@ -332,12 +345,80 @@ __device__ __forceinline__ uint32_t merge_hash(double x, double y, double z)
     return h;
 }
 
+// Occupancy mode of k_merge_probe (pccm_voxel_occupancy): the same table over the joint rows of both clouds, keyed by a row's
+// voxel floor(c / voxel) + 0.0 -- three doubles compared with ==, the correctly rounded fp64 quotient (never a product with a
+// reciprocal: 0.3 / 0.1 floors to 2), -0.0 folded onto 0.0.  After the insert a slot holds the smallest joint row of its voxel, so
+// a voxel holds a point of cloud 0 exactly when that row is < n1.  The find tallies, per wave and in integer atomics alone: the
+// rows that are their voxel's representative (|A u B|), those of them in cloud 0 (|A|), and -- one row of cloud 1 per voxel whose
+// representative is in cloud 0, the one whose exchange on seen[r] finds it unset -- |A n B|.
+__device__ __forceinline__ void occupancy_key(const MergeArgs &A, int64_t row, double k[3])
+{
+    const double *p = row < A.n1 ? A.x + 3 * row : A.x2 + 3 * (row - A.n1);
+    const double v = A.voxel;
+    k[0] = floor(p[0] / v) + 0.0;
+    k[1] = floor(p[1] / v) + 0.0;
+    k[2] = floor(p[2] / v) + 0.0;
+}
+
+template <bool FIND>
+__device__ __forceinline__ void occupancy_probe(const MergeArgs &A, int64_t i)
+{
+    const int64_t n = A.n, n1 = A.n1;
+    uint32_t *tab = A.ws;                                           // (OccupancyLayout::table is 0; the host hands its cap in)
+    int64_t r = -1;
+    if (i < n) {
+        double k[3];
+        occupancy_key(A, i, k);
+        const uint64_t cap = A.cap, mask = cap - 1;
+        uint64_t slot = (uint64_t)merge_hash(k[0], k[1], k[2]) & mask;
+        bool done = false;
+        for (uint64_t probe = 0; probe < cap; ++probe, slot = (slot + 1) & mask) {
+            uint32_t cur = __hip_atomic_load(&tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == kMergeEmpty) {
+                if (FIND) break;
+                cur = atomicCAS(&tab[slot], kMergeEmpty, (uint32_t)i);
+                if (cur == kMergeEmpty) { done = true; break; }
+            }
+            if ((int64_t)cur >= n) break;
+            double o[3];
+            occupancy_key(A, (int64_t)cur, o);
+            if (o[0] == k[0] && o[1] == k[1] && o[2] == k[2]) {
+                if (!FIND) { if (cur > (uint32_t)i) atomicMin(&tab[slot], (uint32_t)i); }
+                else r = (int64_t)cur;
+                done = true;
+                break;
+            }
+        }
+        if (!done) {
+            if (A.err) atomicOr(A.err, kErrMergeTable);
+            r = i;
+        }
+    }
+    if (!FIND) return;
+    const bool own = i < n && r == i;
+    bool first = false;
+    // (the word only ever goes from 0 to 1: a lane that reads 1 has nothing to claim, and a coarse lattice, where a million rows
+    // meet a few voxels, is spared a million exchanges on a few addresses)
+    if (i < n && i >= n1 && r >= 0 && r < n1 && __hip_atomic_load(&A.seen[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+        first = atomicExch(&A.seen[r], 1u) == 0u;
+    const unsigned long long m_union = __ballot(own), m_a = __ballot(own && i < n1), m_both = __ballot(first);
+    if ((threadIdx.x & 63) == 0) {
+        if (m_union) atomicAdd(&A.tally[0], (unsigned long long)__popcll(m_union));
+        if (m_a) atomicAdd(&A.tally[1], (unsigned long long)__popcll(m_a));
+        if (m_both) atomicAdd(&A.tally[2], (unsigned long long)__popcll(m_both));
+    }
+}
+
 // FIND false: the insert.  FIND true: rep[i] (a row, stored in a uint32 word) and the waves' representative masks and counts
 template <bool FIND>
 __global__ __launch_bounds__(256) void k_merge_probe(MergeArgs A)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, n = A.n;
     if (i >= whole_waves(n)) return;
+    if (A.voxel != 0.0) {                                           // (launch-uniform)
+        occupancy_probe<FIND>(A, i);
+        return;
+    }
     const MergeLayout L = merge_layout(n);
     uint32_t *tab = A.ws + L.table;
     int32_t r = -1;
@@ -447,6 +528,29 @@ int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, uint32_t *wor
     PCCM_LAUNCH(ctx, k_merge_probe<true>, merge_blocks(n), dim3(256), 0, ctx->stream, A);
     PCCM_LAUNCH(ctx, k_merge_scan_waves, merge_blocks(L.nw), dim3(256), 0, ctx->stream, A);
     PCCM_LAUNCH(ctx, k_merge_scan_top, merge_blocks(64), dim3(256), 0, ctx->stream, A);
+    PCCM_HIP(hipGetLastError());
+    return PCCM_OK;
+}
+
+int launch_occupancy(pccm_ctx *ctx, const double *x0, int64_t n1, const double *x1, int64_t n2, double voxel, uint32_t *words)
+{
+    ProfScope ps(ctx, PCCM_K_POINT);
+    const OccupancyLayout L = occupancy_layout(n1, n2);
+    PCCM_HIP(hipMemsetAsync(words + L.table, 0xff, (size_t)L.cap * sizeof(uint32_t), ctx->stream));     // kMergeEmpty
+    PCCM_HIP(hipMemsetAsync(words + L.seen, 0, (L.words - L.seen) * sizeof(uint32_t), ctx->stream));    // seen, then the tallies
+    MergeArgs A = {};
+    A.x = x0;
+    A.x2 = x1;
+    A.n1 = n1;
+    A.n = n1 + n2;
+    A.voxel = voxel;
+    A.ws = words + L.table;
+    A.cap = L.cap;
+    A.seen = words + L.seen;
+    A.tally = (unsigned long long *)(words + L.tally);
+    A.err = ctx->host_err;
+    PCCM_LAUNCH(ctx, k_merge_probe<false>, merge_blocks(A.n), dim3(256), 0, ctx->stream, A);
+    PCCM_LAUNCH(ctx, k_merge_probe<true>, merge_blocks(A.n), dim3(256), 0, ctx->stream, A);
     PCCM_HIP(hipGetLastError());
     return PCCM_OK;
 }

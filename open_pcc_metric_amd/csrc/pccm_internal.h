@@ -526,6 +526,9 @@ struct pccm_ctx {
     int path_n[4] = {0, 0, 0, 0};
     bool path_over[4] = {false, false, false, false};   // a kernel did not fit: pccm_nn_path reports the list as incomplete
     unsigned path_mask = 0;
+    // pccm_voxel_occupancy: its table, seen words and tallies (occupancy_layout), then the tallies of up to kOccupancyMax sizes
+    // gathered for one copy back.  A buffer of its own: merge_ws holds the merged rows a cloud may still be read from
+    pccm::DevBuf occupancy_ws;      // (last: every other member keeps its place)
 };
 
 namespace pccm {
@@ -802,6 +805,28 @@ __host__ __device__ inline MergeLayout merge_layout(int64_t n)
     L.words = L.table + (size_t)L.cap;
     return L;
 }
+// The workspace of pccm_voxel_occupancy for clouds of n1 and n2 rows, in uint32 words: the table [cap] over the joint rows, cap =
+// the power of two >= 2 (n1 + n2) and >= 64; seen [n1] (one word per row of cloud 0: a row of cloud 1 has met the voxel it
+// represents); the three 64-bit tallies on an 8-byte boundary (the base is at least that aligned).  seen and the tallies are
+// cleared by one memset.
+constexpr int kOccupancyMax = 4;                   // voxel sizes per pccm_voxel_occupancy call
+struct OccupancyLayout {
+    uint64_t cap;
+    size_t table, seen, tally, words;              // offsets (and the total) in uint32 words
+    size_t bytes() const { return words * sizeof(uint32_t); }
+};
+__host__ __device__ inline OccupancyLayout occupancy_layout(int64_t n1, int64_t n2)
+{
+    OccupancyLayout L;
+    const uint64_t n = (uint64_t)n1 + (uint64_t)n2;
+    L.cap = 64;
+    while (L.cap < 2 * n) L.cap <<= 1;
+    L.table = 0;
+    L.seen = (size_t)L.cap;
+    L.tally = (L.seen + (size_t)n1 + 1) & ~(size_t)1;
+    L.words = L.tally + 6;
+    return L;
+}
 struct PointJobs {
     PointJob j[4];
     int njobs;
@@ -862,6 +887,9 @@ inline size_t merge_ws_bytes(int64_t n) { return merge_layout(n).bytes(); }
 // table filled, insert | find | the two scans; then -- rows were merged away -- the gather into `out` (rgb: the colours to keep
 // per representative row, the cloud's own or the averages).  `words`: the uint32 part of the workspace (MergeLayout)
 int launch_merge_find(pccm_ctx *ctx, const double *x64, int64_t n, uint32_t *words);
+// pccm_voxel_occupancy for one voxel size on the stream: the table filled, seen and the tallies cleared, then the insert and the
+// find of the merge in their occupancy mode over the joint rows (x0's n1, then x1's n2).  `words`: an OccupancyLayout
+int launch_occupancy(pccm_ctx *ctx, const double *x0, int64_t n1, const double *x1, int64_t n2, double voxel, uint32_t *words);
 // refl / refl_out: the reflectance to keep per representative row [n] (the cloud's own column or the averages) and the merged
 // column [n] (written), or both null
 int launch_merge_gather(pccm_ctx *ctx, const double *x64, const double *nrm, const double *rgb, const double *refl, int64_t n, double *out,

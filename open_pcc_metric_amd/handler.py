@@ -4,7 +4,8 @@
                                   [--point-to-plane] [--plane-to-plane] [--point-ssim ATTR ...] [--hausdorff-rank R ...]
                                   [--point-to-distribution] [--p2d-neighbours K] [--p2d-color] [--carry-normals] [--duplicates keep|drop|average]
                                   [--resolution-psnr] [--resolution-neighbours K] [--reflectance] [--reflectance-peak P] [--fscore TAU ...]
-                                  [--chamfer] [--truncate TAU ...] [--dcd ALPHA ...] [--dcd-squared] [--transform FILE] [--align icp] [--csv]
+                                  [--chamfer] [--truncate TAU ...] [--dcd ALPHA ...] [--dcd-squared] [--transform FILE] [--align icp]
+                                  [--occupancy VOXEL ...] [--csv]
 
 Extra, optional flags (defaults reproduce the reference): ``--device``, ``--engine``,
 ``--normal-index row|neighbour`` (row = the reference's D2, which raises IndexError when the clouds
@@ -58,7 +59,12 @@ after every other row, the density-aware Chamfer distance of Wu et al. (NeurIPS 
 1 - exp(-ALPHA d) / m over a cloud's points -- d the distance to the matched point, m the number of points that share it, counted on
 the GPU -- and the average of the two directions; every row lies in [0, 1], and a cloud that piles its points onto a few places is
 penalised where the Chamfer distance is blind.  ``--dcd-squared`` feeds d^2 in d's place; ``--ties mean`` with ``--dcd`` is a usage
-error ("Density-aware Chamfer distance").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
+error ("Density-aware Chamfer distance").  ``--occupancy VOXEL`` (repeatable, VOXEL > 0 in the clouds' units; no
+counterpart in the reference) adds, after every other row, the voxel-occupancy numbers of the reconstruction and learned-codec
+literature at that voxel size: the voxels of the lattice floor(coordinate / VOXEL) each cloud occupies, the share of each cloud's
+voxels the other occupies too (left: voxel recall, right: voxel precision) and their intersection over union -- counted on a GPU
+voxel table, without any search; on integer-voxelised content VOXEL = 2^j reads them at octree level j ("Voxel
+occupancy").  Input files: ply, pcd, xyz, xyzn, xyzrgb, pts (io.py; the formats
 ``o3d.io.read_point_cloud`` picks by extension, handler.py:57).
 """
 import click
@@ -154,6 +160,11 @@ import click
 @click.option("--align-out", "align_out", type=str, default=None, metavar="FILE",
               help="Write the 4 x 4 motion each processed cloud was given (--transform included) to FILE, 17 significant digits; "
                    "with several --pcloud the matrices follow one another.")
+@click.option("--occupancy", "occupancy", type=float, multiple=True, metavar="VOXEL",
+              help="Report the voxel occupancy at this voxel size (> 0, in the clouds' units) as well (may be repeated, at most 4), "
+                   "after all other rows: the voxels floor(coordinate / VOXEL) each cloud occupies, the share of each cloud's "
+                   "voxels the other occupies too (left: recall, right: precision) and their intersection over union.  Counted "
+                   "after --duplicates, --transform and --align; no search involved.")
 @click.option("--csv", required=False, is_flag=True, help="Print output in csv format.")
 @click.option("--device", type=int, default=0, show_default=True, help="GPU to use.")
 @click.option("--engine", type=click.Choice(["auto", "grid", "brute"]), default="auto", show_default=True,
@@ -168,12 +179,12 @@ import click
               help="Neighbour of a point with several equidistant nearest neighbours: the one of the smallest row, or their mean "
                    "(point-to-plane and colour rows then do not depend on the order of the points).")
 def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_ssim, ssim_neighbours, hausdorff_rank,
-        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, dcd, dcd_squared, transform, align, align_distance, align_iterations, align_tolerance, align_out, csv, device, engine, normal_index, extent, tie_exposure,
+        point_to_distribution, p2d_neighbours, p2d_color, carry_normals, duplicates, resolution_psnr, resolution_neighbours, reflectance, reflectance_peak, fscore, chamfer, truncate, dcd, dcd_squared, transform, align, align_distance, align_iterations, align_tolerance, align_out, occupancy, csv, device, engine, normal_index, extent, tie_exposure,
         ties) -> None:
     from .calculator import MetricCalculator
     from .cloud_pair import CloudPair
     from .io import read_point_cloud
-    from .options import (CalculateOptions, check_carry_normals, check_chamfer, check_dcd, check_duplicates, check_fscore, check_hausdorff_rank, check_p2d_color, check_point_ssim,
+    from .options import (CalculateOptions, check_carry_normals, check_chamfer, check_dcd, check_duplicates, check_fscore, check_hausdorff_rank, check_occupancy, check_p2d_color, check_point_ssim,
                           check_point_to_distribution, check_reflectance, check_resolution_psnr, check_truncate, transform_options)
 
     try:                                       # (a bad rank: before any file is read and any GPU context exists)
@@ -183,7 +194,8 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
                                    p2d_color=p2d_color, resolution_psnr=resolution_psnr,
                                    resolution_neighbours=resolution_neighbours, reflectance=reflectance,
                                    reflectance_peak=reflectance_peak, fscore=fscore or None, chamfer=chamfer,
-                                   truncate=truncate or None, dcd=dcd or None, dcd_squared=dcd_squared, align=align)
+                                   truncate=truncate or None, dcd=dcd or None, dcd_squared=dcd_squared, align=align,
+                                   occupancy=occupancy or None)
         check_dcd(options, ties=ties)
         from .align import check_align, read_transform_file
         check_align(align, align_distance, align_iterations, align_tolerance)
@@ -201,6 +213,7 @@ def cli(ocloud, pcloud, color, hausdorff, point_to_plane, plane_to_plane, point_
     check_truncate(options)
     check_point_to_distribution(options)
     check_resolution_psnr(options)
+    check_occupancy(options)
     try:                                       # (the one file a usage error may come from: read before any cloud)
         transform_matrix = None if transform is None else read_transform_file(transform)
     except (OSError, ValueError) as exc:

@@ -571,6 +571,66 @@ class AlignmentRMSE(_AlignmentRow):
     _field = "inlier_rmse"
 
 
+class VoxelCounts(PrimaryMetric):                                # no counterpart in the reference (options.py: occupancy)
+    """(nA, nB, nAB): the voxels of edge ``voxel`` on the absolute lattice floor(coordinate / voxel) that the original cloud
+    occupies, that the processed cloud occupies, and that both do ("Voxel occupancy") -- Python ints, counted on
+    the GPU's voxel table (CloudPair.voxel_occupancy)."""
+    _pccm_waits = True      # reads counts back from the GPU: the calculator evaluates these last
+
+    def __init__(self, voxel: float):
+        self.voxel = float(voxel)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.voxel)
+
+    def _pccm_request(self):
+        return "occupancy", self.voxel
+
+    def calculate(self, cloud_pair: CloudPair) -> None:
+        n_a, n_b, n_ab = cloud_pair.voxel_occupancy(self.voxel)
+        self.value = (int(n_a), int(n_b), int(n_ab))
+
+
+class _OverVoxelCounts(SecondaryMetric):
+    def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
+        return {"voxel_counts": VoxelCounts(voxel=self.voxel)}
+
+
+class OccupiedVoxels(_OverVoxelCounts, DirectionalMetric):
+    """The number of voxels a cloud occupies: the original's (left), the processed cloud's (right)."""
+    def __init__(self, is_left: bool, voxel: float):
+        super().__init__(is_left)
+        self.voxel = float(voxel)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.is_left, self.voxel)
+
+    def calculate(self, voxel_counts: VoxelCounts) -> None:
+        n_a, n_b, _ = voxel_counts.value
+        self.value = np.float64(n_a if self.is_left else n_b)
+
+
+class VoxelCoverage(OccupiedVoxels):
+    """The share of a cloud's voxels that the other cloud occupies too.  Left: of the original's voxels, those the processed
+    cloud reproduced (voxel recall); right: of the processed cloud's voxels, those the original has (voxel precision)."""
+    def calculate(self, voxel_counts: VoxelCounts) -> None:
+        n_a, n_b, n_ab = voxel_counts.value
+        self.value = np.float64(n_ab) / np.float64(n_a if self.is_left else n_b)
+
+
+class VoxelIoU(_OverVoxelCounts):
+    """Intersection over union of the two clouds' occupied voxels (no symmetric row: this is it)."""
+    def __init__(self, voxel: float):
+        self.voxel = float(voxel)
+
+    def _key(self) -> typing.Tuple:
+        return (type(self).__name__, self.voxel)
+
+    def calculate(self, voxel_counts: VoxelCounts) -> None:
+        n_a, n_b, n_ab = voxel_counts.value
+        self.value = np.float64(n_ab) / np.float64(n_a + n_b - n_ab)
+
+
 class _OverAngular(SecondaryMetric, DirectionalMetric):
     def _get_dependencies(self) -> typing.Dict[str, AbstractMetric]:
         return {"angular_similarities": AngularSimilarities(is_left=self.is_left)}

@@ -88,6 +88,14 @@ every row above:
 
   align                        AlignmentFitness (inliers / points of the processed cloud), AlignmentRMSE (of the inliers)
 
+and, with ``occupancy`` (no counterpart in the reference: the voxel-occupancy numbers of the reconstruction and learned-codec
+literature -- 3D-R2N2, occupancy networks -- on the absolute lattice floor(coordinate / voxel); no nearest-neighbour search),
+after every row above, alignment rows included, for each voxel size in ascending order:
+
+  voxel v                      OccupiedVoxels L, R (the clouds' occupied voxels)
+  voxel v                      VoxelCoverage L (shared / original's voxels: recall), VoxelCoverage R (shared / processed's: precision)
+  voxel v                      VoxelIoU (shared / union; no symmetric row: the IoU is it)
+
 ``CloudPair(..., duplicates=)`` / ``--duplicates`` (``check_duplicates`` below) merges duplicate points before any of this: it
 changes which rows the clouds have, never which report rows there are or their order.
 """
@@ -103,7 +111,8 @@ from .metric import (SSIM_CLASSES, AbstractMetric, AlignmentFitness, AlignmentRM
                      GeoRankedHausdorffDistance, GeoRankedHausdorffDistancePSNR, GeoResolutionPSNR, IntrinsicResolution,
                      JointMahalanobisDistance, MahalanobisDistance, MaxColorMahalanobisDistance,
                      MaxJointMahalanobisDistance, MaxMahalanobisDistance, MaxSqrtDistance, MinAngularSimilarity, MinSqrtDistance,
-                     ReflectanceHausdorffDistance, ReflectanceHausdorffDistancePSNR, ReflectanceMSE, ReflectancePSNR, SymmetricMetric)
+                     OccupiedVoxels, ReflectanceHausdorffDistance, ReflectanceHausdorffDistancePSNR, ReflectanceMSE, ReflectancePSNR,
+                     SymmetricMetric, VoxelCoverage, VoxelIoU)
 
 SSIM_ATTRIBUTES = ("geometry", "normal", "curvature", "color")     # the row order of transform_options
 SSIM_MIN_K, SSIM_MAX_K = 2, 64
@@ -111,6 +120,7 @@ MAX_HAUSDORFF_RANKS = 4
 MAX_FSCORE_THRESHOLDS = 4
 MAX_TRUNCATE_THRESHOLDS = 4
 MAX_DCD_ALPHAS = 4
+MAX_OCCUPANCY_VOXELS = 4
 P2D_MIN_K, P2D_MAX_K = 4, 64
 RESOLUTION_MIN_K, RESOLUTION_MAX_K = 1, 63
 
@@ -156,6 +166,27 @@ def _distance_thresholds(value, name: str, most: int) -> typing.Tuple[float, ...
     return tuple(sorted(thresholds))
 
 
+def _occupancy_voxels(value) -> typing.Tuple[float, ...]:
+    """``occupancy`` as a sorted tuple of distinct finite floats > 0 (voxel sizes in the clouds' units); ValueError for anything
+    else."""
+    if value is None:
+        return ()
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"occupancy must be a number or an iterable of numbers > 0, not {value!r}")
+    items = [value] if isinstance(value, numbers.Real) else list(value) if hasattr(value, "__iter__") else [value]
+    voxels = set()
+    for v in items:
+        if isinstance(v, (bool,)) or type(v).__name__ == "bool_" or not isinstance(v, numbers.Real):
+            raise ValueError(f"occupancy: {v!r} is not a finite number > 0")
+        f = float(v)
+        if not math.isfinite(f) or not f > 0.0:
+            raise ValueError(f"occupancy: {v!r} is not a finite number > 0")
+        voxels.add(f)
+    if len(voxels) > MAX_OCCUPANCY_VOXELS:
+        raise ValueError(f"occupancy: at most {MAX_OCCUPANCY_VOXELS} voxel sizes per report, not {len(voxels)}")
+    return tuple(sorted(voxels))
+
+
 def _fscore_thresholds(value) -> typing.Tuple[float, ...]:
     return _distance_thresholds(value, "fscore", MAX_FSCORE_THRESHOLDS)
 
@@ -171,7 +202,7 @@ class CalculateOptions:
                  hausdorff_rank=None, point_to_distribution: bool = False, p2d_neighbours: int = 30,
                  p2d_color: bool = False, resolution_psnr: bool = False, resolution_neighbours: int = 10,
                  reflectance: bool = False, reflectance_peak: float = 65535.0, fscore=None, chamfer: bool = False,
-                 truncate=None, dcd=None, dcd_squared: bool = False, align=None):
+                 truncate=None, dcd=None, dcd_squared: bool = False, align=None, occupancy=None):
         self.color = color
         self.hausdorff = hausdorff
         self.point_to_plane = point_to_plane
@@ -220,6 +251,7 @@ class CalculateOptions:
         if align is not None and (not isinstance(align, str) or align not in ("icp",)):
             raise ValueError('align must be None or "icp"')
         self.align = align
+        self.occupancy = _occupancy_voxels(occupancy)
 
 
 def check_point_ssim(options: CalculateOptions, origin_cloud, reconst_cloud, *, estimate_normals: bool = True,
@@ -282,6 +314,14 @@ def check_dcd(options: CalculateOptions, *, ties: str = "pick", group=None) -> N
         raise ValueError("density-aware Chamfer rows are not defined under ties='mean': a virtual neighbour has no row to count")
     if group is not None:
         raise ValueError("density-aware Chamfer rows are not available for sharded pairs (group=)")
+
+
+def check_occupancy(options: CalculateOptions, *, group=None) -> None:
+    """Raise ``ValueError`` when the voxel-occupancy rows ``options`` asks for cannot be computed for this pair -- before any GPU
+    work (the command line calls it before it makes the pair; CloudPair checks the same before any GPU work of a report).  The
+    voxel table holds the rows of both whole clouds on one GPU: a sharded pair is out of scope."""
+    if getattr(options, "occupancy", ()) and group is not None:
+        raise ValueError("voxel-occupancy rows are not available for sharded pairs (group=)")
 
 
 def check_point_to_distribution(options: CalculateOptions, *, group=None) -> None:
@@ -438,4 +478,7 @@ def transform_options(options: CalculateOptions) -> typing.List[AbstractMetric]:
         metrics += _sides(GeoDensityAwareDistance, alpha=alpha, squared=squared) + [GeoDensityAwareChamfer(alpha=alpha, squared=squared)]
     if getattr(options, "align", None) is not None:
         metrics += [AlignmentFitness(), AlignmentRMSE()]
+    for voxel in getattr(options, "occupancy", None) or ():
+        # left: the original's voxels / voxel recall; right: the processed cloud's / voxel precision; the IoU is the symmetric row
+        metrics += _sides(OccupiedVoxels, voxel=voxel) + _sides(VoxelCoverage, voxel=voxel) + [VoxelIoU(voxel=voxel)]
     return metrics
